@@ -17,6 +17,11 @@ or simply as `python bench.py --gpus N ...`: without a torchrun environment (RAN
 re-launches itself under torch.distributed.run on 127.0.0.1 with N ranks (self_launch()).
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line: `value`, `ms_per_step` and the roofline of the timed
+launches.  --full adds what takes runs of its own: the same open on the other kernel families and validation modes, two opens in
+flight, the protocol path at first sight and under attack, the Gao decoder beside Welch-Berlekamp, the measured copy bandwidth and
+the CPU baselines; their fields are null in a plain run.  --dump-outputs DIR writes what the last timed step computed (dump_outputs()).
 """
 import argparse
 import ctypes
@@ -195,6 +200,37 @@ def traffic_from_profiles(workload):
     """HBM bytes per launch of the dominant kernel (FETCH_SIZE / WRITE_SIZE passes, gfx950 correction)"""
     v = profile_counters(workload).get("hbm_bytes_per_launch")
     return float(v) if v is not None else None
+
+
+DUMP_ROWS = 1 << 17        # --dump-outputs: an output of more elements is written as a fixed, seeded sample of this many
+DUMP_BYTES = 64 << 20      # ... and all the files of one run together stay below this
+
+
+def dump_outputs(out_dir, arrays, seed=20240601):
+    """--dump-outputs: one DIR/<name>.npy per output of the last timed step, float64 (values are exact: below 2^53).  A field element
+    ((rows, limbs) int64 tensor) becomes a row of its 32-bit little-endian words; any other integer array is written as it is, one
+    value a row.  An output of more than DUMP_ROWS elements is sampled: the same seeded, sorted DUMP_ROWS element indices for the
+    same length, written beside it as DIR/<name>_index.npy.  The inputs are seeded too, so two builds' files compare one for one."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        rows = a.shape[0]
+        idx = None
+        if rows > DUMP_ROWS:
+            idx = np.sort(np.random.Generator(np.random.PCG64([seed, rows])).choice(rows, DUMP_ROWS, replace=False))
+            a = a[idx]
+        if a.dtype == np.int64:
+            words = np.ascontiguousarray(a.reshape(a.shape[0], -1)).view(np.uint32)
+        else:
+            words = a.reshape(a.shape[0], -1)
+        files = {name: words.astype(np.float64)}
+        if idx is not None:
+            files[name + "_index"] = idx.astype(np.float64)
+        for fname, v in files.items():
+            total += v.nbytes
+            assert total <= DUMP_BYTES, f"--dump-outputs: more than {DUMP_BYTES >> 20} MB"
+            np.save(os.path.join(out_dir, fname + ".npy"), v)
 
 
 SIMDS, NOMINAL_HZ = 1024, 2.4e9       # 256 CUs x 4 SIMDs; nominal shader clock (MI355X_MICROARCH.md)
@@ -717,6 +753,8 @@ def main_sharded(args, torch, dist, backend, rank, local_rank, world, n, t, B, u
     assert torch.equal(r2_msg, r2_cols[:c_loc]), "R2 message != what party 0 would broadcast"
     all_secrets = gather(secrets, ctx.empty(B))
     assert torch.equal(got, all_secrets), "gathered result differs from the gathered secrets"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"result": got, "r2_msg": r2_msg, "r1_out": r1_out})
     PROGRESS.finish()
 
     if rank == 0:
@@ -758,7 +796,7 @@ def main_sharded(args, torch, dist, backend, rank, local_rank, world, n, t, B, u
                 "bit_exact_vs_secrets": True, "matrix_core_path": bool(so.op.uses_matrix_cores()),
             },
         }
-        if args.cpu_sample > 0 and world == 1:
+        if args.full and args.cpu_sample > 0 and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, t, use_omega, min(args.cpu_sample, 1 << 17))
                 out["detail"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
@@ -843,6 +881,8 @@ def main_p64(args, torch, dist, backend, rank, local_rank, world, n, t, B):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert ok and torch.equal(result, secrets) and torch.equal(r2_msg, r2_cols[:C]), "the 64-bit open differs from the secrets"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"result": result, "r2_msg": r2_msg, "r1_out": r1_out})
     seg_ms = [evs.mean_ms(k, k + 1) for k in range(3)]
     seg_bytes = [8 * C * (d + n), 8 * C * (3 * d + n), 8 * C * (3 * d + n)]      # SURVEY 8d at 8-byte elements: encode 8 C (d + n); decode 8 C 2d + validating re-encode 8 C (d + n)
     names = ["R1 encode (n x d Vandermonde mat-vec)", "R1 decode + validating re-encode + compare", "R2 decode + validating re-encode + compare"]
@@ -873,7 +913,7 @@ def main_p64(args, torch, dist, backend, rank, local_rank, world, n, t, B):
                    "mulmods_per_open": C * (3 * n * d + 2 * d * d), "mulmod_per_s": world * C * (3 * n * d + 2 * d * d) * args.steps / dt,
                    "bit_exact_vs_secrets": True},
     }
-    if args.cpu_sample > 0 and world == 1:
+    if args.full and args.cpu_sample > 0 and world == 1:
         try:
             line["cpu_baseline"] = cpu_baseline_p64(n, t, min(args.cpu_sample, B), z, zc)
             line["detail"]["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
@@ -1048,7 +1088,7 @@ def main_robust(args, torch, dist, backend, rank, local_rank, world, n, t, C):
     def gao():
         ctx.check(lib.hb_gao_decode(ctx.h, np_ptr(xh), n, k, ctx.ptr(bad), C, ctx.ptr(out), ctx.ptr(err), ctx.ptr(elen), ctx.ptr(okf), ctx.stream()), "hb_gao_decode")
 
-    steps = min(args.steps, 20)
+    steps = args.steps
     ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
     ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
     for _ in range(max(1, min(args.warmup, 3))):
@@ -1076,10 +1116,12 @@ def main_robust(args, torch, dist, backend, rank, local_rank, world, n, t, C):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert bool((st == 0).all().item()) and torch.equal(out, msg), "Welch-Berlekamp: wrong coefficients in the timed region"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"coefficients": out, "coefficient_counts": olen, "status": st})
     call_ms = sum(a.elapsed_time(b) for a, b in zip(ev0, ev1)) / steps
-    # the Gao entry point on the same words (untimed for `value`)
+    # the Gao entry point on the same words (--full, untimed for `value`)
     dt_gao = None
-    if not n_era:               # (the Gao entry point takes no erasure mask: callers hand it the surviving points, ntl.gao_interpolate drops them per word)
+    if args.full and not n_era:               # (the Gao entry point takes no erasure mask: callers hand it the surviving points, ntl.gao_interpolate drops them per word)
         out.zero_()
         gao()
         torch.cuda.synchronize()
@@ -1088,7 +1130,7 @@ def main_robust(args, torch, dist, backend, rank, local_rank, world, n, t, C):
             gao()
         torch.cuda.synchronize()
         dt_gao = time.perf_counter() - t1
-    assert n_era or (bool(okf.all().item()) and bool((elen == t + 1).all().item()) and torch.equal(out, msg)), "Gao: wrong coefficients / locator degree"
+    assert dt_gao is None or (bool(okf.all().item()) and bool((elen == t + 1).all().item()) and torch.equal(out, msg)), "Gao: wrong coefficients / locator degree"
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
@@ -1139,7 +1181,7 @@ def main_robust(args, torch, dist, backend, rank, local_rank, world, n, t, C):
                                            "hb_wb_decode takes the Gao kernels' result there (trailing zeros stripped as the reference does) and row-reduces only what they "
                                            "reject (DESIGN.md 4e); every codeword of this workload sits AT the radius (33 errors)"},
     }
-    if args.cpu_sample > 0 and world == 1:
+    if args.full and args.cpu_sample > 0 and world == 1:
         try:
             line["cpu_baseline"] = cpu_baseline_robust(n, t, 4096, 4 if args.workload == "cfg4" else 1)
             line["detail"]["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
@@ -1176,6 +1218,11 @@ def main():
     ap.add_argument("--gather", default="auto", choices=["auto", "direct", "collective"],
                     help="sharded workloads (cfg5): how the opened slices are all-gathered (per-peer sends on the xGMI mesh / RCCL all_gather); "
                          "auto = probe both outside the timed region and use the faster usable one; direct falls back to collective if it fails")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: other kernel families and validation modes, two opens in flight, the first-sight "
+                         "protocol path, the Gao decoder, the copy bandwidth and the CPU baselines (off: those fields are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; rank 0; large outputs as a fixed seeded sample)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -1314,11 +1361,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert ok, "validation mismatch in timed region"
-
-    # ---- secondary (untimed for `value`): the same open on the other kernel family ------------
     mfma = op.uses_matrix_cores()
+    fused_default = bool(op.uses_fused_validate())   # the plan decodes + validates in one launch by default
+    fused_kernel = op.fused_validate_kernel() if fused_default else None      # "small": k_mm8f (hb_mfma_fused.hip); "wide": k_mm8w
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"result": result, "r2_msg": r2_msg, "r1_out": r1_out})
+
+    # ---- secondary (--full, untimed for `value`): the same open on the other kernel family ------------
     dt_other = None
-    if mfma:
+    if args.full and mfma:
         op.set_matrix_cores(False)
         for _ in range(2):
             step()
@@ -1334,30 +1385,32 @@ def main():
         step()
         assert op.ok()
 
-    # ---- secondary (untimed for `value`): validation restricted to the compared points -----------
-    fused_now = op.uses_fused_validate()
-    if fused_now:
-        op.set_fused_validate(False)         # the option below acts on the decode + re-encode + compare pipeline
-    op.set_validate_arrived_only(True)
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    ok4 = op.ok()
-    torch.cuda.synchronize()
-    dt_arrived = time.perf_counter() - t1
-    op.set_validate_arrived_only(False)
-    if fused_now:
-        op.set_fused_validate(True)
-    assert ok4 and torch.equal(result, secrets)
+    # ---- secondary (--full, untimed for `value`): validation restricted to the compared points -----------
+    dt_arrived = None
+    if args.full:
+        fused_now = op.uses_fused_validate()
+        if fused_now:
+            op.set_fused_validate(False)         # the option below acts on the decode + re-encode + compare pipeline
+        op.set_validate_arrived_only(True)
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        ok4 = op.ok()
+        torch.cuda.synchronize()
+        dt_arrived = time.perf_counter() - t1
+        op.set_validate_arrived_only(False)
+        if fused_now:
+            op.set_fused_validate(True)
+        assert ok4 and torch.equal(result, secrets)
 
-    # ---- secondary (untimed for `value`): the fused decode + validate switched off ------------------
+    # ---- secondary (--full, untimed for `value`): the fused decode + validate switched off ------------------
     # Plans with full-size matrix entries validate inside the decode launch (HB_OPEN_OPT_FUSED_VALIDATE); this is the
     # same open as decode, full re-encode of all n points, compare -- the reference's three full encodes.
     dt_unfused = None
-    if op.uses_fused_validate():
+    if args.full and op.uses_fused_validate():
         op.set_fused_validate(False)
         for _ in range(2):
             step()
@@ -1373,11 +1426,11 @@ def main():
         step()
         assert op.ok()
 
-    # ---- secondary (untimed for `value`): the fused decode + validate asked for on a small-entry plan -----
+    # ---- secondary (--full, untimed for `value`): the fused decode + validate asked for on a small-entry plan -----
     # The headline validates like the reference (re-encode all n points on its own kernels); on request the plan also
     # builds [Vinv rows ; V[zc] Vinv] for the full-size kernel and decodes + compares in one launch.
     dt_fused_optin = None
-    if dt_unfused is None and mfma:
+    if args.full and not fused_default and mfma:
         op.set_fused_validate(True)
         if op.uses_fused_validate():
             for _ in range(2):
@@ -1394,12 +1447,12 @@ def main():
         step()
         assert op.ok()
 
-    # ---- secondary (untimed for `value`): two independent opens in flight ------------------------
+    # ---- secondary (--full, untimed for `value`): two independent opens in flight ------------------------
     # A party opens many share arrays concurrently (Mpc.open_share_array under asyncio); with a second plan
     # on a second stream consecutive opens overlap (kernel tails, the elementwise pass, and co-resident
     # workgroups of different launches are not phase-locked).  Throughput only; each open is unchanged.
     dt_two = None
-    if args.two_streams_extra and world == 1:
+    if args.full and args.two_streams_extra and world == 1:
         from honeybadgermpc_amd.device import BatchOpenPipeline
 
         pipe = BatchOpenPipeline(BLS, n, t, depth=2, z=z, zc=zc, use_omega_powers=use_omega, max_shares=B, device=local_rank)
@@ -1431,14 +1484,14 @@ def main():
         assert ok3 and all(torch.equal(o[2], secrets) for o in outs)
         del pipe, outs
 
-    # ---- secondary (untimed for `value`): the protocol path at FIRST SIGHT of every arrival pattern ----------------
+    # ---- secondary (--full, untimed for `value`): the protocol path at FIRST SIGHT of every arrival pattern ----------------
     # What batch_reconstruct_device runs (device_reconstruction.py): the R1 encode, then one DeviceIncrementalDecoder per round, fed
     # column by column in a fresh seeded arrival order every step; nothing is kept per arrival pattern (no open plan: the matrices of
     # an arrival set are built on the device while the columns come in, as the reference rebuilds V^-1 inside every
     # vandermonde_batch_interpolate call, hbmpc_ntl_helpers.pyx:139-197).  The columns are received in place (`columns=`): the
     # decoder is told which row of the party-major buffer has landed.
     dt_first, dt_first_early, first_cols, adv = None, None, None, None
-    if world == 1 and not args.no_matrix_cores:
+    if args.full and world == 1 and not args.no_matrix_cores:
         from honeybadgermpc_amd.device import DeviceIncrementalDecoder
 
         r1v, r2v = r1_cols.view(n, C, 4), r2_cols.view(n, C, 4)
@@ -1545,8 +1598,6 @@ def main():
     sec_pad = secrets
     assert torch.equal(r2_msg, r2_cols[:C]), "R2 message != what party 0 would broadcast"
 
-    fused_default = dt_unfused is not None         # the plan decodes + validates in one launch by default
-    fused_kernel = op.fused_validate_kernel() if fused_default else None      # "small": k_mm8f (hb_mfma_fused.hip); "wide": k_mm8w
     assert fused_default == time_r2 or args.no_matrix_cores, "the events bracketed the wrong launch"
     enc_ms = evs.mean_ms(0, 1) if not time_r2 else None
     r2_ms = evs.mean_ms(2, 3) if time_r2 else None
@@ -1569,7 +1620,7 @@ def main():
         bytes_run = alg_bytes_open
 
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             copy_gbps = measured_copy_gbps()
         except Exception:  # noqa: BLE001 - an extra, never the measurement
@@ -1634,10 +1685,11 @@ def main():
                 "mulmod_per_s": world * mulmods_open * args.steps / dt,
                 "bit_exact_vs_secrets": True,
                 "matrix_core_path": bool(mfma),
-                "shares_per_s_per_gpu_validate_arrived_only": B * args.steps / dt_arrived,
+                "full": bool(args.full),
+                "shares_per_s_per_gpu_validate_arrived_only": (B * args.steps / dt_arrived) if dt_arrived else None,
                 "validate_arrived_only_note": "plan option on the unfused pipeline (decode, re-encode, compare): the guess is re-evaluated at the t compared "
                                               "points only (same accept/reject)",
-                "fused_decode_validate": dt_unfused is not None,
+                "fused_decode_validate": fused_default,
                 "fused_decode_validate_kernel": fused_kernel,
                 "shares_per_s_per_gpu_three_full_encodes": (B * args.steps / dt_unfused) if dt_unfused else None,
                 "fused_decode_validate_note": "each decode launch also produces the guess's values at the compared points as (V[zc] Vinv) y and compares them "
@@ -1668,7 +1720,7 @@ def main():
                 "integer_valu_path_note": "same open with HB_OPEN_OPT_MATRIX_CORES = 0 (second-generation integer-VALU kernels), same validation; bit-identical results",
             },
         }
-        if args.cpu_sample > 0 and world == 1:
+        if args.full and args.cpu_sample > 0 and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, t, use_omega, min(args.cpu_sample, B))
                 out["detail"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

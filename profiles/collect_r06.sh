@@ -13,7 +13,7 @@ pmc() {   # pmc <workload> <extra bench args...>: FETCH_SIZE | WRITE_SIZE | SQ p
   local W="$1"; shift
   for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY"; do
     local name=$(echo "$pass" | cut -d' ' -f1)
-    timeout 600 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d "$OUT/pmc_${W}_$name" -o p -- python bench.py --workload $W --steps 3 --warmup 1 --prewarm 0 --cpu-sample 0 --no-two-streams-extra "$@" > "$OUT/pmc_${W}_$name.log" 2>&1
+    timeout 600 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d "$OUT/pmc_${W}_$name" -o p -- python bench.py --workload $W --steps 3 --warmup 1 --prewarm 0 --cpu-sample 0 --no-two-streams-extra --full "$@" > "$OUT/pmc_${W}_$name.log" 2>&1
   done
   timeout 900 python profiles/summarize_pmc.py "$OUT"/pmc_${W}_* > "$OUT/pmc_summary_$W.txt" 2>&1
   timeout 900 python profiles/make_traffic.py "$OUT/pmc_summary_$W.txt" $W "profiles/r06_pmc_$W.txt (rocprofv3 --pmc, separate passes: FETCH_SIZE | WRITE_SIZE | SQ counters, bench.py --prewarm 0; FETCH x2 gfx950 correction)" > "$OUT/traffic_$W.json" 2> "$OUT/traffic_$W.err"
@@ -25,14 +25,14 @@ stats() {  # stats <name> <command...>
   timeout 600 python profiles/summarize_rocpd.py "$OUT/stats_$N/run_results.db" > "$OUT/kernel_stats_$N.txt" 2>&1
   rm -rf "$OUT/stats_$N"
 }
-timeout 900 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
-stats cfg3 python bench.py --cpu-sample 0
+timeout 900 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+stats cfg3 python bench.py --cpu-sample 0 --full
 pmc cfg3
 for w in cfg5-shard cfg3-omega cfg2 cfg5; do
-  timeout 600 python bench.py --workload $w --steps 30 --warmup 5 --cpu-sample 0 --no-two-streams-extra > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+  timeout 600 python bench.py --workload $w --steps 30 --warmup 5 --cpu-sample 0 --no-two-streams-extra --full > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
 done
-timeout 900 python bench.py --workload cfg4 --cpu-sample 0 > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
-timeout 900 python bench.py --workload cfg4 --erasures 10 --cpu-sample 0 > "$OUT/bench_cfg4_erasures10.json" 2> "$OUT/bench_cfg4_erasures10.err"
+timeout 900 python bench.py --workload cfg4 --cpu-sample 0 --full > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
+timeout 900 python bench.py --workload cfg4 --erasures 10 --cpu-sample 0 --full > "$OUT/bench_cfg4_erasures10.json" 2> "$OUT/bench_cfg4_erasures10.err"
 timeout 900 python bench.py --workload cfg3-p64 --cpu-sample 0 > "$OUT/bench_cfg3-p64.json" 2> "$OUT/bench_cfg3-p64.err"
 stats cfg3-p64 python bench.py --workload cfg3-p64 --cpu-sample 0
 pmc cfg3-p64

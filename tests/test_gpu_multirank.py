@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import REPO
@@ -43,7 +44,7 @@ def _run_plain(extra, timeout=900):
 
 
 def test_self_launch_weak():
-    out = _run_plain(["--workload", "tiny", "--no-two-streams-extra"])
+    out = _run_plain(["--workload", "tiny", "--no-two-streams-extra", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert out["distributed"]["world_size"] == 2 and "self-launch" in out["distributed"]["launcher"]
 
@@ -66,7 +67,7 @@ def test_wrong_world_size_is_reported_not_fatal():
     env = dict(os.environ, HB_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", "4", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--workload", "tiny",
-           "--no-two-streams-extra"]
+           "--no-two-streams-extra", "--full"]
     res = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
@@ -74,7 +75,7 @@ def test_wrong_world_size_is_reported_not_fatal():
 
 
 def test_two_ranks_weak_scaling_path():
-    out = _run(["--workload", "tiny", "--no-two-streams-extra"])
+    out = _run(["--workload", "tiny", "--no-two-streams-extra", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0 and out["detail"]["bit_exact_vs_secrets"]
 
 
@@ -103,7 +104,7 @@ def test_eight_ranks_sharded_open_with_gather(mode):
 
 
 def test_eight_ranks_weak_scaling_path():
-    out = _run(["--workload", "tiny", "--no-two-streams-extra"], nproc=8, timeout=1500)
+    out = _run(["--workload", "tiny", "--no-two-streams-extra", "--full"], nproc=8, timeout=1500)
     assert out["n_gpus"] == 8 and out["scaling"] == "weak" and out["value"] > 0 and out["detail"]["bit_exact_vs_secrets"]
     assert out["distributed"]["world_size"] == 8
 
@@ -138,10 +139,57 @@ def test_the_64_bit_prime_workload_line():
     """bench.py --workload cfg3-p64-mini: the open over p = 2^64 - 59 on the 1-limb kernels, checked bit for bit against the secrets inside
     bench.py, with roofline (three segments) and the CPU baseline on the same modulus"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "HB_BENCH_SHARE_GPU")}
-    res = subprocess.run([sys.executable, "bench.py", "--workload", "cfg3-p64-mini", "--steps", "3", "--warmup", "1", "--cpu-sample", "8192"], cwd=REPO, env=env,
+    res = subprocess.run([sys.executable, "bench.py", "--workload", "cfg3-p64-mini", "--steps", "3", "--warmup", "1", "--cpu-sample", "8192", "--full"], cwd=REPO, env=env,
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert out["value"] > 0 and out["dtype"].startswith("u64") and out["detail"]["bit_exact_vs_secrets"]
     assert len(out["roofline"]["segments"]) == 3 and 0 < out["roofline"]["frac"] < 1
     assert out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["kind"] == "port"
+
+
+# ---- one process, no launcher: what a plain run measures, --dump-outputs, --steps on every workload ----------------------------------------
+def _run_one(extra, timeout=900):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "HB_BENCH_SHARE_GPU")}
+    res = subprocess.run([sys.executable, "bench.py"] + extra, cwd=REPO, env=env, capture_output=True, text=True, timeout=timeout)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def _words_to_ints(a):
+    return [sum(int(w) << (32 * i) for i, w in enumerate(row)) for row in a]
+
+
+def test_plain_run_dumps_its_last_timed_step(tmp_path):
+    """without --full the line holds the headline and null extras; --dump-outputs writes the last timed step's outputs, the same files for
+    the same arguments (tiny: n = 4, t = 1, 256 shares in 128 chunks)"""
+    from conftest import BLS
+
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        out = _run_one(["--workload", "tiny", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)])
+        assert out["steps"] == 7 and out["ms_per_step"] > 0 and out["value"] > 0 and out["detail"]["bit_exact_vs_secrets"]
+        assert not out["detail"]["full"] and "cpu_baseline" not in out and out["roofline"]["copy_GBps_measured"] is None
+        assert out["detail"]["shares_per_s_per_gpu_validate_arrived_only"] is None and out["value_first_sight_protocol_path"] is None
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["r1_out.npy", "r2_msg.npy", "result.npy"]
+    shapes = {"result.npy": (256, 8), "r2_msg.npy": (128, 8), "r1_out.npy": (4 * 128, 8)}
+    for nm in names:
+        a, b = np.load(dirs[0] / nm), np.load(dirs[1] / nm)
+        assert a.dtype == np.float64 and a.shape == shapes[nm] and np.array_equal(a, b), nm
+        assert all(0 <= v < BLS for v in _words_to_ints(a)), nm
+    # the R2 message is the first chunk of each group of d = 2 opened shares evaluated at x_0 = 1: s_2c + s_2c+1
+    res, msg = _words_to_ints(np.load(dirs[0] / "result.npy")), _words_to_ints(np.load(dirs[0] / "r2_msg.npy"))
+    assert msg == [(res[2 * c] + res[2 * c + 1]) % BLS for c in range(128)]
+
+
+def test_robust_workload_times_the_steps_asked_for(tmp_path):
+    """--steps is the number of timed steps on the robust workload too; its dump samples the coefficients (34 x 4096 rows)"""
+    out = _run_one(["--workload", "cfg4-mini", "--steps", "23", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 23 and out["ms_per_step"] > 0 and out["detail"]["gao_codewords_per_s_per_gpu"] is None
+    assert sorted(os.listdir(tmp_path)) == ["coefficient_counts.npy", "coefficients.npy", "coefficients_index.npy", "status.npy"]
+    st = np.load(tmp_path / "status.npy")
+    assert st.shape == (4096, 1) and (st == 0).all()
+    assert np.load(tmp_path / "coefficients.npy").shape == (1 << 17, 8)
