@@ -21,6 +21,8 @@ HB_OK, HB_ERR_SINGULAR, HB_ERR_BAD_ARG, HB_ERR_UNSUPPORTED = 0, 1, 2, 3
 HB_ERR_NO_DEVICE, HB_ERR_HIP, HB_ERR_MISMATCH, HB_ERR_RETRY = 4, 5, 6, 7
 HB_DEC_COLLECTING, HB_DEC_DONE, HB_DEC_DISAGREE, HB_DEC_UNSUPPORTED, HB_DEC_PENDING = 0, 1, 2, 3, 4
 HB_DEC_OPT_DEFER, HB_DEC_OPT_BESIDE = 1, 2
+HB_EW_ADD, HB_EW_SUB, HB_EW_MUL, HB_EW_NEG = 0, 1, 2, 3
+HB_EW_SELFTEST_BEAVER, HB_EW_SELFTEST_INV, HB_EW_SELFTEST_BROADCAST = 4, 5, 0x100
 
 _STATUS_NAMES = {
     1: "HB_ERR_SINGULAR",
@@ -64,6 +66,9 @@ SYMBOLS = {
     "hb_matrix_to_host": (_i, [_vp, _vp, _vp, _vp]),
     "hb_matrix_destroy": (None, [_vp]),
     "hb_reduce": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "hb_ew_op": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _vp]),
+    "hb_ew_beaver": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_ew_inv": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "hb_quick_interp_check": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hb_quick_interp_check_map": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hb_quick_dec_create": (_i, [_vp, _vp, _i, _pp, _vp]),
@@ -115,6 +120,7 @@ SYMBOLS = {
     "hb_open_plan_get_option": (_i, [_vp, _i, _vp]),
     "hb_open_plan_destroy": (None, [_vp]),
     "hb_selftest_mulmod": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "hb_selftest_ew": (_i, [_vp, _i, _i, _vp, _vp, _i64]),
 }
 # include/hbmpc_hip_debug.h: diagnostics for scratch/ scripts and white-box tests, not part of the drop-in surface
 DEBUG_SYMBOLS = {

@@ -256,6 +256,8 @@ inline int nsub_for(int d, int nl, int nw) {
     long n = (d + per - 1) / per;
     return n < 1 ? 1 : (int)n;
 }
+void fp_params_from_limbs(FpParams<9> &P, const uint64_t *p_limbs);   // modulus (4 limbs / 1 limb) -> digits, R, R^2, n0: no device needed
+void fp_params_from_limbs(FpParams<3> &P, const uint64_t *p_limbs);
 int get_int_array(hb_ctx *ctx, const int32_t *host, int n, int32_t **dev, hipStream_t s);   // cached: valid for the current API call only
 int own_int_array(hb_ctx *ctx, const int32_t *host, int n, int32_t **dev, hipStream_t s);   // caller hipFree's it
 void cache_note(hb_ctx *ctx, const std::string &rk, std::function<void()> drop, bool pinned = false);

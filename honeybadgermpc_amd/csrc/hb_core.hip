@@ -65,6 +65,12 @@ template <int NL> void make_params(FpParams<NL> &P, const uint64_t *p_limbs, int
 
 }  // namespace
 
+// the same derivation for the other translation units' host self-tests (hb_ew.hip)
+namespace hb {
+void fp_params_from_limbs(FpParams<9> &P, const uint64_t *p_limbs) { make_params<9>(P, p_limbs, 4); }
+void fp_params_from_limbs(FpParams<3> &P, const uint64_t *p_limbs) { make_params<3>(P, p_limbs, 1); }
+}
+
 // =====================================================================================
 // kernels
 // =====================================================================================

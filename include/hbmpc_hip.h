@@ -117,6 +117,33 @@ int hb_matvec_check(hb_ctx *ctx, const hb_matrix *m, const uint64_t *in_dev, hb_
  * this call.  Asynchronous. */
 int hb_reduce(hb_ctx *ctx, const uint64_t *in_dev, uint64_t *out_dev, int64_t count, int32_t *changed_dev, void *stream);
 
+/* ---- element-wise arithmetic on share arrays (hb_ew.hip) ---------------------------------------------------------
+ * What an MPC program does between its opens, on the packed buffers the opens read and write.  Operands are canonical
+ * residues (every output of this library is; hb_reduce makes foreign buffers so) and so are the results.  All three entry
+ * points are asynchronous on `stream`, allocate nothing, and accept count == 0 (nothing is launched).  Null pointers with
+ * count > 0, a negative count and an unknown op return HB_ERR_BAD_ARG without launching. */
+#define HB_EW_ADD 0
+#define HB_EW_SUB 1
+#define HB_EW_MUL 2
+#define HB_EW_NEG 3
+/* out[i] = a[i] op b[i] for `count` elements; HB_EW_NEG: out[i] = -a[i] (b_dev ignored).  b_broadcast != 0: b_dev is ONE
+ * element used for every i (a public scalar times a share array, a share array plus a public constant).  out_dev may be
+ * a_dev or b_dev (not a broadcast b_dev with count > 1).  Replaces the element loops of ShareArray.__add__ / __sub__ /
+ * __mul__ (progs/mixins/dataflow.py) and of the local product of DoubleSharingMultiplyArrays
+ * (progs/mixins/share_arithmetic.py:96-98). */
+int hb_ew_op(hb_ctx *ctx, int op, const uint64_t *a_dev, const uint64_t *b_dev, int b_broadcast, uint64_t *out_dev, int64_t count,
+             void *stream);
+/* The step of a Beaver multiplication after its two opens, fused: out[i] = d[i] e[i] + d[i] q[i] + e[i] p[i] + pq[i]
+ * (d = x - p and e = y - q opened, (p, q, pq) this party's shares of a triple).  Replaces the list comprehension of
+ * BeaverMultiplyArrays (progs/mixins/share_arithmetic.py:43).  out_dev may be any of the inputs. */
+int hb_ew_beaver(hb_ctx *ctx, const uint64_t *d_dev, const uint64_t *e_dev, const uint64_t *p_dev, const uint64_t *q_dev,
+                 const uint64_t *pq_dev, uint64_t *out_dev, int64_t count, void *stream);
+/* out[i] = 1 / in[i], batched (Montgomery's trick over tiles of the array; in == out allowed).  Replaces `1 / sig` for every
+ * opened sig of InvertShareArray (progs/mixins/share_arithmetic.py:133).  A zero has no inverse: its output is 0, the
+ * other elements are unaffected, and *zeros_dev (when given; the caller zeroes it) is increased by the number of zeros
+ * met -- the caller decides whether that is field.py:126's ZeroDivisionError. */
+int hb_ew_inv(hb_ctx *ctx, const uint64_t *in_dev, uint64_t *out_dev, int64_t count, int32_t *zeros_dev, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip) -------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -361,6 +388,17 @@ void hb_open_plan_destroy(hb_open_plan *plan);
 /* host-side self test of the radix-2^29 arithmetic templates (no GPU needed):
  * out = a*b mod p computed with the same code the kernels use. */
 int hb_selftest_mulmod(const uint64_t *p_limbs, int n_limbs, const uint64_t *a, const uint64_t *b, uint64_t *out);
+/* host-side run of the element-wise kernels' bodies (no GPU needed): the same per-element functions hb_ew_op,
+ * hb_ew_beaver and hb_ew_inv launch, over `count` packed elements of host memory.
+ *   what = HB_EW_ADD | SUB | MUL (operands[0] = a, [1] = b; or-ed with HB_EW_SELFTEST_BROADCAST: b is one element),
+ *          HB_EW_NEG (operands[0] = a),
+ *          HB_EW_SELFTEST_BEAVER (operands[0..4] = d, e, p, q, pq),
+ *          HB_EW_SELFTEST_INV (operands[0] = in, walked tile by tile and lane by lane as the kernel's waves do;
+ *          operands[1], when not NULL, points at one uint64_t that receives the number of zeros met). */
+#define HB_EW_SELFTEST_BEAVER 4
+#define HB_EW_SELFTEST_INV 5
+#define HB_EW_SELFTEST_BROADCAST 0x100
+int hb_selftest_ew(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, uint64_t *out, int64_t count);
 
 #ifdef __cplusplus
 }
