@@ -144,6 +144,33 @@ int hb_ew_beaver(hb_ctx *ctx, const uint64_t *d_dev, const uint64_t *e_dev, cons
  * met -- the caller decides whether that is field.py:126's ZeroDivisionError. */
 int hb_ew_inv(hb_ctx *ctx, const uint64_t *in_dev, uint64_t *out_dev, int64_t count, int32_t *zeros_dev, void *stream);
 
+/* ---- power mixing (hb_pm.hip) -------------------------------------------------------------------------------------
+ * Replaces the NTL program apps/asynchromix/cpp/compute-power-sums.cpp (computePowers :17-84, runWithInputs :192-238) that
+ * apps/asynchromix/powermixing.py:49-59 shells out to once a client, and the files of its phases 1 and 3 (:35-45, :84-90).
+ * c_dev [M]: the opened a_c - b_c; powers_dev [M][k]: this party's shares of b_c^1 .. b_c^k.  With u_j = [b^j] / j! ([b^0] = 1)
+ * and v_i = c^i / i!, [a^m] = m! (u * v)[m]: a convolution.  hb_pm_powers writes this party's shares of a_c^1 .. a_c^k
+ * (out_dev [M][k], what computePowers returns); hb_pm_power_sums their sums over the M clients (sums_dev [k], the .sums file).
+ * method: HB_PM_DIRECT (tiled triangular convolution, any odd prime), HB_PM_NTT (2M forward transforms of order N = the power
+ * of two above 2k, one multiply-accumulate pass, one inverse transform: omega_host a primitive N-th root of unity and
+ * order == N, else HB_ERR_UNSUPPORTED), HB_PM_AUTO (the NTT path when a usable omega is given and k > HB_PM_CROSSOVER, else the
+ * direct path).  Both paths give the same canonical residues.  Asynchronous on `stream` (the first call for a given k builds the
+ * factorial tables and synchronises once).  M == 0 writes zeros.  k <= 0, k >= p, a negative M and null pointers return
+ * HB_ERR_BAD_ARG before any launch.  Neither call changes its inputs; the outputs must not overlap them.
+ * Working set: clients are taken in slabs, so the temporaries -- 2 (k + 1) + 2 N elements a client of a slab (2 (k + 1) on the
+ * direct path), at most 256 MiB a slab (one client's worth if that is more), plus (1024 / ceil(N / 256) + 2) N elements of
+ * partial sums -- do not grow with M.  They are kept with the context per stream and returned by hb_ctx_cache_clear. */
+#define HB_PM_AUTO 0
+#define HB_PM_DIRECT 1
+#define HB_PM_NTT 2
+/* HB_PM_AUTO takes the NTT path for k above this while N fits the batched LDS transform (N <= 2048 for 32-byte elements, 8192 for
+ * 8-byte ones).  Measured, profiles/power_mixing.txt (M = k, BLS12-381 Fr): direct / NTT time 0.74 at k = 256, 1.64 at k = 320 (the direct
+ * kernel takes a second tile of outputs from k = 257), 3.4 at k = 1023; above the LDS order the transforms run one polynomial at a time
+ * and the direct path is 40x (k = 1024) to 4x (k = 4096) faster. */
+#define HB_PM_CROSSOVER 256
+int hb_pm_power_sums(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *powers_dev, int64_t M, int k, int method,
+                     const uint64_t *omega_host, int order, uint64_t *sums_dev, void *stream);
+int hb_pm_powers(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *powers_dev, int64_t M, int k, uint64_t *out_dev, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip) -------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -399,6 +426,22 @@ int hb_selftest_mulmod(const uint64_t *p_limbs, int n_limbs, const uint64_t *a, 
 #define HB_EW_SELFTEST_INV 5
 #define HB_EW_SELFTEST_BROADCAST 0x100
 int hb_selftest_ew(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, uint64_t *out, int64_t count);
+/* host-side run of the power-mixing kernels' bodies (no GPU needed), walked tile by tile and lane by lane as the kernels' workgroups
+ * walk them, over host memory: c_host [M], powers_host [M][k].
+ *   what = HB_PM_SELFTEST_SUMS    out [k]: the direct path's power sums, partial sums over `group` clients each added up afterwards
+ *          HB_PM_SELFTEST_POWERS  out [M][k]: the direct path with groups of one client
+ *          HB_PM_SELFTEST_TABLES  out [2][M][k + 1]: u (1, [b^j] / j!) and then v (c^i / i!) as the table kernels build them
+ *          HB_PM_SELFTEST_MAC     c_host = U, powers_host = V, both [M][k]: out [k] = sum_c U[c][f] V[c][f] as the NTT path's
+ *                                 multiply-accumulate and reduction passes compute it (any k; the first three need k < p)
+ *          HB_PM_SELFTEST_CONV    c_host = u, powers_host = v, both [M][k + 1], taken as they are: out [k], out[m - 1] =
+ *                                 sum_c sum_{j <= m} u[c][j] v[c][m - j] through the direct kernel's staging and windows (any k) */
+#define HB_PM_SELFTEST_SUMS 0
+#define HB_PM_SELFTEST_POWERS 1
+#define HB_PM_SELFTEST_TABLES 2
+#define HB_PM_SELFTEST_MAC 3
+#define HB_PM_SELFTEST_CONV 4
+int hb_selftest_pm(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *c_host, const uint64_t *powers_host, int64_t M, int k,
+                   int64_t group, uint64_t *out);
 
 #ifdef __cplusplus
 }

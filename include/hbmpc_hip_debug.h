@@ -23,6 +23,9 @@ int hb_debug_occupancy(int n_in, int nl, int *mv3, int *dc);
 /* The library reads its environment hooks (HB_NO_QUICK, HB_GAO_PAIR, ...: DESIGN.md section 7) once, at the first question any of them is
  * asked.  A test that flips one inside a process calls this to have them read again. */
 void hb_debug_reload_env(void);
+/* Cap, in bytes, on the per-slab temporaries of hb_pm_power_sums / hb_pm_powers (hbmpc_hip.h; 256 MiB): a test sets a small one to put
+ * a slab boundary inside a small client count.  0 restores the default.  Process-wide. */
+void hb_debug_pm_slab_bytes(int64_t bytes);
 
 
 #ifdef __cplusplus
