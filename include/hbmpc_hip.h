@@ -171,6 +171,23 @@ int hb_pm_power_sums(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *powers_
                      const uint64_t *omega_host, int order, uint64_t *sums_dev, void *stream);
 int hb_pm_powers(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *powers_dev, int64_t M, int k, uint64_t *out_dev, void *stream);
 
+/* ---- the butterfly (switching) network (hb_bf.hip) ------------------------------------------------------------------
+ * One layer of apps/asynchromix/butterfly_network.py:9-53 (batch_switch and the loops that deal its inputs): k inputs, k a power
+ * of two, stride 2^log2_stride, k / 2 switches.  Switch j takes x = in[xi], y = in[yi], xi = ((j >> a) << (a + 1)) | (j & (2^a - 1)),
+ * yi = xi | 2^a (a = log2_stride), a shared sign b_j in {1, -1} and one triple (p_j, q_j, pq_j); m = b_j (x - y) is one Beaver
+ * multiplication and out[2j] = (x + y + m) / 2, out[2j + 1] = (x + y - m) / 2.
+ * hb_bf_mask, before the open: masked_dev[j] = bits[j] - p[j] and masked_dev[k / 2 + j] = in[xi] - in[yi] - q[j] (k elements, one
+ * array to open); bits_dev == NULL (the signs' differences were opened in advance): masked_dev[j] = in[xi] - in[yi] - q[j] alone
+ * (k / 2 elements; p_dev is not read).  hb_bf_switch, after it: d_dev, e_dev [k / 2] the opened halves; writes out_dev [k].
+ * Operands and results are canonical residues; bits_dev, p_dev, q_dev, pq_dev, d_dev, e_dev hold k / 2 elements each.  Both calls
+ * are asynchronous on `stream`, one launch each, allocate nothing and leave their inputs unchanged.  HB_ERR_BAD_ARG before any
+ * launch: null pointers, k not a power of two or below 2, log2_stride outside [0, log2(k)), out_dev / masked_dev overlapping
+ * in_dev (a layer is not in place: ping-pong two buffers). */
+int hb_bf_mask(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *bits_dev, const uint64_t *p_dev, const uint64_t *q_dev, int64_t k,
+               int log2_stride, uint64_t *masked_dev, void *stream);
+int hb_bf_switch(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *d_dev, const uint64_t *e_dev, const uint64_t *p_dev,
+                 const uint64_t *q_dev, const uint64_t *pq_dev, int64_t k, int log2_stride, uint64_t *out_dev, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip) -------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -442,6 +459,17 @@ int hb_selftest_ew(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_PM_SELFTEST_CONV 4
 int hb_selftest_pm(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *c_host, const uint64_t *powers_host, int64_t M, int k,
                    int64_t group, uint64_t *out);
+/* host-side run of the butterfly kernels' bodies (no GPU needed) over host memory, switch by switch:
+ *   what = HB_BF_SELFTEST_MASK    operands[0..3] = in [k], bits, p, q [k / 2]: out as hb_bf_mask writes masked_dev (operands[1] NULL:
+ *                                 the k / 2 data-dependent elements alone)
+ *          HB_BF_SELFTEST_SWITCH  operands[0..5] = in [k], d, e, p, q, pq [k / 2]: out [k] as hb_bf_switch writes out_dev
+ *          HB_BF_SELFTEST_INDEX   no operands: out[2j] = xi, out[2j + 1] = yi of switch j as plain 64-bit integers (k of them)
+ *          HB_BF_SELFTEST_HALVE   operands[0] = v [k], any k >= 0, log2_stride ignored: out[i] = v[i] / 2 as the switch halves its sums */
+#define HB_BF_SELFTEST_MASK 0
+#define HB_BF_SELFTEST_SWITCH 1
+#define HB_BF_SELFTEST_INDEX 2
+#define HB_BF_SELFTEST_HALVE 3
+int hb_selftest_bf(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, int64_t k, int log2_stride, uint64_t *out);
 
 #ifdef __cplusplus
 }
