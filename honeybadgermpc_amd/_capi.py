@@ -26,6 +26,8 @@ HB_EW_SELFTEST_BEAVER, HB_EW_SELFTEST_INV, HB_EW_SELFTEST_BROADCAST = 4, 5, 0x10
 HB_PM_AUTO, HB_PM_DIRECT, HB_PM_NTT = 0, 1, 2
 HB_PM_SELFTEST_SUMS, HB_PM_SELFTEST_POWERS, HB_PM_SELFTEST_TABLES, HB_PM_SELFTEST_MAC, HB_PM_SELFTEST_CONV = 0, 1, 2, 3, 4
 HB_BF_SELFTEST_MASK, HB_BF_SELFTEST_SWITCH, HB_BF_SELFTEST_INDEX, HB_BF_SELFTEST_HALVE = 0, 1, 2, 3
+HB_MIMC_SUB, HB_MIMC_PAIR = 1, 2
+HB_MIMC_SELFTEST_PLAIN, HB_MIMC_SELFTEST_ROUND, HB_MIMC_SELFTEST_FIRST = 0, 1, 2
 
 _STATUS_NAMES = {
     1: "HB_ERR_SINGULAR",
@@ -76,6 +78,9 @@ SYMBOLS = {
     "hb_pm_powers": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "hb_bf_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "hb_bf_switch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "hb_mimc_plain": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i64, _vp]),
+    "hb_mimc_first": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "hb_mimc_round": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _vp]),
     "hb_quick_interp_check": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hb_quick_interp_check_map": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hb_quick_dec_create": (_i, [_vp, _vp, _i, _pp, _vp]),
@@ -130,6 +135,7 @@ SYMBOLS = {
     "hb_selftest_ew": (_i, [_vp, _i, _i, _vp, _vp, _i64]),
     "hb_selftest_pm": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _i64, _vp]),
     "hb_selftest_bf": (_i, [_vp, _i, _i, _vp, _i64, _i, _vp]),
+    "hb_selftest_mimc": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i64, _vp, _i64]),
 }
 # include/hbmpc_hip_debug.h: diagnostics for scratch/ scripts and white-box tests, not part of the drop-in surface
 DEBUG_SYMBOLS = {

@@ -188,7 +188,35 @@ int hb_bf_mask(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *bits_dev, co
 int hb_bf_switch(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *d_dev, const uint64_t *e_dev, const uint64_t *p_dev,
                  const uint64_t *q_dev, const uint64_t *pq_dev, int64_t k, int log2_stride, uint64_t *out_dev, void *stream);
 
-/* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip) -------------------------------------------
+/* ---- the MiMC block cipher (hb_mimc.hip) -----------------------------------------------------------------------------
+ * progs/mimc.py:10-15 (mimc_plain), :25-30 and :46-55 (the cubing round of mimc_mpc and mimc_mpc_batch), and the keystream of
+ * progs/mimc_symmetric.py:10-16, 19-28.  F(x, k): v = x; rounds times v = (v + k + c)^3 for c = 0, 1, ...; F = v + k.
+ * Everywhere: operands and results are canonical residues; key_dev holds ONE element for all (key_broadcast != 0) or `count` of them;
+ * x_dev == NULL means the counters x_i = start + i, start_host one canonical element in host memory (NULL: 0; not below the modulus:
+ * HB_ERR_BAD_ARG).  A public constant is added to a Shamir share alike by every party, so no call asks whether x or key is shared.
+ * hb_mimc_plain, the cleartext cipher in one launch: out[i] = F(x_i, key_i); with addend_dev, addend[i] + F (mimc_encrypt) or, with
+ *   HB_MIMC_SUB, addend[i] - F (its inverse).  HB_MIMC_PAIR: two elements a thread instead of one, same results (DESIGN.md 3k has
+ *   the timings of both).  rounds < 1: HB_ERR_BAD_ARG.
+ * hb_mimc_first: out[i] = x_i + key_i - r0[i], the first array an MPC evaluation opens.
+ * hb_mimc_round, after the open of round ctr: y_dev the opened x - r; r_dev, r2_dev, r3_dev this party's shares of the round's
+ *   cube (r, r^2, r^3); x3 = y^3 + 3 y^2 r + 3 y r2 + r3.  out[i] = x3 + (key_i + ctr + 1) - r_next[i], the next round's array to
+ *   open; r_next_dev == NULL (the last round): out[i] = x3 + key_i.  ctr < 0: HB_ERR_BAD_ARG.
+ * All three are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: null pointers
+ * (with count > 0: an empty array may have none), a negative count, unknown flags, HB_MIMC_SUB without an addend.  count == 0 returns HB_OK and launches nothing; more than
+ * 2^31 - 1 workgroups: HB_ERR_UNSUPPORTED.  In place: out_dev may be any of the arrays of `count` elements a call reads (x, addend,
+ * a key per element, y, r, r2, r3, r_next, r0: a thread reads its elements before it writes them) but not a broadcast key when
+ * count > 1; partial overlaps are the caller's to avoid. */
+#define HB_MIMC_SUB 1
+#define HB_MIMC_PAIR 2
+int hb_mimc_plain(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *start_host, const uint64_t *key_dev, int key_broadcast,
+                  const uint64_t *addend_dev, int flags, int rounds, uint64_t *out_dev, int64_t count, void *stream);
+int hb_mimc_first(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *start_host, const uint64_t *key_dev, int key_broadcast,
+                  const uint64_t *r0_dev, uint64_t *out_dev, int64_t count, void *stream);
+int hb_mimc_round(hb_ctx *ctx, const uint64_t *y_dev, const uint64_t *r_dev, const uint64_t *r2_dev, const uint64_t *r3_dev,
+                  const uint64_t *key_dev, int key_broadcast, int64_t ctr, const uint64_t *r_next_dev, uint64_t *out_dev, int64_t count,
+                  void *stream);
+
+/* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip)-------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
 /* decoder.decode_batch over the arrivals z[0..d) + encoder.encode_batch + the compare loop with the later arrivals zc[0..nc)
@@ -470,6 +498,17 @@ int hb_selftest_pm(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_BF_SELFTEST_INDEX 2
 #define HB_BF_SELFTEST_HALVE 3
 int hb_selftest_bf(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, int64_t k, int log2_stride, uint64_t *out);
+/* host-side run of the MiMC kernels' bodies (no GPU needed) over host memory, element by element; start, key_broadcast and flags as
+ * the device calls take them:
+ *   what = HB_MIMC_SELFTEST_PLAIN  operands[0..2] = x (NULL: the counters start + i), key, addend (or NULL); arg = rounds: out as
+ *                                  hb_mimc_plain writes out_dev (HB_MIMC_PAIR: through the two-element body)
+ *          HB_MIMC_SELFTEST_ROUND  operands[0..5] = y, r, r2, r3, key, r_next (NULL: the last round); arg = ctr: as hb_mimc_round
+ *          HB_MIMC_SELFTEST_FIRST  operands[0..2] = x (or NULL), key, r0: as hb_mimc_first */
+#define HB_MIMC_SELFTEST_PLAIN 0
+#define HB_MIMC_SELFTEST_ROUND 1
+#define HB_MIMC_SELFTEST_FIRST 2
+int hb_selftest_mimc(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const uint64_t *start, int key_broadcast,
+                     int flags, int64_t arg, uint64_t *out, int64_t count);
 
 #ifdef __cplusplus
 }
