@@ -28,6 +28,9 @@ HB_PM_SELFTEST_SUMS, HB_PM_SELFTEST_POWERS, HB_PM_SELFTEST_TABLES, HB_PM_SELFTES
 HB_BF_SELFTEST_MASK, HB_BF_SELFTEST_SWITCH, HB_BF_SELFTEST_INDEX, HB_BF_SELFTEST_HALVE = 0, 1, 2, 3
 HB_MIMC_SUB, HB_MIMC_PAIR = 1, 2
 HB_MIMC_SELFTEST_PLAIN, HB_MIMC_SELFTEST_ROUND, HB_MIMC_SELFTEST_FIRST = 0, 1, 2
+HB_JJ_SCALAR_BROADCAST, HB_JJ_POINT_BROADCAST = 1, 2
+HB_JJ_SELFTEST_SCALAR_MUL, HB_JJ_SELFTEST_DOUBLE_TABLE, HB_JJ_SELFTEST_MASK, HB_JJ_SELFTEST_STAGE1 = 0, 1, 2, 3
+HB_JJ_SELFTEST_STAGE2, HB_JJ_SELFTEST_STAGE3, HB_JJ_SELFTEST_SCALE = 4, 5, 6
 
 _STATUS_NAMES = {
     1: "HB_ERR_SINGULAR",
@@ -81,6 +84,13 @@ SYMBOLS = {
     "hb_mimc_plain": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i64, _vp]),
     "hb_mimc_first": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
     "hb_mimc_round": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _vp]),
+    "hb_jj_scalar_mul": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_jj_double_table": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "hb_jj_add_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "hb_jj_add_stage1": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "hb_jj_add_stage2": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_jj_add_stage3": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "hb_jj_add_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "hb_quick_interp_check": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hb_quick_interp_check_map": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hb_quick_dec_create": (_i, [_vp, _vp, _i, _pp, _vp]),
@@ -136,6 +146,7 @@ SYMBOLS = {
     "hb_selftest_pm": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _i64, _vp]),
     "hb_selftest_bf": (_i, [_vp, _i, _i, _vp, _i64, _i, _vp]),
     "hb_selftest_mimc": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i64, _vp, _i64]),
+    "hb_selftest_jj": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _i64]),
 }
 # include/hbmpc_hip_debug.h: diagnostics for scratch/ scripts and white-box tests, not part of the drop-in surface
 DEBUG_SYMBOLS = {

@@ -216,6 +216,47 @@ int hb_mimc_round(hb_ctx *ctx, const uint64_t *y_dev, const uint64_t *r_dev, con
                   const uint64_t *key_dev, int key_broadcast, int64_t ctr, const uint64_t *r_next_dev, uint64_t *out_dev, int64_t count,
                   void *stream);
 
+/* ---- the Jubjub curve (hb_jj.hip) --------------------------------------------------------------------------------------
+ * The twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 of elliptic_curve.py: Point.__mul__ (:102-122) and the doubling chain of
+ * share_mul (progs/jubjub.py:280-286) in the clear, and SharedPoint.add (progs/jubjub.py:87-113) on share arrays.  Points are two
+ * arrays of canonical residues (x, y); a_host and d_host are ONE canonical element each in host memory (missing where the call
+ * says it needs one, or not below the modulus: HB_ERR_BAD_ARG).  The curve must be complete (a a square, d a non-square) and the
+ * points on it: nothing here checks that, and off the curve a denominator may vanish (its result is then 0).
+ * hb_jj_scalar_mul: (outx, outy)[i] = n_i (x_i, y_i) in one launch; n_broadcast / point_broadcast != 0: element 0 serves every i.
+ *   Scalars are canonical residues (any value below the modulus); n_i = 0 gives (0, 1).
+ * hb_jj_double_table: (xs, ys)[j][i] = 2^j (x_i, y_i) for j < rows, arrays of rows * count elements, row-major; zs_dev is scratch of
+ *   the same size.  Four launches: the projective rows, ONE hb_ew_inv over every Z (zeros_dev as hb_ew_inv takes it, or NULL) and two
+ *   hb_ew_op products.  rows < 1: HB_ERR_BAD_ARG.
+ * The addition of m pairs of SHARED points, for curves with a = -1 (the reference's law):
+ *     x3 = (x1 y2 + y1 x2) / (1 + d x1 x2 y1 y2),   y3 = (y1 y2 + x1 x2) / (1 - d x1 x2 y1 y2)
+ *   consumes 9 Beaver triples and 2 random shares (rx, ry) a pair.  p_dev, q_dev, pq_dev: this party's shares of the triples' first
+ *   factors, second factors and products; triple k of pair i at element k * trip_stride + i (trip_stride >= m, else HB_ERR_BAD_ARG).
+ *   Triple k multiplies: 0 x1 x2, 1 y1 y2, 2 x1 y2, 3 y1 x2, 4 xp yp, 5 nx rx, 6 ny ry, 7 dx rx, 8 dy ry (xp = x1 x2, yp = y1 y2,
+ *   nx = x1 y2 + y1 x2, ny = yp + xp, dx = 1 + d xp yp, dy = 1 - d xp yp).  Between the calls the caller opens what a call wrote:
+ *   hb_jj_add_mask    writes a_dev [8][m]: rows 2k, 2k + 1 the masked factors of products k = 0..3
+ *   hb_jj_add_stage1  opened A -> b_dev [6][m]: the masked factors of products 4..6
+ *   hb_jj_add_stage2  opened B -> uv_dev [2][m] = ([nx rx], [ny ry]), kept by the caller, and c_dev [4][m]: products 7, 8
+ *   hb_jj_add_stage3  opened C -> d_dev [2][m]: the shares of sig_x = dx rx, sig_y = dy ry
+ *   hb_jj_add_finish  opened D -> x3 = uv[0] / sig_x, y3 = uv[1] / sig_y: hb_ew_inv over the 2 m sigs into inv_dev (scratch, [2][m];
+ *                     a zero sig -- r = 0 or operands off the curve -- is counted in *zeros_dev as hb_ew_inv counts) and one scaling launch.
+ *   One launch each (finish: two), asynchronous on `stream`, nothing allocated.  Every output is an array of its own, distinct from
+ *   what the call reads.  Null pointers with m > 0 and a negative m: HB_ERR_BAD_ARG; m == 0 returns HB_OK and launches nothing. */
+int hb_jj_scalar_mul(hb_ctx *ctx, const uint64_t *n_dev, int n_broadcast, const uint64_t *x_dev, const uint64_t *y_dev, int point_broadcast,
+                     const uint64_t *a_host, const uint64_t *d_host, uint64_t *outx_dev, uint64_t *outy_dev, int64_t count, void *stream);
+int hb_jj_double_table(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *a_host, int rows, uint64_t *xs_dev,
+                       uint64_t *ys_dev, uint64_t *zs_dev, int64_t count, int32_t *zeros_dev, void *stream);
+int hb_jj_add_mask(hb_ctx *ctx, const uint64_t *x1_dev, const uint64_t *y1_dev, const uint64_t *x2_dev, const uint64_t *y2_dev,
+                   const uint64_t *p_dev, const uint64_t *q_dev, int64_t trip_stride, uint64_t *a_dev, int64_t m, void *stream);
+int hb_jj_add_stage1(hb_ctx *ctx, const uint64_t *a_open_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev,
+                     int64_t trip_stride, const uint64_t *rx_dev, const uint64_t *ry_dev, uint64_t *b_dev, int64_t m, void *stream);
+int hb_jj_add_stage2(hb_ctx *ctx, const uint64_t *b_open_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev,
+                     int64_t trip_stride, const uint64_t *rx_dev, const uint64_t *ry_dev, const uint64_t *d_host, uint64_t *uv_dev,
+                     uint64_t *c_dev, int64_t m, void *stream);
+int hb_jj_add_stage3(hb_ctx *ctx, const uint64_t *c_open_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev,
+                     int64_t trip_stride, uint64_t *d_dev, int64_t m, void *stream);
+int hb_jj_add_finish(hb_ctx *ctx, const uint64_t *d_open_dev, const uint64_t *uv_dev, uint64_t *inv_dev, uint64_t *x3_dev, uint64_t *y3_dev,
+                     int64_t m, int32_t *zeros_dev, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip)-------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -509,6 +550,28 @@ int hb_selftest_bf(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_MIMC_SELFTEST_FIRST 2
 int hb_selftest_mimc(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const uint64_t *start, int key_broadcast,
                      int flags, int64_t arg, uint64_t *out, int64_t count);
+/* host-side run of the Jubjub kernels' bodies (no GPU needed) over host memory, element by element; a, d one canonical element each
+ * (NULL where `what` does not use it); arrays of several rows are row-major with `count` elements a row:
+ *   what = HB_JJ_SELFTEST_SCALAR_MUL    operands[0..2] = n, x, y; flags = HB_JJ_SCALAR_BROADCAST | HB_JJ_POINT_BROADCAST; a, d;
+ *                                       out [2][count] = the x row, then the y row, as hb_jj_scalar_mul writes them
+ *          HB_JJ_SELFTEST_DOUBLE_TABLE  operands[0..1] = x, y; arg = rows; a; out [3][rows][count]: the PROJECTIVE rows the kernel writes
+ *                                       (Montgomery residues of X, Y, Z: x = X / Z, y = Y / Z)
+ *          HB_JJ_SELFTEST_MASK          operands[0..5] = x1, y1, x2, y2, p, q; arg = trip_stride; out [8][count]
+ *          HB_JJ_SELFTEST_STAGE1        operands[0..5] = opened A, p, q, pq, rx, ry; arg = trip_stride; out [6][count]
+ *          HB_JJ_SELFTEST_STAGE2        operands[0..5] = opened B, p, q, pq, rx, ry; arg = trip_stride; d; out [2][count] uv, then [4][count] C
+ *          HB_JJ_SELFTEST_STAGE3        operands[0..3] = opened C, p, q, pq; arg = trip_stride; out [2][count]
+ *          HB_JJ_SELFTEST_SCALE         operands[0..1] = the inverted sigs [2][count], uv [2][count]; out [2][count] = x3, y3 */
+#define HB_JJ_SCALAR_BROADCAST 1
+#define HB_JJ_POINT_BROADCAST 2
+#define HB_JJ_SELFTEST_SCALAR_MUL 0
+#define HB_JJ_SELFTEST_DOUBLE_TABLE 1
+#define HB_JJ_SELFTEST_MASK 2
+#define HB_JJ_SELFTEST_STAGE1 3
+#define HB_JJ_SELFTEST_STAGE2 4
+#define HB_JJ_SELFTEST_STAGE3 5
+#define HB_JJ_SELFTEST_SCALE 6
+int hb_selftest_jj(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const uint64_t *a, const uint64_t *d,
+                   int flags, int64_t arg, uint64_t *out, int64_t count);
 
 #ifdef __cplusplus
 }
