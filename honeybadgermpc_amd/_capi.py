@@ -31,6 +31,9 @@ HB_MIMC_SELFTEST_PLAIN, HB_MIMC_SELFTEST_ROUND, HB_MIMC_SELFTEST_FIRST = 0, 1, 2
 HB_JJ_SCALAR_BROADCAST, HB_JJ_POINT_BROADCAST = 1, 2
 HB_JJ_SELFTEST_SCALAR_MUL, HB_JJ_SELFTEST_DOUBLE_TABLE, HB_JJ_SELFTEST_MASK, HB_JJ_SELFTEST_STAGE1 = 0, 1, 2, 3
 HB_JJ_SELFTEST_STAGE2, HB_JJ_SELFTEST_STAGE3, HB_JJ_SELFTEST_SCALE = 4, 5, 6
+HB_FXP_MOD, HB_FXP_TRUNC, HB_FXP_NEG_TRUNC = 0, 1, 2
+HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
+HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
 
 _STATUS_NAMES = {
     1: "HB_ERR_SINGULAR",
@@ -91,6 +94,12 @@ SYMBOLS = {
     "hb_jj_add_stage2": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_jj_add_stage3": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "hb_jj_add_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "hb_fxp_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "hb_fxp_trunc_pr": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "hb_fxp_ltl_leaves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "hb_fxp_carry_mask": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxp_carry_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxp_div2m_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i64, _vp]),
     "hb_quick_interp_check": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hb_quick_interp_check_map": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hb_quick_dec_create": (_i, [_vp, _vp, _i, _pp, _vp]),
@@ -147,6 +156,7 @@ SYMBOLS = {
     "hb_selftest_bf": (_i, [_vp, _i, _i, _vp, _i64, _i, _vp]),
     "hb_selftest_mimc": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i64, _vp, _i64]),
     "hb_selftest_jj": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _i64]),
+    "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
 }
 # include/hbmpc_hip_debug.h: diagnostics for scratch/ scripts and white-box tests, not part of the drop-in surface
 DEBUG_SYMBOLS = {

@@ -257,6 +257,49 @@ int hb_jj_add_stage3(hb_ctx *ctx, const uint64_t *c_open_dev, const uint64_t *p_
 int hb_jj_add_finish(hb_ctx *ctx, const uint64_t *d_open_dev, const uint64_t *uv_dev, uint64_t *inv_dev, uint64_t *x3_dev, uint64_t *y3_dev,
                      int64_t m, int32_t *zeros_dev, void *stream);
 
+/* ---- fixed-point arithmetic on shares (hb_fxp.hip) --------------------------------------------------------------------
+ * progs/fixedpoint.py ("Secure Computation With Fixed-Point Numbers", Catrina and Saxena): random2m (:91-98), trunc_pr (:108-120),
+ * get_carry_bit / bit_ltl (:131-172), div2m (:184-193), trunc (:208-211) and FixedPoint.ltz (:266-268) for arrays of `count` values.
+ * Everywhere: operands and results are canonical residues.  A value has k bits, m of them are cut off, kappa is the statistical
+ * security parameter.  Preprocessed random bit shares are bit planes: bits_dev holds rows of `count` elements, row i this party's
+ * shares of bit i of every element's mask.  Arrays of several rows are row-major with `count` elements a row.
+ * hb_fxp_mask: r1 = sum_{i<m} 2^i b_i and r2 = sum_{i<k+kappa-m} 2^i b_{m+i} by Horner over k + kappa rows of bits_dev.
+ *   x_dev given: masked_dev[i] = x_i + 2^(k-1) + r1 + 2^m r2, the array to open, and r1_dev[i] = r1.  x_dev == NULL (random2m alone):
+ *   masked_dev[i] = r2, r1_dev[i] = r1.  HB_ERR_BAD_ARG unless 0 < m < k, kappa >= 0 and k + kappa + 1 <= bits(p) - 1 (the masked
+ *   value c < 2^(k+kappa+1) must not wrap).  masked_dev may be x_dev; r1_dev is an array of its own.
+ * hb_fxp_trunc_pr, after the open: out[i] = (x_i - (c_i mod 2^m) + r1_i) 2^(-m).  inv2m_host: ONE canonical element in host
+ *   memory, 2^(-m) mod p (not below the modulus: HB_ERR_BAD_ARG).  0 < m <= bits(p) - 2.  out_dev may be x_dev, c_dev or r1_dev.
+ * hb_fxp_ltl_leaves: the leaves of the carry tree of c2 + (2^m - 1 - r1) + 1, c2 = c mod 2^m public, from rows 0..m-1 of bits_dev
+ *   (no product: bit a of c2 selects).  g_dev, p_dev [m + 1][count]: row j < m for bit i = m - 1 - j, (g, p) = (1 - b_i, b_i) where
+ *   bit i of c is set and (0, 1 - b_i) where it is not; row m the low carry (1, 0).
+ * One level of the carry tree, (g1, p1) o (g2, p2) = (g1 + p1 g2, p1 p2) on adjacent rows 2j, 2j + 1 of `nodes` rows; an odd last row
+ *   moves up unchanged.  Node j spends triples 2j (p1 g2) and 2j + 1 (p1 p2) of the level: ta_dev, tb_dev, tab_dev hold this party's
+ *   shares of the first factors, second factors and products, one row a triple.  root != 0 (nodes must be 2): only g is wanted,
+ *   one triple.
+ *   hb_fxp_carry_mask     masked_dev rows 2t, 2t + 1 = p1 - ta[t], (t even: g2, t odd: p2) - tb[t]: the level's ONE array to open
+ *   hb_fxp_carry_combine  opened_dev = that array opened; g_out_dev, p_out_dev [ceil(nodes / 2)][count] (root: g_out_dev [count],
+ *                         p_out_dev ignored).  The outputs are arrays of their own.  nodes < 2: HB_ERR_BAD_ARG.
+ * hb_fxp_div2m_finish: u = 1 - carry, a2 = (c mod 2^m) - r1 + 2^m u.  mode HB_FXP_MOD: out = a2 = [x mod 2^m] (x_dev may be NULL);
+ *   HB_FXP_TRUNC: out = (x - a2) 2^(-m); HB_FXP_NEG_TRUNC: its negation (ltz for m = k - 1).  out_dev may be any input array.
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: null pointers (with
+ * count > 0), a negative count, parameters out of range.  count == 0 returns HB_OK and launches nothing. */
+#define HB_FXP_MOD 0
+#define HB_FXP_TRUNC 1
+#define HB_FXP_NEG_TRUNC 2
+int hb_fxp_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *bits_dev, int k, int m, int kappa, uint64_t *masked_dev,
+                uint64_t *r1_dev, int64_t count, void *stream);
+int hb_fxp_trunc_pr(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, int m, const uint64_t *inv2m_host,
+                    uint64_t *out_dev, int64_t count, void *stream);
+int hb_fxp_ltl_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int m, uint64_t *g_dev, uint64_t *p_dev, int64_t count,
+                      void *stream);
+int hb_fxp_carry_mask(hb_ctx *ctx, const uint64_t *g_dev, const uint64_t *p_dev, int nodes, int root, const uint64_t *ta_dev,
+                      const uint64_t *tb_dev, uint64_t *masked_dev, int64_t count, void *stream);
+int hb_fxp_carry_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *g_dev, const uint64_t *p_dev, int nodes, int root,
+                         const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev, uint64_t *g_out_dev, uint64_t *p_out_dev,
+                         int64_t count, void *stream);
+int hb_fxp_div2m_finish(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, const uint64_t *carry_dev, int m,
+                        const uint64_t *inv2m_host, int mode, uint64_t *out_dev, int64_t count, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip)-------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -572,6 +615,22 @@ int hb_selftest_mimc(const uint64_t *p_limbs, int n_limbs, int what, const uint6
 #define HB_JJ_SELFTEST_SCALE 6
 int hb_selftest_jj(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const uint64_t *a, const uint64_t *d,
                    int flags, int64_t arg, uint64_t *out, int64_t count);
+/* host-side run of the fixed-point kernels' bodies (no GPU needed) over host memory, element by element.  params = {k, m, kappa,
+ * nodes or mode, root}; parameters are checked as the device calls check them:
+ *   what = HB_FXP_SELFTEST_MASK     operands[0..1] = x (or NULL), bits [k + kappa][count]; outs[0..1] as hb_fxp_mask writes masked_dev, r1_dev
+ *          HB_FXP_SELFTEST_TRUNC_PR operands[0..3] = x, c, r1, inv2m (one element); outs[0]
+ *          HB_FXP_SELFTEST_LEAVES   operands[0..1] = c, bits [m][count]; outs[0..1] = g, p [m + 1][count]
+ *          HB_FXP_SELFTEST_CARRY_MASK     operands[0..3] = g, p, ta, tb; outs[0] as hb_fxp_carry_mask writes masked_dev
+ *          HB_FXP_SELFTEST_CARRY_COMBINE  operands[0..5] = opened, g, p, ta, tb, tab; outs[0..1] = g_out, p_out (root: outs[1] unused)
+ *          HB_FXP_SELFTEST_FINISH   operands[0..4] = x (NULL with HB_FXP_MOD), c, r1, carry, inv2m; params[3] = mode; outs[0] */
+#define HB_FXP_SELFTEST_MASK 0
+#define HB_FXP_SELFTEST_TRUNC_PR 1
+#define HB_FXP_SELFTEST_LEAVES 2
+#define HB_FXP_SELFTEST_CARRY_MASK 3
+#define HB_FXP_SELFTEST_CARRY_COMBINE 4
+#define HB_FXP_SELFTEST_FINISH 5
+int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                    uint64_t *const *outs, int64_t count);
 
 #ifdef __cplusplus
 }
