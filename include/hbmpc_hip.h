@@ -300,6 +300,40 @@ int hb_fxp_carry_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t
 int hb_fxp_div2m_finish(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, const uint64_t *carry_dev, int m,
                         const uint64_t *inv2m_host, int mode, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- equality of shared values (hb_eq.hip) ---------------------------------------------------------------------------------
+ * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
+ * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
+ * `count` elements, row j holding test bit j's value of every element; arrays of several rows are row-major.  Test bit j opens
+ * c = diff r + _b rp^2 with _b = nr - (nr - 1) b, nr a public quadratic non-residue (that it is one is the caller's business), and its
+ * factor is affine in [b] with coefficients chosen by L = legendre(c).
+ * hb_legendre: out_dev[i] = legendre(a_i) in {-1, 0, 1}, one int8 an element: a^((p-1)/2) by a sliding-window chain whose schedule
+ *   is derived from p on the host and is the same for every lane.  A zero element gives 0 without running the chain.
+ * hb_eq_mask1: diff = x - y (y_dev == NULL: diff = x).  masked_dev [4][rows][count] = diff - pa, r - qa, rp - pb, rp - qb: the ONE
+ *   array to open before the products diff r (triple a) and rp rp (triple b).  masked_dev is an array of its own.
+ * hb_eq_mid: opened_dev = that array opened.  dr_dev [rows][count] = [diff r], masked2_dev [2][rows][count] = _b - pc, [rp^2] - qc:
+ *   the array to open before the product _b rp^2 (triple c).  nr_host: ONE canonical element in host memory (0, 1 or not below the
+ *   modulus: HB_ERR_BAD_ARG).  The outputs are arrays of their own.
+ * hb_eq_cshare: opened2_dev = masked2 opened.  c_dev [rows][count] = [diff r] + [_b rp^2], the third array to open; c_dev may be dr_dev.
+ * hb_eq_finish: c_dev = that array opened.  factor_dev [rows][count]:
+ *   HB_EQ_BIT        (1 - L) / 2 + L [b]: a share of 1 (the bit agrees with "equal") or 0; nr_host is not read
+ *   HB_EQ_REFERENCE  L (nr + L) / 2 - (L (nr - 1) / 2) [b]: the reference's (L / 2) (_b + L)
+ *   c = 0 (L = 0): the factor written is 0 and zero_rows_dev[row] = 1; rows without a zero are not written, so the caller zeroes
+ *   zero_rows_dev [rows] (int32) first.  factor_dev may be c_dev or bits_dev.
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  1 <= rows <= 4096.  HB_ERR_BAD_ARG before any launch:
+ * null pointers (with count > 0), a negative count, parameters out of range.  count == 0 launches nothing. */
+#define HB_EQ_BIT 0
+#define HB_EQ_REFERENCE 1
+int hb_legendre(hb_ctx *ctx, const uint64_t *a_dev, int8_t *out_dev, int64_t count, void *stream);
+int hb_eq_mask1(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *r_dev, const uint64_t *rp_dev, const uint64_t *pa_dev,
+                const uint64_t *qa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev, uint64_t *masked_dev, int rows, int64_t count, void *stream);
+int hb_eq_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *pa_dev, const uint64_t *qa_dev, const uint64_t *pqa_dev, const uint64_t *pb_dev,
+              const uint64_t *qb_dev, const uint64_t *pqb_dev, const uint64_t *bits_dev, const uint64_t *pc_dev, const uint64_t *qc_dev,
+              const uint64_t *nr_host, uint64_t *masked2_dev, uint64_t *dr_dev, int rows, int64_t count, void *stream);
+int hb_eq_cshare(hb_ctx *ctx, const uint64_t *opened2_dev, const uint64_t *dr_dev, const uint64_t *pc_dev, const uint64_t *qc_dev,
+                 const uint64_t *pqc_dev, uint64_t *c_dev, int rows, int64_t count, void *stream);
+int hb_eq_finish(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int mode, const uint64_t *nr_host, uint64_t *factor_dev,
+                 int32_t *zero_rows_dev, int rows, int64_t count, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip)-------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -631,6 +665,20 @@ int hb_selftest_jj(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_FXP_SELFTEST_FINISH 5
 int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                     uint64_t *const *outs, int64_t count);
+/* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
+ *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
+ *          HB_EQ_SELFTEST_MASK1     operands[0..7] = x, y (or NULL), r, rp, pa, qa, pb, qb; outs[0] as hb_eq_mask1 writes masked_dev
+ *          HB_EQ_SELFTEST_MID       operands[0..10] = opened, pa, qa, pqa, pb, qb, pqb, bits, pc, qc, nr (one element); outs[0..1] = masked2, dr
+ *          HB_EQ_SELFTEST_CSHARE    operands[0..4] = opened2, dr, pc, qc, pqc; outs[0] = c
+ *          HB_EQ_SELFTEST_FINISH    operands[0..2] = c, bits, nr (one element; may be NULL with HB_EQ_BIT); outs[0] = factor,
+ *                                   outs[1] = zero_rows, int32 [rows], zeroed by the caller */
+#define HB_EQ_SELFTEST_LEGENDRE 0
+#define HB_EQ_SELFTEST_MASK1 1
+#define HB_EQ_SELFTEST_MID 2
+#define HB_EQ_SELFTEST_CSHARE 3
+#define HB_EQ_SELFTEST_FINISH 4
+int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, void *const *outs,
+                   int64_t count);
 
 #ifdef __cplusplus
 }
