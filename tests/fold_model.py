@@ -31,7 +31,8 @@ def tables(p):
     btot = sum((1 << 20) << (8 * e) for e in range(32))
     return s, mu, c512, btot, tsum
 
-def reduce_model(S, CRorig, p, tb):
+def reduce_model(S, CRorig, p, tb, facts=None):
+    """facts, when given, collects which quotient branch ran ("exact": q == R // p, "under": q == R // p - 1) and the values of `top`"""
     s, mu, c512, btot, tsum = tb
     assert S < 1 << 527
     K2 = (128 * tsum - btot) % p
@@ -64,6 +65,9 @@ def reduce_model(S, CRorig, p, tb):
     assert 0 <= r < 2 * p
     top = (rp >> 256) - q
     assert top in (0, 1) and top == r >> 256
+    if facts is not None:
+        facts.add("exact" if q == R // p else "under")
+        facts.add("top%d" % top)
     if r >= p:
         r -= p
     assert r == (S + CRorig) % p
@@ -89,7 +93,7 @@ def run_wide(iterations, seed=1):
             reduce_model(S, rng.randrange(p), p, tb)
 
 
-def mm8_model(cols, CRorig, p, rng):
+def mm8_model(cols, CRorig, p, rng, facts=None):
     """k_mm8's epilogue (hb_mfma.hip, round 3): 47 non-negative columns < 2 * 5.8e6; the low eight G_k go into P_w as they are, the
     high four make the exact words H (one byte half of the fold table), the word above H times 2^384 mod p."""
     assert len(cols) == 47 and all(0 <= c < 2 * 5800000 for c in cols)
@@ -147,9 +151,13 @@ def mm8_model(cols, CRorig, p, rng):
     rp = sum(u[w] << (32 * w) for w in range(8))
     r = rp - (q << 256)
     assert 0 <= r < 2 * p and (rp >> 256) - q in (0, 1)
+    if facts is not None:
+        facts.add("exact" if q == R // p else "under")
+        facts.add("top%d" % ((rp >> 256) - q))
     if r >= p:
         r -= p
     assert r == (S + CRorig) % p
+    return r
 
 
 def run_mm8(iterations, seed=2):

@@ -153,6 +153,26 @@ def test_switch_elements_on_the_host(p, nl):
         assert rc == 0 and got == switch_ref(p, xs, d, e, ps, qs, pqs, k, a), a
 
 
+@pytest.mark.parametrize("p, nl", PRIMES, ids=IDS)
+def test_bodies_at_edge_values(p, nl):
+    """every operand a value on the edges of the words, the digits and the int8 split, or the Montgomery pre-image of one
+    (tests/edge_values.py): each list walks the pool at its own stride; 128 switches"""
+    import edge_values
+
+    vs = edge_values.operands(p, nl)
+    m, half = len(vs), 128
+    k = 2 * half
+    xs = [vs[(3 * i + 1) % m] for i in range(k)]
+    d, e, ps, qs, pqs = ([vs[(i * s + s) % m] for i in range(half)] for s in (5, 7, 11, 13, 17))
+    rc, got = run(p, nl, HALVE, [vs], m, 0, m)
+    assert rc == 0 and got == [v * pow(2, -1, p) % p for v in vs]
+    for a in (0, 3, 7):
+        rc, got = run(p, nl, MASK, [xs, d, ps, qs], k, a, k)
+        assert rc == 0 and got == mask_ref(p, xs, d, ps, qs, k, a), a
+        rc, got = run(p, nl, SWITCH, [xs, d, e, ps, qs, pqs], k, a, k)
+        assert rc == 0 and got == switch_ref(p, xs, d, e, ps, qs, pqs, k, a), a
+
+
 @pytest.mark.parametrize("p, nl", [(2**256 - 189, 4), (2**64 - 59, 1)], ids=["2^256-189", "2^64-59"])
 def test_switch_halves_every_parity_corner(p, nl):
     """cleartext triple (p = q = pq = 0, d = b, e = x - y): the sums x + y +- m that are halved run over 0, 1, 2, p - 1, p - 2

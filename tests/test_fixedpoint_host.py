@@ -187,6 +187,35 @@ def test_mask_body(p, nl):
 
 
 @pytest.mark.parametrize("p, nl", FIELDS, ids=FIELD_IDS)
+def test_mask_trunc_and_finish_bodies_at_edge_values(p, nl):
+    """the planes, x, c, r1 and the carry values on the edges of the words, the digits and the int8 split, or Montgomery pre-images of
+    such (tests/edge_values.py): each plane and operand walks the list at a stride of its own"""
+    import edge_values
+
+    vs = edge_values.operands(p, nl)
+    count = len(vs)
+    walk = lambda s: [vs[(i * s + s) % count] for i in range(count)]    # noqa: E731
+    for k, m, kappa in shapes_for(p):
+        n = k + kappa
+        planes = [walk(2 * j + 1) for j in range(n)]
+        xs = walk(2 * n + 1)
+        r1 = [sum(planes[i][e] << i for i in range(m)) % p for e in range(count)]
+        r2 = [sum(planes[m + i][e] << i for i in range(n - m)) % p for e in range(count)]
+        rc, (masked, got_r1) = run(p, nl, MASK, [xs, [v for row in planes for v in row]], [k, m, kappa], [1, 1], count)
+        assert rc == 0 and got_r1 == r1 and masked == [(x + (1 << (k - 1)) + a + (b << m)) % p for x, a, b in zip(xs, r1, r2)], (k, m, kappa)
+    x, c, r1, carry = walk(3), walk(5), walk(7), walk(11)
+    for m in (1, 29, 32, 58) + ((64, 128, 253) if nl == 4 else ()):
+        inv = pow(2, -m, p)
+        rc, (got,) = run(p, nl, TRUNC_PR, [x, c, r1, [inv]], [0, m], [1], count)
+        assert rc == 0 and got == [(a - b % (1 << m) + d) * inv % p for a, b, d in zip(x, c, r1)], m
+        for mode in (fx.MOD, fx.TRUNC, fx.NEG_TRUNC):
+            a2 = [(b % (1 << m) - d + (1 << m) * (1 - e)) % p for b, d, e in zip(c, r1, carry)]
+            want = a2 if mode == fx.MOD else [(a - v) * inv * (1 if mode == fx.TRUNC else -1) % p for a, v in zip(x, a2)]
+            rc, (got,) = run(p, nl, FINISH, [None if mode == fx.MOD else x, c, r1, carry, [inv]], [0, m, 0, mode], [1], count)
+            assert rc == 0 and got == want, (m, mode)
+
+
+@pytest.mark.parametrize("p, nl", FIELDS, ids=FIELD_IDS)
 def test_trunc_pr_leaf_and_finish_bodies(p, nl):
     rnd = random.Random(p % 1000 + 5)
     ms = [1, 8, 15, 29, 31, 32, 33, 58, 62] + ([63, 64, 65, 100, 127, 128, 129, 191, 193, 253] if nl == 4 else [])

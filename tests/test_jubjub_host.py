@@ -355,6 +355,36 @@ def test_stage_bodies_every_corner(p, nl):
     assert rc == 0 and out == [[a * b % p for a, b in zip(ri, ru)] for ri, ru in zip(inv, uv)]
 
 
+@pytest.mark.parametrize("p, nl", PRIMES, ids=IDS)
+def test_stage_bodies_at_edge_values(p, nl):
+    """every operand of every stage a value on the edges of the words, the digits and the int8 split, or the Montgomery pre-image of one
+    (tests/edge_values.py): each operand row walks the list at a stride of its own, so the Beaver steps meet them in varying pairs"""
+    import edge_values
+
+    vs = edge_values.operands(p, nl)
+    m = len(vs)
+    strides = iter(range(1, 200, 2))
+    walk = lambda: (lambda s: [vs[(i * s + s) % m] for i in range(m)])(next(strides))    # noqa: E731
+    x1, y1, x2, y2, rx, ry = (walk() for _ in range(6))
+    tp, tq, tpq = ([walk() for _ in range(9)] for _ in range(3))
+    at = lambda rows, i: [r[i] for r in rows]    # noqa: E731
+    rc, A = run(p, nl, MASK, [x1, y1, x2, y2, flat(tp), flat(tq)], m, 8, arg=m)
+    assert rc == 0 and cols(A) == [mask_ref(p, x1[i], y1[i], x2[i], y2[i], at(tp, i), at(tq, i)) for i in range(m)]
+    A = [walk() for _ in range(8)]
+    rc, B = run(p, nl, STAGE1, [flat(A), flat(tp), flat(tq), flat(tpq), rx, ry], m, 6, arg=m)
+    assert rc == 0 and cols(B) == [stage1_ref(p, at(A, i), at(tp, i), at(tq, i), at(tpq, i), rx[i], ry[i]) for i in range(m)]
+    B = [walk() for _ in range(6)]
+    for d in (p - 1, vs[m // 2]):
+        rc, uvC = run(p, nl, STAGE2, [flat(B), flat(tp), flat(tq), flat(tpq), rx, ry], m, 6, d=d, arg=m)
+        assert rc == 0 and cols(uvC) == [stage2_ref(p, at(B, i), at(tp, i), at(tq, i), at(tpq, i), rx[i], ry[i], d) for i in range(m)], d
+    C = [walk() for _ in range(4)]
+    rc, D = run(p, nl, STAGE3, [flat(C), flat(tp), flat(tq), flat(tpq)], m, 2, arg=m)
+    assert rc == 0 and cols(D) == [stage3_ref(p, at(C, i), at(tp, i), at(tq, i), at(tpq, i)) for i in range(m)]
+    inv, uv = [walk(), walk()], [walk(), walk()]
+    rc, out = run(p, nl, SCALE, [flat(inv), flat(uv)], m, 2)
+    assert rc == 0 and out == [[a * b % p for a, b in zip(ri, ru)] for ri, ru in zip(inv, uv)]
+
+
 def test_stage_bodies_largest_case():
     p = (1 << 256) - 189
     m = 4

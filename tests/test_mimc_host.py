@@ -148,6 +148,28 @@ def test_round_body_every_corner(p, nl):
     assert rc == 0 and got == [round_ref(p, *tp[:4], tp[5], ctr, tp[4]) for tp in ts]
 
 
+@pytest.mark.parametrize("p, nl", PRIMES, ids=IDS)
+def test_bodies_at_edge_values(p, nl):
+    """every operand a value on the edges of the words, the digits and the int8 split, or the Montgomery pre-image of one
+    (tests/edge_values.py): each list walks the pool at its own stride"""
+    import edge_values
+
+    vs = edge_values.operands(p, nl)
+    m = len(vs)
+    y, r, r2, r3, key, rn = ([vs[(i * s + s) % m] for i in range(m)] for s in (1, 3, 5, 7, 11, 13))
+    for ctr in (0, 160):
+        rc, got = run(p, nl, ROUND, [y, r, r2, r3, key, rn], m, arg=ctr)
+        assert rc == 0 and got == [round_ref(p, *tp[:4], tp[4], ctr, tp[5]) for tp in zip(y, r, r2, r3, key, rn)], ctr
+        rc, got = run(p, nl, ROUND, [y, r, r2, r3, key, None], m, arg=ctr)
+        assert rc == 0 and got == [round_ref(p, *tp[:4], tp[4], ctr, None) for tp in zip(y, r, r2, r3, key)], ctr
+    rounds = mimc.rounds_for(p)
+    for flags in (0, PAIR):
+        rc, got = run(p, nl, PLAIN, [y, key, None], m, arg=rounds, flags=flags)
+        assert rc == 0 and got == [mimc.mimc_plain(x, k, p, rounds) for x, k in zip(y, key)], flags
+    rc, got = run(p, nl, FIRST, [y, key, r], m)
+    assert rc == 0 and got == [(a + b - c) % p for a, b, c in zip(y, key, r)]
+
+
 def test_round_body_largest_case():
     p = (1 << 256) - 189
     m = [p - 1] * 4

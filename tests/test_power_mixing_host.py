@@ -127,6 +127,22 @@ def test_mac_pass_random(p, nl):
         assert rc == 0 and got == [sum(u[c][f] * v[c][f] for c in range(m)) % p for f in range(n)]
 
 
+@pytest.mark.parametrize("p, nl", PRIMES, ids=IDS)
+def test_mac_pass_at_edge_values(p, nl):
+    """the multiply-accumulate pass over values on the edges of the words, the digits and the int8 split, and their Montgomery pre-images
+    (tests/edge_values.py): every ordered pair meets once across the rows, in windows of one, of the accumulation bound and of all rows"""
+    import edge_values
+
+    vs = edge_values.operands(p, nl)
+    m = len(vs)
+    u = [[vs[(c + f) % m] for f in range(m)] for c in range(m)]
+    v = [[vs[(3 * c + 2 * f + 1) % m] for f in range(m)] for c in range(m)]
+    want = [sum(u[c][f] * v[c][f] for c in range(m)) % p for f in range(m)]
+    for group in (1, ACC_LEN[nl], m):
+        rc, got = run(p, nl, MAC, [x for r in u for x in r], v, m, group=group)
+        assert rc == 0 and got == want, group
+
+
 def test_argument_checks_on_the_host():
     for nl in (4, 1):
         assert run(13, nl, SUMS, [1], [[1] * 13], 13)[0] == 2          # k >= p: HB_ERR_BAD_ARG

@@ -197,6 +197,33 @@ def test_selftest_mask1_mid_cshare(p, nl):
 
 
 @pytest.mark.parametrize("p, nl", FIELDS, ids=FIELD_IDS)
+def test_selftest_bodies_at_edge_values(p, nl):
+    """the Legendre symbol of, and the masking / Beaver bodies over, values on the edges of the words, the digits and the int8 split and
+    their Montgomery pre-images (tests/edge_values.py): each list walks the pool at its own stride"""
+    import edge_values
+
+    vs = edge_values.operands(p, nl)
+    n = len(vs)
+    nr = sc.smallest_nonresidue(p)
+    rc, (got,) = run(p, nl, LEGENDRE, [vs], 0, 0, ["i8"], n)
+    assert rc == 0 and got == [sc.legendre_mod_p(v, p) for v in vs]
+    walk = lambda s, k=n: [vs[(i * s + s) % n] for i in range(k)]    # noqa: E731
+    x, y, r, rp, pa, qa, pb, qb = (walk(s) for s in (1, 3, 5, 7, 11, 13, 17, 19))
+    rc, (got,) = run(p, nl, MASK1, [x, y, r, rp, pa, qa, pb, qb], 1, 0, [4], n)
+    assert rc == 0 and got == [(a - b - c) % p for a, b, c in zip(x, y, pa)] + [(a - b) % p for a, b in zip(r, qa)] + \
+        [(a - b) % p for a, b in zip(rp, pb)] + [(a - b) % p for a, b in zip(rp, qb)]
+    opened, pqa, pqb, bits, pc, qc, pqc = walk(23, 4 * n), walk(29), walk(31), walk(37), walk(41), walk(43), walk(47)
+    rc, (m2, dr) = run(p, nl, MID, [opened, pa, qa, pqa, pb, qb, pqb, bits, pc, qc, [nr]], 1, 0, [2, 1], n)
+    o = [opened[k * n:(k + 1) * n] for k in range(4)]
+    want_dr = [beaver(o[0][i], o[1][i], pa[i], qa[i], pqa[i], p) for i in range(n)]
+    rp2 = [beaver(o[2][i], o[3][i], pb[i], qb[i], pqb[i], p) for i in range(n)]
+    assert rc == 0 and dr == want_dr and m2 == [(nr - (nr - 1) * bits[i] - pc[i]) % p for i in range(n)] + [(rp2[i] - qc[i]) % p for i in range(n)]
+    opened2 = walk(53, 2 * n)
+    rc, (c,) = run(p, nl, CSHARE, [opened2, want_dr, pc, qc, pqc], 1, 0, [1], n)
+    assert rc == 0 and c == [(want_dr[i] + beaver(opened2[i], opened2[n + i], pc[i], qc[i], pqc[i], p)) % p for i in range(n)]
+
+
+@pytest.mark.parametrize("p, nl", FIELDS, ids=FIELD_IDS)
 def test_selftest_finish_both_modes(p, nl):
     rnd = random.Random(p % 1031)
     nr = sc.smallest_nonresidue(p)
