@@ -37,6 +37,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "hb_mm8.hpp"
 
@@ -46,6 +47,9 @@ namespace hb {
 
 constexpr int FS_WAVES = 8, FS_TPW = 4;
 #ifdef HB_MM8_TIMING
+// per wave, ticks of s_memtime summed over its units.  Slot 0: kernel entry to the end of the wave's share of the first unit's scaling (the
+// prologue included; once per workgroup); 7: the wait for its LDS writes ahead of a unit's barrier; 1: the barrier; 2: scaling the next
+// unit; 3 / 5: the MFMA halves; 4: parking half 0; 6: words, reduction, store / compare
 __device__ unsigned long long g_fs_t[256 * 8 * 8];
 #define FS_T(k) do { const unsigned long long tn_ = __builtin_amdgcn_s_memtime(); tacc[k] += tn_ - tlast; tlast = tn_; } while (0)
 #else
@@ -95,10 +99,29 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
     int32_t *maskl = rowl + 32;
     v4i *foldl = reinterpret_cast<v4i *>(maskl + 16 * n_rt);
 
-    // ---- prologue: tables, zeroed element buffers (terms d .. 8 NKB - 1 are never written again) ------------------------
-    if (threadIdx.x < 32) {
-        const int lc = (int)threadIdx.x < d ? (int)threadIdx.x : d - 1;
-        rowl[threadIdx.x] = in_rows ? in_rows[lc] : lc;
+#ifdef HB_MM8_TIMING
+    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
+#endif
+    // one scaling task = term l of a unit's 64 chunks: lane = chunk (tile lane >> 4, column lane & 15).  The first unit's tasks run in the
+    // prologue, before any table is in LDS: they take the row of a term from in_rows itself (wave-uniform: a scalar load)
+    auto unit_chunk = [&](int64_t unit) {
+        const int64_t chunk = unit * 64 + lane;
+        return chunk >= n_chunks ? n_chunks - 1 : chunk;          // (results of padding chunks are never stored or compared)
+    };
+    auto fetch_row = [&](int64_t chunk, int row, uint32_t (&w)[NW], bool &okk) {
+        const int64_t idx = chunk * in_sc + (int64_t)row * in_sl;
+        okk = idx < in_count;
+        load_words<NW>(w, in_pk + (okk ? idx : 0) * NW);
+    };
+    // ---- prologue: the first unit's first loads, tables, zeros for the terms d .. 8 NKB - 1 (never written again) ---------
+    // every wave takes its share of the first unit (terms wave, wave + 8, wave + 16): the loads of its first term are issued ahead of the
+    // tables' copy and return under it
+    const uint32_t first_terms = (0x01010101u << wave) & (d < 32 ? (1u << d) - 1u : ~0u);
+    uint32_t x_first[NW] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool ok_first = false;
+    if (first_terms) {
+        const int l0 = __builtin_ctz(first_terms);
+        fetch_row(unit_chunk(blockIdx.x), in_rows ? in_rows[l0] : l0, x_first, ok_first);
     }
     // the rows of the compared senders were built per PARTY when the first d arrivals were known (k_fs_cand); which of them this launch
     // compares, and in which row, is only known now: their digit pieces and row constants are FETCHED here, ahead of the tables' copy (two
@@ -113,58 +136,69 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         pk_piece = pick.cand[(size_t)pick.zc[j] * (NKB * 8) + pc];
     }
     if (pk_has_crow) pk_crow = reinterpret_cast<const uint4 *>(pick.cand_crow)[(size_t)pick.zc[pk_e >> 2] * 4 + (pk_e & 3)];
-    for (int i = threadIdx.x; i < n_rt * 16; i += NT) maskl[i] = i < n_out ? rowmode[i] : 0;
-    for (int i = threadIdx.x; i < n_rt * 64; i += NT) fs_lds[i] = reinterpret_cast<const uint4 *>(crowd)[i];
-    for (int i = threadIdx.x; i < n_rt * NKB * 2 * 64; i += NT) abuf[i] = a8[i];
-    for (int i = threadIdx.x; i < 2 * bufsz; i += NT) xbuf[i] = make_uint4(0, 0, 0, 0);
-    if (threadIdx.x < MM8_FOLD_Q) foldl[threadIdx.x] = foldg[threadIdx.x];
-    if (pick.cand) {
-        __syncthreads();
-        auto put = [&](int e, const uint4 &v) {
-            const int j = e / (NKB * 8), pc = e - j * (NKB * 8);
-            const int ri = pick.n_coef + j, rt = ri >> 4, r16 = ri & 15, r = 4 * (r16 & 3) + (r16 >> 2);
-            const int kb = pc >> 3, grp = (pc >> 2) & 1, gg = pc & 3;
-            reinterpret_cast<uint4 *>(abuf)[((rt * NKB + kb) * 2 + grp) * 64 + r + 16 * gg] = v;
-        };
-        if (pk_has_piece) put(pk_e, pk_piece);
-        for (int e = pk_e + NT; e < pick.nc * NKB * 8; e += NT) {
-            const int j = e / (NKB * 8), pc = e - j * (NKB * 8);
-            put(e, pick.cand[(size_t)pick.zc[j] * (NKB * 8) + pc]);
-        }
-        if (pk_has_crow) fs_lds[(pick.n_coef + (pk_e >> 2)) * 4 + (pk_e & 3)] = pk_crow;
-        for (int j = threadIdx.x; j < pick.nc; j += NT) maskl[pick.n_coef + j] = (int32_t)pick.zc[j] + 1;
+    // the tables.  Every load of a thread is in flight before its first word is written to LDS (addresses clamped, so that no load stands
+    // under a branch; the image three pieces a thread at a time: config 3's 1152 pieces are one round) -- a copy loop of load, wait, write
+    // pays the loads' latency once per trip, and one table after the other
+    {
+        const int tid = threadIdx.x, n_mask = n_rt * 16, n_crow = n_rt * 64, n_img = n_rt * NKB * 2 * 64;
+        const int lc = tid < d ? tid : d - 1;
+        int32_t rw = in_rows ? in_rows[lc] : lc;
+        int32_t mk = rowmode[tid < n_out ? tid : 0];
+        v4i cr = reinterpret_cast<const v4i *>(crowd)[tid < n_crow ? tid : 0];
+        v4i fo = foldg[tid < MM8_FOLD_Q ? tid : 0];
+        v4i img[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) img[k] = reinterpret_cast<const v4i *>(a8)[tid + k * NT < n_img ? tid + k * NT : 0];
+        // (the words are wanted HERE: hipcc otherwise sinks each load into the branch of its write, one wait per load again)
+        asm volatile("" : "+v"(rw), "+v"(mk), "+v"(cr), "+v"(fo), "+v"(img[0]), "+v"(img[1]), "+v"(img[2]));
+        if (tid < 32) rowl[tid] = rw;
+        if (tid < n_mask) maskl[tid] = tid < n_out ? mk : 0;
+        if (tid < n_crow) reinterpret_cast<v4i *>(fs_lds)[tid] = cr;
+        if (tid < MM8_FOLD_Q) foldl[tid] = fo;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            if (tid + k * NT < n_img) reinterpret_cast<v4i *>(abuf)[tid + k * NT] = img[k];
+        // (what a larger launch has beyond one round)
+        for (int i = tid + NT; i < n_mask; i += NT) maskl[i] = i < n_out ? rowmode[i] : 0;
+        for (int i = tid + NT; i < n_crow; i += NT) fs_lds[i] = reinterpret_cast<const uint4 *>(crowd)[i];
+        for (int i = tid + 3 * NT; i < n_img; i += NT) abuf[i] = a8[i];
     }
-    __syncthreads();
-
+    // the slots [buffer][tile][half][column] of a padding term, 256 in all: no scaling task ever writes them, and they are all that is
+    // zeroed -- every other slot is written by the unit's scaling tasks before a pass reads it
+    for (int i = threadIdx.x; i < (8 * NKB - d) * 256; i += NT) {
+        const int l = d + (i >> 8), b = (i >> 7) & 1, t = (i >> 5) & 3, h = (i >> 4) & 1, c = i & 15;
+        const int kb = l >> 3, gg = (l & 7) >> 1, e = l & 1;
+        xbuf[(size_t)b * bufsz + (size_t)((((t * NKB + kb) * 2 + e) * 2 + h) * 64) + (c + 16 * gg)] = make_uint4(0, 0, 0, 0);
+    }
     // (tile, row tile) pairs of a unit: wave w takes w, w + 8, ...; which terms of the next unit a wave scales beside its passes: split.terms
     const int n_pairs = FS_TPW * n_rt;
     const uint32_t my_terms = (uint32_t)__builtin_amdgcn_readfirstlane((int)split.terms[wave]);
 
-    // one task = term l of the unit's 64 chunks: lane = chunk (tile lane >> 4, column lane & 15); T_q of this term wave-uniform
-    auto scale_unit = [&](int64_t unit, uint4 *dst, uint32_t terms) {
-        int64_t chunk = unit * 64 + lane;
-        if (chunk >= n_chunks) chunk = n_chunks - 1;              // (results of padding chunks are never stored or compared)
+    // T_q of a task's term is wave-uniform (scalar loads).  first: the prologue's call -- its first term's words are already in registers
+    // (x_first), and rowl is not in LDS yet
+    auto scale_unit = [&](auto first, int64_t unit, uint4 *dst, uint32_t terms) {
+        constexpr bool FIRST = decltype(first)::value;
+        const int64_t chunk = unit_chunk(unit);
         const int t = lane >> 4;
         uint32_t xw[NW];
         bool ok = false;
-        auto fetch = [&](int l, uint32_t (&w)[NW], bool &okk) {
-            const int64_t idx = chunk * in_sc + (int64_t)rowl[l] * in_sl;
-            okk = idx < in_count;
-            load_words<NW>(w, in_pk + (okk ? idx : 0) * NW);
-        };
+        auto fetch = [&](int l, uint32_t (&w)[NW], bool &okk) { fetch_row(chunk, FIRST ? (in_rows ? in_rows[l] : l) : rowl[l], w, okk); };
         terms &= d < 32 ? (1u << d) - 1u : ~0u;
         int l = terms ? __builtin_ctz(terms) : d;
-        if (l < d) fetch(l, xw, ok);
+        if constexpr (FIRST) {
+#pragma unroll
+            for (int k = 0; k < NW; k++) xw[k] = x_first[k];
+            ok = ok_first;
+        } else if (l < d) fetch(l, xw, ok);
         while (l < d) {
             terms &= terms - 1u;
             const int ln = terms ? __builtin_ctz(terms) : d;
+            // the next term's words, in flight under this term's arithmetic.  Unconditional: hipcc waits for a load issued under a branch
+            // where the branch joins -- here, ahead of this term's arithmetic, with the whole latency exposed once per task -- so the last
+            // task loads its own words again (a cache hit that nobody reads)
             uint32_t xn[NW];
             bool okn = false;
-            if (ln < d) fetch(ln, xn, okn);
-            else {
-#pragma unroll
-                for (int k = 0; k < NW; k++) xn[k] = 0;
-            }
+            fetch(ln < d ? ln : l, xn, okn);
             const uint32_t *__restrict__ T = KT + (size_t)l * (NL * NL);
             uint32_t xd[NL];
             unpack<NL, NW>(xd, xw);
@@ -221,6 +255,26 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         }
     };
 
+    // the first unit: every wave scales its share into buffer 0.  Nothing it touches depends on the tables (the padding slots are other
+    // slots), so no barrier stands between the copy and this: the loop's first barrier covers both
+    scale_unit(std::true_type{}, blockIdx.x, xbuf, first_terms);
+    if (pick.cand) {
+        __syncthreads();      // (the image's copy is in LDS: the picked rows go over its empty rows)
+        auto put = [&](int e, const uint4 &v) {
+            const int j = e / (NKB * 8), pc = e - j * (NKB * 8);
+            const int ri = pick.n_coef + j, rt = ri >> 4, r16 = ri & 15, r = 4 * (r16 & 3) + (r16 >> 2);
+            const int kb = pc >> 3, grp = (pc >> 2) & 1, gg = pc & 3;
+            reinterpret_cast<uint4 *>(abuf)[((rt * NKB + kb) * 2 + grp) * 64 + r + 16 * gg] = v;
+        };
+        if (pk_has_piece) put(pk_e, pk_piece);
+        for (int e = pk_e + NT; e < pick.nc * NKB * 8; e += NT) {
+            const int j = e / (NKB * 8), pc = e - j * (NKB * 8);
+            put(e, pick.cand[(size_t)pick.zc[j] * (NKB * 8) + pc]);
+        }
+        if (pk_has_crow) fs_lds[(pick.n_coef + (pk_e >> 2)) * 4 + (pk_e & 3)] = pk_crow;
+        for (int j = threadIdx.x; j < pick.nc; j += NT) maskl[pick.n_coef + j] = (int32_t)pick.zc[j] + 1;
+    }
+
     const v4i biasv = v4i{MM8_BIAS, MM8_BIAS, MM8_BIAS, MM8_BIAS};
     uint32_t k256 = 256u, k16m = 1u << 24;      // opaque, so that the word assembly stays two v_mad_u64_u32 per word
     int32_t s1 = 1, s256 = 256, s64k = 1 << 16, s16m = 1 << 24;   // and the gathering of the fold's columns one v_mad_i64_i32 each
@@ -231,10 +285,6 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 
     int buf = 0;
     int64_t unit = blockIdx.x;
-#ifdef HB_MM8_TIMING
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-#endif
-    if (unit < n_units) scale_unit(unit, xbuf, 0x01010101u << wave);  // the first unit: every wave takes its share
     FS_T(0);
     for (; unit < n_units; unit += gridDim.x, buf ^= 1) {
         // every wave's share of this unit's elements is in LDS, and nobody reads the other buffer any more
@@ -242,7 +292,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         FS_T(7);
         __builtin_amdgcn_s_barrier();
         FS_T(1);
-        if (my_terms && unit + gridDim.x < n_units) scale_unit(unit + gridDim.x, xbuf + (size_t)(buf ^ 1) * bufsz, my_terms);
+        if (my_terms && unit + gridDim.x < n_units) scale_unit(std::false_type{}, unit + gridDim.x, xbuf + (size_t)(buf ^ 1) * bufsz, my_terms);
         FS_T(2);
         for (int pidx = wave; pidx < n_pairs; pidx += FS_WAVES) {
             // two row tiles: the waves of one SIMD (w and w + 4) get one of each, so the ragged second tile's shorter passes spread evenly
