@@ -36,6 +36,8 @@ HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
 HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
 HB_EQ_BIT, HB_EQ_REFERENCE = 0, 1
 HB_EQ_SELFTEST_LEGENDRE, HB_EQ_SELFTEST_MASK1, HB_EQ_SELFTEST_MID, HB_EQ_SELFTEST_CSHARE, HB_EQ_SELFTEST_FINISH = 0, 1, 2, 3, 4
+HB_RF_MAX_K, HB_RF_SMALL_DEGREE = 1024, 32
+HB_RF_SELFTEST_NEWTON, HB_RF_SELFTEST_STEP, HB_RF_SELFTEST_GCD, HB_RF_SELFTEST_SHIFT, HB_RF_SELFTEST_ROOTS = 0, 1, 2, 3, 4
 
 _STATUS_NAMES = {
     1: "HB_ERR_SINGULAR",
@@ -84,6 +86,8 @@ SYMBOLS = {
     "hb_ew_inv": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "hb_pm_power_sums": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp]),
     "hb_pm_powers": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "hb_rf_newton": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "hb_rf_roots": (_i, [_vp, _vp, _i, ctypes.c_uint64, _vp, _vp, _vp]),
     "hb_bf_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "hb_bf_switch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "hb_mimc_plain": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i64, _vp]),
@@ -165,6 +169,7 @@ SYMBOLS = {
     "hb_selftest_jj": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_eq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
+    "hb_selftest_rf": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
 }
 # include/hbmpc_hip_debug.h: diagnostics for scratch/ scripts and white-box tests, not part of the drop-in surface
 DEBUG_SYMBOLS = {
@@ -173,6 +178,8 @@ DEBUG_SYMBOLS = {
     "hb_debug_occupancy": (_i, [_i, _i, _vp, _vp]),
     "hb_debug_reload_env": (None, []),
     "hb_debug_pm_slab_bytes": (None, [_i64]),
+    "hb_debug_rf_stats": (None, [_vp]),
+    "hb_debug_rf_profile": (None, [_i]),
 }
 
 _lib = None

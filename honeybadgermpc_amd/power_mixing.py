@@ -21,7 +21,8 @@ messages -- the shuffle: nobody learns which client sent which.
 triangular convolution, any prime above k), "ntt" (transforms of order N = the power of two above 2k; needs N | p - 1), "auto"
 (the library's crossover between the two).  Everything runs on torch's current stream and nothing synchronises, except that the
 first call for a given k builds the factorial tables.  Finding the roots of the polynomial (the reference's FLINT solver,
-apps/asynchromix/solver/solver.cpp) is not part of this package.
+apps/asynchromix/solver/solver.cpp) is honeybadgermpc_amd.solver: solver.solve takes the opened sums to the messages, solver.mix
+runs power_mix and solve; newton_coefficients below is the host model of its first step.
 """
 from ._capi import HB_ERR_UNSUPPORTED, HB_PM_AUTO, HB_PM_DIRECT, HB_PM_NTT, np_ptr
 from .field import GF

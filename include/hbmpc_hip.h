@@ -171,6 +171,26 @@ int hb_pm_power_sums(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *powers_
                      const uint64_t *omega_host, int order, uint64_t *sums_dev, void *stream);
 int hb_pm_powers(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *powers_dev, int64_t M, int k, uint64_t *out_dev, void *stream);
 
+/* ---- root finding: power sums -> messages (hb_rf.hip) ---------------------------------------------------------------
+ * Replaces apps/asynchromix/solver/solver.py:20 solve() and the FLINT program behind it (apps/asynchromix/solver/solver.cpp).
+ * hb_rf_newton: sums_dev [k] = S_1 .. S_k -> coeffs_dev [k + 1], the monic polynomial with those power sums (coefficient of x^i at
+ * i) by Newton's identities: one workgroup, k dependent steps in one launch; asynchronous on `stream`.
+ * hb_rf_roots: coeffs_dev [k + 1], monic -> roots_dev [k], the roots with multiplicity in the order found, *n_roots_host = k; or
+ * *n_roots_host = -1 (and HB_OK) when the polynomial is not a product of k linear factors -- decided, not assumed: see hb_rf.hip.
+ * `seed` chooses the random shifts of the equal-degree splitting (a counter-based generator on (seed, level, node, draw)); the set
+ * of roots does not depend on it.  THIS CALL OWNS THE LEVEL LOOP AND SYNCHRONISES `stream` ONCE A LEVEL of the split tree, and once
+ * for each multiplicity, to read the degrees of the factors -- some 10 + the largest multiplicity waits at k = 1024 -- and once
+ * before it returns: the roots are complete when it does.  A node that no shift splits in 64 draws gives HB_ERR_HIP (probability
+ * 2^-64 a node for p > 64; cannot happen below, where every shift is tried).
+ * k < 1, k >= p, null pointers: HB_ERR_BAD_ARG; k > HB_RF_MAX_K: HB_ERR_UNSUPPORTED (a GCD keeps both remainders, 2 (k + 1)
+ * coefficients of 36 bytes, in one compute unit's LDS: 74 KB at 1024, two workgroups a unit).  Temporaries (the k x k reduction
+ * table is the largest: 38 MB at k = 1024) are kept with the context per stream and returned by hb_ctx_cache_clear. */
+#define HB_RF_MAX_K 1024
+/* nodes of the split tree at or below this degree run their whole chain in one launch of one workgroup each */
+#define HB_RF_SMALL_DEGREE 32
+int hb_rf_newton(hb_ctx *ctx, const uint64_t *sums_dev, int k, uint64_t *coeffs_dev, void *stream);
+int hb_rf_roots(hb_ctx *ctx, const uint64_t *coeffs_dev, int k, uint64_t seed, uint64_t *roots_dev, int32_t *n_roots_host, void *stream);
+
 /* ---- the butterfly (switching) network (hb_bf.hip) ------------------------------------------------------------------
  * One layer of apps/asynchromix/butterfly_network.py:9-53 (batch_switch and the loops that deal its inputs): k inputs, k a power
  * of two, stride 2^log2_stride, k / 2 switches.  Switch j takes x = in[xi], y = in[yi], xi = ((j >> a) << (a + 1)) | (j & (2^a - 1)),
@@ -679,6 +699,24 @@ int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 #define HB_EQ_SELFTEST_FINISH 4
 int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, void *const *outs,
                    int64_t count);
+/* host-side run of the root-finding kernels' bodies (no GPU needed) over host memory, phase by phase as the kernels' workgroups walk
+ * them.  For tests only: not a fallback.
+ *   what = HB_RF_SELFTEST_NEWTON  operands[0] = sums [k]; params = {k}; out [k + 1] as hb_rf_newton writes coeffs_dev
+ *          HB_RF_SELFTEST_STEP    operands[0..2] = s [d + 1] (monic), h [d], a [1]; params = {d, mul}; out [d] = h^2 (x + a)^mul mod s,
+ *                                 one step of the chain as a node of degree d takes it (table, tiled square and reduction above
+ *                                 HB_RF_SMALL_DEGREE, the one-workgroup step at or below)
+ *          HB_RF_SELFTEST_GCD     operands[0..1] = A [da + 1], B [db + 1], db <= da; params = {da, db}; out [da + 2]: word 0 = the degree,
+ *                                 elements 1 .. the monic gcd
+ *          HB_RF_SELFTEST_SHIFT   params = {seed, level, node, draw}; out [1] = the shift
+ *          HB_RF_SELFTEST_ROOTS   operands[0] = coeffs [k + 1]; params = {k, seed}; out [k + 1]: the first 8 bytes = the number of roots
+ *                                 (-1: not a product of linear factors), elements 1 .. the roots in the order found: the whole level
+ *                                 loop of hb_rf_roots over host memory */
+#define HB_RF_SELFTEST_NEWTON 0
+#define HB_RF_SELFTEST_STEP 1
+#define HB_RF_SELFTEST_GCD 2
+#define HB_RF_SELFTEST_SHIFT 3
+#define HB_RF_SELFTEST_ROOTS 4
+int hb_selftest_rf(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *out);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,12 @@ void hb_debug_reload_env(void);
 /* Cap, in bytes, on the per-slab temporaries of hb_pm_power_sums / hb_pm_powers (hbmpc_hip.h; 256 MiB): a test sets a small one to put
  * a slab boundary inside a small client count.  0 restores the default.  Process-wide. */
 void hb_debug_pm_slab_bytes(int64_t bytes);
+/* What the last hb_rf_roots of the process did: out[0..7] = levels of the split tree, kernel launches, stream synchronisations, rounds of
+ * the repeated-root loop, and -- in profile mode only -- microseconds in the chains, in the GCDs and divisions, and waiting for the
+ * degrees; out[7] = nodes processed over all levels.  Profile mode waits for the stream after every stage so that the time can be
+ * charged to it: for scratch/time_solver.py, not for timing the call as a whole.  Process-wide. */
+void hb_debug_rf_stats(int64_t *out);
+void hb_debug_rf_profile(int on);
 
 
 #ifdef __cplusplus
