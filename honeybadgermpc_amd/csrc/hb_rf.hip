@@ -53,6 +53,7 @@ constexpr int RF_TI = 64;               // outputs of a tile of k_rf_sqr / k_rf_
 constexpr int RF_SPLIT = RF_NT / RF_TI;
 
 static int64_t g_rf_stats[8];           // hb_debug_rf_stats: levels, launches, synchronisations, rounds, us in chains / GCDs / waits, nodes
+                                        // (of the last hb_rf_roots, or of the last HB_RF_SELFTEST_ROOTS: levels, rounds and nodes alone)
 static int g_rf_profile = 0;
 
 // the threads of a workgroup, phase by phase
@@ -970,6 +971,9 @@ int selftest_rf(const uint64_t *p_limbs, int what, const uint64_t *const *ops, c
         int32_t nr = 0;
         memset(out, 0, (size_t)(k + 1) * NW * 4);
         const int rc = run.run((uint64_t)params[1], &nr);
+        // the host walk's counters, for a test that holds them against the device's (no launches, waits or times here)
+        memset(g_rf_stats, 0, sizeof(g_rf_stats));
+        g_rf_stats[0] = run.levels; g_rf_stats[3] = run.rounds; g_rf_stats[7] = run.n_nodes;
         if (rc) return rc;
         const int64_t v = nr;
         memcpy(out, &v, 8);

@@ -710,7 +710,7 @@ int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
  *          HB_RF_SELFTEST_SHIFT   params = {seed, level, node, draw}; out [1] = the shift
  *          HB_RF_SELFTEST_ROOTS   operands[0] = coeffs [k + 1]; params = {k, seed}; out [k + 1]: the first 8 bytes = the number of roots
  *                                 (-1: not a product of linear factors), elements 1 .. the roots in the order found: the whole level
- *                                 loop of hb_rf_roots over host memory */
+ *                                 loop of hb_rf_roots over host memory (its levels, rounds and nodes: hb_debug_rf_stats) */
 #define HB_RF_SELFTEST_NEWTON 0
 #define HB_RF_SELFTEST_STEP 1
 #define HB_RF_SELFTEST_GCD 2

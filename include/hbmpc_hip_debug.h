@@ -29,7 +29,9 @@ void hb_debug_pm_slab_bytes(int64_t bytes);
 /* What the last hb_rf_roots of the process did: out[0..7] = levels of the split tree, kernel launches, stream synchronisations, rounds of
  * the repeated-root loop, and -- in profile mode only -- microseconds in the chains, in the GCDs and divisions, and waiting for the
  * degrees; out[7] = nodes processed over all levels.  Profile mode waits for the stream after every stage so that the time can be
- * charged to it: for scratch/time_solver.py, not for timing the call as a whole.  Process-wide. */
+ * charged to it: for scratch/time_solver.py, not for timing the call as a whole.  Process-wide.
+ * hb_selftest_rf(HB_RF_SELFTEST_ROOTS), the same level loop over host memory, publishes its levels, rounds and nodes here too (the
+ * other five are zero: it launches and waits for nothing), so a test can hold the device's walk against the host's. */
 void hb_debug_rf_stats(int64_t *out);
 void hb_debug_rf_profile(int on);
 

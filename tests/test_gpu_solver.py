@@ -1,13 +1,17 @@
 """GPU: honeybadgermpc_amd.solver -- Newton's identities, the root finder of csrc/hb_rf.hip and the mixing protocol end to end.
-The expected outputs are mathematics: the sorted roots a test started from, or None.  Exact equality everywhere."""
+The expected outputs are mathematics: the sorted roots a test started from, or None; for the case table of tests/rootfind_cases.py also
+the walk of the same level loop over host memory, root by root in the order found.  Exact equality everywhere."""
 import asyncio
+import ctypes
 import random
 
 import pytest
 
 from conftest import BLS
 
+import rootfind_cases as cases
 import rootfind_model as model
+import test_solver_host as host
 
 pytestmark = pytest.mark.gpu
 
@@ -172,6 +176,100 @@ def test_arguments_refused_on_the_device():
     # the temporaries go back with the cache, and the next call regrows them
     ctx.cache_clear()
     _check_roots(ctx, [9, 8, 7])
+
+
+# ---- the case table of tests/rootfind_cases.py: the device's walk against the host's ------------------------------------------
+# hb_rf_roots writes the roots in the order found, and so does the level loop over host memory (HB_RF_SELFTEST_ROOTS: the same bodies,
+# the same driver, RfRun<.., DEV = false>) for the same seed: the two UNSORTED lists are equal exactly when every split of every node
+# came out the same on both sides.  solver.roots sorts, so these tests call the library directly.
+def device_walk(ctx, coeffs, seed=0):
+    """hb_rf_roots on the current stream -> host.HostWalk: n_roots, the roots as the library wrote them, levels, rounds, nodes"""
+    k = len(coeffs) - 1
+    dev = ctx.upload_ints(list(coeffs))
+    out = ctx.empty(k)
+    n = ctypes.c_int32(0)
+    ctx.check(ctx.lib.hb_rf_roots(ctx.h, ctx.ptr(dev), k, ctypes.c_uint64(seed), ctx.ptr(out), ctypes.byref(n), ctx.stream()), "hb_rf_roots")
+    stats = (ctypes.c_int64 * 8)()
+    ctx.lib.hb_debug_rf_stats(stats)
+    return host.HostWalk(n.value, tuple(ctx.download_ints(out)) if n.value >= 0 else None, int(stats[0]), int(stats[3]), int(stats[7]))
+
+
+def _case_on_the_device(case_id, seed=0):
+    """one case, one seed: the device's walk is the host's, and the host's is right; -> the device's walk"""
+    case = cases.BY_ID[case_id]
+    want = host.host_walk(case_id, seed)
+    host.check_walk(case, want)
+    got = device_walk(_ctx(case.p, case.n_limbs), cases.coeffs_of(case_id), seed)
+    assert got.n == want.n, (case_id, seed)
+    assert got.roots == want.roots, (case_id, seed)
+    assert (got.levels, got.rounds, got.nodes) == (want.levels, want.rounds, want.nodes), (case_id, seed)
+    host.check_walk(case, got)
+    return got
+
+
+@pytest.mark.parametrize("case", cases.CASES, ids=[c.id for c in cases.CASES])
+def test_case_device_walk_is_the_host_walk(case):
+    from honeybadgermpc_amd import solver
+
+    _case_on_the_device(case.id)
+    ctx = _ctx(case.p, case.n_limbs)
+    assert solver.solve(ctx, list(cases.power_sums_of(case.id))) == case.expected
+
+
+@pytest.mark.parametrize("case_id", sorted(cases.SEEDS))
+def test_case_under_other_seeds(case_id):
+    case = cases.BY_ID[case_id]
+    for seed in (0,) + cases.SEEDS[case_id]:
+        assert sorted(_case_on_the_device(case_id, seed).roots) == case.expected, seed
+
+
+def _run_sequence():
+    """a large solve, then small ones, on one context and the current stream: the arenas, the table and h hold what the larger call left"""
+    walks = [_case_on_the_device(cid) for cid in cases.SEQUENCE]
+    assert cases.SEQUENCE[0] == cases.SEQUENCE[-1] and walks[0] == walks[-1]
+    assert [cases.degree(cases.BY_ID[cid]) for cid in cases.SEQUENCE] == [200, 3, 129, 2, 65, 200]
+    assert walks[4].n == -1
+
+
+def test_a_small_solve_after_a_large_one_on_the_same_context():
+    _run_sequence()
+
+
+def test_the_same_calls_on_a_stream_of_their_own():
+    import torch
+
+    ctx = _ctx(BLS)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        assert ctx.stream().value == side.cuda_stream
+        _run_sequence()
+    side.synchronize()
+
+
+def test_two_contexts_in_turn():
+    assert len({cases.BY_ID[cid].p for cid in cases.ALTERNATING}) == 2
+    assert all(cases.BY_ID[a].p != cases.BY_ID[b].p for a, b in zip(cases.ALTERNATING, cases.ALTERNATING[1:]))
+    for cid in cases.ALTERNATING:
+        _case_on_the_device(cid)
+
+
+@pytest.mark.parametrize("nc", cases.NEWTON, ids=[c.id for c in cases.NEWTON])
+def test_newton_kernel_is_the_host_body_where_the_run_of_a_thread_grows(nc):
+    from honeybadgermpc_amd import solver
+
+    ctx = _ctx(nc.p, nc.n_limbs)
+    got = solver.newton_coefficients_device(ctx, ctx.upload_ints(list(nc.sums)))
+    assert tuple(ctx.download_ints(got)) == host.newton_body(nc.id)
+
+
+def test_newton_kernel_on_1024_pool_values():
+    from honeybadgermpc_amd import power_mixing, solver
+
+    ctx = _ctx(BLS)
+    sums = cases.newton_pool_vector(1024)
+    got = solver.newton_coefficients_device(ctx, ctx.upload_ints(sums))
+    assert ctx.download_ints(got) == power_mixing.newton_coefficients(sums, BLS)
 
 
 # ---- the protocol, end to end over an in-process tagged network ---------------------------------------------------------------

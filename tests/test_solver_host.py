@@ -1,7 +1,9 @@
 """CPU-only: the bodies of the root-finding kernels (csrc/hb_rf.hip) run on the host through hb_selftest_rf -- the same HB_HD phases
 the kernels run, walked thread by thread -- against the plain-Python model of tests/rootfind_model.py and
 power_mixing.newton_coefficients; and what honeybadgermpc_amd.solver checks before it touches a device.  Exact equality."""
+import collections
 import ctypes
+import functools
 import os
 import random
 import re
@@ -11,6 +13,7 @@ import pytest
 
 from conftest import BLS, REPO
 
+import rootfind_cases as cases
 import rootfind_model as model
 
 P256 = (1 << 256) - 189
@@ -200,6 +203,106 @@ def test_the_whole_level_loop_on_the_host(p, nl):
         assert roots_of(model.poly_mul(quad, model.poly_from_roots([1, 2, 2], p), p)) is None
         assert roots_of(model.poly_mul(model.poly_mul(quad, quad, p), [p - 1, 1], p)) is None
         assert roots_of(model.poly_mul(model.irreducible_cubic(p), model.poly_from_roots([3, 4], p), p)) is None
+
+
+# ---- the case table of tests/rootfind_cases.py: every case here, and then on the device against this walk (test_gpu_solver.py) ----
+HostWalk = collections.namedtuple("HostWalk", "n roots levels rounds nodes")
+
+
+@functools.lru_cache(maxsize=None)
+def host_walk(case_id, seed=0):
+    """The level loop over host memory (RfRun<.., DEV = false>) on a case of the table: the number of roots (-1: invalid), the roots
+    in the order found, and the walk's counters.  Kept for the process: the GPU tests hold the device's output against it."""
+    from honeybadgermpc_amd._capi import load_library
+
+    c = cases.BY_ID[case_id]
+    coeffs = list(cases.coeffs_of(case_id))
+    k = len(coeffs) - 1
+    rc, out = run(c.p, c.n_limbs, ROOTS, [coeffs], [k, seed], k + 1)
+    assert rc == 0, (case_id, seed, rc)
+    stats = (ctypes.c_int64 * 8)()
+    load_library().hb_debug_rf_stats(stats)
+    n = int(out[0].view(np.int64)[0])
+    return HostWalk(n, tuple(ints(out[1:], c.n_limbs)) if n >= 0 else None, int(stats[0]), int(stats[3]), int(stats[7]))
+
+
+def check_walk(case, walk):
+    """what mathematics says about a walk of the level loop, host or device"""
+    if case.expected is None:
+        # the first level decides: every node is fresh there, and the one that holds the factor of degree above one fails the count
+        assert walk.n == -1 and walk.levels == 1, (case.id, walk)
+        return
+    assert walk.n == len(case.expected) and sorted(walk.roots) == case.expected, case.id
+    assert walk.rounds == cases.multiplicity(case), (case.id, walk.rounds)
+    # every level works on at least one node; a single root, however often repeated, is the one input that needs no level
+    assert walk.nodes >= walk.levels and (walk.levels >= 1 or len(set(case.expected)) == 1), (case.id, walk)
+
+
+def test_the_case_table_is_what_it_says():
+    assert cases.BLS == BLS and cases.P256 == P256 and cases.P64 == P64
+    sd = small_degree()
+    by_group = collections.Counter(c.id.split("-")[0] for c in cases.CASES)
+    assert set(by_group) == {"tile", "seq", "edge", "small", "mult", "invalid", "seeds"}
+    for c in cases.CASES:
+        f = cases.coeffs_of(c.id)
+        assert f[-1] == 1 and len(f) - 1 == cases.degree(c) < c.p and all(0 <= v < c.p for v in f)
+        if c.roots is None:
+            assert len(f) - 1 > 2 * sd, c.id                                           # the node that holds the factor is in the tiled chain
+        elif not c.id.startswith(("seq-", "mult-65x-", "small-13-")):
+            assert len(set(c.roots)) > sd, c.id                                        # so is the first node of a valid case
+    # every wide modulus has a case above degree 128
+    for name in cases.WIDE:
+        assert any(c.p == cases.MODULI[name][0] and c.roots is not None and len(set(c.roots)) > 128 for c in cases.CASES), name
+    # the pool is 35 .. 55 roots; with the pre-images it crosses a tile (Goldilocks: 62, where many pre-images are pool values)
+    for name in cases.LARGE:
+        assert sd < cases.degree(cases.BY_ID[f"edge-pool-{name}"]) < 64
+        assert cases.degree(cases.BY_ID[f"edge-operands-{name}"]) > (sd if name == "gold" else 64)
+    for cid, seeds in cases.SEEDS.items():
+        assert cid in cases.BY_ID and 0 not in seeds
+    assert all(cid in cases.BY_ID for cid in cases.SEQUENCE + cases.ALTERNATING)
+
+
+@pytest.mark.parametrize("case", cases.CASES, ids=[c.id for c in cases.CASES])
+def test_case_on_the_host(case):
+    """the whole level loop on a case of the table: the roots, the rounds of the repeated-root loop, an invalid input's one level"""
+    check_walk(case, host_walk(case.id))
+
+
+@pytest.mark.parametrize("case_id", sorted(cases.SEEDS))
+def test_case_under_other_seeds_on_the_host(case_id):
+    case = cases.BY_ID[case_id]
+    orders = {host_walk(case_id).roots}
+    for seed in cases.SEEDS[case_id]:
+        walk = host_walk(case_id, seed)
+        check_walk(case, walk)
+        orders.add(walk.roots)
+    assert len(orders) > 1                       # the seed does choose the shifts: the walks differ, the answer does not
+
+
+@pytest.mark.parametrize("case", cases.CASES, ids=[c.id for c in cases.CASES])
+def test_newton_body_gives_back_the_polynomial_of_a_case(case):
+    """power sums of the case's polynomial (Newton run backwards in Python ints) -> the Newton body -> the polynomial, invalid ones too"""
+    k = cases.degree(case)
+    rc, out = run(case.p, case.n_limbs, NEWTON, [list(cases.power_sums_of(case.id))], [k], k + 1)
+    assert rc == 0 and ints(out, case.n_limbs) == list(cases.coeffs_of(case.id))
+
+
+@pytest.mark.parametrize("nc", cases.NEWTON, ids=[c.id for c in cases.NEWTON])
+def test_newton_body_where_the_run_of_a_thread_grows(nc):
+    """k = 255, 256, 257: the last thread idle, every thread one integer, every thread a run of two (and a step's sum two terms a thread)"""
+    from honeybadgermpc_amd.power_mixing import newton_coefficients
+
+    assert newton_body(nc.id) == tuple(newton_coefficients(list(nc.sums), nc.p))
+
+
+@functools.lru_cache(maxsize=None)
+def newton_body(newton_id):
+    """the Newton body over host memory on a case of cases.NEWTON (kept: the GPU test holds the kernel against it)"""
+    nc = next(c for c in cases.NEWTON if c.id == newton_id)
+    k = len(nc.sums)
+    rc, out = run(nc.p, nc.n_limbs, NEWTON, [list(nc.sums)], [k], k + 1)
+    assert rc == 0
+    return tuple(ints(out, nc.n_limbs))
 
 
 def test_model_power_sums_run_backwards():
