@@ -1,0 +1,536 @@
+// hb_lt.hip -- less-than of shared field elements, the reference's LessThan mixin (progs/mixins/share_comparison.py:83-212, "An Improved
+// Multiparty Protocol for Comparison of Secret-shared Values", Reistad 2007) for arrays of values -- restated on fp29.hpp, not translated.
+//
+// For a pair a, b < (p - 1) / 2 the protocol opens c = 2 (a - b) + r, r a dealt random residue with bit shares r_0 .. r_{L-1}, L the
+// bit length of p, and [a < b] = c_0 xor r_0 xor [r > c].  The reference's x = sum_i r_i (1 - c_i) prod_{j>i} (1 + (r_j xor c_j))
+// (:137-163) is the g at the root of the carry tree's operator (g1, p1) o (g2, p2) = (g1 + p1 g2, p1 p2) of hb_fxp.hip over leaves that
+// are affine in [r_i], because c_i is public; its least significant bit is [r > c].  The same tree over the leaves of the comparison
+// itself gives [r > c] as a bit.  The tree's levels are k_fxp_carry_mask / k_fxp_carry_combine of hb_fxp.hip, unchanged.
+//
+// k_lt_mask        2 (a - b) + r, the array to open (b may be absent: 2 a + r).
+// k_lt_leaves      (g, p), L planes each, most significant bit first; bit i of c is taken from the packed words and selects:
+//                     HB_LT_DIRECT     c_i = 0 -> (r_i, 1 - r_i)   c_i = 1 -> (0, r_i)         g = [r_i > c_i], p = [r_i = c_i]: root g = [r > c]
+//                     HB_LT_REFERENCE  c_i = 0 -> (r_i, 1 + r_i)   c_i = 1 -> (0, 2 - r_i)     the reference's r_i (1 - c_i), 1 + (r_i xor c_i): root g = x
+//                  No triple, no open.  (The reference spends a product and an open on every bit, one after the other.)
+// k_lt_xor_mask    DIRECT, after the tree gave w = [r > c]: u = c_0 ? 1 - r_0 : r_0 and the array to open [u - pa, w - qa].
+// k_lt_dmask       REFERENCE, after the tree gave x: u, and ONE array of five planes [s + x, u - pa, s_0 - qa, s_1 - pb, s_2 - qb] with
+//                  s_0, s_1, s_2 = planes 0, L - 1, L - 2 of the second mask's bit shares (:178-182): d = s + x and the masked operands of
+//                  the two products that do not depend on d travel in one open.
+// k_lt_mid         that array opened: v = u xor s_0 and s_1 s_2 by ew_beaver_elem, d_0 by the reference's four-way select (:186-199;
+//                  d < p < 2^L, so the three comparisons of d read bits L - 1 and L - 2 of d alone), the array to open [v - pc, d_0 - qc].
+// k_lt_xor_finish  both modes: u + v - 2 [u v], the last xor.
+//
+// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions: the __global__ wrappers only
+// load, call them and store, and hb_selftest_lt runs the very same functions on the host.
+//
+// Launch shape (all kernels): 256-thread workgroups, one element a thread in x; k_lt_leaves takes the plane in blockIdx.y (c is
+// one element a thread and stays in L2 for the L planes).  No LDS, no grid stride, one launch a call.  Bit planes, triples and opened
+// values are read once: the 32-byte width takes the non-temporal loads, as k_ew_beaver.
+// Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
+//   k_lt_mask<9, 8>        29 VGPRs with b, 30 without: 8 waves a SIMD        k_lt_mask<3, 2>        12 VGPRs: 8 waves
+//   k_lt_leaves<9, 8>      41 VGPRs: 8 waves                                  k_lt_leaves<3, 2>      17 VGPRs: 8 waves
+//   k_lt_xor_mask<9, 8>    56 VGPRs: 8 waves                                  k_lt_xor_mask<3, 2>    24 VGPRs: 8 waves
+//   k_lt_dmask<9, 8>       68 VGPRs: 7 waves                                  k_lt_dmask<3, 2>       34 VGPRs: 8 waves
+//   k_lt_mid<9, 8>         83 VGPRs: 5 waves                                  k_lt_mid<3, 2>         56 VGPRs: 8 waves
+//   k_lt_xor_finish<9, 8>  73 VGPRs: 6 waves                                  k_lt_xor_finish<3, 2>  30 VGPRs: 8 waves
+// (DESIGN.md section 3p has the schedule and the counts.)
+#include "hb_common.hpp"
+#include "hb_ew_elem.hpp"
+
+using namespace hb;
+
+namespace hb {
+
+// ---------------------------------------------------------------- per-element bodies (host and device)
+// bit i of the packed words (a chain of selects: the words stay in registers)
+template <int NW> HB_HD uint32_t lt_bit(const uint32_t (&cw)[NW], int i) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int q = 0; q < NW; q++) w = (q == (i >> 5)) ? cw[q] : w;
+    return (w >> (i & 31)) & 1u;
+}
+template <int NL> HB_HD void lt_small(uint32_t (&r)[NL], uint32_t v) {
+#pragma unroll
+    for (int q = 0; q < NL; q++) r[q] = q == 0 ? v : 0u;
+}
+
+// o = v - a on packed words: a masked difference
+template <int NL, int NW> HB_HD void lt_diff_elem(uint32_t (&o)[NW], const uint32_t (&vw)[NW], const uint32_t (&aw)[NW], const FpParams<NL> &P) {
+    uint32_t v[NL], a[NL], r[NL];
+    unpack<NL, NW>(v, vw);
+    unpack<NL, NW>(a, aw);
+    fp_sub<NL>(r, v, a, P);
+    pack<NL, NW>(o, r);
+}
+
+// o = 2 (a - b) + r; HAS_B = false: 2 a + r
+template <int NL, int NW, bool HAS_B>
+HB_HD void lt_mask_elem(uint32_t (&o)[NW], const uint32_t (&aw)[NW], const uint32_t (&bw)[NW], const uint32_t (&rw)[NW], const FpParams<NL> &P) {
+    uint32_t z[NL], t[NL], u[NL];
+    unpack<NL, NW>(z, aw);
+    if constexpr (HAS_B) {
+        unpack<NL, NW>(t, bw);
+        fp_sub<NL>(u, z, t, P);
+        fp_set<NL>(z, u);
+    }
+    fp_add<NL>(t, z, z, P);
+    unpack<NL, NW>(z, rw);
+    fp_add<NL>(u, t, z, P);
+    pack<NL, NW>(o, u);
+}
+
+// the leaf of the public bit a of c against the share bw of the same bit of r
+template <int NL, int NW>
+HB_HD void lt_leaf_elem(uint32_t (&gw)[NW], uint32_t (&pw)[NW], uint32_t a, const uint32_t (&bw)[NW], int mode, const FpParams<NL> &P) {
+    uint32_t b[NL], k[NL], t[NL], w[NL], g[NL], p[NL];
+    unpack<NL, NW>(b, bw);
+    if (mode == HB_LT_DIRECT) {                        // mode is the same for every lane; the bit a selects
+        lt_small<NL>(k, 1);
+        fp_sub<NL>(t, k, b, P);                        // 1 - r_i
+#pragma unroll
+        for (int q = 0; q < NL; q++) p[q] = a ? b[q] : t[q];
+    } else {
+        lt_small<NL>(k, 2);
+        fp_sub<NL>(t, k, b, P);                        // 2 - r_i
+        lt_small<NL>(k, 1);
+        fp_add<NL>(w, k, b, P);                        // 1 + r_i
+#pragma unroll
+        for (int q = 0; q < NL; q++) p[q] = a ? t[q] : w[q];
+    }
+#pragma unroll
+    for (int q = 0; q < NL; q++) g[q] = a ? 0u : b[q];
+    pack<NL, NW>(gw, g);
+    pack<NL, NW>(pw, p);
+}
+
+// u = c_0 xor [r_0]: c_0 ? 1 - r_0 : r_0
+template <int NL, int NW> HB_HD void lt_u_elem(uint32_t (&uw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r0w)[NW], const FpParams<NL> &P) {
+    uint32_t b[NL], one[NL], t[NL];
+    unpack<NL, NW>(b, r0w);
+    lt_small<NL>(one, 1);
+    fp_sub<NL>(t, one, b, P);
+    const uint32_t c0 = cw[0] & 1u;
+#pragma unroll
+    for (int q = 0; q < NL; q++) t[q] = c0 ? t[q] : b[q];
+    pack<NL, NW>(uw, t);
+}
+
+// DIRECT: u, m0 = u - pa, m1 = w - qa
+template <int NL, int NW>
+HB_HD void lt_xor_mask_elem(uint32_t (&uw)[NW], uint32_t (&m0)[NW], uint32_t (&m1)[NW], const uint32_t (&cw)[NW], const uint32_t (&r0w)[NW], const uint32_t (&ww)[NW],
+                            const uint32_t (&paw)[NW], const uint32_t (&qaw)[NW], const FpParams<NL> &P) {
+    lt_u_elem<NL, NW>(uw, cw, r0w, P);
+    lt_diff_elem<NL, NW>(m0, uw, paw, P);
+    lt_diff_elem<NL, NW>(m1, ww, qaw, P);
+}
+
+// REFERENCE: u, m0 = s + x, m1 = u - pa, m2 = s_0 - qa, m3 = s_1 - pb, m4 = s_2 - qb
+template <int NL, int NW>
+HB_HD void lt_dmask_elem(uint32_t (&uw)[NW], uint32_t (&m0)[NW], uint32_t (&m1)[NW], uint32_t (&m2)[NW], uint32_t (&m3)[NW], uint32_t (&m4)[NW], const uint32_t (&cw)[NW],
+                         const uint32_t (&r0w)[NW], const uint32_t (&xw)[NW], const uint32_t (&sw)[NW], const uint32_t (&s0w)[NW], const uint32_t (&s1w)[NW],
+                         const uint32_t (&s2w)[NW], const uint32_t (&paw)[NW], const uint32_t (&qaw)[NW], const uint32_t (&pbw)[NW], const uint32_t (&qbw)[NW],
+                         const FpParams<NL> &P) {
+    uint32_t s[NL], x[NL], t[NL];
+    unpack<NL, NW>(s, sw);
+    unpack<NL, NW>(x, xw);
+    fp_add<NL>(t, s, x, P);
+    pack<NL, NW>(m0, t);
+    lt_u_elem<NL, NW>(uw, cw, r0w, P);
+    lt_diff_elem<NL, NW>(m1, uw, paw, P);
+    lt_diff_elem<NL, NW>(m2, s0w, qaw, P);
+    lt_diff_elem<NL, NW>(m3, s1w, pbw, P);
+    lt_diff_elem<NL, NW>(m4, s2w, qbw, P);
+}
+
+// o = x + y - 2 [x y] with [x y] the fused Beaver step over the opened masked operands d, e
+template <int NL, int NW>
+HB_HD void lt_xor_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const uint32_t (&yw)[NW], const uint32_t (&dw)[NW], const uint32_t (&ew)[NW], const uint32_t (&pw)[NW],
+                       const uint32_t (&qw)[NW], const uint32_t (&pqw)[NW], const FpParams<NL> &P) {
+    uint32_t mw[NW], m[NL], x[NL], y[NL], t[NL];
+    ew_beaver_elem<NL, NW>(mw, dw, ew, pw, qw, pqw, P);
+    unpack<NL, NW>(m, mw);
+    unpack<NL, NW>(x, xw);
+    unpack<NL, NW>(y, yw);
+    fp_add<NL>(t, x, y, P);
+    fp_sub<NL>(x, t, m, P);
+    fp_sub<NL>(t, x, m, P);
+    pack<NL, NW>(o, t);
+}
+
+// o0 .. o4 the array of lt_dmask_elem opened.  v = u xor s_0; d_0 = (1 - s_1 - s_2 + s_1 s_2) d0 + (s_2 - s_1 s_2) (d0 ^ [d < 2^(L-2)]) +
+// (s_1 - s_1 s_2) (d0 ^ [d < 2^(L-1)]) + s_1 s_2 (d0 ^ [d < 2^(L-1) + 2^(L-2)]): every public factor is a bit, so the sum is a sum of
+// selected terms; m0 = v - pc, m1 = d_0 - qc
+template <int NL, int NW>
+HB_HD void lt_mid_elem(uint32_t (&vw)[NW], uint32_t (&d0w)[NW], uint32_t (&m0)[NW], uint32_t (&m1)[NW], const uint32_t (&o0)[NW], const uint32_t (&o1)[NW],
+                       const uint32_t (&o2)[NW], const uint32_t (&o3)[NW], const uint32_t (&o4)[NW], const uint32_t (&uw)[NW], const uint32_t (&s0w)[NW],
+                       const uint32_t (&s1w)[NW], const uint32_t (&s2w)[NW], const uint32_t (&paw)[NW], const uint32_t (&qaw)[NW], const uint32_t (&pqaw)[NW],
+                       const uint32_t (&pbw)[NW], const uint32_t (&qbw)[NW], const uint32_t (&pqbw)[NW], const uint32_t (&pcw)[NW], const uint32_t (&qcw)[NW], int L,
+                       const FpParams<NL> &P) {
+    lt_xor_elem<NL, NW>(vw, uw, s0w, o1, o2, paw, qaw, pqaw, P);
+    uint32_t spw[NW], sp[NL], s1[NL], s2[NL], t[NL], w[NL], acc[NL];
+    ew_beaver_elem<NL, NW>(spw, o3, o4, pbw, qbw, pqbw, P);
+    unpack<NL, NW>(sp, spw);
+    unpack<NL, NW>(s1, s1w);
+    unpack<NL, NW>(s2, s2w);
+    const uint32_t d0 = o0[0] & 1u, t1 = lt_bit<NW>(o0, L - 1), t2 = lt_bit<NW>(o0, L - 2);
+    const uint32_t dx1 = d0 ^ (t1 ^ 1u), dx2 = d0 ^ ((t1 | t2) ^ 1u), dx12 = d0 ^ ((t1 & t2) ^ 1u);
+    // (1 - s_1 - s_2 + s_1 s_2) d0
+    lt_small<NL>(w, 1);
+    fp_sub<NL>(t, w, s1, P);
+    fp_sub<NL>(w, t, s2, P);
+    fp_add<NL>(t, w, sp, P);
+#pragma unroll
+    for (int q = 0; q < NL; q++) acc[q] = d0 ? t[q] : 0u;
+    fp_sub<NL>(t, s2, sp, P);
+    fp_add<NL>(w, acc, t, P);
+#pragma unroll
+    for (int q = 0; q < NL; q++) acc[q] = dx2 ? w[q] : acc[q];
+    fp_sub<NL>(t, s1, sp, P);
+    fp_add<NL>(w, acc, t, P);
+#pragma unroll
+    for (int q = 0; q < NL; q++) acc[q] = dx1 ? w[q] : acc[q];
+    fp_add<NL>(w, acc, sp, P);
+#pragma unroll
+    for (int q = 0; q < NL; q++) acc[q] = dx12 ? w[q] : acc[q];
+    pack<NL, NW>(d0w, acc);
+    lt_diff_elem<NL, NW>(m0, vw, pcw, P);
+    lt_diff_elem<NL, NW>(m1, d0w, qcw, P);
+}
+
+// ---------------------------------------------------------------- kernels
+// read-once operands (bit planes, triples, what was just opened)
+template <int NW> __device__ __forceinline__ void lt_load_once(uint32_t (&w)[NW], const uint32_t *p) {
+    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
+}
+
+// Every output is an array of its own: __restrict__ throughout.
+template <int NL, int NW, bool HAS_B>
+__global__ void __launch_bounds__(256) k_lt_mask(const FpParams<NL> P, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ r,
+                                                 uint32_t *__restrict__ masked, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    uint32_t aw[NW], bw[NW], rw[NW], ow[NW];
+    load_words<NW>(aw, a + i * NW);
+    if constexpr (HAS_B) load_words<NW>(bw, b + i * NW);
+    else {
+#pragma unroll
+        for (int q = 0; q < NW; q++) bw[q] = 0;
+    }
+    load_words<NW>(rw, r + i * NW);
+    lt_mask_elem<NL, NW, HAS_B>(ow, aw, bw, rw, P);
+    store_words<NW>(masked + i * NW, ow);
+}
+
+// plane j = blockIdx.y holds bit L - 1 - j
+template <int NL, int NW>
+__global__ void __launch_bounds__(256) k_lt_leaves(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ r_bits, int L, int mode,
+                                                   uint32_t *__restrict__ g, uint32_t *__restrict__ p, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int64_t j = blockIdx.y;
+    const int bit = L - 1 - (int)j;
+    uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
+    load_words<NW>(cw, c + i * NW);
+    lt_load_once<NW>(bw, r_bits + ((int64_t)bit * count + i) * NW);
+    lt_leaf_elem<NL, NW>(gw, pw, lt_bit<NW>(cw, bit), bw, mode, P);
+    store_words<NW>(g + (j * count + i) * NW, gw);
+    store_words<NW>(p + (j * count + i) * NW, pw);
+}
+
+// masked: (2, count)
+template <int NL, int NW>
+__global__ void __launch_bounds__(256) k_lt_xor_mask(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ r0, const uint32_t *__restrict__ w,
+                                                     const uint32_t *__restrict__ pa, const uint32_t *__restrict__ qa, uint32_t *__restrict__ u,
+                                                     uint32_t *__restrict__ masked, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    uint32_t cw[NW], rw[NW], ww[NW], paw[NW], qaw[NW], uw[NW], m0[NW], m1[NW];
+    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); lt_load_once<NW>(ww, w + i * NW);
+    lt_load_once<NW>(paw, pa + i * NW); lt_load_once<NW>(qaw, qa + i * NW);
+    lt_xor_mask_elem<NL, NW>(uw, m0, m1, cw, rw, ww, paw, qaw, P);
+    store_words<NW>(u + i * NW, uw);
+    store_words<NW>(masked + i * NW, m0);
+    store_words<NW>(masked + (count + i) * NW, m1);
+}
+
+// masked: (5, count)
+template <int NL, int NW>
+__global__ void __launch_bounds__(256) k_lt_dmask(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ r0, const uint32_t *__restrict__ x,
+                                                  const uint32_t *__restrict__ s, const uint32_t *__restrict__ s_bits, int L, const uint32_t *__restrict__ pa,
+                                                  const uint32_t *__restrict__ qa, const uint32_t *__restrict__ pb, const uint32_t *__restrict__ qb,
+                                                  uint32_t *__restrict__ u, uint32_t *__restrict__ masked, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    uint32_t cw[NW], rw[NW], xw[NW], sw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pbw[NW], qbw[NW], uw[NW], m0[NW], m1[NW], m2[NW], m3[NW], m4[NW];
+    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); lt_load_once<NW>(xw, x + i * NW); load_words<NW>(sw, s + i * NW);
+    load_words<NW>(s0w, s_bits + i * NW);
+    load_words<NW>(s1w, s_bits + ((int64_t)(L - 1) * count + i) * NW);
+    load_words<NW>(s2w, s_bits + ((int64_t)(L - 2) * count + i) * NW);
+    lt_load_once<NW>(paw, pa + i * NW); lt_load_once<NW>(qaw, qa + i * NW); lt_load_once<NW>(pbw, pb + i * NW); lt_load_once<NW>(qbw, qb + i * NW);
+    lt_dmask_elem<NL, NW>(uw, m0, m1, m2, m3, m4, cw, rw, xw, sw, s0w, s1w, s2w, paw, qaw, pbw, qbw, P);
+    store_words<NW>(u + i * NW, uw);
+    store_words<NW>(masked + i * NW, m0);
+    store_words<NW>(masked + (count + i) * NW, m1);
+    store_words<NW>(masked + (2 * count + i) * NW, m2);
+    store_words<NW>(masked + (3 * count + i) * NW, m3);
+    store_words<NW>(masked + (4 * count + i) * NW, m4);
+}
+
+// opened: (5, count); masked: (2, count)
+template <int NL, int NW>
+__global__ void __launch_bounds__(256) k_lt_mid(const FpParams<NL> P, const uint32_t *__restrict__ opened, const uint32_t *__restrict__ u, const uint32_t *__restrict__ s_bits,
+                                                int L, const uint32_t *__restrict__ pa, const uint32_t *__restrict__ qa, const uint32_t *__restrict__ pqa,
+                                                const uint32_t *__restrict__ pb, const uint32_t *__restrict__ qb, const uint32_t *__restrict__ pqb,
+                                                const uint32_t *__restrict__ pc, const uint32_t *__restrict__ qc, uint32_t *__restrict__ v, uint32_t *__restrict__ d0,
+                                                uint32_t *__restrict__ masked, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    uint32_t o0[NW], o1[NW], o2[NW], o3[NW], o4[NW], uw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pqaw[NW], pbw[NW], qbw[NW], pqbw[NW], pcw[NW], qcw[NW];
+    uint32_t vw[NW], d0w[NW], m0[NW], m1[NW];
+    lt_load_once<NW>(o0, opened + i * NW); lt_load_once<NW>(o1, opened + (count + i) * NW); lt_load_once<NW>(o2, opened + (2 * count + i) * NW);
+    lt_load_once<NW>(o3, opened + (3 * count + i) * NW); lt_load_once<NW>(o4, opened + (4 * count + i) * NW);
+    lt_load_once<NW>(uw, u + i * NW);
+    load_words<NW>(s0w, s_bits + i * NW);
+    load_words<NW>(s1w, s_bits + ((int64_t)(L - 1) * count + i) * NW);
+    load_words<NW>(s2w, s_bits + ((int64_t)(L - 2) * count + i) * NW);
+    lt_load_once<NW>(paw, pa + i * NW); lt_load_once<NW>(qaw, qa + i * NW); lt_load_once<NW>(pqaw, pqa + i * NW);
+    lt_load_once<NW>(pbw, pb + i * NW); lt_load_once<NW>(qbw, qb + i * NW); lt_load_once<NW>(pqbw, pqb + i * NW);
+    load_words<NW>(pcw, pc + i * NW); load_words<NW>(qcw, qc + i * NW);
+    lt_mid_elem<NL, NW>(vw, d0w, m0, m1, o0, o1, o2, o3, o4, uw, s0w, s1w, s2w, paw, qaw, pqaw, pbw, qbw, pqbw, pcw, qcw, L, P);
+    store_words<NW>(v + i * NW, vw);
+    store_words<NW>(d0 + i * NW, d0w);
+    store_words<NW>(masked + i * NW, m0);
+    store_words<NW>(masked + (count + i) * NW, m1);
+}
+
+// opened: (2, count)
+template <int NL, int NW>
+__global__ void __launch_bounds__(256) k_lt_xor_finish(const FpParams<NL> P, const uint32_t *__restrict__ opened, const uint32_t *__restrict__ u, const uint32_t *__restrict__ v,
+                                                       const uint32_t *__restrict__ tp, const uint32_t *__restrict__ tq, const uint32_t *__restrict__ tpq,
+                                                       uint32_t *__restrict__ out, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    uint32_t dw[NW], ew[NW], uw[NW], vw[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
+    lt_load_once<NW>(dw, opened + i * NW); lt_load_once<NW>(ew, opened + (count + i) * NW);
+    lt_load_once<NW>(uw, u + i * NW); lt_load_once<NW>(vw, v + i * NW);
+    lt_load_once<NW>(pw, tp + i * NW); lt_load_once<NW>(qw, tq + i * NW); lt_load_once<NW>(pqw, tpq + i * NW);
+    lt_xor_elem<NL, NW>(ow, uw, vw, dw, ew, pw, qw, pqw, P);
+    store_words<NW>(out + i * NW, ow);
+}
+
+// ---------------------------------------------------------------- host side
+static int lt_modulus_bits(const uint64_t *p_limbs, int n_limbs) {
+    for (int l = n_limbs - 1; l >= 0; l--)
+        if (p_limbs[l]) return 64 * l + 64 - __builtin_clzll(p_limbs[l]);
+    return 0;
+}
+static bool lt_mode_ok(int mode) { return mode == HB_LT_DIRECT || mode == HB_LT_REFERENCE; }
+static bool lt_overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+    return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
+}
+struct LtSpan { const void *p; int64_t bytes; };
+// no output overlaps an input or another output
+static bool lt_outputs_apart(const LtSpan *outs, int n_outs, const LtSpan *ins, int n_ins) {
+    for (int o = 0; o < n_outs; o++) {
+        for (int i = 0; i < n_ins; i++)
+            if (lt_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes)) return false;
+        for (int k = o + 1; k < n_outs; k++)
+            if (lt_overlap(outs[o].p, outs[o].bytes, outs[k].p, outs[k].bytes)) return false;
+    }
+    return true;
+}
+
+// host: the same element functions over `count` elements
+template <int NL, int NW>
+static int selftest_lt(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
+    FpParams<NL> P;
+    fp_params_from_limbs(P, p_limbs);
+    const int L = (int)params[0], mode = (int)params[1];
+    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
+    auto O = [](uint64_t *base, int64_t i) -> uint32_t * { return reinterpret_cast<uint32_t *>(base) + i * NW; };
+    const uint32_t none[NW] = {};
+    uint32_t r0[NW], r1[NW], r2[NW], r3[NW], r4[NW], r5[NW];
+    for (int64_t i = 0; i < count; i++) {
+        if (what == HB_LT_SELFTEST_MASK) {
+            if (ops[1]) lt_mask_elem<NL, NW, true>(r0, W(ops[0], i), W(ops[1], i), W(ops[2], i), P);
+            else lt_mask_elem<NL, NW, false>(r0, W(ops[0], i), none, W(ops[2], i), P);
+            memcpy(O(outs[0], i), r0, NW * 4);
+        } else if (what == HB_LT_SELFTEST_LEAVES) {
+            for (int j = 0; j < L; j++) {
+                const int bit = L - 1 - j;
+                lt_leaf_elem<NL, NW>(r0, r1, lt_bit<NW>(W(ops[0], i), bit), W(ops[1], (int64_t)bit * count + i), mode, P);
+                memcpy(O(outs[0], (int64_t)j * count + i), r0, NW * 4);
+                memcpy(O(outs[1], (int64_t)j * count + i), r1, NW * 4);
+            }
+        } else if (what == HB_LT_SELFTEST_XOR_MASK) {
+            lt_xor_mask_elem<NL, NW>(r0, r1, r2, W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), W(ops[4], i), P);
+            memcpy(O(outs[0], i), r0, NW * 4);
+            memcpy(O(outs[1], i), r1, NW * 4); memcpy(O(outs[1], count + i), r2, NW * 4);
+        } else if (what == HB_LT_SELFTEST_DMASK) {
+            lt_dmask_elem<NL, NW>(r0, r1, r2, r3, r4, r5, W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), W(ops[4], i), W(ops[4], (int64_t)(L - 1) * count + i),
+                                  W(ops[4], (int64_t)(L - 2) * count + i), W(ops[5], i), W(ops[6], i), W(ops[7], i), W(ops[8], i), P);
+            memcpy(O(outs[0], i), r0, NW * 4);
+            memcpy(O(outs[1], i), r1, NW * 4); memcpy(O(outs[1], count + i), r2, NW * 4); memcpy(O(outs[1], 2 * count + i), r3, NW * 4);
+            memcpy(O(outs[1], 3 * count + i), r4, NW * 4); memcpy(O(outs[1], 4 * count + i), r5, NW * 4);
+        } else if (what == HB_LT_SELFTEST_MID) {
+            lt_mid_elem<NL, NW>(r0, r1, r2, r3, W(ops[0], i), W(ops[0], count + i), W(ops[0], 2 * count + i), W(ops[0], 3 * count + i), W(ops[0], 4 * count + i), W(ops[1], i),
+                                W(ops[2], i), W(ops[2], (int64_t)(L - 1) * count + i), W(ops[2], (int64_t)(L - 2) * count + i), W(ops[3], i), W(ops[4], i), W(ops[5], i),
+                                W(ops[6], i), W(ops[7], i), W(ops[8], i), W(ops[9], i), W(ops[10], i), L, P);
+            memcpy(O(outs[0], i), r0, NW * 4);
+            memcpy(O(outs[1], i), r1, NW * 4);
+            memcpy(O(outs[2], i), r2, NW * 4); memcpy(O(outs[2], count + i), r3, NW * 4);
+        } else {
+            lt_xor_elem<NL, NW>(r0, W(ops[1], i), W(ops[2], i), W(ops[0], i), W(ops[0], count + i), W(ops[3], i), W(ops[4], i), W(ops[5], i), P);
+            memcpy(O(outs[0], i), r0, NW * 4);
+        }
+    }
+    return HB_OK;
+}
+
+}  // namespace hb
+
+extern "C" {
+
+#define LT_BLOCKS(ctx, name)                                                                                           \
+    const int64_t blocks = (count + 255) / 256;                                                                        \
+    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
+    hipStream_t s = (hipStream_t)stream
+#define U32(p) ((const uint32_t *)(p))
+#define LT_L_OK(ctx) (L == lt_modulus_bits((ctx)->p_limbs, (ctx)->n_limbs))
+
+int hb_lt_mask(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *r_dev, uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
+    if (!ctx || count < 0 || (count > 0 && (!a_dev || !r_dev || !masked_dev))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
+    const LtSpan outs[1] = {{masked_dev, eb}}, ins[3] = {{a_dev, eb}, {b_dev, eb}, {r_dev, eb}};
+    if (!lt_outputs_apart(outs, 1, ins, 3)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mask: masked is an array of its own");
+    LT_BLOCKS(ctx, "hb_lt_mask");
+#define LT_MASK(NL, NW, HAS_B, P) k_lt_mask<NL, NW, HAS_B><<<(unsigned)blocks, 256, 0, s>>>(P, U32(a_dev), U32(b_dev), U32(r_dev), (uint32_t *)masked_dev, count)
+    if (b_dev) HB_DISPATCH(ctx, (LT_MASK(9, 8, true, ctx->pw)), (LT_MASK(3, 2, true, ctx->pn)));
+    else HB_DISPATCH(ctx, (LT_MASK(9, 8, false, ctx->pw)), (LT_MASK(3, 2, false, ctx->pn)));
+#undef LT_MASK
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
+int hb_lt_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r_bits_dev, int L, int mode, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream) {
+    HB_API_GUARD(ctx);
+    if (!ctx || count < 0 || (count > 0 && (!c_dev || !r_bits_dev || !g_dev || !p_dev))) return HB_ERR_BAD_ARG;
+    if (!lt_mode_ok(mode)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: unknown mode");
+    if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: L is the bit length of the modulus");
+    if (count == 0) return HB_OK;
+    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
+    const LtSpan outs[2] = {{g_dev, L * eb}, {p_dev, L * eb}}, ins[2] = {{c_dev, eb}, {r_bits_dev, L * eb}};
+    if (!lt_outputs_apart(outs, 2, ins, 2)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: g and p are arrays of their own");
+    LT_BLOCKS(ctx, "hb_lt_leaves");
+    const dim3 grid((unsigned)blocks, (unsigned)L);
+    HB_DISPATCH(ctx,
+        (k_lt_leaves<9, 8><<<grid, 256, 0, s>>>(ctx->pw, U32(c_dev), U32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)),
+        (k_lt_leaves<3, 2><<<grid, 256, 0, s>>>(ctx->pn, U32(c_dev), U32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)));
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
+int hb_lt_xor_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *w_dev, const uint64_t *pa_dev, const uint64_t *qa_dev, uint64_t *u_dev,
+                   uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
+    if (!ctx || count < 0 || (count > 0 && (!c_dev || !r0_dev || !w_dev || !pa_dev || !qa_dev || !u_dev || !masked_dev))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
+    const LtSpan outs[2] = {{u_dev, eb}, {masked_dev, 2 * eb}}, ins[5] = {{c_dev, eb}, {r0_dev, eb}, {w_dev, eb}, {pa_dev, eb}, {qa_dev, eb}};
+    if (!lt_outputs_apart(outs, 2, ins, 5)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_mask: u and masked are arrays of their own");
+    LT_BLOCKS(ctx, "hb_lt_xor_mask");
+    HB_DISPATCH(ctx,
+        (k_lt_xor_mask<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, U32(c_dev), U32(r0_dev), U32(w_dev), U32(pa_dev), U32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)),
+        (k_lt_xor_mask<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, U32(c_dev), U32(r0_dev), U32(w_dev), U32(pa_dev), U32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)));
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
+int hb_lt_dmask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *x_dev, const uint64_t *s_dev, const uint64_t *s_bits_dev, int L,
+                const uint64_t *pa_dev, const uint64_t *qa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev, uint64_t *u_dev, uint64_t *masked_dev, int64_t count,
+                void *stream) { HB_API_GUARD(ctx);
+    if (!ctx || count < 0 || (count > 0 && (!c_dev || !r0_dev || !x_dev || !s_dev || !s_bits_dev || !pa_dev || !qa_dev || !pb_dev || !qb_dev || !u_dev || !masked_dev)))
+        return HB_ERR_BAD_ARG;
+    if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: L is the bit length of the modulus");
+    if (count == 0) return HB_OK;
+    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
+    const LtSpan outs[2] = {{u_dev, eb}, {masked_dev, 5 * eb}},
+                 ins[9] = {{c_dev, eb}, {r0_dev, eb}, {x_dev, eb}, {s_dev, eb}, {s_bits_dev, L * eb}, {pa_dev, eb}, {qa_dev, eb}, {pb_dev, eb}, {qb_dev, eb}};
+    if (!lt_outputs_apart(outs, 2, ins, 9)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: u and masked are arrays of their own");
+    LT_BLOCKS(ctx, "hb_lt_dmask");
+#define LT_DMASK(NL, NW, P)                                                                                                                                      \
+    k_lt_dmask<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, U32(c_dev), U32(r0_dev), U32(x_dev), U32(s_dev), U32(s_bits_dev), L, U32(pa_dev), U32(qa_dev), U32(pb_dev), \
+                                                        U32(qb_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)
+    HB_DISPATCH(ctx, (LT_DMASK(9, 8, ctx->pw)), (LT_DMASK(3, 2, ctx->pn)));
+#undef LT_DMASK
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
+int hb_lt_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *s_bits_dev, int L, const uint64_t *pa_dev, const uint64_t *qa_dev,
+              const uint64_t *pqa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev, const uint64_t *pqb_dev, const uint64_t *pc_dev, const uint64_t *qc_dev,
+              uint64_t *v_dev, uint64_t *d0_dev, uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
+    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
+    const uint64_t *trip[8] = {pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, pc_dev, qc_dev};
+    if (count > 0) {
+        for (const uint64_t *t : trip) if (!t) return HB_ERR_BAD_ARG;
+        if (!opened_dev || !u_dev || !s_bits_dev || !v_dev || !d0_dev || !masked_dev) return HB_ERR_BAD_ARG;
+    }
+    if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: L is the bit length of the modulus");
+    if (count == 0) return HB_OK;
+    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
+    const LtSpan outs[3] = {{v_dev, eb}, {d0_dev, eb}, {masked_dev, 2 * eb}};
+    LtSpan ins[11] = {{opened_dev, 5 * eb}, {u_dev, eb}, {s_bits_dev, L * eb}};
+    for (int k = 0; k < 8; k++) ins[3 + k] = {trip[k], eb};
+    if (!lt_outputs_apart(outs, 3, ins, 11)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: the outputs are arrays of their own");
+    LT_BLOCKS(ctx, "hb_lt_mid");
+#define LT_MID(NL, NW, P)                                                                                                                                       \
+    k_lt_mid<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, U32(opened_dev), U32(u_dev), U32(s_bits_dev), L, U32(pa_dev), U32(qa_dev), U32(pqa_dev), U32(pb_dev),        \
+                                                      U32(qb_dev), U32(pqb_dev), U32(pc_dev), U32(qc_dev), (uint32_t *)v_dev, (uint32_t *)d0_dev, (uint32_t *)masked_dev, count)
+    HB_DISPATCH(ctx, (LT_MID(9, 8, ctx->pw)), (LT_MID(3, 2, ctx->pn)));
+#undef LT_MID
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
+int hb_lt_xor_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *v_dev, const uint64_t *p_dev, const uint64_t *q_dev,
+                     const uint64_t *pq_dev, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
+    if (!ctx || count < 0 || (count > 0 && (!opened_dev || !u_dev || !v_dev || !p_dev || !q_dev || !pq_dev || !out_dev))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
+    const LtSpan outs[1] = {{out_dev, eb}}, ins[6] = {{opened_dev, 2 * eb}, {u_dev, eb}, {v_dev, eb}, {p_dev, eb}, {q_dev, eb}, {pq_dev, eb}};
+    if (!lt_outputs_apart(outs, 1, ins, 6)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_finish: out is an array of its own");
+    LT_BLOCKS(ctx, "hb_lt_xor_finish");
+    HB_DISPATCH(ctx,
+        (k_lt_xor_finish<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, U32(opened_dev), U32(u_dev), U32(v_dev), U32(p_dev), U32(q_dev), U32(pq_dev), (uint32_t *)out_dev, count)),
+        (k_lt_xor_finish<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, U32(opened_dev), U32(u_dev), U32(v_dev), U32(p_dev), U32(q_dev), U32(pq_dev), (uint32_t *)out_dev, count)));
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
+int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
+    if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
+    const int64_t L = params[0], mode = params[1];
+    int n_ops = 0, n_outs = 1, optional = -1;
+    bool needs_L = false;
+    switch (what) {
+    case HB_LT_SELFTEST_MASK: n_ops = 3; optional = 1; break;
+    case HB_LT_SELFTEST_LEAVES: n_ops = 2; n_outs = 2; needs_L = true; if (!lt_mode_ok((int)(mode < 0 || mode > 1 ? -1 : mode))) return HB_ERR_BAD_ARG; break;
+    case HB_LT_SELFTEST_XOR_MASK: n_ops = 5; n_outs = 2; break;
+    case HB_LT_SELFTEST_DMASK: n_ops = 9; n_outs = 2; needs_L = true; break;
+    case HB_LT_SELFTEST_MID: n_ops = 11; n_outs = 3; needs_L = true; break;
+    case HB_LT_SELFTEST_XOR_FINISH: n_ops = 6; break;
+    default: return HB_ERR_BAD_ARG;
+    }
+    if (needs_L && L != lt_modulus_bits(p_limbs, n_limbs)) return HB_ERR_BAD_ARG;
+    for (int i = 0; i < n_ops; i++) if (count > 0 && !operands[i] && i != optional) return HB_ERR_BAD_ARG;
+    for (int i = 0; i < n_outs; i++) if (count > 0 && !outs[i]) return HB_ERR_BAD_ARG;
+    if (n_limbs == 4) return selftest_lt<9, 8>(p_limbs, what, operands, params, outs, count);
+    return selftest_lt<3, 2>(p_limbs, what, operands, params, outs, count);
+}
+
+#undef LT_L_OK
+#undef U32
+#undef LT_BLOCKS
+}  // extern "C"

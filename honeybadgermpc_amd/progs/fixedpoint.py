@@ -38,6 +38,7 @@ never used).  Levels take their rows one after the other from row 0.
 Protocol level, coroutines over an OpenCoalescer (every party runs the same coroutine, so the opens meet batch for batch):
 
     async trunc_pr(co, x, bits, k, m, kappa)            1 open, 2 launches                        [x / 2^m] rounded up or down   :108-120
+    async carry_tree(co, g, p, triples)                 carry_levels(nodes - 1) opens, 2 per level the root's g of given leaf planes
     async get_carry_bit(co, c, r_bits, triples)         carry_levels(m) opens, 1 + 2 per level    carry of c2 + (2^m - 1 - r) + 1   :131-150
     async bit_ltl(co, c, r_bits, triples)               the same, + 2 launches                    [c2 < r]                       :163-172
     async div2m(co, x, bits, triples, k, m, kappa)      1 + carry_levels(m) opens                 [x mod 2^m]                    :184-193
@@ -345,6 +346,15 @@ async def _carry_tree(co, g, p, triples, m):
             return res
         g, p = res
         nodes, off = (nodes + 1) // 2, off + n
+
+
+async def carry_tree(co, g, p, triples):
+    """Shares of the g at the root of (g1, p1) o (g2, p2) = (g1 + p1 g2, p1 p2) over the leaf planes g, p, (2 <= nodes <= 257, count,
+    limbs) each, most significant first: the level loop of get_carry_bit for leaves made elsewhere (share_comparison.less_than).
+    carry_levels(nodes - 1) opens, carry_triples(nodes - 1) rows of triples."""
+    ctx = co.ctx
+    g, p, nodes, count, _, _ = _level(ctx, g, p, False)
+    return await _carry_tree(co, g, p, _triples(ctx, triples, carry_triples(nodes - 1), count), nodes - 1)
 
 
 async def get_carry_bit(co, c, r_bits, triples):

@@ -1,7 +1,9 @@
 """
-Equality of shared values on the device (csrc/hb_eq.hip): the reference's Equality mixin, progs/mixins/share_comparison.py:9-80 -- the
-probabilistic Legendre-symbol test behind Share.__eq__ -- for whole share arrays, on the (count, limbs) int64 tensors the rest of the
-package speaks.  (LessThan, :83-212, is not here: progs.fixedpoint.lt is the ordered comparison.)
+Comparison of shared values on the device: the two mixins of the reference's progs/mixins/share_comparison.py for whole share arrays, on
+the (count, limbs) int64 tensors the rest of the package speaks.  Equality (:9-80, the probabilistic Legendre-symbol test behind
+Share.__eq__) is csrc/hb_eq.hip and the first half of this module; LessThan (:83-212, Reistad's comparison behind Share.__lt__) is
+csrc/hb_lt.hip and the second half, below under "Less-than".  (progs.fixedpoint.lt is the ordered comparison of SIGNED k-bit values
+with k + kappa + 2 <= bit_length(p); less_than compares any two residues below (p - 1) / 2.)
 
 For a pair with diff = x - y, test bit j draws a bit share [b] and two random shares [r], [rp], opens
 
@@ -53,13 +55,50 @@ pass of the three opens, on the spare rows the caller supplied beyond the counts
 take the next f rows of `bits`, the next 2 f rows of `rands` (f for r, then f for rp) and the next 3 f rows of each triple plane (f for
 diff r, f for rp rp, f for _b rp^2).  Without enough spares: exceptions.PreprocessingExhausted.  Over a 255-bit field this does not
 happen by chance.
+
+Less-than.  L = bit_length(p), z = a - b.  The protocol opens c = 2 z + r with r a dealt random residue whose bit shares r_0 .. r_{L-1}
+are dealt with it (the reference's get_share_bits), and [a < b] = c_0 xor r_0 xor [r > c] (:206-212).  c_i is public, so the terms of
+the reference's x = sum_i r_i (1 - c_i) prod_{j>i} (1 + (r_j xor c_j)) (_compute_x, :137-163) are affine in [r_i]: x is the g at the
+root of fixedpoint's carry tree, (g1, p1) o (g2, p2) = (g1 + p1 g2, p1 p2), over leaves that cost no triple.  Two modes:
+
+    DIRECT (default)  leaves c_i = 0 -> (r_i, 1 - r_i), c_i = 1 -> (0, r_i): the root's g is [r > c] itself, a bit; one product for the
+                      last xor.  2 L - 2 triples, 2 + ceil(log2 L) opens.
+    REFERENCE         leaves c_i = 0 -> (r_i, 1 + r_i), c_i = 1 -> (0, 2 - r_i): the root's g is the reference's x, whose least
+                      significant bit is [r > c].  The reference's _extract_lsb (:167-202) follows: a second dealt s with bit
+                      shares, d = s + x opened, [d_0] by a four-way select on s_{L-1}, s_{L-2}, x_0 = s_0 xor d_0.  xor is a symmetric
+                      polynomial, so (c_0 xor r_0) xor (s_0 xor d_0) is evaluated as ((c_0 xor r_0) xor s_0) xor d_0 and opens to the
+                      same value: the products u s_0 and s_1 s_2 do not wait for d, and their masked operands travel in d's open.
+                      2 L triples, 3 + ceil(log2 L) opens.  It opens what the reference opens: c, d and the result.
+
+The reference computes x by a chain of L - 1 dependent products and L more, one open each: about 2 L = 510 triples and more than 255
+rounds a comparison over the BLS12-381 scalar field, against 508 triples and 10 rounds (DIRECT) here.
+
+    less_than_model(a, b, r, s, p, mode)                 -> {"c", "x" | "w", "d" (REFERENCE), "out"}: the reference line by line on ints
+    less_than_triples(L, mode) = 2 L - 2 | 2 L           triples an element
+    less_than_opens(L, mode)   = 2 | 3 + ceil(log2 L)    coalesced batches for any count: 10 | 11 over BLS12-381, 8 | 9 over 64 bits
+
+    lt_mask(ctx, a, b, r)                                -> 2 (a - b) + r, the array to open (b None: 2 a + r)
+    lt_leaves(ctx, c, r_bits, mode)                      -> (g, p), (L, count, limbs) each, most significant bit first; no product
+    lt_xor_mask(ctx, c, r0, w, pa, qa)                   DIRECT -> (u, (2, count, limbs): u - pa, w - qa); u = c_0 xor r_0, r0 = r_bits[0]
+    lt_dmask(ctx, c, r0, x, s, s_bits, pa, qa, pb, qb)   REFERENCE -> (u, (5, count, limbs): s + x, u - pa, s_0 - qa, s_1 - pb, s_2 - qb)
+    lt_mid(ctx, opened, u, s_bits, ta, tb, pc, qc)       REFERENCE -> (v, d_0, (2, count, limbs): v - pc, d_0 - qc); v = u xor s_0
+    lt_xor_finish(ctx, opened, u, v, t)                  -> u + v - 2 [u v]
+
+    async less_than(co, a, b, r, r_bits, triples, s=None, s_bits=None, mode=DIRECT)     shares of [a < b]      :206-212
+
+r, s are (count, limbs); r_bits, s_bits (L, count, limbs), least significant bit first; `triples = (p, q, pq)`, each (at least
+less_than_triples, count, limbs): rows [0, 2 L - 3) are the tree's, in the order progs.fixedpoint documents for L leaves; then DIRECT
+takes one row for the last xor, REFERENCE three: u s_0, s_1 s_2, the last xor.
 """
-from ._capi import HB_EQ_BIT, HB_EQ_REFERENCE
+from ._capi import HB_EQ_BIT, HB_EQ_REFERENCE, HB_LT_DIRECT, HB_LT_REFERENCE
 from .exceptions import PreprocessingExhausted
+from .progs.fixedpoint import carry_tree
 from .share_arithmetic import beaver_multiply_arrays
 
 KAPPA = 32
 BIT, REFERENCE = HB_EQ_BIT, HB_EQ_REFERENCE
+DIRECT = HB_LT_DIRECT
+assert HB_LT_REFERENCE == REFERENCE
 
 
 # ---- host functions ------------------------------------------------------------------------------------------------------
@@ -327,3 +366,213 @@ async def equal(co, x, y, bits, rands, triples, kappa=KAPPA, nr=None, mode=BIT):
 async def is_zero(co, x, bits, rands, triples, kappa=KAPPA, nr=None, mode=BIT):
     """Shares of [x == 0]: equal() with no second operand"""
     return await equal(co, x, None, bits, rands, triples, kappa, nr, mode)
+
+
+# ---- less-than: host functions ---------------------------------------------------------------------------------------------
+def _check_lt_mode(mode):
+    if mode not in (DIRECT, REFERENCE) or isinstance(mode, bool):
+        raise ValueError(f"mode must be DIRECT or REFERENCE, got {mode!r}")
+
+
+def _bit_length(L):
+    if not isinstance(L, int) or isinstance(L, bool) or L < 2:
+        raise ValueError(f"L must be an integer of at least 2, got {L!r}")
+    return L
+
+
+def less_than_triples(L, mode=DIRECT):
+    """triples an element: 2 L - 3 for the tree over L leaves, then one (DIRECT) or three (REFERENCE)"""
+    _check_lt_mode(mode)
+    return 2 * _bit_length(L) - (2 if mode == DIRECT else 0)
+
+
+def less_than_opens(L, mode=DIRECT):
+    """coalesced batches of one less_than(): c, ceil(log2 L) tree levels, (REFERENCE: d,) the last xor"""
+    _check_lt_mode(mode)
+    return (2 if mode == DIRECT else 3) + (_bit_length(L) - 1).bit_length()
+
+
+def less_than_model(a, b, r, s, p, mode=DIRECT):
+    """what less_than opens to for one pair, on Python ints with the dealt r (and s) as inputs: the reference's _prog line by line
+    (share_comparison.py:117-212), no tree.  -> {"c", "x", "d", "out"} in REFERENCE, {"c", "w", "out"} in DIRECT, which ignores s:
+    w = r_i at the most significant bit where r_i != c_i, that is [r > c] (:140-143)."""
+    _check_lt_mode(mode)
+    L = p.bit_length()
+    xor = lambda u, v: (u + v - 2 * u * v) % p                                              # noqa: E731    _xor_bits, :110-113
+    bits = lambda v: [(v >> i) & 1 for i in range(L)]                                       # noqa: E731    least significant first
+    # _transform_comparison, :117-133
+    z = (a - b) % p
+    c = (2 * z + r) % p
+    r_bits, c_bits = bits(r % p), bits(c)
+    lead = xor(c_bits[0], r_bits[0])
+    if mode == DIRECT:
+        w = next((rb for rb, cb in zip(reversed(r_bits), reversed(c_bits)) if rb != cb), 0)
+        return {"c": c, "w": w, "out": xor(lead, w)}
+    # _compute_x, :137-163
+    power_bits = [(1 + xor(rb, cb)) % p for rb, cb in zip(r_bits[1:], c_bits[1:])]
+    powers = [1]
+    for pb in reversed(power_bits):
+        powers.insert(0, pb * powers[0] % p)
+    x = 0
+    for r_i, c_i, pw in zip(r_bits, c_bits, powers):
+        x = (x + r_i * (1 - c_i) * pw) % p
+    # _extract_lsb, :167-202
+    s_bits = bits(s % p)
+    d = (s + x) % p
+    s_0, s_1, s_2 = s_bits[0], s_bits[L - 1], s_bits[L - 2]
+    s_prod = s_1 * s_2
+    d0 = d & 1
+    d_xor_1 = d0 ^ (d < (1 << (L - 1)))
+    d_xor_2 = d0 ^ (d < (1 << (L - 2)))
+    d_xor_12 = d0 ^ (d < ((1 << (L - 1)) + (1 << (L - 2))))
+    d_0 = ((1 - s_1 - s_2 + s_prod) * d0 + (s_2 - s_prod) * d_xor_2 + (s_1 - s_prod) * d_xor_1 + s_prod * d_xor_12) % p
+    x_0 = xor(s_0, d_0)
+    # _prog, :206-212
+    return {"c": c, "x": x, "d": d, "out": xor(lead, x_0)}
+
+
+# ---- less-than: tensor level -----------------------------------------------------------------------------------------------
+def _lt_elems(ctx, count, *named):
+    return tuple(ctx.elems(v, count, what=w) for v, w in named)
+
+
+def _lt_bits(ctx, t, count, what):
+    L = ctx.modulus.bit_length()
+    return _planes(ctx, t, L, count, what), L
+
+
+def _lt_triple(ctx, t, count, what):
+    try:
+        p, q, pq = t
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: expected (p, q, pq)") from None
+    return _lt_elems(ctx, count, (p, f"{what} p"), (q, f"{what} q"), (pq, f"{what} pq"))
+
+
+def lt_mask(ctx, a, b, r):
+    """-> 2 (a - b) + r, the array to open (share_comparison.py:122-127); b None: 2 a + r.  The inputs are left untouched."""
+    a = ctx.elems(a, what="a")
+    count = a.numel() // ctx.n_limbs
+    if b is not None:
+        b = ctx.elems(b, count, what="b")
+    r = ctx.elems(r, count, what="r")
+    out = ctx.empty(count)
+    ctx.check(ctx.lib.hb_lt_mask(ctx.h, ctx.ptr(a), None if b is None else ctx.ptr(b), ctx.ptr(r), ctx.ptr(out), count, ctx.stream()), "hb_lt_mask")
+    return out
+
+
+def lt_leaves(ctx, c, r_bits, mode=DIRECT):
+    """-> (g, p), (L, count, limbs) each: the leaves of the tree for the opened c against the bit shares r_bits (L, count, limbs), least
+    significant first; the leaves are ordered most significant bit first.  No triple, no open: a public bit selects."""
+    _check_lt_mode(mode)
+    c = ctx.elems(c, what="c")
+    count = c.numel() // ctx.n_limbs
+    r_bits, L = _lt_bits(ctx, r_bits, count, "r_bits")
+    g, p = _new(ctx, L, count), _new(ctx, L, count)
+    ctx.check(ctx.lib.hb_lt_leaves(ctx.h, ctx.ptr(c), ctx.ptr(r_bits), L, mode, ctx.ptr(g), ctx.ptr(p), count, ctx.stream()), "hb_lt_leaves")
+    return g, p
+
+
+def lt_xor_mask(ctx, c, r0, w, pa, qa):
+    """DIRECT, after the tree: w = [r > c], r0 = r_bits[0]; pa, qa the factors of the last triple.  -> (u, masked): u = c_0 xor r_0
+    (count, limbs) and (2, count, limbs) = u - pa, w - qa, the array to open."""
+    c = ctx.elems(c, what="c")
+    count = c.numel() // ctx.n_limbs
+    r0, w, pa, qa = _lt_elems(ctx, count, (r0, "r0"), (w, "w"), (pa, "pa"), (qa, "qa"))
+    u, masked = ctx.empty(count), _new(ctx, 2, count)
+    ctx.check(ctx.lib.hb_lt_xor_mask(ctx.h, ctx.ptr(c), ctx.ptr(r0), ctx.ptr(w), ctx.ptr(pa), ctx.ptr(qa), ctx.ptr(u), ctx.ptr(masked), count, ctx.stream()), "hb_lt_xor_mask")
+    return u, masked
+
+
+def lt_dmask(ctx, c, r0, x, s, s_bits, pa, qa, pb, qb):
+    """REFERENCE, after the tree: x the root's g, s and s_bits (L, count, limbs) the second mask; (pa, qa), (pb, qb) the factors of the
+    triples for u s_0 and s_1 s_2.  -> (u, masked): (5, count, limbs) = s + x, u - pa, s_0 - qa, s_1 - pb, s_2 - qb with s_0, s_1, s_2
+    planes 0, L - 1, L - 2 of s_bits (share_comparison.py:178-182), ONE array to open."""
+    c = ctx.elems(c, what="c")
+    count = c.numel() // ctx.n_limbs
+    r0, x, s, pa, qa, pb, qb = _lt_elems(ctx, count, (r0, "r0"), (x, "x"), (s, "s"), (pa, "pa"), (qa, "qa"), (pb, "pb"), (qb, "qb"))
+    s_bits, L = _lt_bits(ctx, s_bits, count, "s_bits")
+    u, masked = ctx.empty(count), _new(ctx, 5, count)
+    ctx.check(ctx.lib.hb_lt_dmask(ctx.h, ctx.ptr(c), ctx.ptr(r0), ctx.ptr(x), ctx.ptr(s), ctx.ptr(s_bits), L, ctx.ptr(pa), ctx.ptr(qa), ctx.ptr(pb), ctx.ptr(qb),
+                                  ctx.ptr(u), ctx.ptr(masked), count, ctx.stream()), "hb_lt_dmask")
+    return u, masked
+
+
+def lt_mid(ctx, opened, u, s_bits, ta, tb, pc, qc):
+    """REFERENCE, after d's open.  opened: the array of lt_dmask, opened ((5, count, limbs), or flat as an open returns it); ta, tb =
+    (p, q, pq): the triples for u s_0 and s_1 s_2; pc, qc the factors of the last triple.  -> (v, d_0, masked): v = u xor s_0, [d_0] by
+    the reference's select (share_comparison.py:186-199) and (2, count, limbs) = v - pc, d_0 - qc, the array to open."""
+    u = ctx.elems(u, what="u")
+    count = u.numel() // ctx.n_limbs
+    opened = ctx.elems(opened, 5 * count, what="opened")
+    s_bits, L = _lt_bits(ctx, s_bits, count, "s_bits")
+    ta, tb = _lt_triple(ctx, ta, count, "ta"), _lt_triple(ctx, tb, count, "tb")
+    pc, qc = _lt_elems(ctx, count, (pc, "pc"), (qc, "qc"))
+    v, d0, masked = ctx.empty(count), ctx.empty(count), _new(ctx, 2, count)
+    ctx.check(ctx.lib.hb_lt_mid(ctx.h, ctx.ptr(opened), ctx.ptr(u), ctx.ptr(s_bits), L, *(ctx.ptr(t) for t in ta), *(ctx.ptr(t) for t in tb), ctx.ptr(pc), ctx.ptr(qc),
+                                ctx.ptr(v), ctx.ptr(d0), ctx.ptr(masked), count, ctx.stream()), "hb_lt_mid")
+    return v, d0, masked
+
+
+def lt_xor_finish(ctx, opened, u, v, t):
+    """After the last open: -> u + v - 2 [u v] (share_comparison.py:110-113).  opened: (2, count, limbs) = u - p, v - q opened (or
+    flat); t = (p, q, pq) the triple.  REFERENCE hands in lt_mid's v and d_0."""
+    u = ctx.elems(u, what="u")
+    count = u.numel() // ctx.n_limbs
+    v, = _lt_elems(ctx, count, (v, "v"))
+    opened = ctx.elems(opened, 2 * count, what="opened")
+    t = _lt_triple(ctx, t, count, "t")
+    out = ctx.empty(count)
+    ctx.check(ctx.lib.hb_lt_xor_finish(ctx.h, ctx.ptr(opened), ctx.ptr(u), ctx.ptr(v), *(ctx.ptr(w) for w in t), ctx.ptr(out), count, ctx.stream()), "hb_lt_xor_finish")
+    return out
+
+
+# ---- less-than: the protocol -----------------------------------------------------------------------------------------------
+async def less_than(co, a, b, r, r_bits, triples, s=None, s_bits=None, mode=DIRECT):
+    """Shares of [a < b] element by element (LessThan._prog, share_comparison.py:206-212): 1 where a < b, else 0.
+
+    Precondition: a, b < (p - 1) / 2, as the reference requires (:85, :95).  For other inputs the result is what less_than_model
+    gives, which is wrong for about a quarter of the pairs drawn from the whole field.  The only other exception is a mask within
+    about 2^(number of bits in which the operands differ) of the wrap -- r so close to p that c = 2 (a - b) + r wraps differently
+    from the bits dealt, or (REFERENCE) s so close that s + x does -- which is negligible over a 255-bit field.
+
+    r (count, limbs) and r_bits (L, count, limbs), least significant first, L = bit_length(p): a dealt random residue and its bit
+    shares; REFERENCE needs a second pair s, s_bits (ValueError without them; DIRECT ignores them).  less_than_opens(L, mode)
+    batches for any count, less_than_triples(L, mode) rows of triples an element (see the module's header for their order).
+    b None: z = a, that is [a < 0] read as the reference reads it: 1 where a >= (p + 1) / 2.  The inputs are left untouched."""
+    ctx = co.ctx
+    _check_lt_mode(mode)
+    if mode == REFERENCE and (s is None or s_bits is None):
+        raise ValueError("mode REFERENCE needs the second mask: s and s_bits")
+    a = ctx.elems(a, what="a")
+    count = a.numel() // ctx.n_limbs
+    if b is not None:
+        b = ctx.elems(b, count, what="b")
+    r = ctx.elems(r, count, what="r")
+    r_bits, L = _lt_bits(ctx, r_bits, count, "r_bits")
+    if mode == REFERENCE:
+        s = ctx.elems(s, count, what="s")
+        s_bits, _ = _lt_bits(ctx, s_bits, count, "s_bits")
+    try:
+        tp, tq, tpq = triples
+    except (TypeError, ValueError):
+        raise ValueError("triples: expected (p, q, pq)") from None
+    trip = tuple(_planes(ctx, v, less_than_triples(L, mode), count, w, exact=False) for v, w in ((tp, "triples p"), (tq, "triples q"), (tpq, "triples pq")))
+    if count == 0:
+        return ctx.empty(0)
+    nt = 2 * L - 3
+    row = lambda k: tuple(v[k] for v in trip)                                               # noqa: E731
+    c = await co.open_share_array(lt_mask(ctx, a, b, r))
+    g, p = lt_leaves(ctx, c, r_bits, mode)
+    root = await carry_tree(co, g, p, tuple(v[:nt] for v in trip))
+    if mode == DIRECT:
+        t = row(nt)
+        u, masked = lt_xor_mask(ctx, c, r_bits[0], root, t[0], t[1])
+        opened = await co.open_share_array(masked.view(2 * count, ctx.n_limbs))
+        return lt_xor_finish(ctx, opened, u, root, t)
+    ta, tb, tc = row(nt), row(nt + 1), row(nt + 2)
+    u, masked = lt_dmask(ctx, c, r_bits[0], root, s, s_bits, ta[0], ta[1], tb[0], tb[1])
+    opened = await co.open_share_array(masked.view(5 * count, ctx.n_limbs))
+    v, d0, masked2 = lt_mid(ctx, opened, u, s_bits, ta, tb, tc[0], tc[1])
+    opened2 = await co.open_share_array(masked2.view(2 * count, ctx.n_limbs))
+    return lt_xor_finish(ctx, opened2, v, d0, tc)

@@ -354,6 +354,44 @@ int hb_eq_cshare(hb_ctx *ctx, const uint64_t *opened2_dev, const uint64_t *dr_de
 int hb_eq_finish(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int mode, const uint64_t *nr_host, uint64_t *factor_dev,
                  int32_t *zero_rows_dev, int rows, int64_t count, void *stream);
 
+/* ---- less-than of shared field elements (hb_lt.hip) ----------------------------------------------------------------------
+ * The LessThan mixin of progs/mixins/share_comparison.py:83-212 (Reistad 2007) for arrays of `count` pairs a, b < (p - 1) / 2.
+ * Everywhere: operands and results are canonical residues, L is the bit length of the modulus (anything else: HB_ERR_BAD_ARG), bit
+ * shares arrive as planes [L][count], row i this party's shares of bit i (least significant first) of every element's mask; arrays
+ * of several rows are row-major with `count` elements a row.  The protocol opens c = 2 (a - b) + r and [a < b] = c_0 xor r_0 xor
+ * [r > c]; the tree between hb_lt_leaves and the steps after it is hb_fxp_carry_mask / hb_fxp_carry_combine over L rows.
+ * hb_lt_mask: masked_dev[i] = 2 (a_i - b_i) + r_i, the array to open (b_dev == NULL: 2 a_i + r_i).
+ * hb_lt_leaves: g_dev, p_dev [L][count], row j for bit i = L - 1 - j of the opened c against row i of r_bits_dev, no product:
+ *   HB_LT_DIRECT     c_i = 0: (r_i, 1 - r_i); c_i = 1: (0, r_i).      The root's g is [r > c], a bit.
+ *   HB_LT_REFERENCE  c_i = 0: (r_i, 1 + r_i); c_i = 1: (0, 2 - r_i).  The root's g is the reference's x (_compute_x, :137-163).
+ * hb_lt_xor_mask (DIRECT, w_dev the root's g): u_dev[i] = c_0 ? 1 - r_0 : r_0 (r0_dev: row 0 of the bit planes) and masked_dev
+ *   [2][count] = u - pa, w - qa, the array to open before the product u w.
+ * hb_lt_dmask (REFERENCE, x_dev the root's g; s_dev, s_bits_dev the second mask and its bit planes): u_dev as above and masked_dev
+ *   [5][count] = s + x, u - pa, s_0 - qa, s_1 - pb, s_2 - qb with s_0, s_1, s_2 rows 0, L - 1, L - 2 of s_bits_dev (:178-182): ONE
+ *   array to open, d = s + x and the masked operands of u s_0 (triple a) and s_1 s_2 (triple b).
+ * hb_lt_mid: opened_dev = that array opened.  v_dev = u + s_0 - 2 [u s_0], d0_dev = the reference's [d_0] (:186-199), masked_dev
+ *   [2][count] = v - pc, d_0 - qc, the array to open before the product v d_0 (triple c).
+ * hb_lt_xor_finish (both modes): opened_dev [2][count] = the last array opened; out = u + v - 2 [u v] with the triple (p, q, pq) whose
+ *   factors masked u and v (REFERENCE: u_dev, v_dev are hb_lt_mid's v_dev, d0_dev).
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  Every output is an array of its own: one that overlaps
+ * an input or another output is HB_ERR_BAD_ARG, as are null pointers (with count > 0), a negative count and an unknown mode, before
+ * any launch.  count == 0 returns HB_OK and launches nothing. */
+#define HB_LT_DIRECT 0
+#define HB_LT_REFERENCE 1
+int hb_lt_mask(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *r_dev, uint64_t *masked_dev, int64_t count, void *stream);
+int hb_lt_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r_bits_dev, int L, int mode, uint64_t *g_dev, uint64_t *p_dev, int64_t count,
+                 void *stream);
+int hb_lt_xor_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *w_dev, const uint64_t *pa_dev, const uint64_t *qa_dev,
+                   uint64_t *u_dev, uint64_t *masked_dev, int64_t count, void *stream);
+int hb_lt_dmask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *x_dev, const uint64_t *s_dev, const uint64_t *s_bits_dev, int L,
+                const uint64_t *pa_dev, const uint64_t *qa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev, uint64_t *u_dev, uint64_t *masked_dev,
+                int64_t count, void *stream);
+int hb_lt_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *s_bits_dev, int L, const uint64_t *pa_dev,
+              const uint64_t *qa_dev, const uint64_t *pqa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev, const uint64_t *pqb_dev, const uint64_t *pc_dev,
+              const uint64_t *qc_dev, uint64_t *v_dev, uint64_t *d0_dev, uint64_t *masked_dev, int64_t count, void *stream);
+int hb_lt_xor_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *v_dev, const uint64_t *p_dev, const uint64_t *q_dev,
+                     const uint64_t *pq_dev, uint64_t *out_dev, int64_t count, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip)-------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -698,6 +736,23 @@ int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 #define HB_EQ_SELFTEST_CSHARE 3
 #define HB_EQ_SELFTEST_FINISH 4
 int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, void *const *outs,
+                   int64_t count);
+/* host-side run of the less-than kernels' bodies (no GPU needed) over host memory, element by element.  params = {L, mode}; L and
+ * the mode are checked as the device calls check them where the step reads them:
+ *   what = HB_LT_SELFTEST_MASK        operands[0..2] = a, b (or NULL), r; outs[0]
+ *          HB_LT_SELFTEST_LEAVES      operands[0..1] = c, r_bits [L][count]; outs[0..1] = g, p [L][count]
+ *          HB_LT_SELFTEST_XOR_MASK    operands[0..4] = c, r_0, w, pa, qa; outs[0..1] = u, masked [2][count]
+ *          HB_LT_SELFTEST_DMASK       operands[0..8] = c, r_0, x, s, s_bits [L][count], pa, qa, pb, qb; outs[0..1] = u, masked [5][count]
+ *          HB_LT_SELFTEST_MID         operands[0..10] = opened [5][count], u, s_bits [L][count], pa, qa, pqa, pb, qb, pqb, pc, qc;
+ *                                     outs[0..2] = v, d_0, masked [2][count]
+ *          HB_LT_SELFTEST_XOR_FINISH  operands[0..5] = opened [2][count], u, v, p, q, pq; outs[0] */
+#define HB_LT_SELFTEST_MASK 0
+#define HB_LT_SELFTEST_LEAVES 1
+#define HB_LT_SELFTEST_XOR_MASK 2
+#define HB_LT_SELFTEST_DMASK 3
+#define HB_LT_SELFTEST_MID 4
+#define HB_LT_SELFTEST_XOR_FINISH 5
+int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs,
                    int64_t count);
 /* host-side run of the root-finding kernels' bodies (no GPU needed) over host memory, phase by phase as the kernels' workgroups walk
  * them.  For tests only: not a fallback.
