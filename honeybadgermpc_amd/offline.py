@@ -13,12 +13,26 @@ batches, no new arithmetic.
 
 * extract_at_omega_powers -- the randomness extractor of progs/random_refinement.py for any number of contribution vectors.
 
+The protocol that makes preprocessing among the parties (reference offline_randousha.py; csrc/hb_off.hip):
+
+* randousha         -- (n - 2t) k pairs (r_t, r_2t) of sharings of random values nobody knows (:34-151)
+* generate_triples  -- k Beaver triples by degree reduction (:154-191)
+* generate_bits     -- k shared random bits, as +-1 or as 0 / 1 (:194-232)
+* mul_add, invsqrt_scale, degree_check -- the three kernels on tensors; invsqrt_model, degree_check_model -- on Python ints
+
 Element layout as in honeybadgermpc_amd.device: int64 tensors (count, 4), little-endian limbs.
 """
+import asyncio
 import ctypes
 
-from ._capi import Context, HbView, np_ptr
+import numpy as np
+
+from . import wire
+from ._capi import HB_OFF_01, HB_OFF_PM1, Context, HbView, np_ptr
 from .device import BatchOpen
+from .exceptions import HoneyBadgerMPCError
+
+PM1, ZERO_ONE = HB_OFF_PM1, HB_OFF_01            # generate_bits' encodings: a share of +-1 (the reference's) or of 0 / 1
 
 
 def random_elements(modulus, count, generator=None, device=None):
@@ -57,13 +71,14 @@ def random_elements(modulus, count, generator=None, device=None):
 
 
 class ShareDealer:
-    """deal(coeffs): [k][t+1] coefficient rows (flat (k (t+1), 4) tensor) -> [n][k] shares, row i = party i.
+    """deal(coeffs): [k][degree+1] coefficient rows (flat (k (degree+1), 4) tensor) -> [n][k] shares, row i = party i.
 
     It is the R1 encode of the batch open: the matrix-core path when the shape qualifies."""
 
-    def __init__(self, modulus, n, t, max_polys=1 << 16, device=None):
-        self.n, self.t, self.d = n, t, t + 1
-        self.op = BatchOpen(modulus, n, t, max_shares=max_polys * (t + 1), device=device)
+    def __init__(self, modulus, n, t, max_polys=1 << 16, device=None, degree=None):
+        """degree: of the dealt polynomials (default t; RanDouSha also deals at 2 t)"""
+        self.n, self.t, self.d = n, t, (t if degree is None else degree) + 1
+        self.op = BatchOpen(modulus, n, t, degree=degree, max_shares=max_polys * self.d, device=device)
         self.ctx = self.op.ctx
 
     def deal(self, coeffs, out=None):
@@ -71,7 +86,7 @@ class ShareDealer:
         return self.op.r1_encode(coeffs, out=out)
 
     def deal_secrets(self, secrets, generator=None):
-        """Random degree-t polynomials with the given constant terms (a (k, 4) tensor) -> ([n][k] shares, coeffs)."""
+        """Random polynomials of the dealer's degree with the given constant terms (a (k, 4) tensor) -> ([n][k] shares, coeffs)."""
         k = secrets.shape[0]
         coeffs = random_elements(self.ctx.modulus, k * self.d, generator, self.ctx.device).view(k, self.d, self.ctx.n_limbs)
         coeffs[:, 0, :] = secrets
@@ -153,3 +168,289 @@ def extract_at_omega_powers(field, n, t, batches):
         for i, row in zip(which, codec.encode([list(batches[i]) for i in which])):
             out[i] = row[: k - t]
     return out
+
+
+# ---- the offline phase among the parties (reference offline_randousha.py) --------------------------------------------------------
+def _tonelli_constants(p):
+    """p - 1 = q 2^s and c = z^q for the smallest non-residue z >= 2 (csrc/hb_sqrt.hip's choice) -> (q, s, c)"""
+    q, s = p - 1, 0
+    while q % 2 == 0:
+        q //= 2
+        s += 1
+    z = 2
+    while pow(z, (p - 1) // 2, p) != p - 1:
+        z += 1
+    return q, s, pow(z, q, p)
+
+
+def invsqrt_model(x, p):
+    """x^(-1/2) mod p on Python ints as hb_off_invsqrt_scale defines it: w = x^((q-1)/2) c^e with the unique e in [0, 2^(s-1))
+    for which x^q c^(2e) = 1 -> (w, status); status 0, or 1 for x = 0 and 2 for a non-residue (w = 0 for both)."""
+    x %= p
+    if x == 0:
+        return 0, 1
+    q, s, c = _tonelli_constants(p)
+    t = pow(x, q, p)
+    if pow(t, 1 << (s - 1), p) != 1:              # the order of x^q is the full 2^s: no even power of c cancels it
+        return 0, 2
+    e = 0
+    for i in range(s - 1):                        # bit i of e: t c^(2 e_low) has order dividing 2^(s-1-i); is it 2^(s-1-i) itself?
+        if pow(t * pow(c, 2 * e, p) % p, 1 << (s - 2 - i), p) != 1:
+            e |= 1 << i
+    assert t * pow(c, 2 * e, p) % p == 1
+    return pow(x, (q - 1) // 2, p) * pow(c, e, p) % p, 0
+
+
+def degree_check_model(coeffs, n, k, t):
+    """hb_off_degree_check on Python ints: coeffs [n][2k] flat, coefficient-major -> [not of exact degree t, not of exact degree 2t,
+    constants differ], counts over the k columns"""
+    bad = [0, 0, 0]
+    for j in range(k):
+        for which, (col, deg) in enumerate(((j, t), (k + j, 2 * t))):
+            poly = [coeffs[e * 2 * k + col] for e in range(n)]
+            bad[which] += poly[deg] == 0 or any(poly[deg + 1:])
+        bad[2] += coeffs[j] != coeffs[k + j]
+    return bad
+
+
+def _out_like(ctx, out, like, count):
+    if out is None:
+        return ctx.torch.empty_like(like)
+    if isinstance(out, ctx.torch.Tensor) and not out.is_contiguous():
+        raise ValueError("out: must be contiguous")
+    return ctx.elems(out, count, what="out")
+
+
+def mul_add(ctx, a, b, c, out=None):
+    """a b + c element by element in one launch (three reads, one write).  b may be a, and out may be any of the inputs."""
+    a = ctx.elems(a, what="a")
+    count = a.numel() // ctx.n_limbs
+    b, c = ctx.elems(b, count, what="b"), ctx.elems(c, count, what="c")
+    out = _out_like(ctx, out, a, count)
+    ctx.check(ctx.lib.hb_off_mul_add(ctx.h, ctx.ptr(a), ctx.ptr(b), ctx.ptr(c), ctx.ptr(out), count, ctx.stream()), "hb_off_mul_add")
+    return out
+
+
+def invsqrt_scale(ctx, x, u=None, mode=PM1, check=True, out=None):
+    """w = x^(-1/2) (invsqrt_model) of every public x, scaled onto the shares u: mode PM1 -> u w, ZERO_ONE -> (u w + 1) / 2; u None -> w.
+    check=True reads the two status words back -- one synchronisation -- and raises AssertionError when an x was zero or a
+    non-residue, as the reference's GFElement.sqrt does for both.  check=False -> (out, status): an int32 tensor [zeros,
+    non-residues] once the stream has got there; their outputs are 0 and the others are right either way.  Nothing synchronises."""
+    if mode not in (PM1, ZERO_ONE) or isinstance(mode, bool):
+        raise ValueError("mode: PM1 or ZERO_ONE")
+    x = ctx.elems(x, what="x")
+    count = x.numel() // ctx.n_limbs
+    if u is not None:
+        u = ctx.elems(u, count, what="u")
+    out = _out_like(ctx, out, x, count)
+    status = ctx.torch.zeros(2, dtype=ctx.torch.int32, device=ctx.tdev)
+    rc = ctx.lib.hb_off_invsqrt_scale(ctx.h, ctx.ptr(x), None if u is None else ctx.ptr(u), mode, ctx.ptr(out), count, ctx.ptr(status), ctx.stream())
+    ctx.check(rc, "hb_off_invsqrt_scale")
+    if not check:
+        return out, status
+    zeros, nonres = (int(v) for v in status.tolist())
+    if zeros or nonres:
+        raise AssertionError(f"no square root: {zeros} zeros and {nonres} non-residues among {count} values")
+    return out
+
+
+def degree_check(ctx, coeffs, n, t, check=True):
+    """The checkers' verdict on a coefficient-major [n][2k] block (degree_check_model).  check=True -> the three counts as ints (one
+    synchronisation); check=False -> the int32[3] tensor, nothing synchronises."""
+    coeffs = ctx.elems(coeffs, what="coeffs")
+    rows = coeffs.numel() // ctx.n_limbs
+    if n < 1 or t < 0 or 2 * t >= n or rows % (2 * n):
+        raise ValueError("coeffs: expected n rows of 2 k elements, 2 t < n")
+    counters = ctx.torch.zeros(3, dtype=ctx.torch.int32, device=ctx.tdev)
+    rc = ctx.lib.hb_off_degree_check(ctx.h, ctx.ptr(coeffs), n, rows // (2 * n), t, ctx.ptr(counters), ctx.stream())
+    ctx.check(rc, "hb_off_degree_check")
+    return tuple(int(v) for v in counters.tolist()) if check else counters
+
+
+class _Codec:
+    """what one party's RanDouSha needs per (field, n, t): the two dealers, the refinement and the inverse Vandermonde matrix"""
+
+    _cache = {}
+
+    @classmethod
+    def get(cls, ctx, n, t, k):
+        cap = 1 << max(10, (k - 1).bit_length())
+        key = (ctx.modulus, ctx.device, n, t)
+        self = cls._cache.get(key)
+        if self is None or self.cap < cap:
+            self = cls._cache[key] = cls(ctx, n, t, cap)
+        return self
+
+    def __init__(self, ctx, n, t, cap):
+        self.ctx, self.n, self.t, self.cap = ctx, n, t, cap
+        self.deal_t = ShareDealer(ctx.modulus, n, t, max_polys=cap, device=ctx.device)
+        self.deal_2t = ShareDealer(ctx.modulus, n, t, max_polys=cap, device=ctx.device, degree=2 * t)
+        self.hyper = HyperInvertible(ctx.modulus, n, device=ctx.device)
+        m = ctypes.c_void_p()
+        ctx.check(ctx.lib.hb_vand_inverse_create(ctx.h, np_ptr(self.hyper._xh), n, ctypes.byref(m), ctx.stream()), "hb_vand_inverse_create")
+        self._vinv = m
+
+    def interpolate(self, block, width):
+        """[n][width] values at the party points -> [n][width] coefficients, coefficient-major: one mat-vec, no transpose"""
+        out = self.ctx.empty(self.n * width)
+        view = HbView(1, width)
+        rc = self.ctx.lib.hb_matvec(self.ctx.h, self._vinv, self.ctx.ptr(block), view, None, self.ctx.ptr(out), view, width, self.ctx.stream())
+        self.ctx.check(rc, "hb_matvec")
+        return out
+
+    def __del__(self):
+        try:
+            self.ctx.lib.hb_matrix_destroy(self._vinv)
+        except Exception:
+            pass
+
+
+_SUCCESS, _ABORT = "S", "A"                       # HyperInvMessageType
+_INCONSISTENT = "Aborting because the shares were inconsistent."
+
+
+class _Verdicts:
+    """The H3 channel of one run, read from the start: a party still waiting for shares learns of an abort (a checker's, or a party's
+    that met a malformed message) instead of waiting for a message that will not come."""
+
+    def __init__(self, recv):
+        self.received, self.aborted = [], asyncio.Event()
+        self._more = asyncio.Event()
+        self._task = asyncio.ensure_future(self._pump(recv))
+
+    async def _pump(self, recv):
+        while True:
+            sender, msg = await recv()
+            self.received.append((sender, msg))
+            if msg != _SUCCESS:
+                self.aborted.set()
+            self._more.set()
+
+    async def guard(self, coro):
+        """await coro, unless an abort arrives first"""
+        work, stop = asyncio.ensure_future(coro), asyncio.ensure_future(self.aborted.wait())
+        try:
+            await asyncio.wait({work, stop}, return_when=asyncio.FIRST_COMPLETED)
+            if not work.done():
+                raise HoneyBadgerMPCError(_INCONSISTENT)
+            return work.result()
+        finally:
+            work.cancel()
+            stop.cancel()
+
+    async def successes(self, checkers):
+        """wait for a verdict of every checker -> True when all are successes"""
+        while not self.aborted.is_set() and len({s for s, _ in self.received if s in checkers}) < len(checkers):
+            self._more.clear()
+            await self._more.wait()
+        return not self.aborted.is_set()
+
+    def close(self):
+        self._task.cancel()
+
+
+async def _recv_rows(ctx, recv, n, width):
+    """one (width, limbs) blob from every party -> host array [n][width][limbs]; anything else raises HoneyBadgerMPCError"""
+    rows = np.zeros((n, width, ctx.n_limbs), dtype=np.uint64)
+    seen = set()
+    while len(seen) < n:
+        sender, blob = await recv()
+        try:
+            a = wire.unpack_limbs(blob)
+        except ValueError as e:
+            raise HoneyBadgerMPCError(f"malformed share message from party {sender}: {e}") from None
+        if a.shape != (width, ctx.n_limbs) or not isinstance(sender, int) or not 0 <= sender < n or sender in seen:
+            raise HoneyBadgerMPCError(f"malformed share message from party {sender}")
+        rows[sender] = a
+        seen.add(sender)
+    return rows
+
+
+async def randousha(co, k, tag="randousha", generator=None):
+    """(n - 2t) k pairs of sharings (r_t, r_2t) of the same random values, of degree t and 2t (reference offline_randousha.py:34-151,
+    step by step): every party draws k secrets and deals each at both degrees, one blob row_t[i] || row_2t[i] to party i (H1); the
+    received [n][2k] block is refined by one hyper-invertible mat-vec; refined rows n - 2t .. n - 1 go to their checkers (H2), who
+    interpolate with one inverse mat-vec, judge degrees and constants in one launch (hb_off_degree_check) and tell everyone "S" or
+    "A" (H3).  Anything but 2t successes -- and a malformed message, of which the others are told by an "A" -- raises
+    HoneyBadgerMPCError.  Waits for all n parties, as the reference does.
+    -> (r_t, r_2t), ((n - 2t) k, limbs) each; element j (n - 2t) + i is refined sharing i of column j (the reference's order).
+    co: an OpenCoalescer (n, t, myid, ctx, get_send_recv); channels are (tag, "H1"), (tag, "H2"), (tag, "H3")."""
+    n, t, me, ctx = co.n, co.t, co.myid, co.ctx
+    if not (isinstance(k, int) and k >= 1 and t >= 1 and n >= 3 * t + 1):
+        raise ValueError("randousha: t >= 1, n >= 3 t + 1 and k >= 1")
+    torch, L = ctx.torch, ctx.n_limbs
+    codec = _Codec.get(ctx, n, t, k)
+    good = n - 2 * t
+    checkers = set(range(good, n))
+    send1, recv1 = co.get_send_recv((tag, "H1"))
+    send2, recv2 = co.get_send_recv((tag, "H2"))
+    send3, recv3 = co.get_send_recv((tag, "H3"))
+    verdicts = _Verdicts(recv3)
+
+    def rows_out(block, send, to):
+        host = block.view(n, 2 * k, L).cpu().numpy().view(np.uint64)          # one copy for every recipient's row
+        for i in to:
+            send(i, wire.pack_limbs(host[i]))
+
+    async def rows_in(recv):
+        try:
+            host = await verdicts.guard(_recv_rows(ctx, recv, n, 2 * k))
+        except HoneyBadgerMPCError:
+            for i in range(n):
+                send3(i, _ABORT)
+            raise
+        return ctx.reduce_(ctx.to_device(host.reshape(n * 2 * k, L)))         # from outside: residues count
+
+    try:
+        secrets = random_elements(ctx.modulus, k, generator, ctx.device)
+        unref_t, _ = codec.deal_t.deal_secrets(secrets, generator)
+        unref_2t, _ = codec.deal_2t.deal_secrets(secrets, generator)
+        rows_out(torch.cat((unref_t.view(n, k, L), unref_2t.view(n, k, L)), dim=1).contiguous(), send1, range(n))
+        refined = codec.hyper.refine(await rows_in(recv1))                     # [n][2k]: row i = refined sharing i of every column
+        rows_out(refined, send2, sorted(checkers))
+        if me in checkers:
+            bad = degree_check(ctx, codec.interpolate(await rows_in(recv2), 2 * k), n, t)
+            for i in range(n):
+                send3(i, _ABORT if any(bad) else _SUCCESS)
+        if not await verdicts.successes(checkers):
+            raise HoneyBadgerMPCError(_INCONSISTENT)
+    finally:
+        verdicts.close()
+    kept = refined.view(n, 2 * k, L)[:good]
+    return (kept[:, :k].transpose(0, 1).reshape(good * k, L).contiguous(), kept[:, k:].transpose(0, 1).reshape(good * k, L).contiguous())
+
+
+async def generate_triples(co, k, tag="triples", generator=None):
+    """k Beaver triples (a, b, ab), (k, limbs) each, by degree reduction (reference offline_randousha.py:154-191): a, b and a mask r
+    from RanDouSha, ab = open(a b + r_2t, degree 2t) - r_t -- one fused launch (hb_off_mul_add), one coalesced open, one sub.
+    One deliberate difference: the reference runs randousha(3k) and uses 3k of the (n - 2t) 3k sharings it made; this runs
+    randousha(ceil(3k / (n - 2t))) and slices.  The outputs are random sharings either way."""
+    from .share_arithmetic import sub
+
+    if not (isinstance(k, int) and k >= 1):
+        raise ValueError("generate_triples: k >= 1")
+    ctx, good = co.ctx, co.n - 2 * co.t
+    r_t, r_2t = await randousha(co, -(-3 * k // good), tag=(tag, "randousha"), generator=generator)
+    a, b, r = (r_t[i * k:(i + 1) * k] for i in range(3))
+    opened = await co.open_share_array(mul_add(ctx, a, b, r_2t[2 * k:3 * k]), degree=2 * co.t)
+    return a.clone(), b.clone(), sub(ctx, opened, r)
+
+
+async def generate_bits(co, k, encoding=PM1, tag="bits", generator=None):
+    """k shared random bits, (k, limbs) (reference offline_randousha.py:194-232): u and a mask r from RanDouSha,
+    u^2 = open(open(u u + r_2t, degree 2t) - r_t), and u / sqrt(u^2) by the fused inverse root (hb_off_invsqrt_scale): two coalesced
+    opens in all.  encoding PM1 -> shares of +-1 (the reference's), ZERO_ONE -> of 0 / 1, the bit planes fixedpoint and
+    share_comparison take.  An opened u^2 that is zero (probability 1 / p) or a non-residue raises AssertionError, as the
+    reference's sqrt does."""
+    from .share_arithmetic import sub
+
+    if not (isinstance(k, int) and k >= 1):
+        raise ValueError("generate_bits: k >= 1")
+    if encoding not in (PM1, ZERO_ONE) or isinstance(encoding, bool):
+        raise ValueError("encoding: PM1 or ZERO_ONE")
+    ctx, good = co.ctx, co.n - 2 * co.t
+    r_t, r_2t = await randousha(co, -(-2 * k // good), tag=(tag, "randousha"), generator=generator)
+    u, r = r_t[:k], r_t[k:2 * k]
+    opened = await co.open_share_array(mul_add(ctx, u, u, r_2t[k:2 * k]), degree=2 * co.t)
+    squares = await co.open_share_array(sub(ctx, opened, r, out=opened))
+    return invsqrt_scale(ctx, squares, u, encoding, check=True)

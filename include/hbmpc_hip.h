@@ -392,6 +392,30 @@ int hb_lt_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, co
 int hb_lt_xor_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *v_dev, const uint64_t *p_dev, const uint64_t *q_dev,
                      const uint64_t *pq_dev, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- the offline phase: RanDouSha, triples and random bits (hb_off.hip) -----------------------------------------------------
+ * The local arithmetic of offline_randousha.py:34-232; the protocol itself is honeybadgermpc_amd/offline.py.  Operands and results are
+ * canonical residues; every call is one launch, asynchronous on `stream`; count == 0 returns HB_OK and launches nothing; null
+ * pointers (with count > 0), a negative count and an unknown mode are HB_ERR_BAD_ARG before any launch.
+ * hb_off_mul_add: out[i] = a[i] b[i] + c[i] in one pass, the masked local product of both generators (a b + r_2t, u u + r_2t).
+ *   b_dev may be a_dev and out_dev may be any of the inputs.
+ * hb_off_invsqrt_scale: the finish of generate_bits.  x_dev holds the opened u^2, u_dev this party's shares, w(x) = x^(-1/2):
+ *   HB_OFF_PM1  out = u w (a share of +-1, what the reference returns)      HB_OFF_01  out = (u w + 1) / 2 (a share of 0 or 1)
+ *   u_dev == NULL: out = w.  With p - 1 = q 2^s and c = z^q for the smallest non-residue z >= 2, w = x^((q-1)/2) c^e for the unique
+ *   e in [0, 2^(s-1)) with x^q c^(2e) = 1: the inverse of exactly the root hb_sqrt_mod returns.  status_dev is int32[2], zeroed by
+ *   the caller: [0] += the number of x = 0, [1] += the number of non-residues; their outputs are 0 and the other elements are
+ *   unaffected (the convention of hb_ew_inv).  The first call of a context builds a table of s elements and synchronises once.
+ * hb_off_degree_check: the checkers' verdict.  coeffs_dev is [n][2k], coefficient-major: row e holds coefficient e of the k
+ *   interpolated t-sharings, then of the k 2t-sharings (what one hb_matvec with the inverse Vandermonde matrix over the received
+ *   [n][2k] block writes).  counters_dev is int32[3], zeroed by the caller: [0] += columns j < k whose polynomial is not of exact
+ *   degree t (coefficient t zero, or any coefficient above it non-zero), [1] += the same for the 2t-sharings and degree 2t,
+ *   [2] += columns whose two constant terms differ.  2 t < n, else HB_ERR_BAD_ARG. */
+#define HB_OFF_PM1 0
+#define HB_OFF_01 1
+int hb_off_mul_add(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *c_dev, uint64_t *out_dev, int64_t count, void *stream);
+int hb_off_invsqrt_scale(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *u_dev, int mode, uint64_t *out_dev, int64_t count, int32_t *status_dev,
+                         void *stream);
+int hb_off_degree_check(hb_ctx *ctx, const uint64_t *coeffs_dev, int n, int64_t k, int t, int32_t *counters_dev, void *stream);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip)-------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -754,6 +778,16 @@ int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_LT_SELFTEST_XOR_FINISH 5
 int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs,
                    int64_t count);
+/* host-side run of the offline kernels' bodies (no GPU needed) over host memory, element by element:
+ *   what = HB_OFF_SELFTEST_MUL_ADD       operands[0..2] = a, b, c; out may be any of them
+ *          HB_OFF_SELFTEST_INVSQRT       or-ed with (mode << 8): operands[0] = x, [1] = u (or NULL: out = w), [2] = two uint64 words
+ *                                        that receive the status counts (or NULL)
+ *          HB_OFF_SELFTEST_DEGREE_CHECK  operands[0] = coeffs [n][2 count], [1] = two uint64 words {n, t}; count = k; out = the three
+ *                                        counts as uint64 words */
+#define HB_OFF_SELFTEST_MUL_ADD 0
+#define HB_OFF_SELFTEST_INVSQRT 1
+#define HB_OFF_SELFTEST_DEGREE_CHECK 2
+int hb_selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, uint64_t *out, int64_t count);
 /* host-side run of the root-finding kernels' bodies (no GPU needed) over host memory, phase by phase as the kernels' workgroups walk
  * them.  For tests only: not a fallback.
  *   what = HB_RF_SELFTEST_NEWTON  operands[0] = sums [k]; params = {k}; out [k + 1] as hb_rf_newton writes coeffs_dev
