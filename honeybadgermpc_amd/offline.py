@@ -18,6 +18,7 @@ The protocol that makes preprocessing among the parties (reference offline_rando
 * randousha         -- (n - 2t) k pairs (r_t, r_2t) of sharings of random values nobody knows (:34-151)
 * generate_triples  -- k Beaver triples by degree reduction (:154-191)
 * generate_bits     -- k shared random bits, as +-1 or as 0 / 1 (:194-232)
+* generate_matrix_triples -- matrix triples (P, Q, P Q) for linalg.beaver_matmul: generate_triples with a matrix product in the middle
 * mul_add, invsqrt_scale, degree_check -- the three kernels on tensors; invsqrt_model, degree_check_model -- on Python ints
 
 Element layout as in honeybadgermpc_amd.device: int64 tensors (count, 4), little-endian limbs.
@@ -434,6 +435,29 @@ async def generate_triples(co, k, tag="triples", generator=None):
     a, b, r = (r_t[i * k:(i + 1) * k] for i in range(3))
     opened = await co.open_share_array(mul_add(ctx, a, b, r_2t[2 * k:3 * k]), degree=2 * co.t)
     return a.clone(), b.clone(), sub(ctx, opened, r)
+
+
+async def generate_matrix_triples(co, m, k, n, count=1, tag="matrix_triples", generator=None):
+    """count matrix triples (P, Q, PQ = P Q), P (count, m, k, limbs), Q (count, k, n, limbs), PQ (count, m, n, limbs), by degree
+    reduction -- the matrix form of generate_triples: P, Q and a mask r come from ONE randousha, and
+    PQ = open(P Q + r_2t, degree 2t) - r_t: one launch (linalg.matmul with the mask as its epilogue), one coalesced open of
+    count m n elements, one sub.  The same slicing and the same abort behaviour as generate_triples, because it only composes
+    randousha: anything but 2t successes raises HoneyBadgerMPCError in every party."""
+    from .linalg import matmul
+    from .share_arithmetic import sub
+
+    for v, what in ((m, "m"), (k, "k"), (n, "n"), (count, "count")):
+        if not (isinstance(v, int) and not isinstance(v, bool) and v >= 1):
+            raise ValueError(f"generate_matrix_triples: {what} >= 1")
+    ctx, good, L = co.ctx, co.n - 2 * co.t, co.ctx.n_limbs
+    np_, nq, nr = count * m * k, count * k * n, count * m * n
+    r_t, r_2t = await randousha(co, -(-(np_ + nq + nr) // good), tag=(tag, "randousha"), generator=generator)
+    P = r_t[:np_].clone().view(count, m, k, L)
+    Q = r_t[np_:np_ + nq].clone().view(count, k, n, L)
+    r = r_t[np_ + nq:np_ + nq + nr]
+    masked = matmul(ctx, P, Q, add=r_2t[np_ + nq:np_ + nq + nr])
+    opened = await co.open_share_array(masked.view(nr, L), degree=2 * co.t)
+    return P, Q, sub(ctx, opened, r).view(count, m, n, L)
 
 
 async def generate_bits(co, k, encoding=PM1, tag="bits", generator=None):

@@ -46,6 +46,8 @@ Protocol level, coroutines over an OpenCoalescer (every party runs the same coro
     async ltz(co, x, bits, triples, k, kappa)           1 + carry_levels(k - 1) opens             [x < 0]                        :266-268
     async lt(co, x, y, bits, triples, k, kappa)         the same, + 1 launch                      [x < y]                        :274-275
     async mul(co, x, y, triple, bits, f, k, kappa)      2 opens: beaver_multiply_arrays, then trunc_pr(., 2 k, f); 2 k + kappa planes   :240-251
+    async matmul(co, X, Y, prep, bits, method, f, k, kappa)   the shared matrix product (linalg), then ONE trunc_pr an output at width
+                                                        matmul_width(k, inner) = 2 k + ceil(log2(inner)): 2 batches, m n truncation opens
 
 div2m and its kin take 3 + 2 carry_levels(m) launches for any count.  FixedPointArray wraps a share array with +, -, neg(), mul,
 div by a public number, ltz, lt and open() -> list[float].
@@ -441,6 +443,52 @@ async def mul(co, x, y, triple, bits, f=F, k=K, kappa=KAPPA):
     return await trunc_pr(co, xy, bits, 2 * k, f, kappa)
 
 
+def matmul_width(k, inner):
+    """bits of a sum of `inner` products of two signed k-bit values: 2 k + ceil(log2(inner))"""
+    k, inner = _int(k, "k"), _int(inner, "inner")
+    if inner < 1:
+        raise ValueError(f"inner must be positive, got {inner}")
+    return 2 * k + (inner - 1).bit_length()
+
+
+async def matmul(co, X, Y, prep, bits, method, f=F, k=K, kappa=KAPPA):
+    """Shares of the fixed-point matrix product: X (m, inner, limbs) [or (batch, m, inner, limbs)] times Y (inner, n, limbs), by
+    linalg.double_sharing_matmul (method = linalg.DOUBLE_SHARING, prep = (r_t, r_2t)) or linalg.beaver_matmul (method = linalg.BEAVER,
+    prep = (P, Q, PQ)) -- told apart by `method`, never guessed -- then ONE trunc_pr(., matmul_width(k, inner), f) on each of the m n
+    outputs: one rounding an output instead of one a product, m n truncation opens instead of m inner n.  bits: (at least
+    matmul_width(k, inner) + kappa, m n, limbs) planes.  check_params decides whether that width fits the modulus: ValueError if
+    not, before anything is opened."""
+    from .. import linalg
+
+    ctx = co.ctx
+    if method not in (linalg.DOUBLE_SHARING, linalg.BEAVER):
+        raise ValueError(f"method: linalg.DOUBLE_SHARING or linalg.BEAVER, got {method!r}")
+    X, Y = linalg._matrix(ctx, X, "X"), linalg._matrix(ctx, Y, "Y")
+    if Y.dim() != X.dim() or Y.shape[-3] != X.shape[-2] or (X.dim() == 4 and Y.shape[0] != X.shape[0]):
+        raise ValueError(f"Y: shape {tuple(Y.shape)} does not go with X {tuple(X.shape)}")
+    inner = X.shape[-2]
+    if inner < 1:
+        raise ValueError("X: the inner dimension must not be empty")
+    width = matmul_width(k, inner)
+    check_params(ctx.modulus, width, f, kappa)
+    shape = tuple(X.shape[:-2]) + (Y.shape[-2], ctx.n_limbs)
+    count = 1
+    for d in shape[:-1]:
+        count *= d
+    bits, _ = _planes(ctx, bits, width + kappa, count, "bits")
+    try:
+        n_prep = len(prep)
+    except TypeError:
+        n_prep = -1
+    if n_prep != (2 if method == linalg.DOUBLE_SHARING else 3):
+        raise ValueError("prep: expected (r_t, r_2t) for DOUBLE_SHARING, (P, Q, PQ) for BEAVER")
+    if method == linalg.DOUBLE_SHARING:
+        xy = await linalg.double_sharing_matmul(co, X, Y, prep[0], prep[1])
+    else:
+        xy = await linalg.beaver_matmul(co, X, Y, prep)
+    return (await trunc_pr(co, xy.view(count, ctx.n_limbs), bits, width, f, kappa)).view(shape)
+
+
 class FixedPointArray:
     """An array of shared fixed-point numbers (the reference's FixedPoint, fixedpoint.py:214-280, for `count` values at once).
     `shares`: a (count, limbs) tensor of shares of int(a * 2**f) mod p.  Preprocessing goes to the calls that spend it."""
@@ -469,6 +517,14 @@ class FixedPointArray:
 
     async def mul(self, x, triple, bits):
         return self._like(await mul(self.co, self.shares, self._other(x), triple, bits, self.f, self.k, self.kappa))
+
+    async def matmul(self, x, rows, inner, cols, prep, bits, method):
+        """self as a (rows, inner) matrix times x as an (inner, cols) matrix, row-major -> (rows cols) values (fixedpoint.matmul)"""
+        L = self.ctx.n_limbs
+        if self.shares.numel() != rows * inner * L or self._other(x).numel() != inner * cols * L:
+            raise ValueError(f"matmul: expected {rows * inner} and {inner * cols} values, got {self.shares.numel() // L} and {x.shares.numel() // L}")
+        out = await matmul(self.co, self.shares.view(rows, inner, L), x.shares.view(inner, cols, L), prep, bits, method, self.f, self.k, self.kappa)
+        return self._like(out.view(rows * cols, L))
 
     async def div(self, x, bits):
         """by a public number: times to_fixed_point_repr(1 / x), then trunc_pr (FixedPoint.div, fixedpoint.py:277-280; a public

@@ -416,6 +416,27 @@ int hb_off_invsqrt_scale(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *u_d
                          void *stream);
 int hb_off_degree_check(hb_ctx *ctx, const uint64_t *coeffs_dev, int n, int64_t k, int t, int32_t *counters_dev, void *stream);
 
+/* ---- products of share matrices (hb_mat.hip) --------------------------------------------------------------------------------
+ * hb_mat_mul: out[b] = A[b] B[b] (op) C[b] for b < batch; A is m x k, B is k x n, C and out are m x n, all row-major packed canonical
+ * residues, batches back to back.  op: HB_MAT_NONE (c_dev is not read), HB_MAT_ADD (A B + C), HB_MAT_SUB (A B - C): the epilogue is
+ * part of the launch.  Asynchronous on `stream`.  batch, m or n equal to 0 launches nothing; k == 0 gives 0 (op) C.  out_dev may be
+ * c_dev.  HB_ERR_BAD_ARG before any launch: out_dev equal to a_dev or b_dev, a null pointer with a non-empty shape, a negative size,
+ * an unknown c_op, c_dev == NULL with c_op != HB_MAT_NONE.
+ * One launch and no allocation, except when the output gives at most 64 workgroups (tiles of 16 x 32 over all batches) and
+ * k >= 2048: then the inner dimension is cut into slices, a first launch writes partial products to a scratch slot kept with the
+ * context per stream and a second adds them and applies the epilogue, both on `stream`.  That slot never exceeds 512 tiles:
+ * 8 MiB for 32-byte elements, 2 MiB for 8-byte ones; it goes with hb_ctx_cache_clear and with the context.  The result is the same
+ * bit for bit either way.
+ * hb_mat_constants: out[0..HB_MAT_CONSTANTS) = tile rows, tile columns, tile depth, products between two carry passes, products
+ * between two reductions (both for the element width n_limbs), and the split rule: least k, most workgroups, target workgroups. */
+#define HB_MAT_NONE 0
+#define HB_MAT_ADD  1
+#define HB_MAT_SUB  2
+#define HB_MAT_CONSTANTS 8
+int hb_mat_mul(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *c_dev, int c_op,
+               uint64_t *out_dev, int64_t batch, int m, int k, int n, void *stream);
+int hb_mat_constants(int n_limbs, int32_t *out);
+
 /* ---- the robust path of IncrementalDecoder without plans (hb_quick.hip)-------------------------------------------
  * A decoder that is working its way past faulty senders sees every arrival set once: these entry points build what they
  * need on the device and enqueue it; none of them creates tables on the host. */
@@ -806,6 +827,14 @@ int hb_selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 #define HB_RF_SELFTEST_SHIFT 3
 #define HB_RF_SELFTEST_ROOTS 4
 int hb_selftest_rf(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *out);
+/* host-side run of the matrix-product kernels' bodies (no GPU needed) over host memory, workgroup by workgroup and lane by lane.
+ * For tests only: not a fallback.  what = the epilogue (HB_MAT_NONE / ADD / SUB), or-ed with nothing (the unsplit launch),
+ * HB_MAT_SELFTEST_SPLIT (params[4] slices of whole tile depths, then the reduction launch) or HB_MAT_SELFTEST_AUTO (the rule
+ * hb_mat_mul applies).  operands[0..2] = A, B, C; params = {batch, m, k, n, slices}; the argument table of hb_mat_mul. */
+#define HB_MAT_SELFTEST_SPLIT 0x100
+#define HB_MAT_SELFTEST_AUTO 0x200
+int hb_selftest_mat(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands,
+                    const int64_t *params, uint64_t *out);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,9 @@ void hb_debug_pm_slab_bytes(int64_t bytes);
  * other five are zero: it launches and waits for nothing), so a test can hold the device's walk against the host's. */
 void hb_debug_rf_stats(int64_t *out);
 void hb_debug_rf_profile(int on);
+/* How hb_mat_mul cuts the inner dimension: 0 its own rule (hbmpc_hip.h), 1 slices of one tile depth whenever the output gives few
+ * enough workgroups (a small shape takes the split path), -1 never.  Process-wide. */
+void hb_debug_mat_split(int mode);
 
 
 #ifdef __cplusplus
