@@ -201,6 +201,7 @@ DEBUG_SYMBOLS = {
     "hb_debug_rf_stats": (None, [_vp]),
     "hb_debug_rf_profile": (None, [_i]),
     "hb_debug_mat_split": (None, [_i]),
+    "hb_debug_matvec_route": (_i, [_vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -332,6 +332,8 @@ int launch_mm8(hb_ctx *ctx, const Mm8Matrix *m, const uint32_t *in, hb_view iv, 
 // ---- matrix-core mat-vec for full-size entries, hb_mfma_wide.hip ----------------------------------------
 int mm8w_from_host(hb_ctx *ctx, const uint64_t *m_host, int n_out, int n_in, Mm8wMatrix **out, hipStream_t s);
 void mm8w_free(Mm8wMatrix *m);
+// what a launch of C chunks over this image runs (hbmpc_hip_debug.h, hb_debug_matvec_route): the launch's own choice, no launch
+int mm8w_route(hb_ctx *ctx, const Mm8wMatrix *m, int64_t C, int32_t *out);
 int launch_mm8w(hb_ctx *ctx, const Mm8wMatrix *m, const uint32_t *in, hb_view iv, const int32_t *in_rows_dev, int64_t in_count,
                 uint32_t *out, hb_view ov, int64_t out_count, const int32_t *check_mask_dev, int32_t *mismatch_dev,
                 int64_t C, hipStream_t s, const uint32_t *cmp = nullptr, hb_view cv = hb_view{0, 0}, int n_store = 0);

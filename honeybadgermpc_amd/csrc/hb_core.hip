@@ -766,15 +766,17 @@ void hb_matrix_destroy(hb_matrix *m) { HB_API_GUARD((m ? m->ctx : nullptr)); mat
 // ---- mat-vec launcher (shared by hb_matvec, hb_matvec_check and the open plan) ------------
 namespace hb {
 
+// the image a mat-vec of C chunks over m runs on, or nullptr for the integer kernel: full-size entries on the matrix cores when the
+// shape pays for a wave pass of 16 chunks x 16 rows (launch_matvec and hb_debug_matvec_route both ask here)
+static const Mm8wMatrix *matvec_wide(hb_ctx *ctx, const hb_matrix *m, int64_t C, hipStream_t s) {
+    return C >= 256 && m->n_in >= 4 && m->n_out >= 4 ? matrix_wide(ctx, m, s) : nullptr;
+}
+
 int launch_matvec(hb_ctx *ctx, const hb_matrix *m, const uint32_t *in, hb_view iv, const int32_t *in_rows_dev, int64_t in_count,
                   uint32_t *out, hb_view ov, int64_t out_count, const int32_t *check_mask_dev, int32_t *mismatch_dev,
                   int64_t C, hipStream_t s) {
     if (C <= 0 || m->n_out == 0) return HB_OK;
-    // full-size entries on the matrix cores when the shape pays for a wave pass of 16 chunks x 16 rows
-    if (C >= 256 && m->n_in >= 4 && m->n_out >= 4) {
-        const Mm8wMatrix *w = matrix_wide(ctx, m, s);
-        if (w) return launch_mm8w(ctx, w, in, iv, in_rows_dev, in_count, out, ov, out_count, check_mask_dev, mismatch_dev, C, s);
-    }
+    if (const Mm8wMatrix *w = matvec_wide(ctx, m, C, s)) return launch_mm8w(ctx, w, in, iv, in_rows_dev, in_count, out, ov, out_count, check_mask_dev, mismatch_dev, C, s);
     const int tiles = m_tiles(m->n_out);
     const int64_t groups = (C + 63) / 64;
     const int64_t n_waves = groups * tiles;
@@ -819,6 +821,14 @@ int launch_copy_view(hb_ctx *ctx, const uint32_t *src, hb_view sv, uint32_t *dst
 }
 
 }  // namespace hb
+
+extern "C" int hb_debug_matvec_route(hb_ctx *ctx, const hb_matrix *m, int64_t C, int32_t *out) { HB_API_GUARD(ctx);
+    if (!ctx || !m || !out) return HB_ERR_BAD_ARG;
+    for (int j = 0; j < 8; j++) out[j] = 0;
+    if (C <= 0 || m->n_out == 0) return HB_OK;
+    const Mm8wMatrix *w = hb::matvec_wide(ctx, m, C, nullptr);
+    return w ? hb::mm8w_route(ctx, w, C, out) : HB_OK;
+}
 
 extern "C" {
 

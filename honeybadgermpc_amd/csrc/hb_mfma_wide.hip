@@ -959,6 +959,36 @@ int launch_mm8w(hb_ctx *ctx, const Mm8wMatrix *m, const uint32_t *in, hb_view iv
     return launch_mm8w_impl(ctx, m, in, iv, in_rows_dev, in_count, out, ov, out_count, check_mask_dev, mismatch_dev, C, s, cmp, cv, n_store, nullptr, nullptr);
 }
 
+// The launch geometry of n_tiles chunk tiles over this image: tiles a unit, buffers, row tiles a row group and the ring slots of the
+// balanced launch (0 = the unit launch).  The simulation costs tens of microseconds: remembered per matrix, and per context for images
+// that live for one launch.  The launch and the route query (mm8w_route) both ask here.
+static bool mm8w_launch_shape(hb_ctx *ctx, const Mm8wMatrix *m, int64_t n_tiles, int *tpw, int *nbuf, int *rq, int *flat_nb) {
+    if (m->shape_tiles == n_tiles) { *tpw = m->shape_tpw; *nbuf = m->shape_nbuf; *rq = m->shape_rq; *flat_nb = m->shape_flat; return true; }
+    const std::string sk = std::to_string(m->n_rt) + ":" + std::to_string(m->nkb) + ":" + std::to_string(m->tile_rows) + ":" + std::to_string((long long)n_tiles);
+    auto hit = ctx->wide_shapes.find(sk);
+    if (hit != ctx->wide_shapes.end()) { *tpw = hit->second[0]; *nbuf = hit->second[1]; *rq = hit->second[2]; *flat_nb = hit->second[3]; }
+    else {
+        double unit_cost = 0.0;
+        if (!mm8w_shape(m->n_rt, m->nkb, n_tiles, mm8w_num_cus(), tpw, nbuf, rq, &unit_cost)) return false;
+        *flat_nb = mm8w_flat_slots(m->n_rt, m->nkb, m->tile_rows, n_tiles, mm8w_num_cus(), unit_cost);
+        if (ctx->wide_shapes.size() > 4096) ctx->wide_shapes.clear();
+        ctx->wide_shapes[sk] = std::vector<int>{*tpw, *nbuf, *rq, *flat_nb};
+    }
+    m->shape_tiles = n_tiles; m->shape_tpw = *tpw; m->shape_nbuf = *nbuf; m->shape_rq = *rq; m->shape_flat = *flat_nb;
+    return true;
+}
+// K-blocks written out with a share of the reduction each (gen_mm8w.py); the rest is a loop of two-block bodies
+static int mm8w_peel(int nkb) { return nkb <= 2 ? nkb : ((nkb & 1) ? 3 : 4); }
+
+// hb_debug_matvec_route: what a launch of C chunks over this image runs -- out[0] = 1 the unit launch (k_mm8w<.., peel, tile_rows / 4>),
+// 2 the balanced one (k_mm8w_flat); then tile_rows, n_rt, nkb, peel, tpw, rq, ring slots.  Launches nothing.
+int mm8w_route(hb_ctx *ctx, const Mm8wMatrix *m, int64_t C, int32_t *out) {
+    int tpw = 1, nbuf = 1, rq = m->n_rt, flat_nb = 0;
+    if (!mm8w_launch_shape(ctx, m, (C + 15) / 16, &tpw, &nbuf, &rq, &flat_nb)) return fail(ctx, HB_ERR_UNSUPPORTED, "mm8w: shape");
+    out[0] = flat_nb ? 2 : 1; out[1] = m->tile_rows; out[2] = m->n_rt; out[3] = m->nkb; out[4] = mm8w_peel(m->nkb); out[5] = tpw; out[6] = rq; out[7] = flat_nb;
+    return HB_OK;
+}
+
 static int launch_mm8w_impl(hb_ctx *ctx, const Mm8wMatrix *m, const uint32_t *in, hb_view iv, const int32_t *in_rows_dev, int64_t in_count,
                             uint32_t *out, hb_view ov, int64_t out_count, const int32_t *check_mask_dev, int32_t *mismatch_dev,
                             int64_t C, hipStream_t s, const uint32_t *cmp, hb_view cv, int n_store, int32_t *first_bad_dev, uint32_t *bad_map_dev,
@@ -969,21 +999,7 @@ static int launch_mm8w_impl(hb_ctx *ctx, const Mm8wMatrix *m, const uint32_t *in
     if (done_p) done = *done_p;
     int tpw = 1, nbuf = 1, rq = m->n_rt, flat_nb = 0;
     const int64_t n_tiles = (C + 15) / 16;
-    if (m->shape_tiles == n_tiles) { tpw = m->shape_tpw; nbuf = m->shape_nbuf; rq = m->shape_rq; flat_nb = m->shape_flat; }
-    else {
-        // the simulation costs tens of microseconds: remembered per matrix, and per context for images that live for one launch
-        const std::string sk = std::to_string(m->n_rt) + ":" + std::to_string(m->nkb) + ":" + std::to_string(m->tile_rows) + ":" + std::to_string((long long)n_tiles);
-        auto hit = ctx->wide_shapes.find(sk);
-        if (hit != ctx->wide_shapes.end()) { tpw = hit->second[0]; nbuf = hit->second[1]; rq = hit->second[2]; flat_nb = hit->second[3]; }
-        else {
-            double unit_cost = 0.0;
-            if (!mm8w_shape(m->n_rt, m->nkb, n_tiles, mm8w_num_cus(), &tpw, &nbuf, &rq, &unit_cost)) return fail(ctx, HB_ERR_UNSUPPORTED, "mm8w: shape");
-            flat_nb = mm8w_flat_slots(m->n_rt, m->nkb, m->tile_rows, n_tiles, mm8w_num_cus(), unit_cost);
-            if (ctx->wide_shapes.size() > 4096) ctx->wide_shapes.clear();
-            ctx->wide_shapes[sk] = std::vector<int>{tpw, nbuf, rq, flat_nb};
-        }
-        m->shape_tiles = n_tiles; m->shape_tpw = tpw; m->shape_nbuf = nbuf; m->shape_rq = rq; m->shape_flat = flat_nb;
-    }
+    if (!mm8w_launch_shape(ctx, m, n_tiles, &tpw, &nbuf, &rq, &flat_nb)) return fail(ctx, HB_ERR_UNSUPPORTED, "mm8w: shape");
     if (flat_nb) {
         // the balanced launch: one range of the pass list a workgroup (k_mm8w_flat)
         const int64_t n_pass = n_tiles * m->n_rt;
@@ -1040,8 +1056,7 @@ static int launch_mm8w_impl(hb_ctx *ctx, const Mm8wMatrix *m, const uint32_t *in
                            cmp ? cmp : out, cmp ? cv.stride_c : ov.stride_c, cmp ? cv.stride_l : ov.stride_l, cmp ? 1 : 0, cmp ? n_store : 0, \
                            m->n_out, m->n_rt, m->nkb, tpw, nbuf, rq, C, n_units, m->bias, m->wp, first_bad_dev, bad_map_dev, done);      \
     } while (0)
-    // K-blocks written out with a share of the reduction each (gen_mm8w.py); the rest is a loop of two-block bodies
-    const int peel = m->nkb <= 2 ? m->nkb : ((m->nkb & 1) ? 3 : 4);
+    const int peel = mm8w_peel(m->nkb);
 #define MM8W_LAUNCH(CHK, PL) do { if (m->tile_rows == 12) MM8W_LAUNCH_K(CHK, PL, 3); else if (m->tile_rows == 8) MM8W_LAUNCH_K(CHK, PL, 2); else MM8W_LAUNCH_K(CHK, PL, 4); } while (0)
     if (check) { if (peel == 1) MM8W_LAUNCH(true, 1); else if (peel == 2) MM8W_LAUNCH(true, 2); else if (peel == 3) MM8W_LAUNCH(true, 3); else MM8W_LAUNCH(true, 4); }
     else { if (peel == 1) MM8W_LAUNCH(false, 1); else if (peel == 2) MM8W_LAUNCH(false, 2); else if (peel == 3) MM8W_LAUNCH(false, 3); else MM8W_LAUNCH(false, 4); }

@@ -37,6 +37,13 @@ void hb_debug_rf_profile(int on);
 /* How hb_mat_mul cuts the inner dimension: 0 its own rule (hbmpc_hip.h), 1 slices of one tile depth whenever the output gives few
  * enough workgroups (a small shape takes the split path), -1 never.  Process-wide. */
 void hb_debug_mat_split(int mode);
+/* Which kernel an hb_matvec / hb_matvec_check of C chunks over this handle launches, asked of the launch's own rule (launch_matvec,
+ * hb_core.hip; the geometry of hb_mfma_wide.hip with its per-matrix and per-context memo): out[0] = 0 the integer kernel k_matvec, 1 the
+ * full-size matrix-core kernel k_mm8w in its unit launch, 2 its balanced launch k_mm8w_flat; out[1..7] = rows a row tile, row tiles,
+ * K-blocks, K-blocks peeled, chunk tiles a unit, row tiles a row group, ring slots (all 0 with out[0] = 0; k_mm8w<CHECK, PEEL, K> has
+ * PEEL = out[4], K = out[1] / 4).  Builds the handle's int8 image if no launch has yet -- exactly as the first launch would, the
+ * environment hooks of that moment included -- and launches no mat-vec.  out: int32[8], host. */
+int hb_debug_matvec_route(hb_ctx *ctx, const hb_matrix *m, int64_t C, int32_t *out);
 
 
 #ifdef __cplusplus

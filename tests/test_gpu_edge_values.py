@@ -155,10 +155,11 @@ def test_wide_open_at_edge_values(p, path):
     kernel -- "wide" at small-integer points, the default at omega powers, fused and unfused -- and gets it where its image can hold the
     plan's matrices (_full_size_image: every plan over BLS, the (24, 5) plan over the two moduli around 2^255).  Over 2^256 - 189 and
     secp256k1's order no plan gets it: those two ids assert that the plan says so and then run the cases on what serves instead (k_mm8
-    in two launches; the integer kernels at omega powers), so the full-size reduction is NOT driven at the moduli next to 2^256, the only
-    ones where its remainder can reach 2^256.  Under this id only the decodes run k_mm8w: small points encode on k_mm8, omega plans by
-    NTT, and the full-size encode needs large points that are no omega powers, which no shape here has.  The balanced launch k_mm8w_flat
-    is not reached either: it takes 49 rows or more of 57 coefficients or more and some thousand chunks (mm8w_flat_slots).
+    in two launches; the integer kernels at omega powers): at the moduli next to 2^256, the only ones where the full-size reduction's
+    remainder can reach 2^256, tests/test_gpu_wide_matvec.py drives it through hb_matvec over matrices of its own.  Under this id only
+    the decodes run k_mm8w: small points encode on k_mm8, omega plans by NTT, and the full-size encode needs large points that are no
+    omega powers, which no shape here has.  The balanced launch k_mm8w_flat takes 49 rows or more of 57 coefficients or more and some
+    thousand chunks (mm8w_flat_slots): that test has it too.
     valu: the integer-VALU kernels (matrix cores off), every shape."""
     from honeybadgermpc_amd.device import BatchOpen
 
