@@ -34,6 +34,7 @@ HB_JJ_SELFTEST_STAGE2, HB_JJ_SELFTEST_STAGE3, HB_JJ_SELFTEST_SCALE = 4, 5, 6
 HB_FXP_MOD, HB_FXP_TRUNC, HB_FXP_NEG_TRUNC = 0, 1, 2
 HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
 HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
+HB_BD_SELFTEST_LEAVES, HB_BD_SELFTEST_PREFIX_MASK, HB_BD_SELFTEST_PREFIX_COMBINE, HB_BD_SELFTEST_SUM_MASK, HB_BD_SELFTEST_SUM_COMBINE = 0, 1, 2, 3, 4
 HB_EQ_BIT, HB_EQ_REFERENCE = 0, 1
 HB_EQ_SELFTEST_LEGENDRE, HB_EQ_SELFTEST_MASK1, HB_EQ_SELFTEST_MID, HB_EQ_SELFTEST_CSHARE, HB_EQ_SELFTEST_FINISH = 0, 1, 2, 3, 4
 HB_LT_DIRECT, HB_LT_REFERENCE = 0, 1
@@ -112,6 +113,11 @@ SYMBOLS = {
     "hb_fxp_carry_mask": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_fxp_carry_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_fxp_div2m_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i64, _vp]),
+    "hb_bd_leaves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "hb_bd_prefix_mask": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_bd_prefix_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_bd_sum_mask": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_bd_sum_combine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_legendre": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "hb_eq_mask1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "hb_eq_mid": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
@@ -185,6 +191,7 @@ SYMBOLS = {
     "hb_selftest_mimc": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i64, _vp, _i64]),
     "hb_selftest_jj": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
+    "hb_selftest_bd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_eq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_lt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_off": (_i, [_vp, _i, _i, _vp, _vp, _i64]),

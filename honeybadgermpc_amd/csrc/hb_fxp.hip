@@ -36,7 +36,7 @@
 //   k_fxp_finish<9, 8>         64 VGPRs: 8 waves                                   k_fxp_finish<3, 2>         27 VGPRs: 8 waves
 // (DESIGN.md section 3m has the schedule and the counts.)
 #include "hb_common.hpp"
-#include "hb_ew_elem.hpp"
+#include "hb_fxp_elem.hpp"
 
 using namespace hb;
 
@@ -92,14 +92,6 @@ template <int NW> HB_HD void fxp_low_bits(uint32_t (&o)[NW], const uint32_t (&cw
         o[q] = rem >= 32 ? cw[q] : (rem <= 0 ? 0u : (cw[q] & ((1u << rem) - 1u)));
     }
 }
-// bit i of the packed words (a chain of selects: the words stay in registers)
-template <int NW> HB_HD uint32_t fxp_bit(const uint32_t (&cw)[NW], int i) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int q = 0; q < NW; q++) w = (q == (i >> 5)) ? cw[q] : w;
-    return (w >> (i & 31)) & 1u;
-}
-
 // o = (x - (c mod 2^m) + r1) 2^(-m); invm = 2^(-m) R mod p
 template <int NL, int NW>
 HB_HD void fxp_trunc_pr_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r1w)[NW], int m, const uint32_t (&invm)[NL],
@@ -115,40 +107,7 @@ HB_HD void fxp_trunc_pr_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const 
     pack<NL, NW>(o, t);
 }
 
-// the leaf of bit a (public) against the share bw of the mask's bit: a = 1 -> (1 - b, b); a = 0 -> (0, 1 - b)
-template <int NL, int NW>
-HB_HD void fxp_leaf_elem(uint32_t (&gw)[NW], uint32_t (&pw)[NW], uint32_t a, const uint32_t (&bw)[NW], const FpParams<NL> &P) {
-    uint32_t b[NL], one[NL], nb[NL], g[NL], p[NL];
-    unpack<NL, NW>(b, bw);
-#pragma unroll
-    for (int q = 0; q < NL; q++) one[q] = q == 0 ? 1u : 0u;
-    fp_sub<NL>(nb, one, b, P);
-#pragma unroll
-    for (int q = 0; q < NL; q++) { g[q] = a ? nb[q] : 0u; p[q] = a ? b[q] : nb[q]; }
-    pack<NL, NW>(gw, g);
-    pack<NL, NW>(pw, p);
-}
-
-// o = v - a: a masked difference
-template <int NL, int NW> HB_HD void fxp_diff_elem(uint32_t (&o)[NW], const uint32_t (&vw)[NW], const uint32_t (&aw)[NW], const FpParams<NL> &P) {
-    uint32_t v[NL], a[NL], r[NL];
-    unpack<NL, NW>(v, vw);
-    unpack<NL, NW>(a, aw);
-    fp_sub<NL>(r, v, a, P);
-    pack<NL, NW>(o, r);
-}
-
-// g = g1 + [p1 g2], the product by the fused Beaver step of hb_ew_elem.hpp
-template <int NL, int NW>
-HB_HD void fxp_node_g_elem(uint32_t (&o)[NW], const uint32_t (&g1w)[NW], const uint32_t (&dw)[NW], const uint32_t (&ew)[NW], const uint32_t (&aw)[NW],
-                           const uint32_t (&bw)[NW], const uint32_t (&abw)[NW], const FpParams<NL> &P) {
-    uint32_t mw[NW], mm[NL], g1[NL], r[NL];
-    ew_beaver_elem<NL, NW>(mw, dw, ew, aw, bw, abw, P);
-    unpack<NL, NW>(mm, mw);
-    unpack<NL, NW>(g1, g1w);
-    fp_add<NL>(r, g1, mm, P);
-    pack<NL, NW>(o, r);
-}
+// (fxp_bit, fxp_leaf_elem, fxp_diff_elem and fxp_node_g_elem: hb_fxp_elem.hpp, shared with hb_bd.hip)
 
 // mode HB_FXP_MOD: a2 = c2 - r1 + 2^m (1 - carry);  HB_FXP_TRUNC: (x - a2) 2^(-m);  HB_FXP_NEG_TRUNC: (a2 - x) 2^(-m)
 template <int NL, int NW>
@@ -171,11 +130,6 @@ HB_HD void fxp_finish_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const ui
 }
 
 // ---------------------------------------------------------------- kernels
-// read-once operands (bit planes, triples, what was just opened)
-template <int NW> __device__ __forceinline__ void fxp_load_once(uint32_t (&w)[NW], const uint32_t *p) {
-    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
-}
-
 // No __restrict__ where the header allows an output to be an input (a thread reads its element before it writes it).
 template <int NL, int NW, bool HAS_X>
 __global__ void __launch_bounds__(256) k_fxp_mask(const FpParams<NL> P, const uint32_t *x, const uint32_t *bits, int nbits, int m, const FxpConst<NL> half,
@@ -288,18 +242,8 @@ __global__ void __launch_bounds__(256) k_fxp_finish(const FpParams<NL> P, const 
 }
 
 // ---------------------------------------------------------------- host side
-static int fxp_modulus_bits(const uint64_t *p_limbs, int n_limbs) {
-    for (int l = n_limbs - 1; l >= 0; l--)
-        if (p_limbs[l]) return 64 * l + 64 - __builtin_clzll(p_limbs[l]);
-    return 0;
-}
 // the masked value c < 2^(k + kappa + 1) must stay below p
 static bool fxp_params_ok(int bits, int k, int m, int kappa) { return m > 0 && m < k && kappa >= 0 && k <= 256 && kappa <= 256 && k + kappa + 1 <= bits - 1; }
-static bool fxp_m_ok(int bits, int m) { return m > 0 && m <= bits - 2; }
-static bool fxp_overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-    return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
-}
 // 2^e mod p, canonical digits (mont: times R)
 template <int NL> static void fxp_pow2(uint32_t (&r)[NL], int e, bool mont, const FpParams<NL> &P) {
     if (mont) fp_set<NL>(r, P.one);

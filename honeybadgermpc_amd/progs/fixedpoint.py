@@ -542,6 +542,13 @@ class FixedPointArray:
         """-> shares of [self < x]"""
         return await lt(self.co, self.shares, self._other(x), bits, triples, self.k, self.kappa)
 
+    async def bits(self, m, bits, triples):
+        """-> an (m, count, limbs) tensor of shares of the low m bits of int(a * 2**f), least significant first
+        (bit_decomposition.bit_decompose)"""
+        from .bit_decomposition import bit_decompose
+
+        return await bit_decompose(self.co, self.shares, bits, triples, self.k, m, self.kappa)
+
     async def open(self):
         """-> list[float], decoded with the signed rule of FixedPoint.open (fixedpoint.py:253-257)"""
         opened = await self.co.open_share_array(self.shares)

@@ -320,6 +320,39 @@ int hb_fxp_carry_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t
 int hb_fxp_div2m_finish(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, const uint64_t *carry_dev, int m,
                         const uint64_t *inv2m_host, int mode, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- bit decomposition of shared values (hb_bd.hip) ------------------------------------------------------------------------
+ * Shares of the low m bits of a signed k-bit value (Catrina and de Hoogh's BitDec on the masks above), for arrays of `count` values:
+ * after the open of c = x + 2^(k-1) + r1 + 2^m r2 (hb_fxp_mask) they are the bits of c2 + (2^m - 1 - r1) + 1 mod 2^m, c2 = c mod 2^m
+ * public, rows 0..m-1 of bits_dev the bit shares of r1.  A Sklansky prefix network over N = m - 1 (generate, propagate) planes, least
+ * significant first, keeps every carry; arrays of several rows are row-major with `count` elements a row.
+ * hb_bd_leaves: g_dev, p_dev [m - 1][count], row i from bit i of c and row i of bits_dev with no product: (1 - b_i, b_i) where the bit
+ *   is set, (0, 1 - b_i) where it is not; the carry-in 1 is folded into row 0: (g_0 + p_0, 0).  m == 1: nothing is launched.
+ * One level of the network (0 <= level < ceil(log2(m - 1))).  Node y = 0, 1, ... is row j = ((y >> level) << (level + 1)) |
+ *   (1 << level) | (y & ((1 << level) - 1)) while j <= m - 2, its partner q = ((j >> level) << level) - 1, and (g_j, p_j) <-
+ *   (g_j + p_j g_q, p_j p_q).  The nodes y < 2^level are g-only: one product, p_j is left as it is.  With G = min(2^level, nodes) the
+ *   g-only node y uses triple row y, the full node y rows G + 2 (y - G) [p_j g_q] and G + 2 (y - G) + 1 [p_j p_q]; ta_dev, tb_dev,
+ *   tab_dev hold this party's shares of the first factors, second factors and products, one row a triple.
+ *   hb_bd_prefix_mask     masked_dev rows 2t, 2t + 1 = p_j - ta[t], (g_q | p_q) - tb[t]: the level's ONE array to open
+ *   hb_bd_prefix_combine  opened_dev = that array opened; g_dev and p_dev are updated IN PLACE at the level's nodes, every other row is
+ *                         left untouched.
+ * The sum bits: s_0 = a_0 xor b_0, s_i = p_i + C_i - 2 p_i C_i with p_i the leaf's propagate of bit i (recomputed from c_dev and
+ *   bits_dev) and C_i = row i - 1 of g_dev after the last level; triple row i - 1 for bit i.
+ *   hb_bd_sum_mask        masked_dev rows 2t, 2t + 1 = p_{t+1} - ta[t], g[t] - tb[t], t < m - 1.  m == 1: nothing is launched.
+ *   hb_bd_sum_combine     out_dev [m][count], row i this party's share of bit i; an array of its own.  m == 1: opened_dev, g_dev and the
+ *                         triples are not looked at.
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: m outside 0 < m <=
+ * bits(p) - 2, more than 256 planes, a level the network does not have, null pointers (with count > 0), a negative count, an output
+ * that overlaps an input.  count == 0 returns HB_OK and launches nothing. */
+int hb_bd_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int m, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream);
+int hb_bd_prefix_mask(hb_ctx *ctx, const uint64_t *g_dev, const uint64_t *p_dev, int m, int level, const uint64_t *ta_dev, const uint64_t *tb_dev,
+                      uint64_t *masked_dev, int64_t count, void *stream);
+int hb_bd_prefix_combine(hb_ctx *ctx, const uint64_t *opened_dev, uint64_t *g_dev, uint64_t *p_dev, int m, int level, const uint64_t *ta_dev,
+                         const uint64_t *tb_dev, const uint64_t *tab_dev, int64_t count, void *stream);
+int hb_bd_sum_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m, const uint64_t *ta_dev,
+                   const uint64_t *tb_dev, uint64_t *masked_dev, int64_t count, void *stream);
+int hb_bd_sum_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m,
+                      const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev, uint64_t *out_dev, int64_t count, void *stream);
+
 /* ---- equality of shared values (hb_eq.hip) ---------------------------------------------------------------------------------
  * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
  * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
@@ -768,6 +801,20 @@ int hb_selftest_jj(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_FXP_SELFTEST_FINISH 5
 int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                     uint64_t *const *outs, int64_t count);
+/* host-side run of the bit decomposition kernels' bodies (no GPU needed) over host memory, a whole level or step at a time.
+ * params = {m, level}; parameters are checked as the device calls check them:
+ *   what = HB_BD_SELFTEST_LEAVES          operands[0..1] = c, bits [m - 1][count]; outs[0..1] = g, p [m - 1][count]
+ *          HB_BD_SELFTEST_PREFIX_MASK     operands[0..3] = g, p, ta, tb; outs[0] as hb_bd_prefix_mask writes masked_dev
+ *          HB_BD_SELFTEST_PREFIX_COMBINE  operands[0..3] = opened, ta, tb, tab; outs[0..1] = g, p, updated in place
+ *          HB_BD_SELFTEST_SUM_MASK        operands[0..4] = c, bits [m][count], g, ta, tb; outs[0] as hb_bd_sum_mask writes masked_dev
+ *          HB_BD_SELFTEST_SUM_COMBINE     operands[0..6] = opened, c, bits [m][count], g, ta, tb, tab; outs[0] = the m planes */
+#define HB_BD_SELFTEST_LEAVES 0
+#define HB_BD_SELFTEST_PREFIX_MASK 1
+#define HB_BD_SELFTEST_PREFIX_COMBINE 2
+#define HB_BD_SELFTEST_SUM_MASK 3
+#define HB_BD_SELFTEST_SUM_COMBINE 4
+int hb_selftest_bd(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                   uint64_t *const *outs, int64_t count);
 /* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
  *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
  *          HB_EQ_SELFTEST_MASK1     operands[0..7] = x, y (or NULL), r, rp, pa, qa, pb, qb; outs[0] as hb_eq_mask1 writes masked_dev
