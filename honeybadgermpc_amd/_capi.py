@@ -35,6 +35,10 @@ HB_FXP_MOD, HB_FXP_TRUNC, HB_FXP_NEG_TRUNC = 0, 1, 2
 HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
 HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
 HB_BD_SELFTEST_LEAVES, HB_BD_SELFTEST_PREFIX_MASK, HB_BD_SELFTEST_PREFIX_COMBINE, HB_BD_SELFTEST_SUM_MASK, HB_BD_SELFTEST_SUM_COMBINE = 0, 1, 2, 3, 4
+HB_DIV_SIGN, HB_DIV_NORM, HB_DIV_FIRST, HB_DIV_TRUNC = 0, 1, 2, 3
+HB_DIV_T_RESULT, HB_DIV_T_RECIP, HB_DIV_T_GOLD = 0, 1, 2
+HB_DIV_SELFTEST_OR_MASK, HB_DIV_SELFTEST_OR_COMBINE, HB_DIV_SELFTEST_NORM_MASK, HB_DIV_SELFTEST_PRODUCT_STEP, HB_DIV_SELFTEST_TRUNC_STEP = 0, 1, 2, 3, 4
+HB_DIV_SELFTEST_PAIR_MASK = 5
 HB_EQ_BIT, HB_EQ_REFERENCE = 0, 1
 HB_EQ_SELFTEST_LEGENDRE, HB_EQ_SELFTEST_MASK1, HB_EQ_SELFTEST_MID, HB_EQ_SELFTEST_CSHARE, HB_EQ_SELFTEST_FINISH = 0, 1, 2, 3, 4
 HB_LT_DIRECT, HB_LT_REFERENCE = 0, 1
@@ -118,6 +122,12 @@ SYMBOLS = {
     "hb_bd_prefix_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_bd_sum_mask": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_bd_sum_combine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_div_pair_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_div_or_mask": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_div_or_combine": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_div_norm_mask": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_div_product_step": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "hb_div_trunc_step": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_legendre": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "hb_eq_mask1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "hb_eq_mid": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
@@ -192,6 +202,7 @@ SYMBOLS = {
     "hb_selftest_jj": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_bd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
+    "hb_selftest_div": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_eq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_lt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_off": (_i, [_vp, _i, _i, _vp, _vp, _i64]),

@@ -43,9 +43,7 @@ using namespace hb;
 namespace hb {
 
 // ---------------------------------------------------------------- the wiring (host and device)
-// plane of node y of level l, and its partner
-HB_HD int bd_node(int y, int l) { return ((y >> l) << (l + 1)) | (1 << l) | (y & ((1 << l) - 1)); }
-HB_HD int bd_partner(int j, int l) { return ((j >> l) << l) - 1; }
+// (bd_node, bd_partner, bd_levels and bd_active: hb_fxp_elem.hpp, shared with hb_div.hip)
 // triple row t of a level with G g-only nodes -> its node; second: 0 the product p_j g_q, 1 the product p_j p_q
 HB_HD int bd_triple_node(int t, int G, int &second) {
     second = t >= G ? ((t - G) & 1) : 0;
@@ -53,17 +51,6 @@ HB_HD int bd_triple_node(int t, int G, int &second) {
 }
 HB_HD int bd_node_triple(int y, int G) { return y < G ? y : G + 2 * (y - G); }
 
-// levels over n planes: ceil(log2 n), none for n <= 1
-static int bd_levels(int n) {
-    int l = 0;
-    while ((1 << l) < n) l++;
-    return l;
-}
-// planes j < n with bit l set: the nodes of level l
-static int bd_active(int n, int l) {
-    const int rest = (n & ((1 << (l + 1)) - 1)) - (1 << l);
-    return ((n >> (l + 1)) << l) + (rest > 0 ? rest : 0);
-}
 static int bd_g_only(int n, int l) { const int a = bd_active(n, l); return a < (1 << l) ? a : (1 << l); }
 static int bd_level_triples(int n, int l) { return 2 * bd_active(n, l) - bd_g_only(n, l); }
 

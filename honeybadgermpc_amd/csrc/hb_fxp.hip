@@ -42,72 +42,12 @@ using namespace hb;
 
 namespace hb {
 
-// a field element as digits, handed to a kernel by value
-template <int NL> struct FxpConst { uint32_t d[NL]; };
 // what the finish needs: 2^m (canonical), 2^m and 2^(-m) (Montgomery)
 template <int NL> struct FxpFinishConsts { uint32_t pow2[NL], pow2m[NL], inv2m[NL]; };
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-// acc = 2 acc + b: one Horner step over a bit plane
-template <int NL, int NW> HB_HD void fxp_horner(uint32_t (&acc)[NL], const uint32_t (&bw)[NW], const FpParams<NL> &P) {
-    uint32_t b[NL], t[NL];
-    unpack<NL, NW>(b, bw);
-    fp_add<NL>(t, acc, acc, P);
-    fp_add<NL>(acc, t, b, P);
-}
-
-// plane(w, i) loads this element's word of bit plane i.  HAS_X: o0 = x + half + sum_{i<nbits} 2^i b_i (half = 2^(k-1)), o1 = r1 =
-// sum_{i<m} 2^i b_i;  else o0 = r2 = sum_{i<nbits-m} 2^i b_{m+i}, o1 = r1.
-template <int NL, int NW, bool HAS_X, class Load>
-HB_HD void fxp_mask_elem(uint32_t (&o0)[NW], uint32_t (&o1)[NW], const uint32_t (&xw)[NW], Load &&plane, int nbits, int m, const uint32_t (&half)[NL],
-                         const FpParams<NL> &P) {
-    uint32_t hi[NL], lo[NL], bw[NW];
-#pragma unroll
-    for (int q = 0; q < NL; q++) { hi[q] = 0; lo[q] = 0; }
-#pragma unroll 4
-    for (int i = nbits - 1; i >= m; i--) { plane(bw, i); fxp_horner<NL, NW>(hi, bw, P); }
-#pragma unroll 4
-    for (int i = m - 1; i >= 0; i--) {
-        plane(bw, i);
-        fxp_horner<NL, NW>(lo, bw, P);
-        if constexpr (HAS_X) fxp_horner<NL, NW>(hi, bw, P);
-    }
-    if constexpr (HAS_X) {
-        uint32_t x[NL], t[NL];
-        unpack<NL, NW>(x, xw);
-        fp_add<NL>(t, x, half, P);
-        fp_add<NL>(x, t, hi, P);
-        pack<NL, NW>(o0, x);
-    } else {
-        pack<NL, NW>(o0, hi);
-    }
-    pack<NL, NW>(o1, lo);
-}
-
-// o = c mod 2^m on packed words (0 < m < 32 NW)
-template <int NW> HB_HD void fxp_low_bits(uint32_t (&o)[NW], const uint32_t (&cw)[NW], int m) {
-#pragma unroll
-    for (int q = 0; q < NW; q++) {
-        const int rem = m - 32 * q;
-        o[q] = rem >= 32 ? cw[q] : (rem <= 0 ? 0u : (cw[q] & ((1u << rem) - 1u)));
-    }
-}
-// o = (x - (c mod 2^m) + r1) 2^(-m); invm = 2^(-m) R mod p
-template <int NL, int NW>
-HB_HD void fxp_trunc_pr_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r1w)[NW], int m, const uint32_t (&invm)[NL],
-                             const FpParams<NL> &P) {
-    uint32_t c2w[NW], x[NL], c2[NL], t[NL], u[NL];
-    fxp_low_bits<NW>(c2w, cw, m);
-    unpack<NL, NW>(x, xw);
-    unpack<NL, NW>(c2, c2w);
-    fp_sub<NL>(t, x, c2, P);
-    unpack<NL, NW>(c2, r1w);
-    fp_add<NL>(u, t, c2, P);
-    mont_mul<NL>(t, invm, u, P);
-    pack<NL, NW>(o, t);
-}
-
-// (fxp_bit, fxp_leaf_elem, fxp_diff_elem and fxp_node_g_elem: hb_fxp_elem.hpp, shared with hb_bd.hip)
+// (FxpConst, fxp_horner, fxp_mask_elem, fxp_low_bits, fxp_trunc_pr_elem, fxp_bit, fxp_leaf_elem, fxp_diff_elem, fxp_node_g_elem and the host
+// helpers fxp_params_ok, fxp_pow2, fxp_host_mont: hb_fxp_elem.hpp, shared with hb_bd.hip and hb_div.hip)
 
 // mode HB_FXP_MOD: a2 = c2 - r1 + 2^m (1 - carry);  HB_FXP_TRUNC: (x - a2) 2^(-m);  HB_FXP_NEG_TRUNC: (a2 - x) 2^(-m)
 template <int NL, int NW>
@@ -242,26 +182,6 @@ __global__ void __launch_bounds__(256) k_fxp_finish(const FpParams<NL> P, const 
 }
 
 // ---------------------------------------------------------------- host side
-// the masked value c < 2^(k + kappa + 1) must stay below p
-static bool fxp_params_ok(int bits, int k, int m, int kappa) { return m > 0 && m < k && kappa >= 0 && k <= 256 && kappa <= 256 && k + kappa + 1 <= bits - 1; }
-// 2^e mod p, canonical digits (mont: times R)
-template <int NL> static void fxp_pow2(uint32_t (&r)[NL], int e, bool mont, const FpParams<NL> &P) {
-    if (mont) fp_set<NL>(r, P.one);
-    else for (int q = 0; q < NL; q++) r[q] = q == 0 ? 1u : 0u;
-    for (int i = 0; i < e; i++) { uint32_t t[NL]; fp_add<NL>(t, r, r, P); fp_set<NL>(r, t); }
-}
-// one canonical element in host memory -> its Montgomery digits; false if it is not below p
-template <int NL, int NW> static bool fxp_host_mont(uint32_t (&r)[NL], const FpParams<NL> &P, const uint64_t *host) {
-    uint32_t w[NW], d[NL];
-    memcpy(w, host, NW * 4);
-    unpack<NL, NW>(d, w);
-    bool below = false;
-    for (int i = NL - 1; i >= 0; i--)
-        if (d[i] != P.p[i]) { below = d[i] < P.p[i]; break; }
-    if (!below) return false;
-    to_mont<NL>(r, d, P);
-    return true;
-}
 template <int NL, int NW> static bool fxp_finish_consts(FxpFinishConsts<NL> &K, const FpParams<NL> &P, int m, const uint64_t *inv2m_host, bool need_inv) {
     fxp_pow2<NL>(K.pow2, m, false, P);
     fxp_pow2<NL>(K.pow2m, m, true, P);

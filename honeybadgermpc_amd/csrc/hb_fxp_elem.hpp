@@ -1,9 +1,11 @@
-// hb_fxp_elem.hpp -- the per-element bodies of the carry networks over (generate, propagate) planes, shared by hb_fxp.hip (the carry
-// tree of div2m / ltz: only the root is kept) and hb_bd.hip (the prefix network of the bit decomposition: every carry is kept), with
-// the argument checks both files' entry points make.  Host and device: the kernels only load, call and store, and the host self
-// tests run the same functions.
+// hb_fxp_elem.hpp -- the per-element bodies of the fixed-point steps, shared by hb_fxp.hip (masks, truncation, and the carry tree of
+// div2m / ltz: only the root is kept), hb_bd.hip (the prefix network of the bit decomposition: every carry is kept) and hb_div.hip
+// (division: the prefix OR and the fused Goldschmidt steps), with the Sklansky wiring the two networks share and the argument checks
+// the files' entry points make.  Host and device: the kernels only load, call and store, and the host self tests run the same
+// functions.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include "hb_ew_elem.hpp"
 
 namespace hb {
@@ -51,6 +53,84 @@ HB_HD void fxp_node_g_elem(uint32_t (&o)[NW], const uint32_t (&g1w)[NW], const u
     pack<NL, NW>(o, r);
 }
 
+// a field element as digits, handed to a kernel by value
+template <int NL> struct FxpConst { uint32_t d[NL]; };
+
+// acc = 2 acc + b: one Horner step over a bit plane
+template <int NL, int NW> HB_HD void fxp_horner(uint32_t (&acc)[NL], const uint32_t (&bw)[NW], const FpParams<NL> &P) {
+    uint32_t b[NL], t[NL];
+    unpack<NL, NW>(b, bw);
+    fp_add<NL>(t, acc, acc, P);
+    fp_add<NL>(acc, t, b, P);
+}
+
+// plane(w, i) loads this element's word of bit plane i.  HAS_X: o0 = x + half + sum_{i<nbits} 2^i b_i (half = 2^(k-1)), o1 = r1 =
+// sum_{i<m} 2^i b_i;  else o0 = r2 = sum_{i<nbits-m} 2^i b_{m+i}, o1 = r1.
+template <int NL, int NW, bool HAS_X, class Load>
+HB_HD void fxp_mask_elem(uint32_t (&o0)[NW], uint32_t (&o1)[NW], const uint32_t (&xw)[NW], Load &&plane, int nbits, int m, const uint32_t (&half)[NL],
+                         const FpParams<NL> &P) {
+    uint32_t hi[NL], lo[NL], bw[NW];
+#pragma unroll
+    for (int q = 0; q < NL; q++) { hi[q] = 0; lo[q] = 0; }
+#pragma unroll 4
+    for (int i = nbits - 1; i >= m; i--) { plane(bw, i); fxp_horner<NL, NW>(hi, bw, P); }
+#pragma unroll 4
+    for (int i = m - 1; i >= 0; i--) {
+        plane(bw, i);
+        fxp_horner<NL, NW>(lo, bw, P);
+        if constexpr (HAS_X) fxp_horner<NL, NW>(hi, bw, P);
+    }
+    if constexpr (HAS_X) {
+        uint32_t x[NL], t[NL];
+        unpack<NL, NW>(x, xw);
+        fp_add<NL>(t, x, half, P);
+        fp_add<NL>(x, t, hi, P);
+        pack<NL, NW>(o0, x);
+    } else {
+        pack<NL, NW>(o0, hi);
+    }
+    pack<NL, NW>(o1, lo);
+}
+
+// o = c mod 2^m on packed words (0 < m < 32 NW)
+template <int NW> HB_HD void fxp_low_bits(uint32_t (&o)[NW], const uint32_t (&cw)[NW], int m) {
+#pragma unroll
+    for (int q = 0; q < NW; q++) {
+        const int rem = m - 32 * q;
+        o[q] = rem >= 32 ? cw[q] : (rem <= 0 ? 0u : (cw[q] & ((1u << rem) - 1u)));
+    }
+}
+// o = (x - (c mod 2^m) + r1) 2^(-m); invm = 2^(-m) R mod p
+template <int NL, int NW>
+HB_HD void fxp_trunc_pr_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r1w)[NW], int m, const uint32_t (&invm)[NL],
+                             const FpParams<NL> &P) {
+    uint32_t c2w[NW], x[NL], c2[NL], t[NL], u[NL];
+    fxp_low_bits<NW>(c2w, cw, m);
+    unpack<NL, NW>(x, xw);
+    unpack<NL, NW>(c2, c2w);
+    fp_sub<NL>(t, x, c2, P);
+    unpack<NL, NW>(c2, r1w);
+    fp_add<NL>(u, t, c2, P);
+    mont_mul<NL>(t, invm, u, P);
+    pack<NL, NW>(o, t);
+}
+
+// ---------------------------------------------------------------- the Sklansky wiring of hb_bd.hip and hb_div.hip (host and device)
+// plane of node y of level l, and its partner
+HB_HD int bd_node(int y, int l) { return ((y >> l) << (l + 1)) | (1 << l) | (y & ((1 << l) - 1)); }
+HB_HD int bd_partner(int j, int l) { return ((j >> l) << l) - 1; }
+// levels over n planes: ceil(log2 n), none for n <= 1
+static inline int bd_levels(int n) {
+    int l = 0;
+    while ((1 << l) < n) l++;
+    return l;
+}
+// planes j < n with bit l set: the nodes of level l
+static inline int bd_active(int n, int l) {
+    const int rest = (n & ((1 << (l + 1)) - 1)) - (1 << l);
+    return ((n >> (l + 1)) << l) + (rest > 0 ? rest : 0);
+}
+
 // read-once operands (bit planes, triples, what was just opened)
 template <int NW> __device__ __forceinline__ void fxp_load_once(uint32_t (&w)[NW], const uint32_t *p) {
     if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
@@ -66,6 +146,27 @@ static inline bool fxp_m_ok(int bits, int m) { return m > 0 && m <= bits - 2; }
 static inline bool fxp_overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
     const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
     return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
+}
+
+// the masked value c < 2^(k + kappa + 1) must stay below p
+static inline bool fxp_params_ok(int bits, int k, int m, int kappa) { return m > 0 && m < k && kappa >= 0 && k <= 256 && kappa <= 256 && k + kappa + 1 <= bits - 1; }
+// 2^e mod p, canonical digits (mont: times R)
+template <int NL> static void fxp_pow2(uint32_t (&r)[NL], int e, bool mont, const FpParams<NL> &P) {
+    if (mont) fp_set<NL>(r, P.one);
+    else for (int q = 0; q < NL; q++) r[q] = q == 0 ? 1u : 0u;
+    for (int i = 0; i < e; i++) { uint32_t t[NL]; fp_add<NL>(t, r, r, P); fp_set<NL>(r, t); }
+}
+// one canonical element in host memory -> its Montgomery digits; false if it is not below p
+template <int NL, int NW> static bool fxp_host_mont(uint32_t (&r)[NL], const FpParams<NL> &P, const uint64_t *host) {
+    uint32_t w[NW], d[NL];
+    memcpy(w, host, NW * 4);
+    unpack<NL, NW>(d, w);
+    bool below = false;
+    for (int i = NL - 1; i >= 0; i--)
+        if (d[i] != P.p[i]) { below = d[i] < P.p[i]; break; }
+    if (!below) return false;
+    to_mont<NL>(r, d, P);
+    return true;
 }
 
 }  // namespace hb

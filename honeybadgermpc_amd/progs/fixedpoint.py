@@ -50,7 +50,7 @@ Protocol level, coroutines over an OpenCoalescer (every party runs the same coro
                                                         matmul_width(k, inner) = 2 k + ceil(log2(inner)): 2 batches, m n truncation opens
 
 div2m and its kin take 3 + 2 carry_levels(m) launches for any count.  FixedPointArray wraps a share array with +, -, neg(), mul,
-div by a public number, ltz, lt and open() -> list[float].
+div by a public number, divide by a shared one and reciprocal (progs/fixedpoint_division.py), ltz, lt and open() -> list[float].
 """
 from .._capi import HB_FXP_MOD, HB_FXP_NEG_TRUNC, HB_FXP_TRUNC
 from ..share_arithmetic import add, beaver_multiply_arrays, neg, sub
@@ -533,6 +533,18 @@ class FixedPointArray:
             raise NotImplementedError
         prod = _ew_mul(self.ctx, self.shares, to_fixed_point_repr(1.0 / x, self.f) % self.ctx.modulus)
         return self._like(await trunc_pr(self.co, prod, bits, 2 * self.k, self.f, self.kappa))
+
+    async def divide(self, x, bits, triples, signed=True, theta=None):
+        """by a SHARED divisor (fixedpoint_division.div): x != 0 and |self / x| < 2^(k-2-f); signed=False: the caller promises 0 < x"""
+        from .fixedpoint_division import div
+
+        return self._like(await div(self.co, self.shares, self._other(x), bits, triples, self.f, self.k, self.kappa, theta, signed))
+
+    async def reciprocal(self, bits, triples, signed=True, theta=None):
+        """1 / self (fixedpoint_division.reciprocal)"""
+        from .fixedpoint_division import reciprocal
+
+        return self._like(await reciprocal(self.co, self.shares, bits, triples, self.f, self.k, self.kappa, theta, signed))
 
     async def ltz(self, bits, triples):
         """-> a (count, limbs) tensor of shares of [a < 0]"""

@@ -353,6 +353,63 @@ int hb_bd_sum_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev,
 int hb_bd_sum_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m,
                       const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- division of shared fixed-point numbers by a shared divisor (hb_div.hip) ----------------------------------------------
+ * Catrina and Saxena's FPDiv / AppRcr / Norm for signed k-bit values with f fractional bits, for arrays of `count` values; everything
+ * between two opens is one launch.  Operands and results are canonical residues; arrays of several rows are row-major with `count`
+ * elements a row; ta_dev, tb_dev, tab_dev hold this party's shares of the first factors, second factors and products, one row a triple.
+ * One level of a Sklansky prefix OR over n_planes planes (0 <= level < ceil(log2 n_planes)), the wiring of hb_bd_prefix_*: node t is
+ *   network plane j = ((t >> level) << (level + 1)) | (1 << level) | (t & ((1 << level) - 1)) while j <= n_planes - 1, its partner
+ *   q = ((j >> level) << level) - 1, and y_j <- y_j + y_q - [y_j y_q]: one triple a node, triple row t for node t.  from_top != 0:
+ *   network plane r is row n_planes - 1 - r of y_dev, so row i ends as the OR of rows i and above; else row r, the OR of rows r and below.
+ *   hb_div_or_mask     masked_dev rows 2t, 2t + 1 = y_j - ta[t], y_q - tb[t]: the level's ONE array to open
+ *   hb_div_or_combine  opened_dev = that array opened; y_dev is updated IN PLACE at the level's nodes, every other row is left untouched
+ * hb_div_pair_mask: masked_dev rows 0, 1 = x - ta, y - tb (one row each): the masked pair of ONE product [x y] as one array to open.
+ * hb_div_norm_mask: y_dev the prefix OR from the top of the bits of x.  v_dev = sum_i 2^(n_planes-1-i) (y_i - y_{i+1}) (no product), and
+ *   masked_dev rows 0, 1 = x - ta[0], v - tb[0] and, with u_dev (the sign bit; NULL: unsigned), rows 2, 3 = u - ta[1], v - tb[1].
+ * hb_div_product_step: opened_dev [2 products][count] the masked pairs opened.  Beaver-combines them, applies the step's affine map and
+ *   writes what the next open needs:
+ *     HB_DIV_SIGN   products = 1 [u b], aux_dev = b: out0 = b - 2 [u b]
+ *     HB_DIV_NORM   products = 2 [x v], [u v] (or 1: unsigned), aux_dev = v: c = [x v], v' = v - 2 [u v] (unsigned: v).  With nxt_a_dev and
+ *                   nxt_b_dev (the next triple's factors, one row each) and cst_host = alpha': out0 rows 0, 1 = (alpha' - 2 c) - nxt_a,
+ *                   v' - nxt_b; with both NULL: out0 rows 0, 1 = c, v'.
+ *     HB_DIV_FIRST  products = 2 [b w], [a w], cst_host = alpha = 2^(2f): out1 row 1 = alpha - [b w]; Y = [a w] is masked for truncation:
+ *                   out0 row 0 = Y + 2^(width-1) + r1 + 2^m r2, out1 row 0 = Y + r1, from bits_dev [width + kappa][count]
+ *     HB_DIV_TRUNC  products = 1 or 2: product r is masked for truncation from rows r (width + kappa) .. of bits_dev: out0 row r the masked
+ *                   value, out1 row r = product + r1
+ *   The masks are hb_fxp_mask's and width, m, kappa are checked as it checks k, m, kappa.  cst_host: one element in host memory.
+ * hb_div_trunc_step: opened_dev, s_dev [rows][count] the masked values opened and the kept product + r1; t_r = (s_r - (opened_r mod 2^m))
+ *   2^(-m), inv2m_host = 2^(-m) mod p (one element in host memory).
+ *     HB_DIV_T_RESULT  rows = 1, products = 0: out = t_0
+ *     HB_DIV_T_RECIP   rows = 1, products = 2: out rows 0..3 = ext0 - ta[0], t_0 - tb[0], ext1 - ta[1], t_0 - tb[1]
+ *     HB_DIV_T_GOLD    x = t_1 (rows = 2) or x_dev (rows = 1); alpha_host = 2^(2f): out rows 0, 1 = t_0 - ta[0], alpha + x - tb[0] and, with
+ *                      products = 2, rows 2, 3 = x - ta[1], x - tb[1]
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: an unknown mode, counts a
+ * mode does not take, a level the network does not have, more than 256 planes, a truncation the modulus has no room for, a constant
+ * not below the modulus, null pointers (with count > 0), a negative count, an output that overlaps an input or another output.
+ * count == 0 returns HB_OK and launches nothing. */
+#define HB_DIV_SIGN 0
+#define HB_DIV_NORM 1
+#define HB_DIV_FIRST 2
+#define HB_DIV_TRUNC 3
+#define HB_DIV_T_RESULT 0
+#define HB_DIV_T_RECIP 1
+#define HB_DIV_T_GOLD 2
+int hb_div_pair_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev,
+                     int64_t count, void *stream);
+int hb_div_or_mask(hb_ctx *ctx, const uint64_t *y_dev, int n_planes, int level, int from_top, const uint64_t *ta_dev, const uint64_t *tb_dev,
+                   uint64_t *masked_dev, int64_t count, void *stream);
+int hb_div_or_combine(hb_ctx *ctx, const uint64_t *opened_dev, uint64_t *y_dev, int n_planes, int level, int from_top, const uint64_t *ta_dev,
+                      const uint64_t *tb_dev, const uint64_t *tab_dev, int64_t count, void *stream);
+int hb_div_norm_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, int n_planes, const uint64_t *u_dev, const uint64_t *ta_dev,
+                     const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *v_dev, int64_t count, void *stream);
+int hb_div_product_step(hb_ctx *ctx, int mode, int products, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev,
+                        const uint64_t *tab_dev, const uint64_t *aux_dev, const uint64_t *cst_host, const uint64_t *nxt_a_dev,
+                        const uint64_t *nxt_b_dev, const uint64_t *bits_dev, int width, int m, int kappa, uint64_t *out0_dev, uint64_t *out1_dev,
+                        int64_t count, void *stream);
+int hb_div_trunc_step(hb_ctx *ctx, int mode, int rows, int products, const uint64_t *opened_dev, const uint64_t *s_dev, int m,
+                      const uint64_t *inv2m_host, const uint64_t *alpha_host, const uint64_t *x_dev, const uint64_t *ext0_dev,
+                      const uint64_t *ext1_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *out_dev, int64_t count, void *stream);
+
 /* ---- equality of shared values (hb_eq.hip) ---------------------------------------------------------------------------------
  * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
  * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
@@ -815,6 +872,25 @@ int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 #define HB_BD_SELFTEST_SUM_COMBINE 4
 int hb_selftest_bd(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                    uint64_t *const *outs, int64_t count);
+/* host-side run of the division kernels' bodies (no GPU needed) over host memory, a whole level or step at a time; parameters are
+ * checked as the device calls check them:
+ *   what = HB_DIV_SELFTEST_OR_MASK       params = {n_planes, level, from_top}; operands[0..2] = y, ta, tb; outs[0] as hb_div_or_mask writes
+ *                                        masked_dev
+ *          HB_DIV_SELFTEST_OR_COMBINE    params as above; operands[0..3] = opened, ta, tb, tab; outs[0] = y, updated in place
+ *          HB_DIV_SELFTEST_NORM_MASK     params = {n_planes}; operands[0..4] = x, y, u (or NULL), ta, tb; outs[0..1] = masked, v
+ *          HB_DIV_SELFTEST_PRODUCT_STEP  params = {mode, products, width, m, kappa}; operands[0..8] = opened, ta, tb, tab, aux, cst (one
+ *                                        element), nxt_a, nxt_b, bits (NULL where the mode reads none); outs[0..1] = out0, out1
+ *          HB_DIV_SELFTEST_TRUNC_STEP    params = {mode, rows, products, m}; operands[0..8] = opened, s, inv2m, alpha (one element each), x,
+ *                                        ext0, ext1, ta, tb; outs[0]
+ *          HB_DIV_SELFTEST_PAIR_MASK     operands[0..3] = x, y, ta, tb; outs[0] as hb_div_pair_mask writes masked_dev */
+#define HB_DIV_SELFTEST_OR_MASK 0
+#define HB_DIV_SELFTEST_OR_COMBINE 1
+#define HB_DIV_SELFTEST_NORM_MASK 2
+#define HB_DIV_SELFTEST_PRODUCT_STEP 3
+#define HB_DIV_SELFTEST_TRUNC_STEP 4
+#define HB_DIV_SELFTEST_PAIR_MASK 5
+int hb_selftest_div(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                    uint64_t *const *outs, int64_t count);
 /* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
  *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
  *          HB_EQ_SELFTEST_MASK1     operands[0..7] = x, y (or NULL), r, rp, pa, qa, pb, qb; outs[0] as hb_eq_mask1 writes masked_dev
