@@ -7,9 +7,10 @@
 // a bit turns carries into sum bits.  N = m - 1 planes (bits 0 .. m - 2: the carry out of bit m - 1 is never used), least significant
 // first, updated in place.
 //
-// k_bd_leaves          plane i < m - 1 from bit i of c2 (public) and b_i with no product, fxp_leaf_elem: a_i = 1 -> (1 - b_i, b_i),
+// The steps are rows under the generic kernel k_rows (hb_rows.hpp); the leaves' row runs under k_leaves (hb_fxp_elem.hpp):
+// BdLeavesRow          plane i < m - 1 from bit i of c2 (public) and b_i with no product, fxp_leaf_elem: a_i = 1 -> (1 - b_i, b_i),
 //                      a_i = 0 -> (0, 1 - b_i); the carry-in 1 is folded into plane 0: (g_0 + p_0, 0).
-// k_bd_prefix_mask / k_bd_prefix_combine   level l: node y is plane j = ((y >> l) << (l + 1)) | (1 << l) | (y & ((1 << l) - 1)) while
+// BdPrefixMaskRow / BdPrefixCombineRow   level l: node y is plane j = ((y >> l) << (l + 1)) | (1 << l) | (y & ((1 << l) - 1)) while
 //                      j <= N - 1, its partner q = ((j >> l) << l) - 1, and (g_j, p_j) <- (g_j + p_j g_q, p_j p_q).  Bit l of q is clear,
 //                      so q is no node of level l and the level runs in place.  The nodes y < 2^l lie in the block that starts at plane
 //                      0, whose p is 0 after the fold: they are g-only, ONE product, p never written (and never read again: such a j has
@@ -17,23 +18,24 @@
 //                      G + 2 (y - G) [p_j g_q] and G + 2 (y - G) + 1 [p_j p_q].  The mask writes the two masked differences of every
 //                      product of the level into one array (one thread a triple), the combine takes that array opened and updates the
 //                      planes (one thread a node).  After the last level plane i holds the carry into bit i + 1.
-// k_bd_sum_mask / k_bd_sum_combine   s_0 = a_0 xor b_0 is a select; s_i = p_i + C_i - 2 p_i C_i with p_i the leaf's propagate, recomputed
+// BdSumMaskRow / BdSumCombineRow   s_0 = a_0 xor b_0 is a select; s_i = p_i + C_i - 2 p_i C_i with p_i the leaf's propagate, recomputed
 //                      from bit i of c and plane i of `bits` (not kept), and C_i = g of plane i - 1: m - 1 products in one batch.
 //
 // Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions (hb_fxp_elem.hpp, hb_ew_elem.hpp and
-// below): the __global__ wrappers only load, call them and store, and hb_selftest_bd runs the very same functions on the host.
+// below); a step's row -- which operands it loads, which body it calls, where it stores -- is an HB_HD function over a memory policy,
+// so hb_selftest_bd runs on the host the very rows, arithmetic and addressing, that k_rows runs on the device.
 //
 // Launch shape (all kernels): 256-thread workgroups, one element a thread in x, so a wave's accesses to a plane cover consecutive
-// elements (64 x 32 bytes = 2 KiB, whole dwordx4 accesses); the triple / node / plane in blockIdx.y (k_bd_leaves walks the planes in
+// elements (64 x 32 bytes = 2 KiB, whole dwordx4 accesses); the triple / node / plane in blockIdx.y (BdLeavesRow walks the planes in
 // the thread: c is read once).  No LDS, no grid stride, one launch a call.  Triples, opened values and bit planes are read once and
-// take the non-temporal loads (fxp_load_once); p_j, which the two triples of a full node both read, and c, which every plane of the
+// take the non-temporal loads (load_once); p_j, which the two triples of a full node both read, and c, which every plane of the
 // sum step reads, take the plain ones and are served from cache the second time.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
-//   k_bd_leaves<9, 8>          56 VGPRs: 8 waves a SIMD                            k_bd_leaves<3, 2>          56 VGPRs: 8 waves
-//   k_bd_prefix_mask<9, 8>     38 VGPRs: 8 waves                                   k_bd_prefix_mask<3, 2>     15 VGPRs: 8 waves
-//   k_bd_prefix_combine<9, 8>  74 VGPRs: 6 waves                                   k_bd_prefix_combine<3, 2>  33 VGPRs: 8 waves
-//   k_bd_sum_mask<9, 8>        40 VGPRs: 8 waves                                   k_bd_sum_mask<3, 2>        22 VGPRs: 8 waves
-//   k_bd_sum_combine<9, 8>     77 VGPRs: 6 waves                                   k_bd_sum_combine<3, 2>     39 VGPRs: 8 waves
+//   BdLeavesRow<9, 8>          56 VGPRs: 8 waves a SIMD                            BdLeavesRow<3, 2>          56 VGPRs: 8 waves
+//   BdPrefixMaskRow<9, 8>      41 VGPRs: 8 waves                                   BdPrefixMaskRow<3, 2>      15 VGPRs: 8 waves
+//   BdPrefixCombineRow<9, 8>   74 VGPRs: 6 waves                                   BdPrefixCombineRow<3, 2>   32 VGPRs: 8 waves
+//   BdSumMaskRow<9, 8>         40 VGPRs: 8 waves                                   BdSumMaskRow<3, 2>         20 VGPRs: 8 waves
+//   BdSumCombineRow<9, 8>      76 VGPRs: 6 waves                                   BdSumCombineRow<3, 2>      38 VGPRs: 8 waves
 // (DESIGN.md section 3s has the schedule and the counts.)
 #include "hb_common.hpp"
 #include "hb_fxp_elem.hpp"
@@ -99,185 +101,142 @@ HB_HD void bd_sum_elem(uint32_t (&o)[NW], const uint32_t (&pw)[NW], const uint32
     pack<NL, NW>(o, t);
 }
 
-// ---------------------------------------------------------------- kernels
-// g, p: m - 1 planes each, distinct from c and bits
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_bd_leaves(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ bits, int m,
-                                                   uint32_t *__restrict__ g, uint32_t *__restrict__ p, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
-    load_words<NW>(cw, c + i * NW);
+// ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
+// g, p: m - 1 planes each, distinct from c and bits (the body under k_leaves, hb_fxp_elem.hpp, which has the __restrict__)
+struct BdLeavesRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void planes(const uint32_t *c, const uint32_t *bits, uint32_t *g, uint32_t *p, int m, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
+        mem.load(cw, c, i);
 #pragma unroll 4
-    for (int j = 0; j < m - 1; j++) {
-        fxp_load_once<NW>(bw, bits + ((int64_t)j * count + i) * NW);
-        fxp_leaf_elem<NL, NW>(gw, pw, fxp_bit<NW>(cw, j), bw, P);
-        if (j == 0) bd_fold_elem<NL, NW>(gw, pw, P);
-        store_words<NW>(g + ((int64_t)j * count + i) * NW, gw);
-        store_words<NW>(p + ((int64_t)j * count + i) * NW, pw);
+        for (int j = 0; j < m - 1; j++) {
+            mem.once(bw, bits, (int64_t)j * count + i);
+            fxp_leaf_elem<NL, NW>(gw, pw, word_bit<NW>(cw, j), bw, P);
+            if (j == 0) bd_fold_elem<NL, NW>(gw, pw, P);
+            mem.store(g, (int64_t)j * count + i, gw);
+            mem.store(p, (int64_t)j * count + i, pw);
+        }
     }
-}
-
-// triple t = blockIdx.y of level l: its first factor is p_j, its second g_q or p_q
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_bd_prefix_mask(const FpParams<NL> P, const uint32_t *__restrict__ g, const uint32_t *__restrict__ p, int l, int G,
-                                                        const uint32_t *__restrict__ ta, const uint32_t *__restrict__ tb, uint32_t *__restrict__ masked,
-                                                        int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t t = blockIdx.y;
-    int second;
-    const int64_t j = bd_node(bd_triple_node((int)t, G, second), l), q = bd_partner((int)j, l);
-    uint32_t p1[NW], y[NW], aw[NW], bw[NW], o0[NW], o1[NW];
-    load_words<NW>(p1, p + (j * count + i) * NW);
-    load_words<NW>(y, (second ? p : g) + (q * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW);
-    fxp_load_once<NW>(bw, tb + (t * count + i) * NW);
-    fxp_diff_elem<NL, NW>(o0, p1, aw, P);
-    fxp_diff_elem<NL, NW>(o1, y, bw, P);
-    store_words<NW>(masked + ((2 * t) * count + i) * NW, o0);
-    store_words<NW>(masked + ((2 * t + 1) * count + i) * NW, o1);
-}
-
-// node y = blockIdx.y of level l, in place: g and p are read and written at plane j alone (no __restrict__: they alias themselves)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_bd_prefix_combine(const FpParams<NL> P, const uint32_t *__restrict__ opened, uint32_t *g, uint32_t *p, int l, int G,
-                                                           const uint32_t *__restrict__ ta, const uint32_t *__restrict__ tb, const uint32_t *__restrict__ tab,
-                                                           int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int y = (int)blockIdx.y;
-    const int64_t j = bd_node(y, l);
-    int64_t t = bd_node_triple(y, G);
-    uint32_t g1[NW], dw[NW], ew[NW], aw[NW], bw[NW], abw[NW], ow[NW];
-    load_words<NW>(g1, g + (j * count + i) * NW);
-    fxp_load_once<NW>(dw, opened + ((2 * t) * count + i) * NW); fxp_load_once<NW>(ew, opened + ((2 * t + 1) * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW); fxp_load_once<NW>(bw, tb + (t * count + i) * NW); fxp_load_once<NW>(abw, tab + (t * count + i) * NW);
-    fxp_node_g_elem<NL, NW>(ow, g1, dw, ew, aw, bw, abw, P);
-    store_words<NW>(g + (j * count + i) * NW, ow);
-    if (y < G) return;
-    t++;
-    fxp_load_once<NW>(dw, opened + ((2 * t) * count + i) * NW); fxp_load_once<NW>(ew, opened + ((2 * t + 1) * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW); fxp_load_once<NW>(bw, tb + (t * count + i) * NW); fxp_load_once<NW>(abw, tab + (t * count + i) * NW);
-    ew_beaver_elem<NL, NW>(ow, dw, ew, aw, bw, abw, P);
-    store_words<NW>(p + (j * count + i) * NW, ow);
-}
-
-// triple t = blockIdx.y, the product of bit t + 1: the leaf's p_{t+1} times the carry g[t]
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_bd_sum_mask(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ bits,
-                                                     const uint32_t *__restrict__ g, const uint32_t *__restrict__ ta, const uint32_t *__restrict__ tb,
-                                                     uint32_t *__restrict__ masked, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t t = blockIdx.y;
-    uint32_t cw[NW], xw[NW], pw[NW], aw[NW], bw[NW], o0[NW], o1[NW];
-    load_words<NW>(cw, c + i * NW);
-    fxp_load_once<NW>(xw, bits + ((t + 1) * count + i) * NW);
-    bd_leaf_p_elem<NL, NW>(pw, fxp_bit<NW>(cw, (int)t + 1), xw, P);
-    load_words<NW>(xw, g + (t * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW);
-    fxp_load_once<NW>(bw, tb + (t * count + i) * NW);
-    fxp_diff_elem<NL, NW>(o0, pw, aw, P);
-    fxp_diff_elem<NL, NW>(o1, xw, bw, P);
-    store_words<NW>(masked + ((2 * t) * count + i) * NW, o0);
-    store_words<NW>(masked + ((2 * t + 1) * count + i) * NW, o1);
-}
-
-// plane b = blockIdx.y of the result
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_bd_sum_combine(const FpParams<NL> P, const uint32_t *__restrict__ opened, const uint32_t *__restrict__ c,
-                                                        const uint32_t *__restrict__ bits, const uint32_t *__restrict__ g, const uint32_t *__restrict__ ta,
-                                                        const uint32_t *__restrict__ tb, const uint32_t *__restrict__ tab, uint32_t *__restrict__ out,
-                                                        int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t b = blockIdx.y, t = b - 1;
-    uint32_t cw[NW], xw[NW], pw[NW], gw[NW], dw[NW], ew[NW], aw[NW], bw[NW], abw[NW], ow[NW];
-    load_words<NW>(cw, c + i * NW);
-    fxp_load_once<NW>(xw, bits + (b * count + i) * NW);
-    if (b == 0) {
-        bd_sum0_elem<NL, NW>(ow, fxp_bit<NW>(cw, 0), xw, P);
-        store_words<NW>(out + i * NW, ow);
-        return;
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LeavesArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        planes<NL, NW>(A.c, A.bits, A.g, A.p, A.m, i, count, mem, P);
     }
-    bd_leaf_p_elem<NL, NW>(pw, fxp_bit<NW>(cw, (int)b), xw, P);
-    fxp_load_once<NW>(gw, g + (t * count + i) * NW);
-    fxp_load_once<NW>(dw, opened + ((2 * t) * count + i) * NW); fxp_load_once<NW>(ew, opened + ((2 * t + 1) * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW); fxp_load_once<NW>(bw, tb + (t * count + i) * NW); fxp_load_once<NW>(abw, tab + (t * count + i) * NW);
-    bd_sum_elem<NL, NW>(ow, pw, gw, dw, ew, aw, bw, abw, P);
-    store_words<NW>(out + (b * count + i) * NW, ow);
-}
+};
 
-// ---------------------------------------------------------------- host: the same element functions over `count` elements
+// One level.  The mask reads g and p; the combine works in place: g and p are read and written at plane j alone.
+struct BdPrefixArgs { const uint32_t *opened, *ta, *tb, *tab; uint32_t *g, *p, *masked; int l, G; };
+
+// triple t of level l: its first factor is p_j, its second g_q or p_q
+struct BdPrefixMaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const BdPrefixArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t t = y;
+        int second;
+        const int64_t j = bd_node(bd_triple_node(y, A.G, second), A.l), q = bd_partner((int)j, A.l);
+        uint32_t p1[NW], yw[NW], aw[NW], bw[NW], o0[NW], o1[NW];
+        mem.load(p1, A.p, j * count + i);
+        mem.load(yw, second ? A.p : A.g, q * count + i);
+        mem.once(aw, A.ta, t * count + i);
+        mem.once(bw, A.tb, t * count + i);
+        diff_elem<NL, NW>(o0, p1, aw, P);
+        diff_elem<NL, NW>(o1, yw, bw, P);
+        mem.store(A.masked, (2 * t) * count + i, o0);
+        mem.store(A.masked, (2 * t + 1) * count + i, o1);
+    }
+};
+
+// node y of level l
+struct BdPrefixCombineRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const BdPrefixArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        update<NL, NW>(A.opened, A.ta, A.tb, A.tab, A, y, i, count, mem, P);
+    }
+    // what is only read is apart from the planes: __restrict__ (pointers in an argument struct do not carry it)
+    template <int NL, int NW, class Mem>
+    HB_HD static void update(const uint32_t *__restrict__ opened, const uint32_t *__restrict__ ta, const uint32_t *__restrict__ tb, const uint32_t *__restrict__ tab,
+                             const BdPrefixArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t j = bd_node(y, A.l);
+        int64_t t = bd_node_triple(y, A.G);
+        uint32_t g1[NW], dw[NW], ew[NW], aw[NW], bw[NW], abw[NW], ow[NW];
+        mem.load(g1, A.g, j * count + i);
+        mem.once(dw, opened, (2 * t) * count + i); mem.once(ew, opened, (2 * t + 1) * count + i);
+        mem.once(aw, ta, t * count + i); mem.once(bw, tb, t * count + i); mem.once(abw, tab, t * count + i);
+        fxp_node_g_elem<NL, NW>(ow, g1, dw, ew, aw, bw, abw, P);
+        mem.store(A.g, j * count + i, ow);
+        if (y < A.G) return;
+        t++;
+        mem.once(dw, opened, (2 * t) * count + i); mem.once(ew, opened, (2 * t + 1) * count + i);
+        mem.once(aw, ta, t * count + i); mem.once(bw, tb, t * count + i); mem.once(abw, tab, t * count + i);
+        ew_beaver_elem<NL, NW>(ow, dw, ew, aw, bw, abw, P);
+        mem.store(A.p, j * count + i, ow);
+    }
+};
+
+// The sum step.  The mask writes `masked`, the combine `out`.
+struct BdSumArgs { const uint32_t *opened, *c, *bits, *g, *ta, *tb, *tab; uint32_t *masked, *out; };
+
+// triple t, the product of bit t + 1: the leaf's p_{t+1} times the carry g[t]
+struct BdSumMaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const BdSumArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t t = y;
+        uint32_t cw[NW], xw[NW], pw[NW], aw[NW], bw[NW], o0[NW], o1[NW];
+        mem.load(cw, A.c, i);
+        mem.once(xw, A.bits, (t + 1) * count + i);
+        bd_leaf_p_elem<NL, NW>(pw, word_bit<NW>(cw, y + 1), xw, P);
+        mem.load(xw, A.g, t * count + i);
+        mem.once(aw, A.ta, t * count + i);
+        mem.once(bw, A.tb, t * count + i);
+        diff_elem<NL, NW>(o0, pw, aw, P);
+        diff_elem<NL, NW>(o1, xw, bw, P);
+        mem.store(A.masked, (2 * t) * count + i, o0);
+        mem.store(A.masked, (2 * t + 1) * count + i, o1);
+    }
+};
+
+// plane b of the result
+struct BdSumCombineRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const BdSumArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t b = y, t = b - 1;
+        uint32_t cw[NW], xw[NW], pw[NW], gw[NW], dw[NW], ew[NW], aw[NW], bw[NW], abw[NW], ow[NW];
+        mem.load(cw, A.c, i);
+        mem.once(xw, A.bits, b * count + i);
+        if (b == 0) {
+            bd_sum0_elem<NL, NW>(ow, word_bit<NW>(cw, 0), xw, P);
+            mem.store(A.out, i, ow);
+            return;
+        }
+        bd_leaf_p_elem<NL, NW>(pw, word_bit<NW>(cw, y), xw, P);
+        mem.once(gw, A.g, t * count + i);
+        mem.once(dw, A.opened, (2 * t) * count + i); mem.once(ew, A.opened, (2 * t + 1) * count + i);
+        mem.once(aw, A.ta, t * count + i); mem.once(bw, A.tb, t * count + i); mem.once(abw, A.tab, t * count + i);
+        bd_sum_elem<NL, NW>(ow, pw, gw, dw, ew, aw, bw, abw, P);
+        mem.store(A.out, b * count + i, ow);
+    }
+};
+
+// ---------------------------------------------------------------- host: the same rows over `count` elements
 template <int NL, int NW>
 static int selftest_bd(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
     const int m = (int)params[0], l = (int)params[1], n = m - 1;
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    auto O = [](uint64_t *base, int64_t i) -> uint32_t * { return reinterpret_cast<uint32_t *>(base) + i * NW; };
-    uint32_t r0[NW], r1[NW];
     if (what == HB_BD_SELFTEST_LEAVES) {
-        for (int64_t i = 0; i < count; i++)
-            for (int j = 0; j < n; j++) {
-                fxp_leaf_elem<NL, NW>(r0, r1, fxp_bit<NW>(W(ops[0], i), j), W(ops[1], (int64_t)j * count + i), P);
-                if (j == 0) bd_fold_elem<NL, NW>(r0, r1, P);
-                memcpy(O(outs[0], (int64_t)j * count + i), r0, NW * 4);
-                memcpy(O(outs[1], (int64_t)j * count + i), r1, NW * 4);
-            }
+        const LeavesArgs A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1]), m};
+        host_rows<BdLeavesRow, NL, NW>(A, n ? 1 : 0, count, P);                  // m == 1: no plane, and c is not looked at
     } else if (what == HB_BD_SELFTEST_PREFIX_MASK) {
-        const int G = bd_g_only(n, l), triples = bd_level_triples(n, l);
-        for (int64_t t = 0; t < triples; t++)
-            for (int64_t i = 0; i < count; i++) {
-                int second;
-                const int64_t j = bd_node(bd_triple_node((int)t, G, second), l), q = bd_partner((int)j, l);
-                fxp_diff_elem<NL, NW>(r0, W(ops[1], j * count + i), W(ops[2], t * count + i), P);
-                fxp_diff_elem<NL, NW>(r1, W(second ? ops[1] : ops[0], q * count + i), W(ops[3], t * count + i), P);
-                memcpy(O(outs[0], 2 * t * count + i), r0, NW * 4);
-                memcpy(O(outs[0], (2 * t + 1) * count + i), r1, NW * 4);
-            }
+        const BdPrefixArgs A = {nullptr, u32(ops[2]), u32(ops[3]), nullptr, const_cast<uint32_t *>(u32(ops[0])), const_cast<uint32_t *>(u32(ops[1])), u32(outs[0]), l, bd_g_only(n, l)};
+        host_rows<BdPrefixMaskRow, NL, NW>(A, bd_level_triples(n, l), count, P);
     } else if (what == HB_BD_SELFTEST_PREFIX_COMBINE) {
-        const int G = bd_g_only(n, l), active = bd_active(n, l);
-        for (int y = 0; y < active; y++)
-            for (int64_t i = 0; i < count; i++) {
-                const int64_t j = bd_node(y, l);
-                int64_t t = bd_node_triple(y, G);
-                uint32_t g1[NW];
-                memcpy(g1, O(outs[0], j * count + i), NW * 4);
-                fxp_node_g_elem<NL, NW>(r0, g1, W(ops[0], 2 * t * count + i), W(ops[0], (2 * t + 1) * count + i), W(ops[1], t * count + i), W(ops[2], t * count + i),
-                                        W(ops[3], t * count + i), P);
-                memcpy(O(outs[0], j * count + i), r0, NW * 4);
-                if (y < G) continue;
-                t++;
-                ew_beaver_elem<NL, NW>(r1, W(ops[0], 2 * t * count + i), W(ops[0], (2 * t + 1) * count + i), W(ops[1], t * count + i), W(ops[2], t * count + i),
-                                       W(ops[3], t * count + i), P);
-                memcpy(O(outs[1], j * count + i), r1, NW * 4);
-            }
+        const BdPrefixArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0]), u32(outs[1]), nullptr, l, bd_g_only(n, l)};
+        host_rows<BdPrefixCombineRow, NL, NW>(A, bd_active(n, l), count, P);
     } else if (what == HB_BD_SELFTEST_SUM_MASK) {
-        for (int64_t t = 0; t < n; t++)
-            for (int64_t i = 0; i < count; i++) {
-                uint32_t pw[NW];
-                bd_leaf_p_elem<NL, NW>(pw, fxp_bit<NW>(W(ops[0], i), (int)t + 1), W(ops[1], (t + 1) * count + i), P);
-                fxp_diff_elem<NL, NW>(r0, pw, W(ops[3], t * count + i), P);
-                fxp_diff_elem<NL, NW>(r1, W(ops[2], t * count + i), W(ops[4], t * count + i), P);
-                memcpy(O(outs[0], 2 * t * count + i), r0, NW * 4);
-                memcpy(O(outs[0], (2 * t + 1) * count + i), r1, NW * 4);
-            }
+        const BdSumArgs A = {nullptr, u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), nullptr, u32(outs[0]), nullptr};
+        host_rows<BdSumMaskRow, NL, NW>(A, n, count, P);
     } else {
-        for (int64_t b = 0; b < m; b++)
-            for (int64_t i = 0; i < count; i++) {
-                if (b == 0) {
-                    bd_sum0_elem<NL, NW>(r0, fxp_bit<NW>(W(ops[1], i), 0), W(ops[2], i), P);
-                } else {
-                    const int64_t t = b - 1;
-                    uint32_t pw[NW];
-                    bd_leaf_p_elem<NL, NW>(pw, fxp_bit<NW>(W(ops[1], i), (int)b), W(ops[2], b * count + i), P);
-                    bd_sum_elem<NL, NW>(r0, pw, W(ops[3], t * count + i), W(ops[0], 2 * t * count + i), W(ops[0], (2 * t + 1) * count + i), W(ops[4], t * count + i),
-                                        W(ops[5], t * count + i), W(ops[6], t * count + i), P);
-                }
-                memcpy(O(outs[0], b * count + i), r0, NW * 4);
-            }
+        const BdSumArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), nullptr, u32(outs[0])};
+        host_rows<BdSumCombineRow, NL, NW>(A, m, count, P);
     }
     return HB_OK;
 }
@@ -290,122 +249,80 @@ static bool bd_level_ok(int m, int level) { return level >= 0 && level < bd_leve
 
 extern "C" {
 
-#define BD_BLOCKS(ctx, name)                                                                                           \
-    const int64_t blocks = (count + 255) / 256;                                                                        \
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
-    hipStream_t s = (hipStream_t)stream
-
 int hb_bd_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int m, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_leaves: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_leaves: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
     if (count > 0 && m > 1 && (!c_dev || !bits_dev || !g_dev || !p_dev)) return HB_ERR_BAD_ARG;
     if (count == 0 || m == 1) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ob = (m - 1) * count * eb;
-    if (fxp_overlap(g_dev, ob, p_dev, ob) || fxp_overlap(g_dev, ob, c_dev, count * eb) || fxp_overlap(p_dev, ob, c_dev, count * eb) ||
-        fxp_overlap(g_dev, ob, bits_dev, ob) || fxp_overlap(p_dev, ob, bits_dev, ob))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_leaves: g and p are arrays of their own");
-    BD_BLOCKS(ctx, "hb_bd_leaves");
-    HB_DISPATCH(ctx,
-        (k_bd_leaves<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, m, (uint32_t *)g_dev, (uint32_t *)p_dev, count)),
-        (k_bd_leaves<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, m, (uint32_t *)g_dev, (uint32_t *)p_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const RowSpan outs[2] = {{g_dev, m - 1}, {p_dev, m - 1}}, ins[2] = {{c_dev, 1}, {bits_dev, m - 1}};
+    if (!outputs_apart(outs, 2, ins, 2, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_leaves: g and p are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_bd_leaves");
+    return launch_leaves<BdLeavesRow>(ctx, {u32(c_dev), u32(bits_dev), u32(g_dev), u32(p_dev), m}, (unsigned)blocks, s, count);
 }
 
 int hb_bd_prefix_mask(hb_ctx *ctx, const uint64_t *g_dev, const uint64_t *p_dev, int m, int level, const uint64_t *ta_dev, const uint64_t *tb_dev,
                       uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!g_dev || !p_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
     if (!bd_level_ok(m, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: no such level");
     if (count == 0) return HB_OK;
-    const int n = m - 1, G = bd_g_only(n, level), triples = bd_level_triples(n, level);
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ib = (int64_t)n * count * eb, mb = 2 * (int64_t)triples * count * eb;
-    if (fxp_overlap(masked_dev, mb, g_dev, ib) || fxp_overlap(masked_dev, mb, p_dev, ib) || fxp_overlap(masked_dev, mb, ta_dev, mb / 2) ||
-        fxp_overlap(masked_dev, mb, tb_dev, mb / 2))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: masked is an array of its own");
-    BD_BLOCKS(ctx, "hb_bd_prefix_mask");
-    const dim3 grid((unsigned)blocks, (unsigned)triples);
-    HB_DISPATCH(ctx,
-        (k_bd_prefix_mask<9, 8><<<grid, 256, 0, s>>>(ctx->pw, (const uint32_t *)g_dev, (const uint32_t *)p_dev, level, G, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev,
-                                                    (uint32_t *)masked_dev, count)),
-        (k_bd_prefix_mask<3, 2><<<grid, 256, 0, s>>>(ctx->pn, (const uint32_t *)g_dev, (const uint32_t *)p_dev, level, G, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev,
-                                                    (uint32_t *)masked_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const int n = m - 1, triples = bd_level_triples(n, level);
+    const RowSpan outs[1] = {{masked_dev, 2 * triples}}, ins[4] = {{g_dev, n}, {p_dev, n}, {ta_dev, triples}, {tb_dev, triples}};
+    if (!outputs_apart(outs, 1, ins, 4, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: masked is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_bd_prefix_mask");
+    const BdPrefixArgs A = {nullptr, u32(ta_dev), u32(tb_dev), nullptr, const_cast<uint32_t *>(u32(g_dev)), const_cast<uint32_t *>(u32(p_dev)), u32(masked_dev), level,
+                            bd_g_only(n, level)};
+    return launch_rows<BdPrefixMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)triples), s, count);
 }
 
 int hb_bd_prefix_combine(hb_ctx *ctx, const uint64_t *opened_dev, uint64_t *g_dev, uint64_t *p_dev, int m, int level, const uint64_t *ta_dev,
                          const uint64_t *tb_dev, const uint64_t *tab_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!opened_dev || !g_dev || !p_dev || !ta_dev || !tb_dev || !tab_dev))) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
     if (!bd_level_ok(m, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: no such level");
     if (count == 0) return HB_OK;
-    const int n = m - 1, G = bd_g_only(n, level), active = bd_active(n, level), triples = bd_level_triples(n, level);
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ib = (int64_t)n * count * eb, tb_ = (int64_t)triples * count * eb;
-    const uint64_t *planes[2] = {g_dev, p_dev};
-    for (const uint64_t *o : planes)
-        if (fxp_overlap(o, ib, opened_dev, 2 * tb_) || fxp_overlap(o, ib, ta_dev, tb_) || fxp_overlap(o, ib, tb_dev, tb_) || fxp_overlap(o, ib, tab_dev, tb_))
-            return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: g and p are arrays of their own");
-    if (fxp_overlap(g_dev, ib, p_dev, ib)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: g overlaps p");
-    BD_BLOCKS(ctx, "hb_bd_prefix_combine");
-    const dim3 grid((unsigned)blocks, (unsigned)active);
-    HB_DISPATCH(ctx,
-        (k_bd_prefix_combine<9, 8><<<grid, 256, 0, s>>>(ctx->pw, (const uint32_t *)opened_dev, (uint32_t *)g_dev, (uint32_t *)p_dev, level, G, (const uint32_t *)ta_dev,
-                                                       (const uint32_t *)tb_dev, (const uint32_t *)tab_dev, count)),
-        (k_bd_prefix_combine<3, 2><<<grid, 256, 0, s>>>(ctx->pn, (const uint32_t *)opened_dev, (uint32_t *)g_dev, (uint32_t *)p_dev, level, G, (const uint32_t *)ta_dev,
-                                                       (const uint32_t *)tb_dev, (const uint32_t *)tab_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const int n = m - 1, triples = bd_level_triples(n, level);
+    const RowSpan outs[2] = {{g_dev, n}, {p_dev, n}}, ins[4] = {{opened_dev, 2 * triples}, {ta_dev, triples}, {tb_dev, triples}, {tab_dev, triples}};
+    if (!outputs_apart(outs, 2, ins, 4, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: g and p are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_bd_prefix_combine");
+    const BdPrefixArgs A = {u32(opened_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(g_dev), u32(p_dev), nullptr, level, bd_g_only(n, level)};
+    return launch_rows<BdPrefixCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)bd_active(n, level)), s, count);
 }
 
 int hb_bd_sum_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m, const uint64_t *ta_dev, const uint64_t *tb_dev,
                    uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
     if (count > 0 && m > 1 && (!c_dev || !bits_dev || !g_dev || !ta_dev || !tb_dev || !masked_dev)) return HB_ERR_BAD_ARG;
     if (count == 0 || m == 1) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ib = (int64_t)(m - 1) * count * eb, mb = 2 * ib;
-    if (fxp_overlap(masked_dev, mb, c_dev, count * eb) || fxp_overlap(masked_dev, mb, bits_dev, ib + count * eb) || fxp_overlap(masked_dev, mb, g_dev, ib) ||
-        fxp_overlap(masked_dev, mb, ta_dev, ib) || fxp_overlap(masked_dev, mb, tb_dev, ib))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_mask: masked is an array of its own");
-    BD_BLOCKS(ctx, "hb_bd_sum_mask");
-    const dim3 grid((unsigned)blocks, (unsigned)(m - 1));
-    HB_DISPATCH(ctx,
-        (k_bd_sum_mask<9, 8><<<grid, 256, 0, s>>>(ctx->pw, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, (const uint32_t *)g_dev, (const uint32_t *)ta_dev,
-                                                 (const uint32_t *)tb_dev, (uint32_t *)masked_dev, count)),
-        (k_bd_sum_mask<3, 2><<<grid, 256, 0, s>>>(ctx->pn, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, (const uint32_t *)g_dev, (const uint32_t *)ta_dev,
-                                                 (const uint32_t *)tb_dev, (uint32_t *)masked_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const RowSpan outs[1] = {{masked_dev, 2 * (m - 1)}}, ins[5] = {{c_dev, 1}, {bits_dev, m}, {g_dev, m - 1}, {ta_dev, m - 1}, {tb_dev, m - 1}};
+    if (!outputs_apart(outs, 1, ins, 5, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_mask: masked is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_bd_sum_mask");
+    const BdSumArgs A = {nullptr, u32(c_dev), u32(bits_dev), u32(g_dev), u32(ta_dev), u32(tb_dev), nullptr, u32(masked_dev), nullptr};
+    return launch_rows<BdSumMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)(m - 1)), s, count);
 }
 
 int hb_bd_sum_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m, const uint64_t *ta_dev,
                       const uint64_t *tb_dev, const uint64_t *tab_dev, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
     if (count > 0 && (!c_dev || !bits_dev || !out_dev || (m > 1 && (!opened_dev || !g_dev || !ta_dev || !tb_dev || !tab_dev)))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ib = (int64_t)(m - 1) * count * eb, ob = ib + count * eb;
-    if (fxp_overlap(out_dev, ob, c_dev, count * eb) || fxp_overlap(out_dev, ob, bits_dev, ob) ||
-        (m > 1 && (fxp_overlap(out_dev, ob, opened_dev, 2 * ib) || fxp_overlap(out_dev, ob, g_dev, ib) || fxp_overlap(out_dev, ob, ta_dev, ib) ||
-                   fxp_overlap(out_dev, ob, tb_dev, ib) || fxp_overlap(out_dev, ob, tab_dev, ib))))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_combine: out is an array of its own");
-    BD_BLOCKS(ctx, "hb_bd_sum_combine");
-    const dim3 grid((unsigned)blocks, (unsigned)m);
-    HB_DISPATCH(ctx,
-        (k_bd_sum_combine<9, 8><<<grid, 256, 0, s>>>(ctx->pw, (const uint32_t *)opened_dev, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, (const uint32_t *)g_dev,
-                                                    (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, (const uint32_t *)tab_dev, (uint32_t *)out_dev, count)),
-        (k_bd_sum_combine<3, 2><<<grid, 256, 0, s>>>(ctx->pn, (const uint32_t *)opened_dev, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, (const uint32_t *)g_dev,
-                                                    (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, (const uint32_t *)tab_dev, (uint32_t *)out_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const bool prod = m > 1;                                                    // with m == 1 there is no product: its operands are not looked at
+    const RowSpan outs[1] = {{out_dev, m}};
+    const RowSpan ins[7] = {{c_dev, 1}, {bits_dev, m}, {prod ? opened_dev : nullptr, 2 * (m - 1)}, {prod ? g_dev : nullptr, m - 1}, {prod ? ta_dev : nullptr, m - 1},
+                            {prod ? tb_dev : nullptr, m - 1}, {prod ? tab_dev : nullptr, m - 1}};
+    if (!outputs_apart(outs, 1, ins, 7, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_combine: out is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_bd_sum_combine");
+    const BdSumArgs A = {u32(opened_dev), u32(c_dev), u32(bits_dev), u32(g_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), nullptr, u32(out_dev)};
+    return launch_rows<BdSumCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)m), s, count);
 }
 
 int hb_selftest_bd(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
     if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 2; i++) if (params[i] < -(1 << 30) || params[i] > (1 << 30)) return HB_ERR_BAD_ARG;
     const int m = (int)params[0], level = (int)params[1];
-    if (!bd_m_ok(fxp_modulus_bits(p_limbs, n_limbs), m)) return HB_ERR_BAD_ARG;
+    if (!bd_m_ok(modulus_bits(p_limbs, n_limbs), m)) return HB_ERR_BAD_ARG;
     int n_ops = 0, n_outs = 1;
     switch (what) {
     case HB_BD_SELFTEST_LEAVES: n_ops = 2; n_outs = 2; break;

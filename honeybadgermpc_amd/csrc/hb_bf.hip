@@ -29,6 +29,7 @@
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DESIGN.md section 3j.
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
+#include "hb_rows.hpp"
 
 using namespace hb;
 
@@ -111,9 +112,6 @@ template <int NW> __device__ __forceinline__ void bf_store_pair(uint32_t *__rest
 }
 static bool bf_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 // read-once operands (the triple, the sign, the opened values)
-template <int NW> __device__ __forceinline__ void bf_load_once(uint32_t (&w)[NW], const uint32_t *__restrict__ p) {
-    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
-}
 
 // masked[(BITS ? half : 0) + j] = in[xi] - in[yi] - q[j];  BITS: masked[j] = bits[j] - p[j].  `masked` does not overlap `in`.
 template <int NL, int NW, bool BITS, bool ADJ>
@@ -123,11 +121,11 @@ __global__ void __launch_bounds__(256) k_bf_mask(const FpParams<NL> P, const uin
     if (j >= half) return;
     uint32_t xw[NW], yw[NW], qw[NW], ow[NW];
     bf_load_pair<NW, ADJ>(xw, yw, in, j, a);
-    bf_load_once<NW>(qw, q + j * NW);
+    load_once<NW>(qw, q + j * NW);
     if constexpr (BITS) {
         uint32_t bw[NW], pw[NW], mw[NW];
-        bf_load_once<NW>(bw, bits + j * NW);
-        bf_load_once<NW>(pw, p + j * NW);
+        load_once<NW>(bw, bits + j * NW);
+        load_once<NW>(pw, p + j * NW);
         bf_mask_bit<NL, NW>(mw, bw, pw, P);
         store_words<NW>(masked + j * NW, mw);
     }
@@ -144,18 +142,14 @@ __global__ void __launch_bounds__(256) k_bf_switch(const FpParams<NL> P, const u
     if (j >= half) return;
     uint32_t xw[NW], yw[NW], dw[NW], ew[NW], pw[NW], qw[NW], pqw[NW], o0[NW], o1[NW];
     bf_load_pair<NW, ADJ>(xw, yw, in, j, a);
-    bf_load_once<NW>(dw, d + j * NW); bf_load_once<NW>(ew, e + j * NW); bf_load_once<NW>(qw, q + j * NW);
-    bf_load_once<NW>(pw, p + j * NW); bf_load_once<NW>(pqw, pq + j * NW);
+    load_once<NW>(dw, d + j * NW); load_once<NW>(ew, e + j * NW); load_once<NW>(qw, q + j * NW);
+    load_once<NW>(pw, p + j * NW); load_once<NW>(pqw, pq + j * NW);
     bf_switch_elem<NL, NW>(o0, o1, xw, yw, dw, ew, pw, qw, pqw, P);
     bf_store_pair<NW>(out, j, o0, o1);
 }
 
 // k a power of two >= 2 and 0 <= a < log2(k)
 static bool bf_shape_ok(int64_t k, int a) { return k >= 2 && (k & (k - 1)) == 0 && a >= 0 && a < 62 && ((int64_t)1 << a) < k; }
-static bool bf_overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-    return a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
-}
 
 template <int NL, int NW, bool BITS>
 static void launch_mask(const FpParams<NL> &P, const uint32_t *in, const uint32_t *b, const uint32_t *p, const uint32_t *q, int64_t half, int a, uint32_t *o,
@@ -218,7 +212,7 @@ int hb_bf_mask(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *bits_dev, co
     if (!ctx || !in_dev || !q_dev || !masked_dev || (bits_dev && !p_dev)) return HB_ERR_BAD_ARG;
     if (!bf_shape_ok(k, log2_stride)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bf_mask: k must be a power of two >= 2 and 0 <= log2_stride < log2(k)");
     const int64_t eb = 8 * (int64_t)ctx->n_limbs, half = k / 2;
-    if (bf_overlap(masked_dev, (bits_dev ? k : half) * eb, in_dev, k * eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bf_mask: masked overlaps in");
+    if (overlap(masked_dev, (bits_dev ? k : half) * eb, in_dev, k * eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bf_mask: masked overlaps in");
     const int64_t blocks = (half + 255) / 256;
     if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_bf_mask: layer too large for one launch");
     hipStream_t s = (hipStream_t)stream;
@@ -239,7 +233,7 @@ int hb_bf_switch(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *d_dev, con
     if (!ctx || !in_dev || !d_dev || !e_dev || !p_dev || !q_dev || !pq_dev || !out_dev) return HB_ERR_BAD_ARG;
     if (!bf_shape_ok(k, log2_stride)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bf_switch: k must be a power of two >= 2 and 0 <= log2_stride < log2(k)");
     const int64_t eb = 8 * (int64_t)ctx->n_limbs, half = k / 2;
-    if (bf_overlap(out_dev, k * eb, in_dev, k * eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bf_switch: out overlaps in (a layer is not in place)");
+    if (overlap(out_dev, k * eb, in_dev, k * eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bf_switch: out overlaps in (a layer is not in place)");
     const int64_t blocks = (half + 255) / 256;
     if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_bf_switch: layer too large for one launch");
     hipStream_t s = (hipStream_t)stream;

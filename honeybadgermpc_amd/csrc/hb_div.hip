@@ -2,15 +2,15 @@
 // Computation With Fixed-Point Numbers", for signed k-bit values with f fractional bits), for arrays of values.  Everything between two
 // opens is ONE launch.  (The reference stops at division by a public number, fixedpoint.py:277-280: nothing here is a translation.)
 //
-// k_div_pair_mask      (x - a, y - b): the masked pair of one product [x y] as one array to open (the sign step's [u b]).
-// k_div_or_mask / k_div_or_combine   one level of a Sklansky prefix OR over N planes, the wiring of hb_bd.hip (bd_node, bd_partner):
+// DivPairMaskRow      (x - a, y - b): the masked pair of one product [x y] as one array to open (the sign step's [u b]).
+// DivOrMaskRow / DivOrCombineRow   one level of a Sklansky prefix OR over N planes, the wiring of hb_bd.hip (bd_node, bd_partner):
 //                      node t is network plane j, its partner q, and y_j <- y_j + y_q - [y_j y_q], ONE triple a node, triple row t for
 //                      node t.  from_top: network plane r is plane N - 1 - r of the array, so plane i ends as OR_{j >= i}; nothing is
 //                      copied, only the index is reversed.  Bit l of q is clear, so q is no node of level l and the level runs in place.
-// k_div_norm_mask      v = sum_i 2^(N-1-i) (y_i - y_{i+1}) = 2^(N-1) y_0 - sum_{i>=1} 2^(N-1-i) y_i by Horner, acc = 2 acc - y_i, one doubling
+// DivNormMaskRow      v = sum_i 2^(N-1-i) (y_i - y_{i+1}) = 2^(N-1) y_0 - sum_{i>=1} 2^(N-1-i) y_i by Horner, acc = 2 acc - y_i, one doubling
 //                      and one subtraction a plane and no product (the planes are walked in the thread: each is read once); writes v and
 //                      the masked pairs of [x v] and, signed, [u v] as one array to open.
-// k_div_product_step   after an open of masked products: the Beaver combine of one or two products, the step's affine map, and what the
+// DivProductRow   after an open of masked products: the Beaver combine of one or two products, the step's affine map, and what the
 //                      next open needs.  blockIdx.y = the row.
 //                        HB_DIV_SIGN    x = b - 2 [u b]
 //                        HB_DIV_NORM    row 0: c = [x v], d = alpha' - 2 c; row 1: v' = v - 2 [u v] (one product: v' = v).  With the next triple's
@@ -19,7 +19,7 @@
 //                        HB_DIV_TRUNC   row r: the product and its truncation mask (W, the iteration's Y and X, the last Y)
 //                      A truncation mask is hb_fxp_mask's (fxp_mask_elem: Horner over width + kappa bit planes): masked = V + 2^(width-1) + r1
 //                      + 2^m r2 to open, and s = V + r1 kept, so the step after the open reads ONE array a value, not V and r1.
-// k_div_trunc_step     after the open of masked truncations: t = (s - (c mod 2^m)) 2^(-m) for one or two values, and what the next open
+// DivTruncRow     after the open of masked truncations: t = (s - (c mod 2^m)) 2^(-m) for one or two values, and what the next open
 //                      needs.  blockIdx.y = the product the thread masks.
 //                        HB_DIV_T_RESULT  t alone
 //                        HB_DIV_T_RECIP   (b - a0, w - b0, a - a1, w - b1): the masked pairs of [b w] and [a w]
@@ -28,19 +28,19 @@
 //
 // Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions (below, hb_fxp_elem.hpp and
 // hb_ew_elem.hpp); a step's row -- which operands it loads, which body it calls, where it stores -- is an HB_HD function over a memory
-// policy, so the __global__ wrappers only pick the element and the row, and hb_selftest_div runs the very same rows on the host.
+// policy (hb_rows.hpp): k_rows runs a row on the device, host_rows the very same row in hb_selftest_div.
 //
-// Launch shape (all kernels): 256-thread workgroups, one element a thread in x, the node / triple / row in blockIdx.y (k_div_norm_mask
+// Launch shape (all kernels): 256-thread workgroups, one element a thread in x, the node / triple / row in blockIdx.y (DivNormMaskRow
 // walks the planes in the thread).  No LDS, no grid stride, one launch a call.  Triples, opened values, bit planes and kept values are
-// read once and take the non-temporal loads (fxp_load_once); y_j and y_q of a level, which the mask and the combine both read, and the
+// read once and take the non-temporal loads (load_once); y_j and y_q of a level, which the mask and the combine both read, and the
 // operands a and b of the division take the plain ones.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
-//   k_div_pair_mask<9, 8>      26 VGPRs: 8 waves a SIMD                            k_div_pair_mask<3, 2>      14 VGPRs: 8 waves
-//   k_div_or_mask<9, 8>        38 VGPRs: 8 waves                                   k_div_or_mask<3, 2>        15 VGPRs: 8 waves
-//   k_div_or_combine<9, 8>     74 VGPRs: 6 waves                                   k_div_or_combine<3, 2>     30 VGPRs: 8 waves
-//   k_div_norm_mask<9, 8>      59 VGPRs: 8 waves                                   k_div_norm_mask<3, 2>      28 VGPRs: 8 waves
-//   k_div_product_step<9, 8>   81 VGPRs: 5 waves                                   k_div_product_step<3, 2>   32 VGPRs: 8 waves
-//   k_div_trunc_step<9, 8>     56 VGPRs: 8 waves                                   k_div_trunc_step<3, 2>     18 VGPRs: 8 waves
+//   DivPairMaskRow<9, 8>      26 VGPRs: 8 waves a SIMD                            DivPairMaskRow<3, 2>      14 VGPRs: 8 waves
+//   DivOrMaskRow<9, 8>        39 VGPRs: 8 waves                                   DivOrMaskRow<3, 2>        15 VGPRs: 8 waves
+//   DivOrCombineRow<9, 8>     74 VGPRs: 6 waves                                   DivOrCombineRow<3, 2>     30 VGPRs: 8 waves
+//   DivNormMaskRow<9, 8>      59 VGPRs: 8 waves                                   DivNormMaskRow<3, 2>      28 VGPRs: 8 waves
+//   DivProductRow<9, 8>       81 VGPRs: 5 waves                                   DivProductRow<3, 2>       32 VGPRs: 8 waves
+//   DivTruncRow<9, 8>         56 VGPRs: 8 waves                                   DivTruncRow<3, 2>         18 VGPRs: 8 waves
 // (DESIGN.md section 3t has the schedule, the error and width derivations and the counts.)
 #include "hb_common.hpp"
 #include "hb_fxp_elem.hpp"
@@ -116,28 +116,33 @@ HB_HD void div_trunc_elem(uint32_t (&o)[NW], const uint32_t (&sw)[NW], const uin
 }
 
 // ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy)
-// Mem: load / once (w, base, element index) and store (base, element index, w); element index = row * count + i
+// (Mem, k_rows and host_rows: hb_rows.hpp)
 struct DivOrArgs { const uint32_t *opened, *ta, *tb, *tab; uint32_t *y, *masked; int n, level, from_top; };
 
 HB_HD int64_t div_plane(const DivOrArgs &A, int j) { return A.from_top ? A.n - 1 - j : j; }
 
+struct DivOrMaskRow {
 template <int NL, int NW, class Mem>
-HB_HD void div_or_mask_row(const DivOrArgs &A, int64_t t, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
-    const int j = bd_node((int)t, A.level), q = bd_partner(j, A.level);
+HB_HD static void run(const DivOrArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+    const int64_t t = y;
+    const int j = bd_node(y, A.level), q = bd_partner(j, A.level);
     uint32_t yj[NW], yq[NW], aw[NW], bw[NW], o0[NW], o1[NW];
     mem.load(yj, A.y, div_plane(A, j) * count + i);
     mem.load(yq, A.y, div_plane(A, q) * count + i);
     mem.once(aw, A.ta, t * count + i);
     mem.once(bw, A.tb, t * count + i);
-    fxp_diff_elem<NL, NW>(o0, yj, aw, P);
-    fxp_diff_elem<NL, NW>(o1, yq, bw, P);
+    diff_elem<NL, NW>(o0, yj, aw, P);
+    diff_elem<NL, NW>(o1, yq, bw, P);
     mem.store(A.masked, (2 * t) * count + i, o0);
     mem.store(A.masked, (2 * t + 1) * count + i, o1);
 }
+};
 
+struct DivOrCombineRow {
 template <int NL, int NW, class Mem>
-HB_HD void div_or_combine_row(const DivOrArgs &A, int64_t t, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
-    const int j = bd_node((int)t, A.level), q = bd_partner(j, A.level);
+HB_HD static void run(const DivOrArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+    const int64_t t = y;
+    const int j = bd_node(y, A.level), q = bd_partner(j, A.level);
     uint32_t yj[NW], yq[NW], dw[NW], ew[NW], aw[NW], bw[NW], abw[NW], ow[NW];
     mem.load(yj, A.y, div_plane(A, j) * count + i);
     mem.load(yq, A.y, div_plane(A, q) * count + i);
@@ -146,41 +151,46 @@ HB_HD void div_or_combine_row(const DivOrArgs &A, int64_t t, int64_t i, int64_t 
     div_or_elem<NL, NW>(ow, yj, yq, dw, ew, aw, bw, abw, P);
     mem.store(A.y, div_plane(A, j) * count + i, ow);
 }
+};
 
 struct DivPairArgs { const uint32_t *x, *y, *ta, *tb; uint32_t *masked; };
 
+struct DivPairMaskRow {
 template <int NL, int NW, class Mem>
-HB_HD void div_pair_mask_rows(const DivPairArgs &A, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+HB_HD static void run(const DivPairArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
     uint32_t w[NW], aw[NW], o[NW];
     mem.load(w, A.x, i); mem.once(aw, A.ta, i);
-    fxp_diff_elem<NL, NW>(o, w, aw, P);
+    diff_elem<NL, NW>(o, w, aw, P);
     mem.store(A.masked, i, o);
     mem.load(w, A.y, i); mem.once(aw, A.tb, i);
-    fxp_diff_elem<NL, NW>(o, w, aw, P);
+    diff_elem<NL, NW>(o, w, aw, P);
     mem.store(A.masked, count + i, o);
 }
+};
 
 struct DivNormArgs { const uint32_t *x, *y, *u, *ta, *tb; uint32_t *masked, *v; int n; };
 
+struct DivNormMaskRow {
 template <int NL, int NW, class Mem>
-HB_HD void div_norm_mask_elem_rows(const DivNormArgs &A, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+HB_HD static void run(const DivNormArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
     uint32_t vw[NW], w[NW], aw[NW], o[NW];
     div_scale_elem<NL, NW>(vw, [&](uint32_t (&pw)[NW], int row) { mem.once(pw, A.y, (int64_t)row * count + i); }, A.n, P);
     mem.store(A.v, i, vw);
     mem.load(w, A.x, i); mem.once(aw, A.ta, i);
-    fxp_diff_elem<NL, NW>(o, w, aw, P);
+    diff_elem<NL, NW>(o, w, aw, P);
     mem.store(A.masked, i, o);
     mem.once(aw, A.tb, i);
-    fxp_diff_elem<NL, NW>(o, vw, aw, P);
+    diff_elem<NL, NW>(o, vw, aw, P);
     mem.store(A.masked, count + i, o);
     if (!A.u) return;
     mem.load(w, A.u, i); mem.once(aw, A.ta, count + i);
-    fxp_diff_elem<NL, NW>(o, w, aw, P);
+    diff_elem<NL, NW>(o, w, aw, P);
     mem.store(A.masked, 2 * count + i, o);
     mem.once(aw, A.tb, count + i);
-    fxp_diff_elem<NL, NW>(o, vw, aw, P);
+    diff_elem<NL, NW>(o, vw, aw, P);
     mem.store(A.masked, 3 * count + i, o);
 }
+};
 
 template <int NL> struct DivProductArgs {
     const uint32_t *opened, *ta, *tb, *tab, *aux, *nxt_a, *nxt_b, *bits;
@@ -189,8 +199,9 @@ template <int NL> struct DivProductArgs {
     FxpConst<NL> cst, half;
 };
 
+struct DivProductRow {
 template <int NL, int NW, class Mem>
-HB_HD void div_product_row(const DivProductArgs<NL> &A, int r, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+HB_HD static void run(const DivProductArgs<NL> &A, int r, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
     uint32_t pw[NW], vw[NW], xw[NW], o0[NW], o1[NW], zero[NL];
 #pragma unroll
     for (int q = 0; q < NL; q++) zero[q] = 0u;
@@ -216,7 +227,7 @@ HB_HD void div_product_row(const DivProductArgs<NL> &A, int r, int64_t i, int64_
         }
         if (A.nxt_a) {
             mem.once(xw, r == 0 ? A.nxt_a : A.nxt_b, i);
-            fxp_diff_elem<NL, NW>(o0, vw, xw, P);
+            diff_elem<NL, NW>(o0, vw, xw, P);
             mem.store(A.out0, (int64_t)r * count + i, o0);
         } else {
             mem.store(A.out0, (int64_t)r * count + i, vw);
@@ -232,6 +243,7 @@ HB_HD void div_product_row(const DivProductArgs<NL> &A, int r, int64_t i, int64_
         mem.store(A.out1, (int64_t)set * count + i, o1);
     }
 }
+};
 
 template <int NL> struct DivTruncArgs {
     const uint32_t *opened, *s, *x_in, *ext0, *ext1, *ta, *tb;
@@ -240,8 +252,9 @@ template <int NL> struct DivTruncArgs {
     FxpConst<NL> invm, alpha;
 };
 
+struct DivTruncRow {
 template <int NL, int NW, class Mem>
-HB_HD void div_trunc_row(const DivTruncArgs<NL> &A, int q, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+HB_HD static void run(const DivTruncArgs<NL> &A, int q, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
     uint32_t sw[NW], cw[NW], t0[NW], xw[NW], first[NW], second[NW], aw[NW], o[NW], zero[NW];
 #pragma unroll
     for (int w = 0; w < NW; w++) zero[w] = 0u;
@@ -269,72 +282,15 @@ HB_HD void div_trunc_row(const DivTruncArgs<NL> &A, int q, int64_t i, int64_t co
         }
     }
     mem.once(aw, A.ta, (int64_t)q * count + i);
-    fxp_diff_elem<NL, NW>(o, first, aw, P);
+    diff_elem<NL, NW>(o, first, aw, P);
     mem.store(A.out, (int64_t)(2 * q) * count + i, o);
     mem.once(aw, A.tb, (int64_t)q * count + i);
-    fxp_diff_elem<NL, NW>(o, second, aw, P);
+    diff_elem<NL, NW>(o, second, aw, P);
     mem.store(A.out, (int64_t)(2 * q + 1) * count + i, o);
 }
-
-// ---------------------------------------------------------------- memory policies
-template <int NW> struct DivDeviceMem {
-    __device__ __forceinline__ void load(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { load_words<NW>(w, base + e * NW); }
-    __device__ __forceinline__ void once(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { fxp_load_once<NW>(w, base + e * NW); }
-    __device__ __forceinline__ void store(uint32_t *base, int64_t e, const uint32_t (&w)[NW]) const { store_words<NW>(base + e * NW, w); }
 };
-template <int NW> struct DivHostMem {
-    void load(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { memcpy(w, base + e * NW, NW * 4); }
-    void once(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { memcpy(w, base + e * NW, NW * 4); }
-    void store(uint32_t *base, int64_t e, const uint32_t (&w)[NW]) const { memcpy(base + e * NW, w, NW * 4); }
-};
-
-// ---------------------------------------------------------------- kernels
-// y is read at planes j and q and, by the combine, written at plane j alone (no __restrict__ on it: it aliases itself)
-template <int NL, int NW> __global__ void __launch_bounds__(256) k_div_or_mask(const FpParams<NL> P, const DivOrArgs A, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    div_or_mask_row<NL, NW>(A, (int64_t)blockIdx.y, i, count, DivDeviceMem<NW>(), P);
-}
-template <int NL, int NW> __global__ void __launch_bounds__(256) k_div_or_combine(const FpParams<NL> P, const DivOrArgs A, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    div_or_combine_row<NL, NW>(A, (int64_t)blockIdx.y, i, count, DivDeviceMem<NW>(), P);
-}
-template <int NL, int NW> __global__ void __launch_bounds__(256) k_div_pair_mask(const FpParams<NL> P, const DivPairArgs A, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    div_pair_mask_rows<NL, NW>(A, i, count, DivDeviceMem<NW>(), P);
-}
-template <int NL, int NW> __global__ void __launch_bounds__(256) k_div_norm_mask(const FpParams<NL> P, const DivNormArgs A, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    div_norm_mask_elem_rows<NL, NW>(A, i, count, DivDeviceMem<NW>(), P);
-}
-template <int NL, int NW> __global__ void __launch_bounds__(256) k_div_product_step(const FpParams<NL> P, const DivProductArgs<NL> A, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    div_product_row<NL, NW>(A, (int)blockIdx.y, i, count, DivDeviceMem<NW>(), P);
-}
-template <int NL, int NW> __global__ void __launch_bounds__(256) k_div_trunc_step(const FpParams<NL> P, const DivTruncArgs<NL> A, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    div_trunc_row<NL, NW>(A, (int)blockIdx.y, i, count, DivDeviceMem<NW>(), P);
-}
 
 // ---------------------------------------------------------------- host side
-struct DivSpan { const void *p; int64_t rows; };
-
-// no output may lie over an input or over another output
-static bool div_outputs_apart(const DivSpan *outs, int n_outs, const DivSpan *ins, int n_ins, int64_t row_bytes) {
-    for (int o = 0; o < n_outs; o++) {
-        for (int i = 0; i < n_ins; i++)
-            if (fxp_overlap(outs[o].p, outs[o].rows * row_bytes, ins[i].p, ins[i].rows * row_bytes)) return false;
-        for (int o2 = o + 1; o2 < n_outs; o2++)
-            if (fxp_overlap(outs[o].p, outs[o].rows * row_bytes, outs[o2].p, outs[o2].rows * row_bytes)) return false;
-    }
-    return true;
-}
-
 static bool div_or_ok(int n, int level) { return n >= 1 && n <= 256 && level >= 0 && level < bd_levels(n); }
 static bool div_product_ok(int bits, int mode, int products, int width, int m, int kappa) {
     switch (mode) {
@@ -369,32 +325,18 @@ template <int NL, int NW> static bool div_host_digits(uint32_t (&r)[NL], const F
     return false;
 }
 
-template <int NL, int NW>
+template <int NL>
 static bool div_product_consts(DivProductArgs<NL> &A, const FpParams<NL> &P, const uint64_t *cst_host, int width) {
     for (int q = 0; q < NL; q++) { A.cst.d[q] = 0; A.half.d[q] = 0; }
     if (A.mode == HB_DIV_FIRST || A.mode == HB_DIV_TRUNC) fxp_pow2<NL>(A.half.d, width - 1, false, P);
-    if (A.mode == HB_DIV_FIRST || (A.mode == HB_DIV_NORM && A.nxt_a)) return div_host_digits<NL, NW>(A.cst.d, P, cst_host);
+    if (A.mode == HB_DIV_FIRST || (A.mode == HB_DIV_NORM && A.nxt_a)) return div_host_digits<NL, words_of(NL)>(A.cst.d, P, cst_host);
     return true;
 }
-template <int NL, int NW>
+template <int NL>
 static bool div_trunc_consts(DivTruncArgs<NL> &A, const FpParams<NL> &P, const uint64_t *inv2m_host, const uint64_t *alpha_host) {
     for (int q = 0; q < NL; q++) A.alpha.d[q] = 0;
-    if (!fxp_host_mont<NL, NW>(A.invm.d, P, inv2m_host)) return false;
-    return A.mode == HB_DIV_T_GOLD ? div_host_digits<NL, NW>(A.alpha.d, P, alpha_host) : true;
-}
-
-template <int NL, int NW>
-static bool launch_div_product(const FpParams<NL> &P, DivProductArgs<NL> A, const uint64_t *cst_host, int width, int64_t count, unsigned blocks, hipStream_t s) {
-    if (!div_product_consts<NL, NW>(A, P, cst_host, width)) return false;
-    if (count) k_div_product_step<NL, NW><<<dim3(blocks, (unsigned)div_product_rows(A.mode, A.products)), 256, 0, s>>>(P, A, count);
-    return true;
-}
-template <int NL, int NW>
-static bool launch_div_trunc(const FpParams<NL> &P, DivTruncArgs<NL> A, const uint64_t *inv2m_host, const uint64_t *alpha_host, int64_t count, unsigned blocks,
-                             hipStream_t s) {
-    if (!div_trunc_consts<NL, NW>(A, P, inv2m_host, alpha_host)) return false;
-    if (count) k_div_trunc_step<NL, NW><<<dim3(blocks, (unsigned)(A.products ? A.products : 1)), 256, 0, s>>>(P, A, count);
-    return true;
+    if (!fxp_host_mont<NL, words_of(NL)>(A.invm.d, P, inv2m_host)) return false;
+    return A.mode == HB_DIV_T_GOLD ? div_host_digits<NL, words_of(NL)>(A.alpha.d, P, alpha_host) : true;
 }
 
 // host: the same rows over `count` elements
@@ -402,42 +344,28 @@ template <int NL, int NW>
 static int selftest_div(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
-    auto U = [](const uint64_t *b) { return reinterpret_cast<const uint32_t *>(b); };
-    auto V = [](uint64_t *b) { return reinterpret_cast<uint32_t *>(b); };
-    const DivHostMem<NW> mem;
     if (what == HB_DIV_SELFTEST_OR_MASK || what == HB_DIV_SELFTEST_OR_COMBINE) {
         const bool mask = what == HB_DIV_SELFTEST_OR_MASK;
-        DivOrArgs A = {mask ? nullptr : U(ops[0]), U(ops[1]), U(ops[2]), mask ? nullptr : U(ops[3]), mask ? const_cast<uint32_t *>(U(ops[0])) : V(outs[0]),
-                       mask ? V(outs[0]) : nullptr, (int)params[0], (int)params[1], (int)params[2]};
-        const int nodes = bd_active(A.n, A.level);
-        for (int64_t t = 0; t < nodes; t++)
-            for (int64_t i = 0; i < count; i++) {
-                if (mask) div_or_mask_row<NL, NW>(A, t, i, count, mem, P);
-                else div_or_combine_row<NL, NW>(A, t, i, count, mem, P);
-            }
+        const DivOrArgs A = {mask ? nullptr : u32(ops[0]), u32(ops[1]), u32(ops[2]), mask ? nullptr : u32(ops[3]), mask ? const_cast<uint32_t *>(u32(ops[0])) : u32(outs[0]),
+                             mask ? u32(outs[0]) : nullptr, (int)params[0], (int)params[1], (int)params[2]};
+        if (mask) host_rows<DivOrMaskRow, NL, NW>(A, bd_active(A.n, A.level), count, P);
+        else host_rows<DivOrCombineRow, NL, NW>(A, bd_active(A.n, A.level), count, P);
     } else if (what == HB_DIV_SELFTEST_PAIR_MASK) {
-        DivPairArgs A = {U(ops[0]), U(ops[1]), U(ops[2]), U(ops[3]), V(outs[0])};
-        for (int64_t i = 0; i < count; i++) div_pair_mask_rows<NL, NW>(A, i, count, mem, P);
+        const DivPairArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0])};
+        host_rows<DivPairMaskRow, NL, NW>(A, 1, count, P);
     } else if (what == HB_DIV_SELFTEST_NORM_MASK) {
-        DivNormArgs A = {U(ops[0]), U(ops[1]), ops[2] ? U(ops[2]) : nullptr, U(ops[3]), U(ops[4]), V(outs[0]), V(outs[1]), (int)params[0]};
-        for (int64_t i = 0; i < count; i++) div_norm_mask_elem_rows<NL, NW>(A, i, count, mem, P);
+        const DivNormArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(outs[0]), u32(outs[1]), (int)params[0]};
+        host_rows<DivNormMaskRow, NL, NW>(A, 1, count, P);
     } else if (what == HB_DIV_SELFTEST_PRODUCT_STEP) {
-        DivProductArgs<NL> A;
-        A.opened = U(ops[0]); A.ta = U(ops[1]); A.tb = U(ops[2]); A.tab = U(ops[3]); A.aux = ops[4] ? U(ops[4]) : nullptr;
-        A.nxt_a = ops[6] ? U(ops[6]) : nullptr; A.nxt_b = ops[7] ? U(ops[7]) : nullptr; A.bits = ops[8] ? U(ops[8]) : nullptr;
-        A.out0 = V(outs[0]); A.out1 = outs[1] ? V(outs[1]) : nullptr;
-        A.mode = (int)params[0]; A.products = (int)params[1]; A.nbits = (int)(params[2] + params[4]); A.m = (int)params[3];
-        if (!div_product_consts<NL, NW>(A, P, ops[5], (int)params[2])) return HB_ERR_BAD_ARG;
-        for (int r = 0; r < div_product_rows(A.mode, A.products); r++)
-            for (int64_t i = 0; i < count; i++) div_product_row<NL, NW>(A, r, i, count, mem, P);
+        DivProductArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(outs[0]), u32(outs[1]),
+                                (int)params[0], (int)params[1], (int)(params[2] + params[4]), (int)params[3]};
+        if (!div_product_consts<NL>(A, P, ops[5], (int)params[2])) return HB_ERR_BAD_ARG;
+        host_rows<DivProductRow, NL, NW>(A, div_product_rows(A.mode, A.products), count, P);
     } else {
-        DivTruncArgs<NL> A;
-        A.opened = U(ops[0]); A.s = U(ops[1]); A.x_in = ops[4] ? U(ops[4]) : nullptr; A.ext0 = ops[5] ? U(ops[5]) : nullptr; A.ext1 = ops[6] ? U(ops[6]) : nullptr;
-        A.ta = ops[7] ? U(ops[7]) : nullptr; A.tb = ops[8] ? U(ops[8]) : nullptr; A.out = V(outs[0]);
-        A.mode = (int)params[0]; A.rows = (int)params[1]; A.products = (int)params[2]; A.m = (int)params[3];
-        if (!div_trunc_consts<NL, NW>(A, P, ops[2], ops[3])) return HB_ERR_BAD_ARG;
-        for (int q = 0; q < (A.products ? A.products : 1); q++)
-            for (int64_t i = 0; i < count; i++) div_trunc_row<NL, NW>(A, q, i, count, mem, P);
+        DivTruncArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(outs[0]),
+                              (int)params[0], (int)params[1], (int)params[2], (int)params[3]};
+        if (!div_trunc_consts<NL>(A, P, ops[2], ops[3])) return HB_ERR_BAD_ARG;
+        host_rows<DivTruncRow, NL, NW>(A, A.products ? A.products : 1, count, P);
     }
     return HB_OK;
 }
@@ -464,11 +392,6 @@ static unsigned div_trunc_needs(int mode, int rows, int products) {
 
 extern "C" {
 
-#define DIV_BLOCKS(ctx, name)                                                                                          \
-    const int64_t blocks = (count + 255) / 256;                                                                        \
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
-    hipStream_t s = (hipStream_t)stream
-
 int hb_div_or_mask(hb_ctx *ctx, const uint64_t *y_dev, int n_planes, int level, int from_top, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev,
                    int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!y_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
@@ -476,14 +399,11 @@ int hb_div_or_mask(hb_ctx *ctx, const uint64_t *y_dev, int n_planes, int level, 
     if (count == 0) return HB_OK;
     const int nodes = bd_active(n_planes, level);
     const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const DivSpan outs[1] = {{masked_dev, 2 * nodes}}, ins[3] = {{y_dev, n_planes}, {ta_dev, nodes}, {tb_dev, nodes}};
-    if (!div_outputs_apart(outs, 1, ins, 3, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_mask: masked is an array of its own");
-    DIV_BLOCKS(ctx, "hb_div_or_mask");
-    const DivOrArgs A = {nullptr, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, nullptr, (uint32_t *)y_dev, (uint32_t *)masked_dev, n_planes, level, from_top ? 1 : 0};
-    const dim3 grid((unsigned)blocks, (unsigned)nodes);
-    HB_DISPATCH(ctx, (k_div_or_mask<9, 8><<<grid, 256, 0, s>>>(ctx->pw, A, count)), (k_div_or_mask<3, 2><<<grid, 256, 0, s>>>(ctx->pn, A, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const RowSpan outs[1] = {{masked_dev, 2 * nodes}}, ins[3] = {{y_dev, n_planes}, {ta_dev, nodes}, {tb_dev, nodes}};
+    if (!outputs_apart(outs, 1, ins, 3, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_mask: masked is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_div_or_mask");
+    const DivOrArgs A = {nullptr, u32(ta_dev), u32(tb_dev), nullptr, const_cast<uint32_t *>(u32(y_dev)), u32(masked_dev), n_planes, level, from_top ? 1 : 0};
+    return launch_rows<DivOrMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)nodes), s, count);
 }
 
 int hb_div_or_combine(hb_ctx *ctx, const uint64_t *opened_dev, uint64_t *y_dev, int n_planes, int level, int from_top, const uint64_t *ta_dev, const uint64_t *tb_dev,
@@ -493,15 +413,12 @@ int hb_div_or_combine(hb_ctx *ctx, const uint64_t *opened_dev, uint64_t *y_dev, 
     if (count == 0) return HB_OK;
     const int nodes = bd_active(n_planes, level);
     const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const DivSpan outs[1] = {{y_dev, n_planes}}, ins[4] = {{opened_dev, 2 * nodes}, {ta_dev, nodes}, {tb_dev, nodes}, {tab_dev, nodes}};
-    if (!div_outputs_apart(outs, 1, ins, 4, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_combine: y is an array of its own");
-    DIV_BLOCKS(ctx, "hb_div_or_combine");
-    const DivOrArgs A = {(const uint32_t *)opened_dev, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, (const uint32_t *)tab_dev, (uint32_t *)y_dev, nullptr, n_planes, level,
+    const RowSpan outs[1] = {{y_dev, n_planes}}, ins[4] = {{opened_dev, 2 * nodes}, {ta_dev, nodes}, {tb_dev, nodes}, {tab_dev, nodes}};
+    if (!outputs_apart(outs, 1, ins, 4, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_combine: y is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_div_or_combine");
+    const DivOrArgs A = {u32(opened_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(y_dev), nullptr, n_planes, level,
                          from_top ? 1 : 0};
-    const dim3 grid((unsigned)blocks, (unsigned)nodes);
-    HB_DISPATCH(ctx, (k_div_or_combine<9, 8><<<grid, 256, 0, s>>>(ctx->pw, A, count)), (k_div_or_combine<3, 2><<<grid, 256, 0, s>>>(ctx->pn, A, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    return launch_rows<DivOrCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)nodes), s, count);
 }
 
 int hb_div_pair_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, int64_t count,
@@ -509,13 +426,11 @@ int hb_div_pair_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, 
     if (!ctx || count < 0 || (count > 0 && (!x_dev || !y_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
     const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const DivSpan outs[1] = {{masked_dev, 2}}, ins[4] = {{x_dev, 1}, {y_dev, 1}, {ta_dev, 1}, {tb_dev, 1}};
-    if (!div_outputs_apart(outs, 1, ins, 4, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_pair_mask: masked is an array of its own");
-    DIV_BLOCKS(ctx, "hb_div_pair_mask");
-    const DivPairArgs A = {(const uint32_t *)x_dev, (const uint32_t *)y_dev, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, (uint32_t *)masked_dev};
-    HB_DISPATCH(ctx, (k_div_pair_mask<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, A, count)), (k_div_pair_mask<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, A, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const RowSpan outs[1] = {{masked_dev, 2}}, ins[4] = {{x_dev, 1}, {y_dev, 1}, {ta_dev, 1}, {tb_dev, 1}};
+    if (!outputs_apart(outs, 1, ins, 4, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_pair_mask: masked is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_div_pair_mask");
+    const DivPairArgs A = {u32(x_dev), u32(y_dev), u32(ta_dev), u32(tb_dev), u32(masked_dev)};
+    return launch_rows<DivPairMaskRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_div_norm_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, int n_planes, const uint64_t *u_dev, const uint64_t *ta_dev, const uint64_t *tb_dev,
@@ -525,21 +440,19 @@ int hb_div_norm_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, 
     if (count == 0) return HB_OK;
     const int products = u_dev ? 2 : 1;
     const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const DivSpan outs[2] = {{masked_dev, 2 * products}, {v_dev, 1}}, ins[5] = {{x_dev, 1}, {y_dev, n_planes}, {u_dev, 1}, {ta_dev, products}, {tb_dev, products}};
-    if (!div_outputs_apart(outs, 2, ins, 5, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_norm_mask: masked and v are arrays of their own");
-    DIV_BLOCKS(ctx, "hb_div_norm_mask");
-    const DivNormArgs A = {(const uint32_t *)x_dev, (const uint32_t *)y_dev, (const uint32_t *)u_dev, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, (uint32_t *)masked_dev,
-                           (uint32_t *)v_dev, n_planes};
-    HB_DISPATCH(ctx, (k_div_norm_mask<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, A, count)), (k_div_norm_mask<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, A, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const RowSpan outs[2] = {{masked_dev, 2 * products}, {v_dev, 1}}, ins[5] = {{x_dev, 1}, {y_dev, n_planes}, {u_dev, 1}, {ta_dev, products}, {tb_dev, products}};
+    if (!outputs_apart(outs, 2, ins, 5, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_norm_mask: masked and v are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_div_norm_mask");
+    const DivNormArgs A = {u32(x_dev), u32(y_dev), u32(u_dev), u32(ta_dev), u32(tb_dev), u32(masked_dev),
+                           u32(v_dev), n_planes};
+    return launch_rows<DivNormMaskRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_div_product_step(hb_ctx *ctx, int mode, int products, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev,
                         const uint64_t *aux_dev, const uint64_t *cst_host, const uint64_t *nxt_a_dev, const uint64_t *nxt_b_dev, const uint64_t *bits_dev, int width, int m,
                         int kappa, uint64_t *out0_dev, uint64_t *out1_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!div_product_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), mode, products, width, m, kappa))
+    if (!div_product_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), mode, products, width, m, kappa))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: unknown mode, a product count the mode does not take, or a truncation the modulus has no room for");
     if (mode == HB_DIV_NORM && (!nxt_a_dev) != (!nxt_b_dev)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: nxt_a and nxt_b go together");
     const bool nxt = mode == HB_DIV_NORM && nxt_a_dev;
@@ -549,32 +462,24 @@ int hb_div_product_step(hb_ctx *ctx, int mode, int products, const uint64_t *ope
     if (count > 0 && (!opened_dev || !ta_dev || !tb_dev || !tab_dev || !out0_dev || (o1 && !out1_dev) || ((need & (1u << 4)) && !aux_dev) || ((need & (1u << 8)) && !bits_dev)))
         return HB_ERR_BAD_ARG;
     const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const DivSpan outs[2] = {{out0_dev, o0}, {o1 ? out1_dev : nullptr, o1}};
-    const DivSpan ins[8] = {{opened_dev, 2 * products}, {ta_dev, products}, {tb_dev, products}, {tab_dev, products}, {(need & (1u << 4)) ? aux_dev : nullptr, 1},
+    const RowSpan outs[2] = {{out0_dev, o0}, {o1 ? out1_dev : nullptr, o1}};
+    const RowSpan ins[8] = {{opened_dev, 2 * products}, {ta_dev, products}, {tb_dev, products}, {tab_dev, products}, {(need & (1u << 4)) ? aux_dev : nullptr, 1},
                             {nxt ? nxt_a_dev : nullptr, 1}, {nxt ? nxt_b_dev : nullptr, 1}, {sets ? bits_dev : nullptr, (int64_t)sets * (width + kappa)}};
-    if (count > 0 && !div_outputs_apart(outs, 2, ins, 8, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: the outputs are arrays of their own");
-    DIV_BLOCKS(ctx, "hb_div_product_step");
-    bool ok;
-#define DIV_PRODUCT_ARGS(NL)                                                                                                                                      \
-    DivProductArgs<NL> A;                                                                                                                                         \
-    A.opened = (const uint32_t *)opened_dev; A.ta = (const uint32_t *)ta_dev; A.tb = (const uint32_t *)tb_dev; A.tab = (const uint32_t *)tab_dev;                \
-    A.aux = (const uint32_t *)aux_dev; A.nxt_a = nxt ? (const uint32_t *)nxt_a_dev : nullptr; A.nxt_b = nxt ? (const uint32_t *)nxt_b_dev : nullptr;             \
-    A.bits = (const uint32_t *)bits_dev; A.out0 = (uint32_t *)out0_dev; A.out1 = (uint32_t *)out1_dev;                                                           \
-    A.mode = mode; A.products = products; A.nbits = width + kappa; A.m = m
-    HB_DISPATCH(ctx,
-        ({ DIV_PRODUCT_ARGS(9); ok = launch_div_product<9, 8>(ctx->pw, A, cst_host, width, count, (unsigned)blocks, s); }),
-        ({ DIV_PRODUCT_ARGS(3); ok = launch_div_product<3, 2>(ctx->pn, A, cst_host, width, count, (unsigned)blocks, s); }));
-#undef DIV_PRODUCT_ARGS
-    if (!ok) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: the constant is not below the modulus");
-    if (count) HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    if (count > 0 && !outputs_apart(outs, 2, ins, 8, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: the outputs are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_div_product_step");
+    const int rc = launch_rows<DivProductRow, DivProductArgs>(ctx, [&](auto &A, const auto &P) {
+        A = {u32(opened_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(aux_dev), nxt ? u32(nxt_a_dev) : nullptr, nxt ? u32(nxt_b_dev) : nullptr, u32(bits_dev),
+             u32(out0_dev), u32(out1_dev), mode, products, width + kappa, m};
+        return div_product_consts(A, P, cst_host, width);
+    }, dim3((unsigned)blocks, (unsigned)div_product_rows(mode, products)), s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_div_product_step: the constant is not below the modulus") : rc;
 }
 
 int hb_div_trunc_step(hb_ctx *ctx, int mode, int rows, int products, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
                       const uint64_t *alpha_host, const uint64_t *x_dev, const uint64_t *ext0_dev, const uint64_t *ext1_dev, const uint64_t *ta_dev, const uint64_t *tb_dev,
                       uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!div_trunc_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), mode, rows, products, m))
+    if (!div_trunc_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), mode, rows, products, m))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_div_trunc_step: unknown mode, row or product counts the mode does not take, or m outside 0 < m <= bits(p) - 2");
     const unsigned need = div_trunc_needs(mode, rows, products);
     if (!inv2m_host || ((need & (1u << 3)) && !alpha_host)) return HB_ERR_BAD_ARG;
@@ -582,30 +487,22 @@ int hb_div_trunc_step(hb_ctx *ctx, int mode, int rows, int products, const uint6
                       ((need & (1u << 7)) && (!ta_dev || !tb_dev))))
         return HB_ERR_BAD_ARG;
     const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const DivSpan outs[1] = {{out_dev, products ? 2 * products : 1}};
-    const DivSpan ins[7] = {{opened_dev, rows}, {s_dev, rows}, {(need & (1u << 4)) ? x_dev : nullptr, 1}, {(need & (1u << 5)) ? ext0_dev : nullptr, 1},
+    const RowSpan outs[1] = {{out_dev, products ? 2 * products : 1}};
+    const RowSpan ins[7] = {{opened_dev, rows}, {s_dev, rows}, {(need & (1u << 4)) ? x_dev : nullptr, 1}, {(need & (1u << 5)) ? ext0_dev : nullptr, 1},
                             {(need & (1u << 5)) ? ext1_dev : nullptr, 1}, {products ? ta_dev : nullptr, products}, {products ? tb_dev : nullptr, products}};
-    if (count > 0 && !div_outputs_apart(outs, 1, ins, 7, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_trunc_step: out is an array of its own");
-    DIV_BLOCKS(ctx, "hb_div_trunc_step");
-    bool ok;
-#define DIV_TRUNC_ARGS(NL)                                                                                                                                        \
-    DivTruncArgs<NL> A;                                                                                                                                           \
-    A.opened = (const uint32_t *)opened_dev; A.s = (const uint32_t *)s_dev; A.x_in = (const uint32_t *)x_dev; A.ext0 = (const uint32_t *)ext0_dev;               \
-    A.ext1 = (const uint32_t *)ext1_dev; A.ta = (const uint32_t *)ta_dev; A.tb = (const uint32_t *)tb_dev; A.out = (uint32_t *)out_dev;                          \
-    A.mode = mode; A.rows = rows; A.products = products; A.m = m
-    HB_DISPATCH(ctx,
-        ({ DIV_TRUNC_ARGS(9); ok = launch_div_trunc<9, 8>(ctx->pw, A, inv2m_host, alpha_host, count, (unsigned)blocks, s); }),
-        ({ DIV_TRUNC_ARGS(3); ok = launch_div_trunc<3, 2>(ctx->pn, A, inv2m_host, alpha_host, count, (unsigned)blocks, s); }));
-#undef DIV_TRUNC_ARGS
-    if (!ok) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_trunc_step: a constant is not below the modulus");
-    if (count) HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    if (count > 0 && !outputs_apart(outs, 1, ins, 7, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_trunc_step: out is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_div_trunc_step");
+    const int rc = launch_rows<DivTruncRow, DivTruncArgs>(ctx, [&](auto &A, const auto &P) {
+        A = {u32(opened_dev), u32(s_dev), u32(x_dev), u32(ext0_dev), u32(ext1_dev), u32(ta_dev), u32(tb_dev), u32(out_dev), mode, rows, products, m};
+        return div_trunc_consts(A, P, inv2m_host, alpha_host);
+    }, dim3((unsigned)blocks, (unsigned)(products ? products : 1)), s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_div_trunc_step: a constant is not below the modulus") : rc;
 }
 
 int hb_selftest_div(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
     if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 5; i++) if (params[i] < -(1 << 30) || params[i] > (1 << 30)) return HB_ERR_BAD_ARG;
-    const int bits = fxp_modulus_bits(p_limbs, n_limbs);
+    const int bits = modulus_bits(p_limbs, n_limbs);
     unsigned need = 0;
     int n_outs = 1;
     switch (what) {

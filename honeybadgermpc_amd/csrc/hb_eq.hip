@@ -31,6 +31,7 @@
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DESIGN.md section 3n.
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
+#include "hb_rows.hpp"
 
 using namespace hb;
 
@@ -89,13 +90,6 @@ template <int NL, int NW> HB_HD int eq_legendre_elem(const uint32_t (&aw)[NW], c
 }
 
 // o = v - a on packed words
-template <int NL, int NW> HB_HD void eq_diff_elem(uint32_t (&o)[NW], const uint32_t (&vw)[NW], const uint32_t (&aw)[NW], const FpParams<NL> &P) {
-    uint32_t v[NL], a[NL], r[NL];
-    unpack<NL, NW>(v, vw);
-    unpack<NL, NW>(a, aw);
-    fp_sub<NL>(r, v, a, P);
-    pack<NL, NW>(o, r);
-}
 
 // the four masked differences of one test bit of one element; HAS_Y = false: diff = x
 template <int NL, int NW, bool HAS_Y>
@@ -112,9 +106,9 @@ HB_HD void eq_mask1_elem(uint32_t (&o0)[NW], uint32_t (&o1)[NW], uint32_t (&o2)[
     unpack<NL, NW>(a, paw);
     fp_sub<NL>(t, d, a, P);
     pack<NL, NW>(o0, t);
-    eq_diff_elem<NL, NW>(o1, rw, qaw, P);
-    eq_diff_elem<NL, NW>(o2, rpw, pbw, P);
-    eq_diff_elem<NL, NW>(o3, rpw, qbw, P);
+    diff_elem<NL, NW>(o1, rw, qaw, P);
+    diff_elem<NL, NW>(o2, rpw, pbw, P);
+    diff_elem<NL, NW>(o3, rpw, qbw, P);
 }
 
 // m0 = _b - pc, m1 = [rp^2] - qc, dr = [diff r];  o0..o3 the first array opened
@@ -132,7 +126,7 @@ HB_HD void eq_mid_elem(uint32_t (&m0)[NW], uint32_t (&m1)[NW], uint32_t (&dr)[NW
     unpack<NL, NW>(b, pcw);
     fp_sub<NL>(t, u, b, P);
     pack<NL, NW>(m0, t);
-    eq_diff_elem<NL, NW>(m1, rp2, qcw, P);
+    diff_elem<NL, NW>(m1, rp2, qcw, P);
 }
 
 // [c] = [diff r] + [_b rp^2]
@@ -168,9 +162,6 @@ HB_HD int eq_finish_elem(uint32_t (&o)[NW], const uint32_t (&cw)[NW], const uint
 
 // ---------------------------------------------------------------- kernels
 // read-once operands (planes, triples, what was just opened)
-template <int NW> __device__ __forceinline__ void eq_load_once(uint32_t (&w)[NW], const uint32_t *p) {
-    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
-}
 
 template <int NL, int NW>
 __global__ void __launch_bounds__(256) k_legendre(const FpParams<NL> P, const EqSched S, const uint32_t *__restrict__ a, int8_t *__restrict__ out, int64_t count) {
@@ -197,8 +188,8 @@ __global__ void __launch_bounds__(256) k_eq_mask1(const FpParams<NL> P, const ui
 #pragma unroll
         for (int q = 0; q < NW; q++) yw[q] = 0;
     }
-    eq_load_once<NW>(rw, r + e); eq_load_once<NW>(rpw, rp + e);
-    eq_load_once<NW>(paw, pa + e); eq_load_once<NW>(qaw, qa + e); eq_load_once<NW>(pbw, pb + e); eq_load_once<NW>(qbw, qb + e);
+    load_once<NW>(rw, r + e); load_once<NW>(rpw, rp + e);
+    load_once<NW>(paw, pa + e); load_once<NW>(qaw, qa + e); load_once<NW>(pbw, pb + e); load_once<NW>(qbw, qb + e);
     eq_mask1_elem<NL, NW, HAS_Y>(o0, o1, o2, o3, xw, yw, rw, rpw, paw, qaw, pbw, qbw, P);
     store_words<NW>(masked + e, o0);
     store_words<NW>(masked + plane + e, o1);
@@ -216,10 +207,10 @@ __global__ void __launch_bounds__(256) k_eq_mid(const FpParams<NL> P, const uint
     if (i >= count) return;
     const int64_t e = ((int64_t)blockIdx.y * count + i) * NW, plane = rows * count * NW;
     uint32_t o0[NW], o1[NW], o2[NW], o3[NW], paw[NW], qaw[NW], pqaw[NW], pbw[NW], qbw[NW], pqbw[NW], bw[NW], pcw[NW], qcw[NW], m0[NW], m1[NW], drw[NW];
-    eq_load_once<NW>(o0, opened + e); eq_load_once<NW>(o1, opened + plane + e); eq_load_once<NW>(o2, opened + 2 * plane + e); eq_load_once<NW>(o3, opened + 3 * plane + e);
-    eq_load_once<NW>(paw, pa + e); eq_load_once<NW>(qaw, qa + e); eq_load_once<NW>(pqaw, pqa + e);
-    eq_load_once<NW>(pbw, pb + e); eq_load_once<NW>(qbw, qb + e); eq_load_once<NW>(pqbw, pqb + e);
-    load_words<NW>(bw, bits + e); eq_load_once<NW>(pcw, pc + e); load_words<NW>(qcw, qc + e);
+    load_once<NW>(o0, opened + e); load_once<NW>(o1, opened + plane + e); load_once<NW>(o2, opened + 2 * plane + e); load_once<NW>(o3, opened + 3 * plane + e);
+    load_once<NW>(paw, pa + e); load_once<NW>(qaw, qa + e); load_once<NW>(pqaw, pqa + e);
+    load_once<NW>(pbw, pb + e); load_once<NW>(qbw, qb + e); load_once<NW>(pqbw, pqb + e);
+    load_words<NW>(bw, bits + e); load_once<NW>(pcw, pc + e); load_words<NW>(qcw, qc + e);
     eq_mid_elem<NL, NW>(m0, m1, drw, o0, o1, o2, o3, paw, qaw, pqaw, pbw, qbw, pqbw, bw, pcw, qcw, K, P);
     store_words<NW>(masked2 + e, m0);
     store_words<NW>(masked2 + plane + e, m1);
@@ -234,9 +225,9 @@ __global__ void __launch_bounds__(256) k_eq_cshare(const FpParams<NL> P, const u
     if (i >= count) return;
     const int64_t e = ((int64_t)blockIdx.y * count + i) * NW, plane = rows * count * NW;
     uint32_t dw[NW], ew[NW], drw[NW], pcw[NW], qcw[NW], pqcw[NW], ow[NW];
-    eq_load_once<NW>(dw, opened2 + e); eq_load_once<NW>(ew, opened2 + plane + e);
+    load_once<NW>(dw, opened2 + e); load_once<NW>(ew, opened2 + plane + e);
     load_words<NW>(drw, dr + e);
-    eq_load_once<NW>(pcw, pc + e); eq_load_once<NW>(qcw, qc + e); eq_load_once<NW>(pqcw, pqc + e);
+    load_once<NW>(pcw, pc + e); load_once<NW>(qcw, qc + e); load_once<NW>(pqcw, pqc + e);
     eq_cshare_elem<NL, NW>(ow, drw, dw, ew, pcw, qcw, pqcw, P);
     store_words<NW>(c + e, ow);
 }
@@ -345,10 +336,6 @@ template <int NL, int NW> static bool eq_finish_consts(EqFinishConsts<NL> &K, co
     return true;
 }
 
-static bool eq_overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-    return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
-}
 static bool eq_rows_ok(int rows) { return rows >= 1 && rows <= 4096; }
 
 // host: the same element functions over `count` elements
@@ -403,7 +390,6 @@ static int selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uin
     return HB_OK;
 }
 
-#define U32(p) ((const uint32_t *)(p))
 template <int NL, int NW>
 static bool launch_eq_mid(const FpParams<NL> &P, const uint64_t *opened, const uint64_t *pa, const uint64_t *qa, const uint64_t *pqa, const uint64_t *pb, const uint64_t *qb,
                           const uint64_t *pqb, const uint64_t *bits, const uint64_t *pc, const uint64_t *qc, const uint64_t *nr_host, uint64_t *masked2, uint64_t *dr, int rows,
@@ -411,7 +397,7 @@ static bool launch_eq_mid(const FpParams<NL> &P, const uint64_t *opened, const u
     EqMidConsts<NL> K;
     if (!eq_mid_consts<NL, NW>(K, P, nr_host)) return false;
     if (count)
-        k_eq_mid<NL, NW><<<dim3(blocks, (unsigned)rows), 256, 0, s>>>(P, U32(opened), U32(pa), U32(qa), U32(pqa), U32(pb), U32(qb), U32(pqb), U32(bits), U32(pc), U32(qc), K,
+        k_eq_mid<NL, NW><<<dim3(blocks, (unsigned)rows), 256, 0, s>>>(P, u32(opened), u32(pa), u32(qa), u32(pqa), u32(pb), u32(qb), u32(pqb), u32(bits), u32(pc), u32(qc), K,
                                                                       (uint32_t *)masked2, (uint32_t *)dr, rows, count);
     return true;
 }
@@ -421,7 +407,7 @@ static bool launch_eq_finish(const FpParams<NL> &P, const EqSched &S, const uint
                              const uint64_t *nr_host, uint64_t *factor, int32_t *zero_rows, int rows, int64_t count, unsigned blocks, hipStream_t s) {
     EqFinishConsts<NL> K;
     if (!eq_finish_consts<NL, NW>(K, P, p_limbs, n_limbs, mode, nr_host)) return false;
-    if (count) k_eq_finish<NL, NW><<<dim3(blocks, (unsigned)rows), 256, 0, s>>>(P, S, K, U32(c), U32(bits), (uint32_t *)factor, zero_rows, count);
+    if (count) k_eq_finish<NL, NW><<<dim3(blocks, (unsigned)rows), 256, 0, s>>>(P, S, K, u32(c), u32(bits), (uint32_t *)factor, zero_rows, count);
     return true;
 }
 
@@ -429,20 +415,16 @@ static bool launch_eq_finish(const FpParams<NL> &P, const EqSched &S, const uint
 
 extern "C" {
 
-#define EQ_BLOCKS(ctx, name)                                                                                           \
-    const int64_t blocks = (count + 255) / 256;                                                                        \
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
-    hipStream_t s = (hipStream_t)stream
 
 int hb_legendre(hb_ctx *ctx, const uint64_t *a_dev, int8_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!a_dev || !out_dev))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
     EqSched S;
     if (!eq_make_sched(S, ctx->p_limbs, ctx->n_limbs)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_legendre: no schedule for this modulus");
-    if (eq_overlap(out_dev, count, a_dev, count * 8 * (int64_t)ctx->n_limbs)) return fail(ctx, HB_ERR_BAD_ARG, "hb_legendre: out overlaps a");
-    EQ_BLOCKS(ctx, "hb_legendre");
-    HB_DISPATCH(ctx, (k_legendre<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, S, U32(a_dev), out_dev, count)),
-                (k_legendre<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, S, U32(a_dev), out_dev, count)));
+    if (overlap(out_dev, count, a_dev, count * 8 * (int64_t)ctx->n_limbs)) return fail(ctx, HB_ERR_BAD_ARG, "hb_legendre: out overlaps a");
+    HB_ROW_BLOCKS(ctx, "hb_legendre");
+    HB_DISPATCH(ctx, (k_legendre<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, S, u32(a_dev), out_dev, count)),
+                (k_legendre<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, S, u32(a_dev), out_dev, count)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -455,13 +437,13 @@ int hb_eq_mask1(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const
     const int64_t eb = 8 * (int64_t)ctx->n_limbs, pb_ = rows * count * eb;
     const uint64_t *planes[6] = {r_dev, rp_dev, pa_dev, qa_dev, pb_dev, qb_dev};
     for (const uint64_t *in : planes)
-        if (eq_overlap(masked_dev, 4 * pb_, in, pb_)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
-    if (eq_overlap(masked_dev, 4 * pb_, x_dev, count * eb) || eq_overlap(masked_dev, 4 * pb_, y_dev, count * eb))
+        if (overlap(masked_dev, 4 * pb_, in, pb_)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
+    if (overlap(masked_dev, 4 * pb_, x_dev, count * eb) || overlap(masked_dev, 4 * pb_, y_dev, count * eb))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
-    EQ_BLOCKS(ctx, "hb_eq_mask1");
+    HB_ROW_BLOCKS(ctx, "hb_eq_mask1");
     const dim3 grid((unsigned)blocks, (unsigned)rows);
 #define EQ_MASK1(NL, NW, HAS_Y, P) \
-    k_eq_mask1<NL, NW, HAS_Y><<<grid, 256, 0, s>>>(P, U32(x_dev), U32(y_dev), U32(r_dev), U32(rp_dev), U32(pa_dev), U32(qa_dev), U32(pb_dev), U32(qb_dev), (uint32_t *)masked_dev, rows, count)
+    k_eq_mask1<NL, NW, HAS_Y><<<grid, 256, 0, s>>>(P, u32(x_dev), u32(y_dev), u32(r_dev), u32(rp_dev), u32(pa_dev), u32(qa_dev), u32(pb_dev), u32(qb_dev), (uint32_t *)masked_dev, rows, count)
     if (y_dev) HB_DISPATCH(ctx, (EQ_MASK1(9, 8, true, ctx->pw)), (EQ_MASK1(3, 2, true, ctx->pn)));
     else HB_DISPATCH(ctx, (EQ_MASK1(9, 8, false, ctx->pw)), (EQ_MASK1(3, 2, false, ctx->pn)));
 #undef EQ_MASK1
@@ -483,11 +465,11 @@ int hb_eq_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *pa_dev, c
     if (count > 0) {
         for (int k = 0; k < 10; k++) {
             const int64_t ib = k == 0 ? 4 * pb_ : pb_;
-            if (eq_overlap(masked2_dev, 2 * pb_, ins[k], ib) || eq_overlap(dr_dev, pb_, ins[k], ib)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: the outputs are arrays of their own");
+            if (overlap(masked2_dev, 2 * pb_, ins[k], ib) || overlap(dr_dev, pb_, ins[k], ib)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: the outputs are arrays of their own");
         }
-        if (eq_overlap(masked2_dev, 2 * pb_, dr_dev, pb_)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: masked2 overlaps dr");
+        if (overlap(masked2_dev, 2 * pb_, dr_dev, pb_)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: masked2 overlaps dr");
     }
-    EQ_BLOCKS(ctx, "hb_eq_mid");
+    HB_ROW_BLOCKS(ctx, "hb_eq_mid");
     bool ok;
     HB_DISPATCH(ctx,
         (ok = launch_eq_mid<9, 8>(ctx->pw, opened_dev, pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, bits_dev, pc_dev, qc_dev, nr_host, masked2_dev, dr_dev, rows, count, (unsigned)blocks, s)),
@@ -503,14 +485,14 @@ int hb_eq_cshare(hb_ctx *ctx, const uint64_t *opened2_dev, const uint64_t *dr_de
     if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_cshare: needs 1 <= rows <= 4096");
     if (count == 0) return HB_OK;
     const int64_t eb = 8 * (int64_t)ctx->n_limbs, pb_ = rows * count * eb;
-    if (eq_overlap(c_dev, pb_, opened2_dev, 2 * pb_) || eq_overlap(c_dev, pb_, pc_dev, pb_) || eq_overlap(c_dev, pb_, qc_dev, pb_) || eq_overlap(c_dev, pb_, pqc_dev, pb_) ||
-        (c_dev != dr_dev && eq_overlap(c_dev, pb_, dr_dev, pb_)))
+    if (overlap(c_dev, pb_, opened2_dev, 2 * pb_) || overlap(c_dev, pb_, pc_dev, pb_) || overlap(c_dev, pb_, qc_dev, pb_) || overlap(c_dev, pb_, pqc_dev, pb_) ||
+        (c_dev != dr_dev && overlap(c_dev, pb_, dr_dev, pb_)))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_cshare: c may be dr itself and no other input");
-    EQ_BLOCKS(ctx, "hb_eq_cshare");
+    HB_ROW_BLOCKS(ctx, "hb_eq_cshare");
     const dim3 grid((unsigned)blocks, (unsigned)rows);
     HB_DISPATCH(ctx,
-        (k_eq_cshare<9, 8><<<grid, 256, 0, s>>>(ctx->pw, U32(opened2_dev), U32(dr_dev), U32(pc_dev), U32(qc_dev), U32(pqc_dev), (uint32_t *)c_dev, rows, count)),
-        (k_eq_cshare<3, 2><<<grid, 256, 0, s>>>(ctx->pn, U32(opened2_dev), U32(dr_dev), U32(pc_dev), U32(qc_dev), U32(pqc_dev), (uint32_t *)c_dev, rows, count)));
+        (k_eq_cshare<9, 8><<<grid, 256, 0, s>>>(ctx->pw, u32(opened2_dev), u32(dr_dev), u32(pc_dev), u32(qc_dev), u32(pqc_dev), (uint32_t *)c_dev, rows, count)),
+        (k_eq_cshare<3, 2><<<grid, 256, 0, s>>>(ctx->pn, u32(opened2_dev), u32(dr_dev), u32(pc_dev), u32(qc_dev), u32(pqc_dev), (uint32_t *)c_dev, rows, count)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -524,11 +506,11 @@ int hb_eq_finish(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, i
     EqSched S;
     if (!eq_make_sched(S, ctx->p_limbs, ctx->n_limbs)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_eq_finish: no schedule for this modulus");
     const int64_t eb = 8 * (int64_t)ctx->n_limbs, pb_ = rows * count * eb;
-    if (count > 0 && (eq_overlap(zero_rows_dev, 4 * (int64_t)rows, c_dev, pb_) || eq_overlap(zero_rows_dev, 4 * (int64_t)rows, bits_dev, pb_) ||
-                      eq_overlap(zero_rows_dev, 4 * (int64_t)rows, factor_dev, pb_) || (factor_dev != c_dev && eq_overlap(factor_dev, pb_, c_dev, pb_)) ||
-                      (factor_dev != bits_dev && eq_overlap(factor_dev, pb_, bits_dev, pb_))))
+    if (count > 0 && (overlap(zero_rows_dev, 4 * (int64_t)rows, c_dev, pb_) || overlap(zero_rows_dev, 4 * (int64_t)rows, bits_dev, pb_) ||
+                      overlap(zero_rows_dev, 4 * (int64_t)rows, factor_dev, pb_) || (factor_dev != c_dev && overlap(factor_dev, pb_, c_dev, pb_)) ||
+                      (factor_dev != bits_dev && overlap(factor_dev, pb_, bits_dev, pb_))))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_finish: factor may be c or bits themselves; zero_rows is an array of its own");
-    EQ_BLOCKS(ctx, "hb_eq_finish");
+    HB_ROW_BLOCKS(ctx, "hb_eq_finish");
     bool ok;
     HB_DISPATCH(ctx,
         (ok = launch_eq_finish<9, 8>(ctx->pw, S, ctx->p_limbs, ctx->n_limbs, c_dev, bits_dev, mode, nr_host, factor_dev, zero_rows_dev, rows, count, (unsigned)blocks, s)),
@@ -560,5 +542,4 @@ int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
     return selftest_eq<3, 2>(p_limbs, n_limbs, what, operands, params, outs, count);
 }
 
-#undef U32
 }  // extern "C"

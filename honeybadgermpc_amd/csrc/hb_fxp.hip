@@ -7,33 +7,35 @@
 // c2 = c mod 2^m in the clear and corrects it by the borrow of c2 - r1, the carry bit of c2 + (2^m - 1 - r1) + 1 out of a prefix tree.
 // The bit shares arrive as planes: row i of `bits` holds [b_i] of every element, so a wave's loads of a plane cover consecutive elements.
 //
-// k_fxp_mask       r1 = sum_{i<m} 2^i b_i and r1 + 2^m r2 = sum_{i<k+kappa} 2^i b_i by Horner from the top plane down: one modular
+// The steps are rows under the generic kernel k_rows (hb_rows.hpp); the leaves' row runs under k_leaves (hb_fxp_elem.hpp):
+// FxpMaskRow       r1 = sum_{i<m} 2^i b_i and r1 + 2^m r2 = sum_{i<k+kappa} 2^i b_i by Horner from the top plane down: one modular
 //                  doubling and one addition a plane, no product (the planes below m feed two accumulators).  Writes x + 2^(k-1) + r1 +
 //                  2^m r2 and r1; without x (random2m alone) r2 and r1.  k + kappa + 1 reads and two writes an element.
-// k_fxp_trunc_pr   after the open: (x - (c mod 2^m) + r1) 2^(-m); c mod 2^m is a mask on the packed words, 2^(-m) a kernel argument in
+// FxpTruncPrRow    after the open: (x - (c mod 2^m) + r1) 2^(-m); c mod 2^m is a mask on the packed words, 2^(-m) a kernel argument in
 //                  Montgomery form (wave-uniform, SGPRs: the `a` operand of mac), so the scaling is ONE product.
-// k_fxp_leaves     the tree's leaves with no product: a_i, bit i of c2, is public, so carry_i = a_i (1 - b_i) and all_one_i = a_i +
+// FxpLeavesRow     the tree's leaves with no product: a_i, bit i of c2, is public, so carry_i = a_i (1 - b_i) and all_one_i = a_i +
 //                  (1 - b_i) - 2 carry_i are selects: a_i = 1 -> (g, p) = (1 - b_i, b_i), a_i = 0 -> (0, 1 - b_i).  m + 1 leaf planes, most
 //                  significant bit first, the low carry (1, 0) last.  (The reference spends a triple and an open on each of these.)
-// k_fxp_carry_mask / k_fxp_carry_combine   one level of the tree, (g1, p1) o (g2, p2) = (g1 + p1 g2, p1 p2) on adjacent planes: the mask
+// FxpCarryMaskRow / FxpCarryCombineRow   one level of the tree, (g1, p1) o (g2, p2) = (g1 + p1 g2, p1 p2) on adjacent planes: the mask
 //                  writes the two masked differences of every Beaver product of the level into one array (one thread a triple), the
 //                  combine takes that array opened and writes the next level's planes (one thread a node, ew_beaver_elem twice; an odd
 //                  last plane is copied).  At the root only g is computed.
-// k_fxp_finish     u = 1 - carry, a2 = c2 - r1 + 2^m u = [x mod 2^m]; or (x - a2) 2^(-m) = [floor(x / 2^m)]; or its negation (ltz).
+// FxpFinishRow     u = 1 - carry, a2 = c2 - r1 + 2^m u = [x mod 2^m]; or (x - a2) 2^(-m) = [floor(x / 2^m)]; or its negation (ltz).
 //
-// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions: the __global__ wrappers only
-// load, call them and store, and hb_selftest_fxp runs the very same functions on the host.
+// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions (hb_fxp_elem.hpp and below); a
+// step's row -- which operands it loads, which body it calls, where it stores -- is an HB_HD function over a memory policy, so
+// hb_selftest_fxp runs on the host the very rows, arithmetic and addressing, that k_rows runs on the device.
 //
-// Launch shape (all kernels): 256-thread workgroups, one element a thread in x; the tree's kernels take the triple / node in
+// Launch shape (all kernels): 256-thread workgroups, one element a thread in x; the tree's rows take the triple / node in
 // blockIdx.y.  No LDS, no grid stride, one launch a call.  Planes, triples and opened values are read once: the 32-byte width takes
 // the non-temporal loads, as k_ew_beaver.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
-//   k_fxp_mask<9, 8>           83 VGPRs with x (5 waves a SIMD), 68 without (7)     k_fxp_mask<3, 2>           34 / 27 VGPRs: 8 waves
-//   k_fxp_trunc_pr<9, 8>       45 VGPRs: 8 waves                                   k_fxp_trunc_pr<3, 2>       15 VGPRs: 8 waves
-//   k_fxp_leaves<9, 8>         69 VGPRs: 7 waves                                   k_fxp_leaves<3, 2>         49 VGPRs: 8 waves
-//   k_fxp_carry_mask<9, 8>     40 VGPRs: 8 waves                                   k_fxp_carry_mask<3, 2>     15 VGPRs: 8 waves
-//   k_fxp_carry_combine<9, 8>  67 VGPRs: 7 waves                                   k_fxp_carry_combine<3, 2>  28 VGPRs: 8 waves
-//   k_fxp_finish<9, 8>         64 VGPRs: 8 waves                                   k_fxp_finish<3, 2>         27 VGPRs: 8 waves
+//   FxpMaskRow<9, 8>           83 VGPRs with x (5 waves a SIMD), 68 without (7)     FxpMaskRow<3, 2>           34 / 27 VGPRs: 8 waves
+//   FxpTruncPrRow<9, 8>        43 VGPRs: 8 waves                                   FxpTruncPrRow<3, 2>        15 VGPRs: 8 waves
+//   FxpLeavesRow<9, 8>         69 VGPRs: 7 waves                                   FxpLeavesRow<3, 2>         49 VGPRs: 8 waves
+//   FxpCarryMaskRow<9, 8>      41 VGPRs: 8 waves                                   FxpCarryMaskRow<3, 2>      15 VGPRs: 8 waves
+//   FxpCarryCombineRow<9, 8>   67 VGPRs: 7 waves                                   FxpCarryCombineRow<3, 2>   27 VGPRs: 8 waves
+//   FxpFinishRow<9, 8>         64 VGPRs: 8 waves                                   FxpFinishRow<3, 2>         27 VGPRs: 8 waves
 // (DESIGN.md section 3m has the schedule and the counts.)
 #include "hb_common.hpp"
 #include "hb_fxp_elem.hpp"
@@ -46,8 +48,8 @@ namespace hb {
 template <int NL> struct FxpFinishConsts { uint32_t pow2[NL], pow2m[NL], inv2m[NL]; };
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-// (FxpConst, fxp_horner, fxp_mask_elem, fxp_low_bits, fxp_trunc_pr_elem, fxp_bit, fxp_leaf_elem, fxp_diff_elem, fxp_node_g_elem and the host
-// helpers fxp_params_ok, fxp_pow2, fxp_host_mont: hb_fxp_elem.hpp, shared with hb_bd.hip and hb_div.hip)
+// (FxpConst, fxp_horner, fxp_mask_elem, fxp_low_bits, fxp_trunc_pr_elem, fxp_leaf_elem, fxp_node_g_elem and the host helpers
+// fxp_params_ok, fxp_pow2, fxp_host_mont: hb_fxp_elem.hpp, shared with hb_bd.hip and hb_div.hip; word_bit, diff_elem: hb_rows.hpp)
 
 // mode HB_FXP_MOD: a2 = c2 - r1 + 2^m (1 - carry);  HB_FXP_TRUNC: (x - a2) 2^(-m);  HB_FXP_NEG_TRUNC: (a2 - x) 2^(-m)
 template <int NL, int NW>
@@ -69,226 +71,174 @@ HB_HD void fxp_finish_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const ui
     pack<NL, NW>(o, a);
 }
 
-// ---------------------------------------------------------------- kernels
-// No __restrict__ where the header allows an output to be an input (a thread reads its element before it writes it).
-template <int NL, int NW, bool HAS_X>
-__global__ void __launch_bounds__(256) k_fxp_mask(const FpParams<NL> P, const uint32_t *x, const uint32_t *bits, int nbits, int m, const FxpConst<NL> half,
-                                                  uint32_t *masked, uint32_t *r1, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t xw[NW], o0[NW], o1[NW];
-    if constexpr (HAS_X) load_words<NW>(xw, x + i * NW);
-    fxp_mask_elem<NL, NW, HAS_X>(o0, o1, xw, [&](uint32_t (&w)[NW], int row) { fxp_load_once<NW>(w, bits + ((int64_t)row * count + i) * NW); }, nbits, m, half.d, P);
-    store_words<NW>(masked + i * NW, o0);
-    store_words<NW>(r1 + i * NW, o1);
-}
+// ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
+// Where the header allows an output to be an input, a thread reads its element before it writes it.
+template <int NL> struct FxpMaskArgs { const uint32_t *x, *bits; uint32_t *masked, *r1; int nbits, m; FxpConst<NL> half; };
 
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_fxp_trunc_pr(const FpParams<NL> P, const uint32_t *x, const uint32_t *c, const uint32_t *r1, int m, const FxpConst<NL> invm,
-                                                      uint32_t *out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t xw[NW], cw[NW], rw[NW], ow[NW];
-    load_words<NW>(xw, x + i * NW); fxp_load_once<NW>(cw, c + i * NW); fxp_load_once<NW>(rw, r1 + i * NW);
-    fxp_trunc_pr_elem<NL, NW>(ow, xw, cw, rw, m, invm.d, P);
-    store_words<NW>(out + i * NW, ow);
-}
+template <bool HAS_X> struct FxpMaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const FxpMaskArgs<NL> &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t xw[NW], o0[NW], o1[NW];
+        if constexpr (HAS_X) mem.load(xw, A.x, i);
+        fxp_mask_elem<NL, NW, HAS_X>(o0, o1, xw, [&](uint32_t (&w)[NW], int row) { mem.once(w, A.bits, (int64_t)row * count + i); }, A.nbits, A.m, A.half.d, P);
+        mem.store(A.masked, i, o0);
+        mem.store(A.r1, i, o1);
+    }
+};
 
-// g, p: m + 1 planes each, distinct from c and bits
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_fxp_leaves(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ bits, int m,
-                                                    uint32_t *__restrict__ g, uint32_t *__restrict__ p, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
-    load_words<NW>(cw, c + i * NW);
+template <int NL> struct FxpTruncPrArgs { const uint32_t *x, *c, *r1; uint32_t *out; int m; FxpConst<NL> invm; };
+
+struct FxpTruncPrRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const FxpTruncPrArgs<NL> &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t xw[NW], cw[NW], rw[NW], ow[NW];
+        mem.load(xw, A.x, i); mem.once(cw, A.c, i); mem.once(rw, A.r1, i);
+        fxp_trunc_pr_elem<NL, NW>(ow, xw, cw, rw, A.m, A.invm.d, P);
+        mem.store(A.out, i, ow);
+    }
+};
+
+// g, p: m + 1 planes each, distinct from c and bits (the body under k_leaves, hb_fxp_elem.hpp, which has the __restrict__)
+struct FxpLeavesRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void planes(const uint32_t *c, const uint32_t *bits, uint32_t *g, uint32_t *p, int m, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
+        mem.load(cw, c, i);
 #pragma unroll 4
-    for (int j = 0; j < m; j++) {
-        const int bit = m - 1 - j;
-        fxp_load_once<NW>(bw, bits + ((int64_t)bit * count + i) * NW);
-        fxp_leaf_elem<NL, NW>(gw, pw, fxp_bit<NW>(cw, bit), bw, P);
-        store_words<NW>(g + ((int64_t)j * count + i) * NW, gw);
-        store_words<NW>(p + ((int64_t)j * count + i) * NW, pw);
-    }
+        for (int j = 0; j < m; j++) {
+            const int bit = m - 1 - j;
+            mem.once(bw, bits, (int64_t)bit * count + i);
+            fxp_leaf_elem<NL, NW>(gw, pw, word_bit<NW>(cw, bit), bw, P);
+            mem.store(g, (int64_t)j * count + i, gw);
+            mem.store(p, (int64_t)j * count + i, pw);
+        }
 #pragma unroll
-    for (int q = 0; q < NW; q++) { gw[q] = q == 0 ? 1u : 0u; pw[q] = 0u; }
-    store_words<NW>(g + ((int64_t)m * count + i) * NW, gw);
-    store_words<NW>(p + ((int64_t)m * count + i) * NW, pw);
-}
-
-// triple t = blockIdx.y of the level: node t / 2; its first factor is p1, its second g2 (t even) or p2 (t odd)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_fxp_carry_mask(const FpParams<NL> P, const uint32_t *__restrict__ g, const uint32_t *__restrict__ p,
-                                                        const uint32_t *__restrict__ ta, const uint32_t *__restrict__ tb, uint32_t *__restrict__ masked, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t t = blockIdx.y, node = t >> 1;
-    uint32_t p1[NW], y[NW], aw[NW], bw[NW], o0[NW], o1[NW];
-    load_words<NW>(p1, p + ((2 * node) * count + i) * NW);
-    load_words<NW>(y, ((t & 1) ? p : g) + ((2 * node + 1) * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW);
-    fxp_load_once<NW>(bw, tb + (t * count + i) * NW);
-    fxp_diff_elem<NL, NW>(o0, p1, aw, P);
-    fxp_diff_elem<NL, NW>(o1, y, bw, P);
-    store_words<NW>(masked + ((2 * t) * count + i) * NW, o0);
-    store_words<NW>(masked + ((2 * t + 1) * count + i) * NW, o1);
-}
-
-// node j = blockIdx.y of the next level: from planes 2j, 2j + 1, or plane 2j alone moved up (an odd count of planes)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_fxp_carry_combine(const FpParams<NL> P, const uint32_t *__restrict__ opened, const uint32_t *__restrict__ g,
-                                                           const uint32_t *__restrict__ p, int pairs, int root, const uint32_t *__restrict__ ta,
-                                                           const uint32_t *__restrict__ tb, const uint32_t *__restrict__ tab, uint32_t *__restrict__ g_out,
-                                                           uint32_t *__restrict__ p_out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t j = blockIdx.y;
-    uint32_t g1[NW], dw[NW], ew[NW], aw[NW], bw[NW], abw[NW], ow[NW];
-    if (j >= pairs) {
-        load_words<NW>(g1, g + ((2 * j) * count + i) * NW);
-        store_words<NW>(g_out + (j * count + i) * NW, g1);
-        load_words<NW>(g1, p + ((2 * j) * count + i) * NW);
-        store_words<NW>(p_out + (j * count + i) * NW, g1);
-        return;
+        for (int q = 0; q < NW; q++) { gw[q] = q == 0 ? 1u : 0u; pw[q] = 0u; }
+        mem.store(g, (int64_t)m * count + i, gw);
+        mem.store(p, (int64_t)m * count + i, pw);
     }
-    int64_t t = 2 * j;
-    load_words<NW>(g1, g + ((2 * j) * count + i) * NW);
-    fxp_load_once<NW>(dw, opened + ((2 * t) * count + i) * NW); fxp_load_once<NW>(ew, opened + ((2 * t + 1) * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW); fxp_load_once<NW>(bw, tb + (t * count + i) * NW); fxp_load_once<NW>(abw, tab + (t * count + i) * NW);
-    fxp_node_g_elem<NL, NW>(ow, g1, dw, ew, aw, bw, abw, P);
-    store_words<NW>(g_out + (j * count + i) * NW, ow);
-    if (root) return;
-    t = 2 * j + 1;
-    fxp_load_once<NW>(dw, opened + ((2 * t) * count + i) * NW); fxp_load_once<NW>(ew, opened + ((2 * t + 1) * count + i) * NW);
-    fxp_load_once<NW>(aw, ta + (t * count + i) * NW); fxp_load_once<NW>(bw, tb + (t * count + i) * NW); fxp_load_once<NW>(abw, tab + (t * count + i) * NW);
-    ew_beaver_elem<NL, NW>(ow, dw, ew, aw, bw, abw, P);
-    store_words<NW>(p_out + (j * count + i) * NW, ow);
-}
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LeavesArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        planes<NL, NW>(A.c, A.bits, A.g, A.p, A.m, i, count, mem, P);
+    }
+};
 
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_fxp_finish(const FpParams<NL> P, const uint32_t *x, const uint32_t *c, const uint32_t *r1, const uint32_t *carry, int m, int mode,
-                                                    const FxpFinishConsts<NL> K, uint32_t *out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t xw[NW], cw[NW], rw[NW], kw[NW], ow[NW];
-    if (mode != HB_FXP_MOD) load_words<NW>(xw, x + i * NW);
-    else {
+// triple t of the level: node t / 2; its first factor is p1, its second g2 (t even) or p2 (t odd)
+struct FxpCarryMaskArgs { const uint32_t *g, *p, *ta, *tb; uint32_t *masked; };
+
+struct FxpCarryMaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const FxpCarryMaskArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t t = y, node = t >> 1;
+        uint32_t p1[NW], yw[NW], aw[NW], bw[NW], o0[NW], o1[NW];
+        mem.load(p1, A.p, (2 * node) * count + i);
+        mem.load(yw, (t & 1) ? A.p : A.g, (2 * node + 1) * count + i);
+        mem.once(aw, A.ta, t * count + i);
+        mem.once(bw, A.tb, t * count + i);
+        diff_elem<NL, NW>(o0, p1, aw, P);
+        diff_elem<NL, NW>(o1, yw, bw, P);
+        mem.store(A.masked, (2 * t) * count + i, o0);
+        mem.store(A.masked, (2 * t + 1) * count + i, o1);
+    }
+};
+
+// node j of the next level: from planes 2j, 2j + 1, or plane 2j alone moved up (an odd count of planes)
+struct FxpCarryCombineArgs { const uint32_t *opened, *g, *p, *ta, *tb, *tab; uint32_t *g_out, *p_out; int pairs, root; };
+
+struct FxpCarryCombineRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const FxpCarryCombineArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t j = y;
+        uint32_t g1[NW], dw[NW], ew[NW], aw[NW], bw[NW], abw[NW], ow[NW];
+        mem.load(g1, A.g, (2 * j) * count + i);
+        if (j >= A.pairs) {                                                     // both loads ahead of the stores
+            mem.load(ow, A.p, (2 * j) * count + i);
+            mem.store(A.g_out, j * count + i, g1);
+            mem.store(A.p_out, j * count + i, ow);
+            return;
+        }
+        int64_t t = 2 * j;
+        mem.once(dw, A.opened, (2 * t) * count + i); mem.once(ew, A.opened, (2 * t + 1) * count + i);
+        mem.once(aw, A.ta, t * count + i); mem.once(bw, A.tb, t * count + i); mem.once(abw, A.tab, t * count + i);
+        fxp_node_g_elem<NL, NW>(ow, g1, dw, ew, aw, bw, abw, P);
+        mem.store(A.g_out, j * count + i, ow);
+        if (A.root) return;
+        t = 2 * j + 1;
+        mem.once(dw, A.opened, (2 * t) * count + i); mem.once(ew, A.opened, (2 * t + 1) * count + i);
+        mem.once(aw, A.ta, t * count + i); mem.once(bw, A.tb, t * count + i); mem.once(abw, A.tab, t * count + i);
+        ew_beaver_elem<NL, NW>(ow, dw, ew, aw, bw, abw, P);
+        mem.store(A.p_out, j * count + i, ow);
+    }
+};
+
+template <int NL> struct FxpFinishArgs { const uint32_t *x, *c, *r1, *carry; uint32_t *out; int m, mode; FxpFinishConsts<NL> K; };
+
+struct FxpFinishRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const FxpFinishArgs<NL> &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t xw[NW], cw[NW], rw[NW], kw[NW], ow[NW];
+        if (A.mode != HB_FXP_MOD) mem.load(xw, A.x, i);
+        else {
 #pragma unroll
-        for (int q = 0; q < NW; q++) xw[q] = 0;
+            for (int q = 0; q < NW; q++) xw[q] = 0;
+        }
+        mem.once(cw, A.c, i); mem.once(rw, A.r1, i); mem.once(kw, A.carry, i);
+        fxp_finish_elem<NL, NW>(ow, xw, cw, rw, kw, A.m, A.mode, A.K, P);
+        mem.store(A.out, i, ow);
     }
-    fxp_load_once<NW>(cw, c + i * NW); fxp_load_once<NW>(rw, r1 + i * NW); fxp_load_once<NW>(kw, carry + i * NW);
-    fxp_finish_elem<NL, NW>(ow, xw, cw, rw, kw, m, mode, K, P);
-    store_words<NW>(out + i * NW, ow);
-}
+};
 
 // ---------------------------------------------------------------- host side
-template <int NL, int NW> static bool fxp_finish_consts(FxpFinishConsts<NL> &K, const FpParams<NL> &P, int m, const uint64_t *inv2m_host, bool need_inv) {
-    fxp_pow2<NL>(K.pow2, m, false, P);
-    fxp_pow2<NL>(K.pow2m, m, true, P);
-    for (int q = 0; q < NL; q++) K.inv2m[q] = 0;
-    return need_inv ? fxp_host_mont<NL, NW>(K.inv2m, P, inv2m_host) : true;
-}
-
-template <int NL, int NW>
-static void launch_fxp_mask(const FpParams<NL> &P, const uint32_t *x, const uint32_t *bits, int k, int m, int kappa, uint32_t *masked, uint32_t *r1, int64_t count,
-                            unsigned blocks, hipStream_t s) {
-    FxpConst<NL> half;
-    fxp_pow2<NL>(half.d, k - 1, false, P);
-    if (x) k_fxp_mask<NL, NW, true><<<blocks, 256, 0, s>>>(P, x, bits, k + kappa, m, half, masked, r1, count);
-    else k_fxp_mask<NL, NW, false><<<blocks, 256, 0, s>>>(P, nullptr, bits, k + kappa, m, half, masked, r1, count);
-}
-template <int NL, int NW>
-static bool launch_fxp_trunc_pr(const FpParams<NL> &P, const uint32_t *x, const uint32_t *c, const uint32_t *r1, int m, const uint64_t *inv2m_host, uint32_t *out,
-                                int64_t count, unsigned blocks, hipStream_t s) {
-    FxpConst<NL> invm;
-    if (!fxp_host_mont<NL, NW>(invm.d, P, inv2m_host)) return false;
-    if (count) k_fxp_trunc_pr<NL, NW><<<blocks, 256, 0, s>>>(P, x, c, r1, m, invm, out, count);
+// the constants of a step from its parameters; false if inv2m is not below the modulus
+template <int NL> static bool fxp_mask_consts(FxpMaskArgs<NL> &A, const FpParams<NL> &P, int k, int m, int kappa) {
+    A.nbits = k + kappa; A.m = m;
+    fxp_pow2<NL>(A.half.d, k - 1, false, P);
     return true;
 }
-template <int NL, int NW>
-static bool launch_fxp_finish(const FpParams<NL> &P, const uint32_t *x, const uint32_t *c, const uint32_t *r1, const uint32_t *carry, int m, const uint64_t *inv2m_host,
-                              int mode, uint32_t *out, int64_t count, unsigned blocks, hipStream_t s) {
-    FxpFinishConsts<NL> K;
-    if (!fxp_finish_consts<NL, NW>(K, P, m, inv2m_host, mode != HB_FXP_MOD)) return false;
-    if (count) k_fxp_finish<NL, NW><<<blocks, 256, 0, s>>>(P, x, c, r1, carry, m, mode, K, out, count);
-    return true;
+template <int NL> static bool fxp_trunc_pr_consts(FxpTruncPrArgs<NL> &A, const FpParams<NL> &P, int m, const uint64_t *inv2m_host) {
+    A.m = m;
+    return fxp_host_mont<NL, words_of(NL)>(A.invm.d, P, inv2m_host);
+}
+template <int NL> static bool fxp_finish_consts(FxpFinishArgs<NL> &A, const FpParams<NL> &P, int m, int mode, const uint64_t *inv2m_host) {
+    A.m = m; A.mode = mode;
+    fxp_pow2<NL>(A.K.pow2, m, false, P);
+    fxp_pow2<NL>(A.K.pow2m, m, true, P);
+    for (int q = 0; q < NL; q++) A.K.inv2m[q] = 0;
+    return mode != HB_FXP_MOD ? fxp_host_mont<NL, words_of(NL)>(A.K.inv2m, P, inv2m_host) : true;
 }
 
-// host: the same element functions over `count` elements
+// nodes planes of a level; root: the level of two planes whose p is not wanted
+static bool fxp_level_ok(int nodes, int root) { return nodes >= 2 && nodes <= 257 && (!root || nodes == 2); }
+static int fxp_level_triples(int nodes, int root) { return root ? 1 : 2 * (nodes / 2); }
+
+// host: the same rows over `count` elements
 template <int NL, int NW>
 static int selftest_fxp(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
     const int k = (int)params[0], m = (int)params[1], kappa = (int)params[2], aux = (int)params[3], root = (int)params[4];
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    auto O = [](uint64_t *base, int64_t i) -> uint32_t * { return reinterpret_cast<uint32_t *>(base) + i * NW; };
-    const uint32_t none[NW] = {};
-    uint32_t r0[NW], r1[NW];
     if (what == HB_FXP_SELFTEST_MASK) {
-        FxpConst<NL> half;
-        fxp_pow2<NL>(half.d, k - 1, false, P);
-        for (int64_t i = 0; i < count; i++) {
-            auto plane = [&](uint32_t (&w)[NW], int row) { memcpy(w, W(ops[1], (int64_t)row * count + i), NW * 4); };
-            if (ops[0]) fxp_mask_elem<NL, NW, true>(r0, r1, W(ops[0], i), plane, k + kappa, m, half.d, P);
-            else fxp_mask_elem<NL, NW, false>(r0, r1, none, plane, k + kappa, m, half.d, P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-            memcpy(O(outs[1], i), r1, NW * 4);
-        }
+        FxpMaskArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1])};
+        fxp_mask_consts<NL>(A, P, k, m, kappa);
+        if (A.x) host_rows<FxpMaskRow<true>, NL, NW>(A, 1, count, P);
+        else host_rows<FxpMaskRow<false>, NL, NW>(A, 1, count, P);
     } else if (what == HB_FXP_SELFTEST_TRUNC_PR) {
-        FxpConst<NL> invm;
-        if (!fxp_host_mont<NL, NW>(invm.d, P, ops[3])) return HB_ERR_BAD_ARG;
-        for (int64_t i = 0; i < count; i++) {
-            fxp_trunc_pr_elem<NL, NW>(r0, W(ops[0], i), W(ops[1], i), W(ops[2], i), m, invm.d, P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-        }
+        FxpTruncPrArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(outs[0])};
+        if (!fxp_trunc_pr_consts<NL>(A, P, m, ops[3])) return HB_ERR_BAD_ARG;
+        host_rows<FxpTruncPrRow, NL, NW>(A, 1, count, P);
     } else if (what == HB_FXP_SELFTEST_LEAVES) {
-        for (int64_t i = 0; i < count; i++) {
-            for (int j = 0; j < m; j++) {
-                const int bit = m - 1 - j;
-                fxp_leaf_elem<NL, NW>(r0, r1, fxp_bit<NW>(W(ops[0], i), bit), W(ops[1], (int64_t)bit * count + i), P);
-                memcpy(O(outs[0], (int64_t)j * count + i), r0, NW * 4);
-                memcpy(O(outs[1], (int64_t)j * count + i), r1, NW * 4);
-            }
-            uint32_t one[NW] = {1u};
-            memcpy(O(outs[0], (int64_t)m * count + i), one, NW * 4);
-            memcpy(O(outs[1], (int64_t)m * count + i), none, NW * 4);
-        }
+        const LeavesArgs A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1]), m};
+        host_rows<FxpLeavesRow, NL, NW>(A, 1, count, P);
     } else if (what == HB_FXP_SELFTEST_CARRY_MASK) {
-        const int64_t triples = root ? 1 : 2 * (aux / 2);
-        for (int64_t t = 0; t < triples; t++)
-            for (int64_t i = 0; i < count; i++) {
-                const int64_t node = t >> 1;
-                fxp_diff_elem<NL, NW>(r0, W(ops[1], 2 * node * count + i), W(ops[2], t * count + i), P);
-                fxp_diff_elem<NL, NW>(r1, W((t & 1) ? ops[1] : ops[0], (2 * node + 1) * count + i), W(ops[3], t * count + i), P);
-                memcpy(O(outs[0], 2 * t * count + i), r0, NW * 4);
-                memcpy(O(outs[0], (2 * t + 1) * count + i), r1, NW * 4);
-            }
+        const FxpCarryMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0])};
+        host_rows<FxpCarryMaskRow, NL, NW>(A, fxp_level_triples(aux, root), count, P);
     } else if (what == HB_FXP_SELFTEST_CARRY_COMBINE) {
-        const int64_t pairs = aux / 2, out_nodes = (aux + 1) / 2;
-        for (int64_t j = 0; j < out_nodes; j++)
-            for (int64_t i = 0; i < count; i++) {
-                if (j >= pairs) {
-                    memcpy(O(outs[0], j * count + i), W(ops[1], 2 * j * count + i), NW * 4);
-                    memcpy(O(outs[1], j * count + i), W(ops[2], 2 * j * count + i), NW * 4);
-                    continue;
-                }
-                int64_t t = 2 * j;
-                fxp_node_g_elem<NL, NW>(r0, W(ops[1], 2 * j * count + i), W(ops[0], 2 * t * count + i), W(ops[0], (2 * t + 1) * count + i), W(ops[3], t * count + i),
-                                        W(ops[4], t * count + i), W(ops[5], t * count + i), P);
-                memcpy(O(outs[0], j * count + i), r0, NW * 4);
-                if (root) continue;
-                t = 2 * j + 1;
-                ew_beaver_elem<NL, NW>(r1, W(ops[0], 2 * t * count + i), W(ops[0], (2 * t + 1) * count + i), W(ops[3], t * count + i), W(ops[4], t * count + i),
-                                       W(ops[5], t * count + i), P);
-                memcpy(O(outs[1], j * count + i), r1, NW * 4);
-            }
+        const FxpCarryCombineArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(outs[0]), u32(outs[1]), aux / 2, root};
+        host_rows<FxpCarryCombineRow, NL, NW>(A, (aux + 1) / 2, count, P);
     } else {
-        FxpFinishConsts<NL> K;
-        if (!fxp_finish_consts<NL, NW>(K, P, m, ops[4], aux != HB_FXP_MOD)) return HB_ERR_BAD_ARG;
-        for (int64_t i = 0; i < count; i++) {
-            fxp_finish_elem<NL, NW>(r0, aux == HB_FXP_MOD ? none : W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), m, aux, K, P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-        }
+        FxpFinishArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0])};
+        if (!fxp_finish_consts<NL>(A, P, m, aux, ops[4])) return HB_ERR_BAD_ARG;
+        host_rows<FxpFinishRow, NL, NW>(A, 1, count, P);
     }
     return HB_OK;
 }
@@ -297,76 +247,55 @@ static int selftest_fxp(const uint64_t *p_limbs, int what, const uint64_t *const
 
 extern "C" {
 
-#define FXP_BLOCKS(ctx, name)                                                                                          \
-    const int64_t blocks = (count + 255) / 256;                                                                        \
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
-    hipStream_t s = (hipStream_t)stream
-
 int hb_fxp_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *bits_dev, int k, int m, int kappa, uint64_t *masked_dev, uint64_t *r1_dev, int64_t count,
                 void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!bits_dev || !masked_dev || !r1_dev))) return HB_ERR_BAD_ARG;
-    if (!fxp_params_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), k, m, kappa))
+    if (!fxp_params_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), k, m, kappa))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_mask: needs 0 < m < k, kappa >= 0 and k + kappa + 1 <= bits(p) - 1");
     if (count > 0 && masked_dev == r1_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_mask: masked and r1 are one array");
     if (count == 0) return HB_OK;
-    FXP_BLOCKS(ctx, "hb_fxp_mask");
-    HB_DISPATCH(ctx,
-        (launch_fxp_mask<9, 8>(ctx->pw, (const uint32_t *)x_dev, (const uint32_t *)bits_dev, k, m, kappa, (uint32_t *)masked_dev, (uint32_t *)r1_dev, count, (unsigned)blocks, s)),
-        (launch_fxp_mask<3, 2>(ctx->pn, (const uint32_t *)x_dev, (const uint32_t *)bits_dev, k, m, kappa, (uint32_t *)masked_dev, (uint32_t *)r1_dev, count, (unsigned)blocks, s)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    HB_ROW_BLOCKS(ctx, "hb_fxp_mask");
+    const auto fill = [&](auto &A, const auto &P) {
+        A.x = u32(x_dev); A.bits = u32(bits_dev); A.masked = u32(masked_dev); A.r1 = u32(r1_dev);
+        return fxp_mask_consts(A, P, k, m, kappa);
+    };
+    if (x_dev) return launch_rows<FxpMaskRow<true>, FxpMaskArgs>(ctx, fill, (unsigned)blocks, s, count);
+    return launch_rows<FxpMaskRow<false>, FxpMaskArgs>(ctx, fill, (unsigned)blocks, s, count);
 }
 
 int hb_fxp_trunc_pr(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, int m, const uint64_t *inv2m_host, uint64_t *out_dev,
                     int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || !inv2m_host || (count > 0 && (!x_dev || !c_dev || !r1_dev || !out_dev))) return HB_ERR_BAD_ARG;
-    if (!fxp_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_trunc_pr: needs 0 < m <= bits(p) - 2");
-    FXP_BLOCKS(ctx, "hb_fxp_trunc_pr");
-    bool ok;
-    HB_DISPATCH(ctx,
-        (ok = launch_fxp_trunc_pr<9, 8>(ctx->pw, (const uint32_t *)x_dev, (const uint32_t *)c_dev, (const uint32_t *)r1_dev, m, inv2m_host, (uint32_t *)out_dev, count, (unsigned)blocks, s)),
-        (ok = launch_fxp_trunc_pr<3, 2>(ctx->pn, (const uint32_t *)x_dev, (const uint32_t *)c_dev, (const uint32_t *)r1_dev, m, inv2m_host, (uint32_t *)out_dev, count, (unsigned)blocks, s)));
-    if (!ok) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_trunc_pr: inv2m is not below the modulus");
-    if (count) HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    if (!fxp_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_trunc_pr: needs 0 < m <= bits(p) - 2");
+    HB_ROW_BLOCKS(ctx, "hb_fxp_trunc_pr");
+    const int rc = launch_rows<FxpTruncPrRow, FxpTruncPrArgs>(ctx, [&](auto &A, const auto &P) {
+        A.x = u32(x_dev); A.c = u32(c_dev); A.r1 = u32(r1_dev); A.out = u32(out_dev);
+        return fxp_trunc_pr_consts(A, P, m, inv2m_host);
+    }, (unsigned)blocks, s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_fxp_trunc_pr: inv2m is not below the modulus") : rc;
 }
 
 int hb_fxp_ltl_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int m, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!c_dev || !bits_dev || !g_dev || !p_dev))) return HB_ERR_BAD_ARG;
-    if (!fxp_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: needs 0 < m <= bits(p) - 2");
+    if (!fxp_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: needs 0 < m <= bits(p) - 2");
     if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ob = (m + 1) * count * eb;
-    if (fxp_overlap(g_dev, ob, p_dev, ob) || fxp_overlap(g_dev, ob, c_dev, count * eb) || fxp_overlap(p_dev, ob, c_dev, count * eb) ||
-        fxp_overlap(g_dev, ob, bits_dev, m * count * eb) || fxp_overlap(p_dev, ob, bits_dev, m * count * eb))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: g and p are arrays of their own");
-    FXP_BLOCKS(ctx, "hb_fxp_ltl_leaves");
-    HB_DISPATCH(ctx,
-        (k_fxp_leaves<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, m, (uint32_t *)g_dev, (uint32_t *)p_dev, count)),
-        (k_fxp_leaves<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)c_dev, (const uint32_t *)bits_dev, m, (uint32_t *)g_dev, (uint32_t *)p_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const RowSpan outs[2] = {{g_dev, m + 1}, {p_dev, m + 1}}, ins[2] = {{c_dev, 1}, {bits_dev, m}};
+    if (!outputs_apart(outs, 2, ins, 2, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: g and p are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_fxp_ltl_leaves");
+    return launch_leaves<FxpLeavesRow>(ctx, {u32(c_dev), u32(bits_dev), u32(g_dev), u32(p_dev), m}, (unsigned)blocks, s, count);
 }
-
-// nodes planes of a level; root: the level of two planes whose p is not wanted
-static bool fxp_level_ok(int nodes, int root) { return nodes >= 2 && nodes <= 257 && (!root || nodes == 2); }
 
 int hb_fxp_carry_mask(hb_ctx *ctx, const uint64_t *g_dev, const uint64_t *p_dev, int nodes, int root, const uint64_t *ta_dev, const uint64_t *tb_dev,
                       uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!g_dev || !p_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
     if (!fxp_level_ok(nodes, root)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_mask: needs 2 <= nodes <= 257, and nodes == 2 at the root");
     if (count == 0) return HB_OK;
-    const int triples = root ? 1 : 2 * (nodes / 2);
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ib = (int64_t)nodes * count * eb, mb = 2 * (int64_t)triples * count * eb;
-    if (fxp_overlap(masked_dev, mb, g_dev, ib) || fxp_overlap(masked_dev, mb, p_dev, ib) || fxp_overlap(masked_dev, mb, ta_dev, mb / 2) ||
-        fxp_overlap(masked_dev, mb, tb_dev, mb / 2))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_mask: masked is an array of its own");
-    FXP_BLOCKS(ctx, "hb_fxp_carry_mask");
-    const dim3 grid((unsigned)blocks, (unsigned)triples);
-    HB_DISPATCH(ctx,
-        (k_fxp_carry_mask<9, 8><<<grid, 256, 0, s>>>(ctx->pw, (const uint32_t *)g_dev, (const uint32_t *)p_dev, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, (uint32_t *)masked_dev, count)),
-        (k_fxp_carry_mask<3, 2><<<grid, 256, 0, s>>>(ctx->pn, (const uint32_t *)g_dev, (const uint32_t *)p_dev, (const uint32_t *)ta_dev, (const uint32_t *)tb_dev, (uint32_t *)masked_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const int triples = fxp_level_triples(nodes, root);
+    const RowSpan outs[1] = {{masked_dev, 2 * triples}}, ins[4] = {{g_dev, nodes}, {p_dev, nodes}, {ta_dev, triples}, {tb_dev, triples}};
+    if (!outputs_apart(outs, 1, ins, 4, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_mask: masked is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_fxp_carry_mask");
+    const FxpCarryMaskArgs A = {u32(g_dev), u32(p_dev), u32(ta_dev), u32(tb_dev), u32(masked_dev)};
+    return launch_rows<FxpCarryMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)triples), s, count);
 }
 
 int hb_fxp_carry_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *g_dev, const uint64_t *p_dev, int nodes, int root, const uint64_t *ta_dev,
@@ -374,23 +303,13 @@ int hb_fxp_carry_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t
     if (!ctx || count < 0 || (count > 0 && (!opened_dev || !g_dev || !p_dev || !ta_dev || !tb_dev || !tab_dev || !g_out_dev || (!root && !p_out_dev)))) return HB_ERR_BAD_ARG;
     if (!fxp_level_ok(nodes, root)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_combine: needs 2 <= nodes <= 257, and nodes == 2 at the root");
     if (count == 0) return HB_OK;
-    const int pairs = nodes / 2, out_nodes = (nodes + 1) / 2, triples = root ? 1 : 2 * pairs;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, ib = (int64_t)nodes * count * eb, ob = (int64_t)out_nodes * count * eb, tb_ = (int64_t)triples * count * eb;
-    const uint64_t *outs[2] = {g_out_dev, root ? nullptr : p_out_dev};
-    for (const uint64_t *o : outs)
-        if (fxp_overlap(o, ob, g_dev, ib) || fxp_overlap(o, ob, p_dev, ib) || fxp_overlap(o, ob, opened_dev, 2 * tb_) || fxp_overlap(o, ob, ta_dev, tb_) ||
-            fxp_overlap(o, ob, tb_dev, tb_) || fxp_overlap(o, ob, tab_dev, tb_))
-            return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_combine: the outputs are arrays of their own");
-    if (fxp_overlap(outs[0], ob, outs[1], ob)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_combine: g_out overlaps p_out");
-    FXP_BLOCKS(ctx, "hb_fxp_carry_combine");
-    const dim3 grid((unsigned)blocks, (unsigned)out_nodes);
-    HB_DISPATCH(ctx,
-        (k_fxp_carry_combine<9, 8><<<grid, 256, 0, s>>>(ctx->pw, (const uint32_t *)opened_dev, (const uint32_t *)g_dev, (const uint32_t *)p_dev, pairs, root, (const uint32_t *)ta_dev,
-                                                       (const uint32_t *)tb_dev, (const uint32_t *)tab_dev, (uint32_t *)g_out_dev, (uint32_t *)p_out_dev, count)),
-        (k_fxp_carry_combine<3, 2><<<grid, 256, 0, s>>>(ctx->pn, (const uint32_t *)opened_dev, (const uint32_t *)g_dev, (const uint32_t *)p_dev, pairs, root, (const uint32_t *)ta_dev,
-                                                       (const uint32_t *)tb_dev, (const uint32_t *)tab_dev, (uint32_t *)g_out_dev, (uint32_t *)p_out_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const int pairs = nodes / 2, out_nodes = (nodes + 1) / 2, triples = fxp_level_triples(nodes, root);
+    const RowSpan outs[2] = {{g_out_dev, out_nodes}, {root ? nullptr : p_out_dev, out_nodes}};
+    const RowSpan ins[6] = {{g_dev, nodes}, {p_dev, nodes}, {opened_dev, 2 * triples}, {ta_dev, triples}, {tb_dev, triples}, {tab_dev, triples}};
+    if (!outputs_apart(outs, 2, ins, 6, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_combine: the outputs are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_fxp_carry_combine");
+    const FxpCarryCombineArgs A = {u32(opened_dev), u32(g_dev), u32(p_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(g_out_dev), u32(p_out_dev), pairs, root};
+    return launch_rows<FxpCarryCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)out_nodes), s, count);
 }
 
 int hb_fxp_div2m_finish(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, const uint64_t *carry_dev, int m, const uint64_t *inv2m_host,
@@ -398,23 +317,19 @@ int hb_fxp_div2m_finish(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_de
     if (!ctx || count < 0) return HB_ERR_BAD_ARG;
     if (mode != HB_FXP_MOD && mode != HB_FXP_TRUNC && mode != HB_FXP_NEG_TRUNC) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: unknown mode");
     if ((mode != HB_FXP_MOD && !inv2m_host) || (count > 0 && (!c_dev || !r1_dev || !carry_dev || !out_dev || (mode != HB_FXP_MOD && !x_dev)))) return HB_ERR_BAD_ARG;
-    if (!fxp_m_ok(fxp_modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: needs 0 < m <= bits(p) - 2");
-    FXP_BLOCKS(ctx, "hb_fxp_div2m_finish");
-    bool ok;
-    HB_DISPATCH(ctx,
-        (ok = launch_fxp_finish<9, 8>(ctx->pw, (const uint32_t *)x_dev, (const uint32_t *)c_dev, (const uint32_t *)r1_dev, (const uint32_t *)carry_dev, m, inv2m_host, mode,
-                                      (uint32_t *)out_dev, count, (unsigned)blocks, s)),
-        (ok = launch_fxp_finish<3, 2>(ctx->pn, (const uint32_t *)x_dev, (const uint32_t *)c_dev, (const uint32_t *)r1_dev, (const uint32_t *)carry_dev, m, inv2m_host, mode,
-                                      (uint32_t *)out_dev, count, (unsigned)blocks, s)));
-    if (!ok) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: inv2m is not below the modulus");
-    if (count) HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    if (!fxp_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: needs 0 < m <= bits(p) - 2");
+    HB_ROW_BLOCKS(ctx, "hb_fxp_div2m_finish");
+    const int rc = launch_rows<FxpFinishRow, FxpFinishArgs>(ctx, [&](auto &A, const auto &P) {
+        A.x = u32(x_dev); A.c = u32(c_dev); A.r1 = u32(r1_dev); A.carry = u32(carry_dev); A.out = u32(out_dev);
+        return fxp_finish_consts(A, P, m, mode, inv2m_host);
+    }, (unsigned)blocks, s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_fxp_div2m_finish: inv2m is not below the modulus") : rc;
 }
 
 int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
     if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 5; i++) if (params[i] < -(1 << 30) || params[i] > (1 << 30)) return HB_ERR_BAD_ARG;
-    const int bits = fxp_modulus_bits(p_limbs, n_limbs);
+    const int bits = modulus_bits(p_limbs, n_limbs);
     const int k = (int)params[0], m = (int)params[1], kappa = (int)params[2], aux = (int)params[3], root = (int)params[4];
     int n_ops = 0, n_outs = 1, first_op = 0;
     switch (what) {

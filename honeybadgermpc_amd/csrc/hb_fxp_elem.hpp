@@ -1,22 +1,15 @@
 // hb_fxp_elem.hpp -- the per-element bodies of the fixed-point steps, shared by hb_fxp.hip (masks, truncation, and the carry tree of
 // div2m / ltz: only the root is kept), hb_bd.hip (the prefix network of the bit decomposition: every carry is kept) and hb_div.hip
 // (division: the prefix OR and the fused Goldschmidt steps), with the Sklansky wiring the two networks share and the argument checks
-// the files' entry points make.  Host and device: the kernels only load, call and store, and the host self tests run the same
-// functions.
+// the files' entry points make, and the leaves' kernel k_leaves.  Host and device: a step's row (hb_rows.hpp) loads, calls these and
+// stores, and the host self tests run the same rows.
 #pragma once
 #include <cstdint>
 #include <cstring>
 #include "hb_ew_elem.hpp"
+#include "hb_rows.hpp"
 
 namespace hb {
-
-// bit i of the packed words (a chain of selects: the words stay in registers)
-template <int NW> HB_HD uint32_t fxp_bit(const uint32_t (&cw)[NW], int i) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int q = 0; q < NW; q++) w = (q == (i >> 5)) ? cw[q] : w;
-    return (w >> (i & 31)) & 1u;
-}
 
 // the leaf of bit a (public) against the share bw of the mask's bit: a = 1 -> (1 - b, b); a = 0 -> (0, 1 - b)
 template <int NL, int NW>
@@ -30,15 +23,6 @@ HB_HD void fxp_leaf_elem(uint32_t (&gw)[NW], uint32_t (&pw)[NW], uint32_t a, con
     for (int q = 0; q < NL; q++) { g[q] = a ? nb[q] : 0u; p[q] = a ? b[q] : nb[q]; }
     pack<NL, NW>(gw, g);
     pack<NL, NW>(pw, p);
-}
-
-// o = v - a: a masked difference
-template <int NL, int NW> HB_HD void fxp_diff_elem(uint32_t (&o)[NW], const uint32_t (&vw)[NW], const uint32_t (&aw)[NW], const FpParams<NL> &P) {
-    uint32_t v[NL], a[NL], r[NL];
-    unpack<NL, NW>(v, vw);
-    unpack<NL, NW>(a, aw);
-    fp_sub<NL>(r, v, a, P);
-    pack<NL, NW>(o, r);
 }
 
 // g = g1 + [p1 g2], the product by the fused Beaver step of hb_ew_elem.hpp
@@ -131,22 +115,31 @@ static inline int bd_active(int n, int l) {
     return ((n >> (l + 1)) << l) + (rest > 0 ? rest : 0);
 }
 
-// read-once operands (bit planes, triples, what was just opened)
-template <int NW> __device__ __forceinline__ void fxp_load_once(uint32_t (&w)[NW], const uint32_t *p) {
-    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
+// ---------------------------------------------------------------- the leaves steps of hb_fxp.hip and hb_bd.hip
+// c (one row) and bits in, g and p out: arrays of their own
+struct LeavesArgs { const uint32_t *c, *bits; uint32_t *g, *p; int m; };
+
+// A leaves row walks the planes in the thread: a plane's load, then its two stores.  The loads of the next planes go out ahead of
+// those stores only where the compiler knows the arrays apart, and at the 32-byte width it takes __restrict__ on the kernel's own
+// parameters to tell it (pointers in an argument struct carry none, and on an inlined function's parameters it restores the 8-byte
+// width's schedule alone).  So these two steps keep explicit pointers around the row's body, Row::planes; the host runs the same
+// body through Row::run and host_rows.
+template <class Row, int NL, int NW>
+__global__ void __launch_bounds__(256) k_leaves(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ bits, int m, uint32_t *__restrict__ g,
+                                                uint32_t *__restrict__ p, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    Row::template planes<NL, NW>(c, bits, g, p, m, i, count, DeviceMem<NW>(), P);
+}
+template <class Row> int launch_leaves(hb_ctx *ctx, const LeavesArgs &A, unsigned blocks, hipStream_t s, int64_t count) {
+    if (ctx->n_limbs == 4) k_leaves<Row, 9, 8><<<blocks, 256, 0, s>>>(ctx->pw, A.c, A.bits, A.m, A.g, A.p, count);
+    else k_leaves<Row, 3, 2><<<blocks, 256, 0, s>>>(ctx->pn, A.c, A.bits, A.m, A.g, A.p, count);
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
 }
 
 // ---------------------------------------------------------------- host side: argument checks
-static inline int fxp_modulus_bits(const uint64_t *p_limbs, int n_limbs) {
-    for (int l = n_limbs - 1; l >= 0; l--)
-        if (p_limbs[l]) return 64 * l + 64 - __builtin_clzll(p_limbs[l]);
-    return 0;
-}
 static inline bool fxp_m_ok(int bits, int m) { return m > 0 && m <= bits - 2; }
-static inline bool fxp_overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-    return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
-}
 
 // the masked value c < 2^(k + kappa + 1) must stay below p
 static inline bool fxp_params_ok(int bits, int k, int m, int kappa) { return m > 0 && m < k && kappa >= 0 && k <= 256 && kappa <= 256 && k + kappa + 1 <= bits - 1; }

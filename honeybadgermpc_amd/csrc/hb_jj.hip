@@ -41,6 +41,7 @@
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DESIGN.md section 3l and profiles/jubjub.txt.
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
+#include "hb_rows.hpp"
 
 using namespace hb;
 
@@ -53,16 +54,9 @@ template <int NL> struct JjPoint { uint32_t X[NL], Y[NL], Z[NL], T[NL]; };
 struct JjTrip { const uint32_t *p, *q, *pq; int64_t stride; };
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-template <int NW> HB_HD void jj_load_once(uint32_t (&w)[NW], const uint32_t *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
-#else
-    load_words<NW>(w, p);
-#endif
-}
 template <int NL, int NW> HB_HD void jj_digits_once(uint32_t (&d)[NL], const uint32_t *p) {
     uint32_t w[NW];
-    jj_load_once<NW>(w, p);
+    load_once<NW>(w, p);
     unpack<NL, NW>(d, w);
 }
 
@@ -177,11 +171,11 @@ template <int NL, int NW>
 HB_HD void jj_beaver(uint32_t (&o)[NL], const uint32_t *dp, const uint32_t *ep, const JjTrip &t, int k, int64_t i, const FpParams<NL> &P) {
     uint32_t dw[NW], ew[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
     const int64_t at = ((int64_t)k * t.stride + i) * NW;
-    jj_load_once<NW>(dw, dp + i * NW);
-    jj_load_once<NW>(ew, ep + i * NW);
-    jj_load_once<NW>(pw, t.p + at);
-    jj_load_once<NW>(qw, t.q + at);
-    jj_load_once<NW>(pqw, t.pq + at);
+    load_once<NW>(dw, dp + i * NW);
+    load_once<NW>(ew, ep + i * NW);
+    load_once<NW>(pw, t.p + at);
+    load_once<NW>(qw, t.q + at);
+    load_once<NW>(pqw, t.pq + at);
     ew_beaver_elem<NL, NW>(ow, dw, ew, pw, qw, pqw, P);
     unpack<NL, NW>(o, ow);
 }

@@ -5,7 +5,7 @@
 // bit length of p, and [a < b] = c_0 xor r_0 xor [r > c].  The reference's x = sum_i r_i (1 - c_i) prod_{j>i} (1 + (r_j xor c_j))
 // (:137-163) is the g at the root of the carry tree's operator (g1, p1) o (g2, p2) = (g1 + p1 g2, p1 p2) of hb_fxp.hip over leaves that
 // are affine in [r_i], because c_i is public; its least significant bit is [r > c].  The same tree over the leaves of the comparison
-// itself gives [r > c] as a bit.  The tree's levels are k_fxp_carry_mask / k_fxp_carry_combine of hb_fxp.hip, unchanged.
+// itself gives [r > c] as a bit.  The tree's levels are FxpCarryMaskRow / FxpCarryCombineRow of hb_fxp.hip, unchanged.
 //
 // k_lt_mask        2 (a - b) + r, the array to open (b may be absent: 2 a + r).
 // k_lt_leaves      (g, p), L planes each, most significant bit first; bit i of c is taken from the packed words and selects:
@@ -36,31 +36,16 @@
 // (DESIGN.md section 3p has the schedule and the counts.)
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
+#include "hb_rows.hpp"
 
 using namespace hb;
 
 namespace hb {
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-// bit i of the packed words (a chain of selects: the words stay in registers)
-template <int NW> HB_HD uint32_t lt_bit(const uint32_t (&cw)[NW], int i) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int q = 0; q < NW; q++) w = (q == (i >> 5)) ? cw[q] : w;
-    return (w >> (i & 31)) & 1u;
-}
 template <int NL> HB_HD void lt_small(uint32_t (&r)[NL], uint32_t v) {
 #pragma unroll
     for (int q = 0; q < NL; q++) r[q] = q == 0 ? v : 0u;
-}
-
-// o = v - a on packed words: a masked difference
-template <int NL, int NW> HB_HD void lt_diff_elem(uint32_t (&o)[NW], const uint32_t (&vw)[NW], const uint32_t (&aw)[NW], const FpParams<NL> &P) {
-    uint32_t v[NL], a[NL], r[NL];
-    unpack<NL, NW>(v, vw);
-    unpack<NL, NW>(a, aw);
-    fp_sub<NL>(r, v, a, P);
-    pack<NL, NW>(o, r);
 }
 
 // o = 2 (a - b) + r; HAS_B = false: 2 a + r
@@ -120,8 +105,8 @@ template <int NL, int NW>
 HB_HD void lt_xor_mask_elem(uint32_t (&uw)[NW], uint32_t (&m0)[NW], uint32_t (&m1)[NW], const uint32_t (&cw)[NW], const uint32_t (&r0w)[NW], const uint32_t (&ww)[NW],
                             const uint32_t (&paw)[NW], const uint32_t (&qaw)[NW], const FpParams<NL> &P) {
     lt_u_elem<NL, NW>(uw, cw, r0w, P);
-    lt_diff_elem<NL, NW>(m0, uw, paw, P);
-    lt_diff_elem<NL, NW>(m1, ww, qaw, P);
+    diff_elem<NL, NW>(m0, uw, paw, P);
+    diff_elem<NL, NW>(m1, ww, qaw, P);
 }
 
 // REFERENCE: u, m0 = s + x, m1 = u - pa, m2 = s_0 - qa, m3 = s_1 - pb, m4 = s_2 - qb
@@ -136,10 +121,10 @@ HB_HD void lt_dmask_elem(uint32_t (&uw)[NW], uint32_t (&m0)[NW], uint32_t (&m1)[
     fp_add<NL>(t, s, x, P);
     pack<NL, NW>(m0, t);
     lt_u_elem<NL, NW>(uw, cw, r0w, P);
-    lt_diff_elem<NL, NW>(m1, uw, paw, P);
-    lt_diff_elem<NL, NW>(m2, s0w, qaw, P);
-    lt_diff_elem<NL, NW>(m3, s1w, pbw, P);
-    lt_diff_elem<NL, NW>(m4, s2w, qbw, P);
+    diff_elem<NL, NW>(m1, uw, paw, P);
+    diff_elem<NL, NW>(m2, s0w, qaw, P);
+    diff_elem<NL, NW>(m3, s1w, pbw, P);
+    diff_elem<NL, NW>(m4, s2w, qbw, P);
 }
 
 // o = x + y - 2 [x y] with [x y] the fused Beaver step over the opened masked operands d, e
@@ -172,7 +157,7 @@ HB_HD void lt_mid_elem(uint32_t (&vw)[NW], uint32_t (&d0w)[NW], uint32_t (&m0)[N
     unpack<NL, NW>(sp, spw);
     unpack<NL, NW>(s1, s1w);
     unpack<NL, NW>(s2, s2w);
-    const uint32_t d0 = o0[0] & 1u, t1 = lt_bit<NW>(o0, L - 1), t2 = lt_bit<NW>(o0, L - 2);
+    const uint32_t d0 = o0[0] & 1u, t1 = word_bit<NW>(o0, L - 1), t2 = word_bit<NW>(o0, L - 2);
     const uint32_t dx1 = d0 ^ (t1 ^ 1u), dx2 = d0 ^ ((t1 | t2) ^ 1u), dx12 = d0 ^ ((t1 & t2) ^ 1u);
     // (1 - s_1 - s_2 + s_1 s_2) d0
     lt_small<NL>(w, 1);
@@ -193,16 +178,11 @@ HB_HD void lt_mid_elem(uint32_t (&vw)[NW], uint32_t (&d0w)[NW], uint32_t (&m0)[N
 #pragma unroll
     for (int q = 0; q < NL; q++) acc[q] = dx12 ? w[q] : acc[q];
     pack<NL, NW>(d0w, acc);
-    lt_diff_elem<NL, NW>(m0, vw, pcw, P);
-    lt_diff_elem<NL, NW>(m1, d0w, qcw, P);
+    diff_elem<NL, NW>(m0, vw, pcw, P);
+    diff_elem<NL, NW>(m1, d0w, qcw, P);
 }
 
 // ---------------------------------------------------------------- kernels
-// read-once operands (bit planes, triples, what was just opened)
-template <int NW> __device__ __forceinline__ void lt_load_once(uint32_t (&w)[NW], const uint32_t *p) {
-    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
-}
-
 // Every output is an array of its own: __restrict__ throughout.
 template <int NL, int NW, bool HAS_B>
 __global__ void __launch_bounds__(256) k_lt_mask(const FpParams<NL> P, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ r,
@@ -231,8 +211,8 @@ __global__ void __launch_bounds__(256) k_lt_leaves(const FpParams<NL> P, const u
     const int bit = L - 1 - (int)j;
     uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
     load_words<NW>(cw, c + i * NW);
-    lt_load_once<NW>(bw, r_bits + ((int64_t)bit * count + i) * NW);
-    lt_leaf_elem<NL, NW>(gw, pw, lt_bit<NW>(cw, bit), bw, mode, P);
+    load_once<NW>(bw, r_bits + ((int64_t)bit * count + i) * NW);
+    lt_leaf_elem<NL, NW>(gw, pw, word_bit<NW>(cw, bit), bw, mode, P);
     store_words<NW>(g + (j * count + i) * NW, gw);
     store_words<NW>(p + (j * count + i) * NW, pw);
 }
@@ -245,8 +225,8 @@ __global__ void __launch_bounds__(256) k_lt_xor_mask(const FpParams<NL> P, const
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     uint32_t cw[NW], rw[NW], ww[NW], paw[NW], qaw[NW], uw[NW], m0[NW], m1[NW];
-    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); lt_load_once<NW>(ww, w + i * NW);
-    lt_load_once<NW>(paw, pa + i * NW); lt_load_once<NW>(qaw, qa + i * NW);
+    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); load_once<NW>(ww, w + i * NW);
+    load_once<NW>(paw, pa + i * NW); load_once<NW>(qaw, qa + i * NW);
     lt_xor_mask_elem<NL, NW>(uw, m0, m1, cw, rw, ww, paw, qaw, P);
     store_words<NW>(u + i * NW, uw);
     store_words<NW>(masked + i * NW, m0);
@@ -262,11 +242,11 @@ __global__ void __launch_bounds__(256) k_lt_dmask(const FpParams<NL> P, const ui
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     uint32_t cw[NW], rw[NW], xw[NW], sw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pbw[NW], qbw[NW], uw[NW], m0[NW], m1[NW], m2[NW], m3[NW], m4[NW];
-    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); lt_load_once<NW>(xw, x + i * NW); load_words<NW>(sw, s + i * NW);
+    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); load_once<NW>(xw, x + i * NW); load_words<NW>(sw, s + i * NW);
     load_words<NW>(s0w, s_bits + i * NW);
     load_words<NW>(s1w, s_bits + ((int64_t)(L - 1) * count + i) * NW);
     load_words<NW>(s2w, s_bits + ((int64_t)(L - 2) * count + i) * NW);
-    lt_load_once<NW>(paw, pa + i * NW); lt_load_once<NW>(qaw, qa + i * NW); lt_load_once<NW>(pbw, pb + i * NW); lt_load_once<NW>(qbw, qb + i * NW);
+    load_once<NW>(paw, pa + i * NW); load_once<NW>(qaw, qa + i * NW); load_once<NW>(pbw, pb + i * NW); load_once<NW>(qbw, qb + i * NW);
     lt_dmask_elem<NL, NW>(uw, m0, m1, m2, m3, m4, cw, rw, xw, sw, s0w, s1w, s2w, paw, qaw, pbw, qbw, P);
     store_words<NW>(u + i * NW, uw);
     store_words<NW>(masked + i * NW, m0);
@@ -287,14 +267,14 @@ __global__ void __launch_bounds__(256) k_lt_mid(const FpParams<NL> P, const uint
     if (i >= count) return;
     uint32_t o0[NW], o1[NW], o2[NW], o3[NW], o4[NW], uw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pqaw[NW], pbw[NW], qbw[NW], pqbw[NW], pcw[NW], qcw[NW];
     uint32_t vw[NW], d0w[NW], m0[NW], m1[NW];
-    lt_load_once<NW>(o0, opened + i * NW); lt_load_once<NW>(o1, opened + (count + i) * NW); lt_load_once<NW>(o2, opened + (2 * count + i) * NW);
-    lt_load_once<NW>(o3, opened + (3 * count + i) * NW); lt_load_once<NW>(o4, opened + (4 * count + i) * NW);
-    lt_load_once<NW>(uw, u + i * NW);
+    load_once<NW>(o0, opened + i * NW); load_once<NW>(o1, opened + (count + i) * NW); load_once<NW>(o2, opened + (2 * count + i) * NW);
+    load_once<NW>(o3, opened + (3 * count + i) * NW); load_once<NW>(o4, opened + (4 * count + i) * NW);
+    load_once<NW>(uw, u + i * NW);
     load_words<NW>(s0w, s_bits + i * NW);
     load_words<NW>(s1w, s_bits + ((int64_t)(L - 1) * count + i) * NW);
     load_words<NW>(s2w, s_bits + ((int64_t)(L - 2) * count + i) * NW);
-    lt_load_once<NW>(paw, pa + i * NW); lt_load_once<NW>(qaw, qa + i * NW); lt_load_once<NW>(pqaw, pqa + i * NW);
-    lt_load_once<NW>(pbw, pb + i * NW); lt_load_once<NW>(qbw, qb + i * NW); lt_load_once<NW>(pqbw, pqb + i * NW);
+    load_once<NW>(paw, pa + i * NW); load_once<NW>(qaw, qa + i * NW); load_once<NW>(pqaw, pqa + i * NW);
+    load_once<NW>(pbw, pb + i * NW); load_once<NW>(qbw, qb + i * NW); load_once<NW>(pqbw, pqb + i * NW);
     load_words<NW>(pcw, pc + i * NW); load_words<NW>(qcw, qc + i * NW);
     lt_mid_elem<NL, NW>(vw, d0w, m0, m1, o0, o1, o2, o3, o4, uw, s0w, s1w, s2w, paw, qaw, pqaw, pbw, qbw, pqbw, pcw, qcw, L, P);
     store_words<NW>(v + i * NW, vw);
@@ -311,35 +291,15 @@ __global__ void __launch_bounds__(256) k_lt_xor_finish(const FpParams<NL> P, con
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     uint32_t dw[NW], ew[NW], uw[NW], vw[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
-    lt_load_once<NW>(dw, opened + i * NW); lt_load_once<NW>(ew, opened + (count + i) * NW);
-    lt_load_once<NW>(uw, u + i * NW); lt_load_once<NW>(vw, v + i * NW);
-    lt_load_once<NW>(pw, tp + i * NW); lt_load_once<NW>(qw, tq + i * NW); lt_load_once<NW>(pqw, tpq + i * NW);
+    load_once<NW>(dw, opened + i * NW); load_once<NW>(ew, opened + (count + i) * NW);
+    load_once<NW>(uw, u + i * NW); load_once<NW>(vw, v + i * NW);
+    load_once<NW>(pw, tp + i * NW); load_once<NW>(qw, tq + i * NW); load_once<NW>(pqw, tpq + i * NW);
     lt_xor_elem<NL, NW>(ow, uw, vw, dw, ew, pw, qw, pqw, P);
     store_words<NW>(out + i * NW, ow);
 }
 
 // ---------------------------------------------------------------- host side
-static int lt_modulus_bits(const uint64_t *p_limbs, int n_limbs) {
-    for (int l = n_limbs - 1; l >= 0; l--)
-        if (p_limbs[l]) return 64 * l + 64 - __builtin_clzll(p_limbs[l]);
-    return 0;
-}
 static bool lt_mode_ok(int mode) { return mode == HB_LT_DIRECT || mode == HB_LT_REFERENCE; }
-static bool lt_overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-    return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
-}
-struct LtSpan { const void *p; int64_t bytes; };
-// no output overlaps an input or another output
-static bool lt_outputs_apart(const LtSpan *outs, int n_outs, const LtSpan *ins, int n_ins) {
-    for (int o = 0; o < n_outs; o++) {
-        for (int i = 0; i < n_ins; i++)
-            if (lt_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes)) return false;
-        for (int k = o + 1; k < n_outs; k++)
-            if (lt_overlap(outs[o].p, outs[o].bytes, outs[k].p, outs[k].bytes)) return false;
-    }
-    return true;
-}
 
 // host: the same element functions over `count` elements
 template <int NL, int NW>
@@ -359,7 +319,7 @@ static int selftest_lt(const uint64_t *p_limbs, int what, const uint64_t *const 
         } else if (what == HB_LT_SELFTEST_LEAVES) {
             for (int j = 0; j < L; j++) {
                 const int bit = L - 1 - j;
-                lt_leaf_elem<NL, NW>(r0, r1, lt_bit<NW>(W(ops[0], i), bit), W(ops[1], (int64_t)bit * count + i), mode, P);
+                lt_leaf_elem<NL, NW>(r0, r1, word_bit<NW>(W(ops[0], i), bit), W(ops[1], (int64_t)bit * count + i), mode, P);
                 memcpy(O(outs[0], (int64_t)j * count + i), r0, NW * 4);
                 memcpy(O(outs[1], (int64_t)j * count + i), r1, NW * 4);
             }
@@ -392,21 +352,16 @@ static int selftest_lt(const uint64_t *p_limbs, int what, const uint64_t *const 
 
 extern "C" {
 
-#define LT_BLOCKS(ctx, name)                                                                                           \
-    const int64_t blocks = (count + 255) / 256;                                                                        \
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
-    hipStream_t s = (hipStream_t)stream
-#define U32(p) ((const uint32_t *)(p))
-#define LT_L_OK(ctx) (L == lt_modulus_bits((ctx)->p_limbs, (ctx)->n_limbs))
+#define LT_L_OK(ctx) (L == modulus_bits((ctx)->p_limbs, (ctx)->n_limbs))
 
 int hb_lt_mask(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *r_dev, uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!a_dev || !r_dev || !masked_dev))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
     const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const LtSpan outs[1] = {{masked_dev, eb}}, ins[3] = {{a_dev, eb}, {b_dev, eb}, {r_dev, eb}};
-    if (!lt_outputs_apart(outs, 1, ins, 3)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mask: masked is an array of its own");
-    LT_BLOCKS(ctx, "hb_lt_mask");
-#define LT_MASK(NL, NW, HAS_B, P) k_lt_mask<NL, NW, HAS_B><<<(unsigned)blocks, 256, 0, s>>>(P, U32(a_dev), U32(b_dev), U32(r_dev), (uint32_t *)masked_dev, count)
+    const RowSpan outs[1] = {{masked_dev, 1}}, ins[3] = {{a_dev, 1}, {b_dev, 1}, {r_dev, 1}};
+    if (!outputs_apart(outs, 1, ins, 3, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mask: masked is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_lt_mask");
+#define LT_MASK(NL, NW, HAS_B, P) k_lt_mask<NL, NW, HAS_B><<<(unsigned)blocks, 256, 0, s>>>(P, u32(a_dev), u32(b_dev), u32(r_dev), (uint32_t *)masked_dev, count)
     if (b_dev) HB_DISPATCH(ctx, (LT_MASK(9, 8, true, ctx->pw)), (LT_MASK(3, 2, true, ctx->pn)));
     else HB_DISPATCH(ctx, (LT_MASK(9, 8, false, ctx->pw)), (LT_MASK(3, 2, false, ctx->pn)));
 #undef LT_MASK
@@ -421,13 +376,13 @@ int hb_lt_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r_bits_dev,
     if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: L is the bit length of the modulus");
     if (count == 0) return HB_OK;
     const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const LtSpan outs[2] = {{g_dev, L * eb}, {p_dev, L * eb}}, ins[2] = {{c_dev, eb}, {r_bits_dev, L * eb}};
-    if (!lt_outputs_apart(outs, 2, ins, 2)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: g and p are arrays of their own");
-    LT_BLOCKS(ctx, "hb_lt_leaves");
+    const RowSpan outs[2] = {{g_dev, L}, {p_dev, L}}, ins[2] = {{c_dev, 1}, {r_bits_dev, L}};
+    if (!outputs_apart(outs, 2, ins, 2, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: g and p are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_lt_leaves");
     const dim3 grid((unsigned)blocks, (unsigned)L);
     HB_DISPATCH(ctx,
-        (k_lt_leaves<9, 8><<<grid, 256, 0, s>>>(ctx->pw, U32(c_dev), U32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)),
-        (k_lt_leaves<3, 2><<<grid, 256, 0, s>>>(ctx->pn, U32(c_dev), U32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)));
+        (k_lt_leaves<9, 8><<<grid, 256, 0, s>>>(ctx->pw, u32(c_dev), u32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)),
+        (k_lt_leaves<3, 2><<<grid, 256, 0, s>>>(ctx->pn, u32(c_dev), u32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -437,12 +392,12 @@ int hb_lt_xor_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, c
     if (!ctx || count < 0 || (count > 0 && (!c_dev || !r0_dev || !w_dev || !pa_dev || !qa_dev || !u_dev || !masked_dev))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
     const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const LtSpan outs[2] = {{u_dev, eb}, {masked_dev, 2 * eb}}, ins[5] = {{c_dev, eb}, {r0_dev, eb}, {w_dev, eb}, {pa_dev, eb}, {qa_dev, eb}};
-    if (!lt_outputs_apart(outs, 2, ins, 5)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_mask: u and masked are arrays of their own");
-    LT_BLOCKS(ctx, "hb_lt_xor_mask");
+    const RowSpan outs[2] = {{u_dev, 1}, {masked_dev, 2}}, ins[5] = {{c_dev, 1}, {r0_dev, 1}, {w_dev, 1}, {pa_dev, 1}, {qa_dev, 1}};
+    if (!outputs_apart(outs, 2, ins, 5, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_mask: u and masked are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_lt_xor_mask");
     HB_DISPATCH(ctx,
-        (k_lt_xor_mask<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, U32(c_dev), U32(r0_dev), U32(w_dev), U32(pa_dev), U32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)),
-        (k_lt_xor_mask<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, U32(c_dev), U32(r0_dev), U32(w_dev), U32(pa_dev), U32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)));
+        (k_lt_xor_mask<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, u32(c_dev), u32(r0_dev), u32(w_dev), u32(pa_dev), u32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)),
+        (k_lt_xor_mask<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, u32(c_dev), u32(r0_dev), u32(w_dev), u32(pa_dev), u32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -455,13 +410,13 @@ int hb_lt_dmask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, cons
     if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: L is the bit length of the modulus");
     if (count == 0) return HB_OK;
     const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const LtSpan outs[2] = {{u_dev, eb}, {masked_dev, 5 * eb}},
-                 ins[9] = {{c_dev, eb}, {r0_dev, eb}, {x_dev, eb}, {s_dev, eb}, {s_bits_dev, L * eb}, {pa_dev, eb}, {qa_dev, eb}, {pb_dev, eb}, {qb_dev, eb}};
-    if (!lt_outputs_apart(outs, 2, ins, 9)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: u and masked are arrays of their own");
-    LT_BLOCKS(ctx, "hb_lt_dmask");
+    const RowSpan outs[2] = {{u_dev, 1}, {masked_dev, 5}},
+                 ins[9] = {{c_dev, 1}, {r0_dev, 1}, {x_dev, 1}, {s_dev, 1}, {s_bits_dev, L}, {pa_dev, 1}, {qa_dev, 1}, {pb_dev, 1}, {qb_dev, 1}};
+    if (!outputs_apart(outs, 2, ins, 9, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: u and masked are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_lt_dmask");
 #define LT_DMASK(NL, NW, P)                                                                                                                                      \
-    k_lt_dmask<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, U32(c_dev), U32(r0_dev), U32(x_dev), U32(s_dev), U32(s_bits_dev), L, U32(pa_dev), U32(qa_dev), U32(pb_dev), \
-                                                        U32(qb_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)
+    k_lt_dmask<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, u32(c_dev), u32(r0_dev), u32(x_dev), u32(s_dev), u32(s_bits_dev), L, u32(pa_dev), u32(qa_dev), u32(pb_dev), \
+                                                        u32(qb_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)
     HB_DISPATCH(ctx, (LT_DMASK(9, 8, ctx->pw)), (LT_DMASK(3, 2, ctx->pn)));
 #undef LT_DMASK
     HB_LAUNCH_CHECK(ctx);
@@ -480,14 +435,14 @@ int hb_lt_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, co
     if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: L is the bit length of the modulus");
     if (count == 0) return HB_OK;
     const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const LtSpan outs[3] = {{v_dev, eb}, {d0_dev, eb}, {masked_dev, 2 * eb}};
-    LtSpan ins[11] = {{opened_dev, 5 * eb}, {u_dev, eb}, {s_bits_dev, L * eb}};
-    for (int k = 0; k < 8; k++) ins[3 + k] = {trip[k], eb};
-    if (!lt_outputs_apart(outs, 3, ins, 11)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: the outputs are arrays of their own");
-    LT_BLOCKS(ctx, "hb_lt_mid");
+    const RowSpan outs[3] = {{v_dev, 1}, {d0_dev, 1}, {masked_dev, 2}};
+    RowSpan ins[11] = {{opened_dev, 5}, {u_dev, 1}, {s_bits_dev, L}};
+    for (int k = 0; k < 8; k++) ins[3 + k] = {trip[k], 1};
+    if (!outputs_apart(outs, 3, ins, 11, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: the outputs are arrays of their own");
+    HB_ROW_BLOCKS(ctx, "hb_lt_mid");
 #define LT_MID(NL, NW, P)                                                                                                                                       \
-    k_lt_mid<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, U32(opened_dev), U32(u_dev), U32(s_bits_dev), L, U32(pa_dev), U32(qa_dev), U32(pqa_dev), U32(pb_dev),        \
-                                                      U32(qb_dev), U32(pqb_dev), U32(pc_dev), U32(qc_dev), (uint32_t *)v_dev, (uint32_t *)d0_dev, (uint32_t *)masked_dev, count)
+    k_lt_mid<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, u32(opened_dev), u32(u_dev), u32(s_bits_dev), L, u32(pa_dev), u32(qa_dev), u32(pqa_dev), u32(pb_dev),        \
+                                                      u32(qb_dev), u32(pqb_dev), u32(pc_dev), u32(qc_dev), (uint32_t *)v_dev, (uint32_t *)d0_dev, (uint32_t *)masked_dev, count)
     HB_DISPATCH(ctx, (LT_MID(9, 8, ctx->pw)), (LT_MID(3, 2, ctx->pn)));
 #undef LT_MID
     HB_LAUNCH_CHECK(ctx);
@@ -499,12 +454,12 @@ int hb_lt_xor_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_
     if (!ctx || count < 0 || (count > 0 && (!opened_dev || !u_dev || !v_dev || !p_dev || !q_dev || !pq_dev || !out_dev))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
     const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const LtSpan outs[1] = {{out_dev, eb}}, ins[6] = {{opened_dev, 2 * eb}, {u_dev, eb}, {v_dev, eb}, {p_dev, eb}, {q_dev, eb}, {pq_dev, eb}};
-    if (!lt_outputs_apart(outs, 1, ins, 6)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_finish: out is an array of its own");
-    LT_BLOCKS(ctx, "hb_lt_xor_finish");
+    const RowSpan outs[1] = {{out_dev, 1}}, ins[6] = {{opened_dev, 2}, {u_dev, 1}, {v_dev, 1}, {p_dev, 1}, {q_dev, 1}, {pq_dev, 1}};
+    if (!outputs_apart(outs, 1, ins, 6, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_finish: out is an array of its own");
+    HB_ROW_BLOCKS(ctx, "hb_lt_xor_finish");
     HB_DISPATCH(ctx,
-        (k_lt_xor_finish<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, U32(opened_dev), U32(u_dev), U32(v_dev), U32(p_dev), U32(q_dev), U32(pq_dev), (uint32_t *)out_dev, count)),
-        (k_lt_xor_finish<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, U32(opened_dev), U32(u_dev), U32(v_dev), U32(p_dev), U32(q_dev), U32(pq_dev), (uint32_t *)out_dev, count)));
+        (k_lt_xor_finish<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, u32(opened_dev), u32(u_dev), u32(v_dev), u32(p_dev), u32(q_dev), u32(pq_dev), (uint32_t *)out_dev, count)),
+        (k_lt_xor_finish<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, u32(opened_dev), u32(u_dev), u32(v_dev), u32(p_dev), u32(q_dev), u32(pq_dev), (uint32_t *)out_dev, count)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -523,7 +478,7 @@ int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
     case HB_LT_SELFTEST_XOR_FINISH: n_ops = 6; break;
     default: return HB_ERR_BAD_ARG;
     }
-    if (needs_L && L != lt_modulus_bits(p_limbs, n_limbs)) return HB_ERR_BAD_ARG;
+    if (needs_L && L != modulus_bits(p_limbs, n_limbs)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < n_ops; i++) if (count > 0 && !operands[i] && i != optional) return HB_ERR_BAD_ARG;
     for (int i = 0; i < n_outs; i++) if (count > 0 && !outs[i]) return HB_ERR_BAD_ARG;
     if (n_limbs == 4) return selftest_lt<9, 8>(p_limbs, what, operands, params, outs, count);
@@ -531,6 +486,4 @@ int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 }
 
 #undef LT_L_OK
-#undef U32
-#undef LT_BLOCKS
 }  // extern "C"

@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "hb_common.hpp"
+#include "hb_rows.hpp"
 #include "../../include/hbmpc_hip_debug.h"
 
 using namespace hb;
@@ -306,7 +307,6 @@ int selftest_mat(const uint64_t *p_limbs, const uint64_t *a_host, const uint64_t
 
 extern "C" {
 
-#define U32(p) ((const uint32_t *)(p))
 
 int hb_mat_mul(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *c_dev, int c_op, uint64_t *out_dev, int64_t batch, int m, int k, int n,
                void *stream) { HB_API_GUARD(ctx);
@@ -317,12 +317,12 @@ int hb_mat_mul(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const 
     const int64_t W = batch * tiles_m * tiles_n, elems = batch * m * n;
     if ((int64_t)tiles_m * tiles_n > 0x7fffffffLL || W > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_mat_mul: too many output tiles for one launch");
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t *C = c_op == HB_MAT_NONE ? nullptr : U32(c_dev);
+    const uint32_t *C = c_op == HB_MAT_NONE ? nullptr : u32(c_dev);
     const MatPlan pl = mat_plan(W, k, g_mat_split_mode);
     if (pl.slices == 1) {
         HB_DISPATCH(ctx,
-            (k_mat_mul<9, 8><<<dim3((unsigned)W, 1), MAT_THREADS, 0, s>>>(ctx->pw, U32(a_dev), U32(b_dev), C, c_op, (uint32_t *)out_dev, m, k, n, tiles_m, tiles_n, pl.kslice, 0)),
-            (k_mat_mul<3, 2><<<dim3((unsigned)W, 1), MAT_THREADS, 0, s>>>(ctx->pn, U32(a_dev), U32(b_dev), C, c_op, (uint32_t *)out_dev, m, k, n, tiles_m, tiles_n, pl.kslice, 0)));
+            (k_mat_mul<9, 8><<<dim3((unsigned)W, 1), MAT_THREADS, 0, s>>>(ctx->pw, u32(a_dev), u32(b_dev), C, c_op, (uint32_t *)out_dev, m, k, n, tiles_m, tiles_n, pl.kslice, 0)),
+            (k_mat_mul<3, 2><<<dim3((unsigned)W, 1), MAT_THREADS, 0, s>>>(ctx->pn, u32(a_dev), u32(b_dev), C, c_op, (uint32_t *)out_dev, m, k, n, tiles_m, tiles_n, pl.kslice, 0)));
         HB_LAUNCH_CHECK(ctx);
         return HB_OK;
     }
@@ -334,9 +334,9 @@ int hb_mat_mul(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const 
     uint32_t *part = (uint32_t *)base;
     const unsigned rblocks = (unsigned)((elems + 255) / 256);
     HB_DISPATCH(ctx,
-        (k_mat_mul<9, 8><<<dim3((unsigned)W, (unsigned)pl.slices), MAT_THREADS, 0, s>>>(ctx->pw, U32(a_dev), U32(b_dev), nullptr, HB_MAT_NONE, part, m, k, n, tiles_m, tiles_n,
+        (k_mat_mul<9, 8><<<dim3((unsigned)W, (unsigned)pl.slices), MAT_THREADS, 0, s>>>(ctx->pw, u32(a_dev), u32(b_dev), nullptr, HB_MAT_NONE, part, m, k, n, tiles_m, tiles_n,
                                                                                       pl.kslice, elems)),
-        (k_mat_mul<3, 2><<<dim3((unsigned)W, (unsigned)pl.slices), MAT_THREADS, 0, s>>>(ctx->pn, U32(a_dev), U32(b_dev), nullptr, HB_MAT_NONE, part, m, k, n, tiles_m, tiles_n,
+        (k_mat_mul<3, 2><<<dim3((unsigned)W, (unsigned)pl.slices), MAT_THREADS, 0, s>>>(ctx->pn, u32(a_dev), u32(b_dev), nullptr, HB_MAT_NONE, part, m, k, n, tiles_m, tiles_n,
                                                                                       pl.kslice, elems)));
     HB_DISPATCH(ctx,
         (k_mat_reduce<9, 8><<<rblocks, 256, 0, s>>>(ctx->pw, part, elems, pl.slices, C, c_op, (uint32_t *)out_dev)),
@@ -377,5 +377,4 @@ int hb_selftest_mat(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 
 void hb_debug_mat_split(int mode) { g_mat_split_mode = mode > 0 ? 1 : (mode < 0 ? -1 : 0); }
 
-#undef U32
 }  // extern "C"

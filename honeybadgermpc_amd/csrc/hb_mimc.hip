@@ -24,6 +24,7 @@
 // operands of a round are read once: the 32-byte width takes the non-temporal loads, as k_ew_beaver.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage) and the timings: DESIGN.md section 3k.
 #include "hb_common.hpp"
+#include "hb_rows.hpp"
 
 using namespace hb;
 
@@ -183,9 +184,6 @@ HB_HD void mimc_round_elem(uint32_t (&o)[NW], const uint32_t (&yw)[NW], const ui
 
 // ---------------------------------------------------------------- kernels
 // read-once operands (what was just opened, the round's cube)
-template <int NW> __device__ __forceinline__ void mimc_load_once(uint32_t (&w)[NW], const uint32_t *p) {
-    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
-}
 // the key of element i; BCAST: element 0 for every lane, made wave-uniform with readfirstlane (UNIFORM) -- but for the paired
 // cleartext kernel: in the 32-byte width the forced scalars of its two chains spilled 25 SGPRs; left to the compiler it spills none
 template <int NW, bool BCAST, bool UNIFORM = true> __device__ __forceinline__ void mimc_load_key(uint32_t (&w)[NW], const uint32_t *key, int64_t i) {
@@ -231,7 +229,7 @@ __global__ void __launch_bounds__(256) k_mimc_first(const FpParams<NL> P, const 
     uint32_t xw[NW], kw[NW], rw[NW], ow[NW];
     if (x) load_words<NW>(xw, x + i * NW);
     mimc_load_key<NW, BCAST>(kw, key, i);
-    mimc_load_once<NW>(rw, r0 + i * NW);
+    load_once<NW>(rw, r0 + i * NW);
     mimc_first_elem<NL, NW>(ow, x == nullptr, xw, start.d, i, kw, rw, P);
     store_words<NW>(out + i * NW, ow);
 }
@@ -242,10 +240,10 @@ __global__ void __launch_bounds__(256) k_mimc_round(const FpParams<NL> P, const 
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     uint32_t yw[NW], rw[NW], r2w[NW], r3w[NW], kw[NW], rnw[NW], ow[NW];
-    mimc_load_once<NW>(yw, y + i * NW); mimc_load_once<NW>(rw, r + i * NW); mimc_load_once<NW>(r2w, r2 + i * NW);
-    mimc_load_once<NW>(r3w, r3 + i * NW);
+    load_once<NW>(yw, y + i * NW); load_once<NW>(rw, r + i * NW); load_once<NW>(r2w, r2 + i * NW);
+    load_once<NW>(r3w, r3 + i * NW);
     mimc_load_key<NW, BCAST>(kw, key, i);
-    if constexpr (!LAST) mimc_load_once<NW>(rnw, r_next + i * NW);
+    if constexpr (!LAST) load_once<NW>(rnw, r_next + i * NW);
     mimc_round_elem<NL, NW, LAST>(ow, yw, rw, r2w, r3w, kw, cst.d, rnw, P);
     store_words<NW>(out + i * NW, ow);
 }

@@ -37,6 +37,7 @@
 //   k_off_degree_check<8>      44 VGPRs: 8 waves              k_off_degree_check<2>      20 VGPRs: 8 waves
 // (the constants and the table of the inverse root are read through wave-uniform addresses: scalar loads, scalar branches)
 #include "hb_common.hpp"
+#include "hb_rows.hpp"
 
 using namespace hb;
 
@@ -350,7 +351,6 @@ static int selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const ui
 
 extern "C" {
 
-#define U32(p) ((const uint32_t *)(p))
 
 int hb_off_mul_add(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *c_dev, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!a_dev || !b_dev || !c_dev || !out_dev))) return HB_ERR_BAD_ARG;
@@ -359,8 +359,8 @@ int hb_off_mul_add(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, co
     if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_off_mul_add: batch too large for one launch");
     hipStream_t s = (hipStream_t)stream;
     HB_DISPATCH(ctx,
-        (k_off_mul_add<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, U32(a_dev), U32(b_dev), U32(c_dev), (uint32_t *)out_dev, count)),
-        (k_off_mul_add<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, U32(a_dev), U32(b_dev), U32(c_dev), (uint32_t *)out_dev, count)));
+        (k_off_mul_add<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, u32(a_dev), u32(b_dev), u32(c_dev), (uint32_t *)out_dev, count)),
+        (k_off_mul_add<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, u32(a_dev), u32(b_dev), u32(c_dev), (uint32_t *)out_dev, count)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -379,8 +379,8 @@ int hb_off_invsqrt_scale(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *u_d
     const OffConsts *K = (const OffConsts *)blob;
     const uint32_t *tab = (const uint32_t *)(blob + OFF_TAB_AT);
     HB_DISPATCH(ctx,
-        (k_off_invsqrt_scale<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, K, tab, U32(x_dev), U32(u_dev), mode, (uint32_t *)out_dev, count, status_dev)),
-        (k_off_invsqrt_scale<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, K, tab, U32(x_dev), U32(u_dev), mode, (uint32_t *)out_dev, count, status_dev)));
+        (k_off_invsqrt_scale<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, K, tab, u32(x_dev), u32(u_dev), mode, (uint32_t *)out_dev, count, status_dev)),
+        (k_off_invsqrt_scale<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, K, tab, u32(x_dev), u32(u_dev), mode, (uint32_t *)out_dev, count, status_dev)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -393,8 +393,8 @@ int hb_off_degree_check(hb_ctx *ctx, const uint64_t *coeffs_dev, int n, int64_t 
     if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_off_degree_check: batch too large for one launch");
     hipStream_t s = (hipStream_t)stream;
     HB_DISPATCH(ctx,
-        (k_off_degree_check<8><<<(unsigned)blocks, 256, 0, s>>>(U32(coeffs_dev), n, k, t, counters_dev)),
-        (k_off_degree_check<2><<<(unsigned)blocks, 256, 0, s>>>(U32(coeffs_dev), n, k, t, counters_dev)));
+        (k_off_degree_check<8><<<(unsigned)blocks, 256, 0, s>>>(u32(coeffs_dev), n, k, t, counters_dev)),
+        (k_off_degree_check<2><<<(unsigned)blocks, 256, 0, s>>>(u32(coeffs_dev), n, k, t, counters_dev)));
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -414,5 +414,4 @@ int hb_selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const uint64
     return selftest_off<3, 2>(p_limbs, n_limbs, what, operands, out, count);
 }
 
-#undef U32
 }  // extern "C"

@@ -1,0 +1,129 @@
+// hb_rows.hpp -- what the share-array step files (hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip, hb_eq.hip, hb_bf.hip, hb_mimc.hip,
+// hb_jj.hip, hb_off.hip, hb_mat.hip) share, one of each: the read-once load, the small element helpers, the argument checks of the
+// entry points, and the shape of a step.
+//
+// A step is a ROW: a type with
+//     template <int NL, int NW, class Mem> HB_HD static void run(const Args &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P)
+// that works element i of row y (a node, a triple, a plane, a product: whatever the step counts in blockIdx.y) -- which operands it
+// loads, which element body it calls, where it stores.  Args is the step's argument struct, handed to the kernel by value; Mem is a
+// memory policy: load / once (w, base, element index) and store (base, element index, w), element index = row * count + i.  k_rows
+// runs a row on the device (256-thread workgroups, one element a thread in x, the row in blockIdx.y, no LDS, no grid stride), host_rows
+// runs the same row on the host, so a host self test exercises the addressing the device runs, not a restatement of it.
+#pragma once
+#include "hb_common.hpp"
+
+namespace hb {
+
+// ---------------------------------------------------------------- element helpers (host and device)
+// read-once operands (bit planes, triples, what was just opened): the 32-byte width takes the non-temporal loads
+template <int NW> HB_HD void load_once(uint32_t (&w)[NW], const uint32_t *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (NW % 4 == 0) load_words_nt<NW>(w, p); else load_words<NW>(w, p);
+#else
+    load_words<NW>(w, p);
+#endif
+}
+
+// bit i of the packed words (a chain of selects: the words stay in registers)
+template <int NW> HB_HD uint32_t word_bit(const uint32_t (&cw)[NW], int i) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int q = 0; q < NW; q++) w = (q == (i >> 5)) ? cw[q] : w;
+    return (w >> (i & 31)) & 1u;
+}
+
+// o = v - a: a masked difference
+template <int NL, int NW> HB_HD void diff_elem(uint32_t (&o)[NW], const uint32_t (&vw)[NW], const uint32_t (&aw)[NW], const FpParams<NL> &P) {
+    uint32_t v[NL], a[NL], r[NL];
+    unpack<NL, NW>(v, vw);
+    unpack<NL, NW>(a, aw);
+    fp_sub<NL>(r, v, a, P);
+    pack<NL, NW>(o, r);
+}
+
+// ---------------------------------------------------------------- memory policies
+template <int NW> struct DeviceMem {
+    __device__ __forceinline__ void load(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { load_words<NW>(w, base + e * NW); }
+    __device__ __forceinline__ void once(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { load_once<NW>(w, base + e * NW); }
+    __device__ __forceinline__ void store(uint32_t *base, int64_t e, const uint32_t (&w)[NW]) const { store_words<NW>(base + e * NW, w); }
+};
+template <int NW> struct HostMem {
+    void load(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { memcpy(w, base + e * NW, NW * 4); }
+    void once(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { memcpy(w, base + e * NW, NW * 4); }
+    void store(uint32_t *base, int64_t e, const uint32_t (&w)[NW]) const { memcpy(base + e * NW, w, NW * 4); }
+};
+
+// ---------------------------------------------------------------- a row on the device and on the host
+template <class Row, int NL, int NW, class Args> __global__ void __launch_bounds__(256) k_rows(const FpParams<NL> P, const Args A, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    Row::template run<NL, NW>(A, (int)blockIdx.y, i, count, DeviceMem<NW>(), P);
+}
+
+template <class Row, int NL, int NW, class Args> void host_rows(const Args &A, int rows, int64_t count, const FpParams<NL> &P) {
+    for (int y = 0; y < rows; y++)
+        for (int64_t i = 0; i < count; i++) Row::template run<NL, NW>(A, y, i, count, HostMem<NW>(), P);
+}
+
+// ---------------------------------------------------------------- host side: argument checks
+// packed words of the instantiation with NL digits: <9, 8> or <3, 2>
+constexpr int words_of(int nl) { return nl == 9 ? 8 : 2; }
+
+inline const uint32_t *u32(const void *p) { return (const uint32_t *)p; }
+inline uint32_t *u32(void *p) { return (uint32_t *)p; }
+
+inline int modulus_bits(const uint64_t *p_limbs, int n_limbs) {
+    for (int l = n_limbs - 1; l >= 0; l--)
+        if (p_limbs[l]) return 64 * l + 64 - __builtin_clzll(p_limbs[l]);
+    return 0;
+}
+inline bool overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+    return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
+}
+
+// `rows` rows of row_bytes each from p on; a null p is an operand the call does not take
+struct RowSpan { const void *p; int64_t rows; };
+
+// no output may lie over an input or over another output
+inline bool outputs_apart(const RowSpan *outs, int n_outs, const RowSpan *ins, int n_ins, int64_t row_bytes) {
+    for (int o = 0; o < n_outs; o++) {
+        for (int i = 0; i < n_ins; i++)
+            if (overlap(outs[o].p, outs[o].rows * row_bytes, ins[i].p, ins[i].rows * row_bytes)) return false;
+        for (int o2 = o + 1; o2 < n_outs; o2++)
+            if (overlap(outs[o].p, outs[o].rows * row_bytes, outs[o2].p, outs[o2].rows * row_bytes)) return false;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------- host side: the launch
+// blocks of 256 elements in x, refused where one launch cannot hold them; s = the caller's stream
+#define HB_ROW_BLOCKS(ctx, name)                                                                                       \
+    const int64_t blocks = (count + 255) / 256;                                                                        \
+    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
+    hipStream_t s = (hipStream_t)stream
+
+// Row over `grid` for the context's field, <9, 8> with ctx->pw or <3, 2> with ctx->pn, and the launch check.
+template <class Row, class Args> int launch_rows(hb_ctx *ctx, const Args &A, dim3 grid, hipStream_t s, int64_t count) {
+    if (ctx->n_limbs == 4) k_rows<Row, 9, 8><<<grid, 256, 0, s>>>(ctx->pw, A, count);
+    else k_rows<Row, 3, 2><<<grid, 256, 0, s>>>(ctx->pn, A, count);
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+// The same for a step whose argument struct ArgsT<NL> carries constants as digits of the field: fill(A, P) sets it up and returns
+// false where a constant is refused (HB_ERR_BAD_ARG: the entry point adds its message).  An empty batch is checked and not launched.
+template <class Row, template <int> class ArgsT, class Fill> int launch_rows(hb_ctx *ctx, Fill &&fill, dim3 grid, hipStream_t s, int64_t count) {
+    if (ctx->n_limbs == 4) {
+        ArgsT<9> A;
+        if (!fill(A, ctx->pw)) return HB_ERR_BAD_ARG;
+        if (count) k_rows<Row, 9, 8><<<grid, 256, 0, s>>>(ctx->pw, A, count);
+    } else {
+        ArgsT<3> A;
+        if (!fill(A, ctx->pn)) return HB_ERR_BAD_ARG;
+        if (count) k_rows<Row, 3, 2><<<grid, 256, 0, s>>>(ctx->pn, A, count);
+    }
+    if (count) HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
+}  // namespace hb

@@ -114,6 +114,11 @@ def run_bd(p, nl, what, operands, params, outs, count):
     return _run("hb_selftest_bd", 2, p, nl, what, operands, params, outs, count)
 
 
+def run_fxp(p, nl, what, operands, params, outs, count):
+    """hb_selftest_fxp over lists of ints; params = [k, m, kappa, aux, root]"""
+    return _run("hb_selftest_fxp", 5, p, nl, what, operands, params, outs, count)
+
+
 def run_fxp_mask(p, nl, xs, planes, k, m, kappa, count):
     """hb_selftest_fxp's mask body -> (masked, r1)"""
     rc, (masked, r1) = _run("hb_selftest_fxp", 5, p, nl, 0, [xs, planes], [k, m, kappa], [1, 1], count)

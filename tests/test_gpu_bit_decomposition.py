@@ -146,6 +146,57 @@ def test_prefix_level_kernels_in_place(p):
                                 assert q1[j][e] == bc.beaver(o[2 * r1][e], o[2 * r1 + 1][e], a[r1][e], b[r1][e], ab[r1][e], p), (m, level, j, e)
 
 
+@pytest.mark.parametrize("count", (1, 257))
+@pytest.mark.parametrize("p", bc.GPU_FIELDS, ids=bc.GPU_FIELD_IDS)
+def test_every_step_equals_the_host_self_test(p, count):
+    """One row body: for every step of csrc/hb_bd.hip the device's output equals, bit for bit, what hb_selftest_bd computes on the host
+    from the same inputs -- the self test runs the rows the kernels run, addressing included.  m = 6: five planes and three levels, a
+    g-only and a full node, two g-only nodes, then a single g-only node; m = 1: the sum step without a plane.  count 1 is one partial
+    workgroup, 257 a second workgroup that holds one element."""
+    from honeybadgermpc_amd.progs import bit_decomposition as bd
+
+    ctx = gpu_ctx(p)
+    torch, nl = ctx.torch, ctx.n_limbs
+    seeds = iter(range(400, 500))
+
+    def rnd(rows=None):
+        return random_tensor(ctx, next(seeds), count, rows)
+
+    def host(what, operands, params, outs):
+        as_ints = [o if o is None or isinstance(o, (list, int)) else (ctx.download_ints(o.reshape(-1, nl)) if o.numel() else []) for o in operands + outs]
+        rc, res = bc.run_bd(p, nl, what, as_ints[:len(operands)], params, as_ints[len(operands):], count)
+        assert rc == 0
+        return [ctx.upload_ints(o) for o in res]
+
+    def same(dev, want):
+        return torch.equal(dev.reshape(-1, nl), want)
+
+    m, n = 6, 5
+    c, bits = rnd(), rnd(m)
+    g, q = bd.sub_leaves(ctx, c, bits, m)
+    h = host(bc.LEAVES, [c, bits[:n]], [m], [n, n])
+    assert same(g, h[0]) and same(q, h[1])
+    assert [len(bd.prefix_nodes(n, level)) for level in range(bd.prefix_levels(m))] == [2, 2, 1]
+    for level in range(3):
+        triples = bd.prefix_level_triples(m, level)
+        ta, tb, tab, opened = rnd(triples), rnd(triples), rnd(triples), rnd(2 * triples)
+        masked = bd.prefix_mask(ctx, g, q, level, ta, tb)
+        assert same(masked, host(bc.PREFIX_MASK, [g, q, ta, tb], [m, level], [2 * triples])[0]), level
+        h = host(bc.PREFIX_COMBINE, [opened, ta, tb, tab], [m, level], [g, q])               # the planes before the level: updated in place
+        bd.prefix_combine(ctx, opened.view(-1, nl), g, q, level, ta, tb, tab)
+        assert same(g, h[0]) and same(q, h[1]), level
+    for m in (6, 1):
+        n = m - 1
+        c, bits, carries = rnd(), rnd(m), g if n else rnd(0)
+        ta, tb, tab, opened = rnd(n), rnd(n), rnd(n), rnd(2 * n)
+        masked = bd.sum_mask(ctx, c, bits, carries, m, ta, tb)
+        if n:
+            assert same(masked, host(bc.SUM_MASK, [c, bits, carries, ta, tb], [m], [2 * n])[0])
+        out = bd.sum_combine(ctx, opened.view(2 * n * count, nl), c, bits, carries, m, ta, tb, tab)
+        assert tuple(out.shape) == (m, count, nl)
+        assert same(out, host(bc.SUM_COMBINE, [opened, c, bits, carries, ta, tb, tab], [m], [m])[0]), m
+
+
 @pytest.mark.parametrize("p, m", [(BLS, 33), (BLS, 9), (BLS, 2), (bc.P64, 17)], ids=["bls-33", "bls-9", "bls-2", "2^64-59-17"])
 def test_chain_on_cleartext_values_gives_the_difference_bits(p, m):
     """the five calls chained on degree-0 shares (what a step opens is what its mask wrote): corners of c, and r all zeros, all ones

@@ -201,6 +201,64 @@ def test_leaf_carry_and_finish_kernels(p):
                 assert ctx.download_ints(fx.div2m_finish(ctx, x, c, r1, carry, m, fx.TRUNC).index_select(0, sel)) == want
 
 
+@pytest.mark.parametrize("count", (1, 257))
+@pytest.mark.parametrize("p", FIELDS, ids=FIELD_IDS)
+def test_every_step_equals_the_host_self_test(p, count):
+    """One row body: for every step of csrc/hb_fxp.hip the device's output equals, bit for bit, what hb_selftest_fxp computes on the host
+    from the same inputs -- the self test runs the rows the kernels run, addressing included.  m = 4: the tree's levels have 5, 3 and 2
+    nodes, so the odd plane is copied at 5 and at 3 and the root, where p is not written, has 2.  count 1 is one partial workgroup, 257
+    a second workgroup that holds one element."""
+    import bitdec_cases as bc
+    from honeybadgermpc_amd.progs import fixedpoint as fx
+
+    ctx = _ctx(p)
+    torch, nl = ctx.torch, ctx.n_limbs
+    k, m, kappa = 8, 4, 8
+    MASK, TRUNC_PR, LEAVES, CARRY_MASK, CARRY_COMBINE, FINISH = range(6)
+    seeds = iter(range(300, 400))
+
+    def rnd(rows=None):
+        return _random_tensor(ctx, next(seeds), count, rows)
+
+    def host(what, operands, params, out_rows):
+        rc, outs = bc.run_fxp(p, nl, what, [o if o is None or isinstance(o, list) else _ints(ctx, o) for o in operands], params, out_rows, count)
+        assert rc == 0
+        return [None if o is None else ctx.upload_ints(o) for o in outs]
+
+    def same(dev, want):
+        return torch.equal(dev.reshape(-1, nl), want)
+
+    x, c, bits, inv = rnd(), rnd(), rnd(k + kappa), [pow(2, -m, p)]
+    masked, r1 = fx.trunc_mask(ctx, x, bits, k, m, kappa)
+    h = host(MASK, [x, bits], [k, m, kappa], [1, 1])
+    assert same(masked, h[0]) and same(r1, h[1])
+    q1, q2 = fx.random2m(ctx, bits, k, m, kappa)
+    h = host(MASK, [None, bits], [k, m, kappa], [1, 1])
+    assert same(q2, h[0]) and same(q1, h[1])
+    assert same(fx.trunc_pr_finish(ctx, x, c, r1, m), host(TRUNC_PR, [x, c, r1, inv], [k, m, kappa], [1])[0])
+    g, q = fx.ltl_leaves(ctx, c, bits[:m], m)
+    h = host(LEAVES, [c, bits[:m]], [k, m, kappa], [m + 1, m + 1])
+    assert same(g, h[0]) and same(q, h[1])
+    for nodes, root in ((5, False), (3, False), (2, True)):
+        assert g.shape[0] == q.shape[0] == nodes
+        triples, out_nodes = 1 if root else 2 * (nodes // 2), (nodes + 1) // 2
+        ta, tb, tab = rnd(triples), rnd(triples), rnd(triples)
+        masked = fx.carry_mask(ctx, g, q, ta, tb, root=root)
+        assert same(masked, host(CARRY_MASK, [g, q, ta, tb], [k, m, kappa, nodes, int(root)], [2 * triples])[0]), nodes
+        opened = rnd(2 * triples)
+        res = fx.carry_combine(ctx, opened.view(-1, nl), g, q, ta, tb, tab, root=root)
+        h = host(CARRY_COMBINE, [opened, g, q, ta, tb, tab], [k, m, kappa, nodes, int(root)], [out_nodes, None if root else out_nodes])
+        if root:
+            assert same(res, h[0])
+        else:
+            assert same(res[0], h[0]) and same(res[1], h[1]), nodes
+            g, q = res
+    carry = res
+    for mode in (fx.MOD, fx.TRUNC, fx.NEG_TRUNC):
+        xin = None if mode == fx.MOD else x
+        assert same(fx.div2m_finish(ctx, xin, c, r1, carry, m, mode), host(FINISH, [xin, c, r1, carry, inv], [k, m, kappa, mode], [1])[0]), mode
+
+
 def test_inputs_untouched_out_given_arguments_checked_and_asynchronous():
     from honeybadgermpc_amd import share_arithmetic as sa
     from honeybadgermpc_amd._capi import HB_ERR_BAD_ARG
