@@ -61,15 +61,25 @@ def half_columns(half):
     return sorted(c for rho in HALF_RHOS[half] for c in cols_of(rho))
 
 
-def lds_loads(kb, xs_op, as_op):
-    """K-block kb: both elements of the lane (2 x 32 bytes) and both digit groups"""
+NCP = 39                    # virtual columns of a packed pass: one per window
+
+
+def packed_columns(half):
+    """a packed pass has one accumulator per window s, the virtual column c' = s + 7: in M rows 0-7 (digit group 0) it is column
+    c' of the output, in M rows 8-15 (the digit group 1 of the same outputs) column c' + 8"""
+    return sorted(4 * q + rho + 7 for rho in HALF_RHOS[half] for q in windows(rho))
+
+
+def lds_loads(kb, xs_op, as_op, packed=False):
+    """K-block kb: both elements of the lane (2 x 32 bytes) and both digit groups (packed: the one piece that holds both)"""
     a0, a1 = ABUF[kb & 1]
     out = []
     for e in (0, 1):
         for h in (0, 1):
             out.append(f"ds_read_b128 v[{XB + 8 * e + 4 * h}:{XB + 8 * e + 4 * h + 3}], {xs_op} offset:{((kb * 2 + e) * 2 + h) * 1024}")
     out.append(f"ds_read_b128 v[{a0}:{a0 + 3}], {as_op} offset:{(kb * 2) * 1024}")
-    out.append(f"ds_read_b128 v[{a1}:{a1 + 3}], {as_op} offset:{(kb * 2 + 1) * 1024}")
+    if not packed:
+        out.append(f"ds_read_b128 v[{a1}:{a1 + 3}], {as_op} offset:{(kb * 2 + 1) * 1024}")
     return out
 
 
@@ -92,12 +102,15 @@ def interleave(mfmas, ops):
     return out
 
 
-def asm_half(half, nkb, skip=False):
-    """skip: the matrix has no digit above the eighth in its first eight terms (Vandermonde matrices at small points: x^l < 2^56
+def asm_half(half, nkb, skip=False, packed=False):
+    """packed: the row tile holds the two digit groups of an output on M rows m and m + 8 of ONE sixteen-byte piece per K-block, so a
+    window is one MFMA instead of two (39 n_kb in all) and the accumulators are the virtual columns of packed_columns().
+    skip: the matrix has no digit above the eighth in its first eight terms (Vandermonde matrices at small points: x^l < 2^56
     for l < 8), so the MFMAs of digit group 1 in K-block 0 would add zeros -- they are left out (39 of 78 n_kb), and the columns only
     group 1 reaches start from the bias in K-block 1 instead"""
     assert not skip or nkb >= 2
-    cols = half_columns(half)
+    assert not (skip and packed)
+    cols = packed_columns(half) if packed else half_columns(half)
     pos = {c: i for i, c in enumerate(cols)}
     ncol = len(cols)
     xs_op, as_op, bias = f"%{ncol}", f"%{ncol + 1}", f"%{ncol + 2}"
@@ -107,7 +120,7 @@ def asm_half(half, nkb, skip=False):
         for k in (-2, 8):
             for e in (0, 1):
                 L.append(f"v_mov_b32 v{f(s, k, e)}, 0")
-    L += lds_loads(0, xs_op, as_op)[:(5 if skip else 6)]          # (skip: group 1's digits of K-block 0 are not needed)
+    L += lds_loads(0, xs_op, as_op, packed)[:(5 if skip else 6)]          # (skip: group 1's digits of K-block 0 are not needed)
     groups = [(kb, rho) for kb in range(nkb) for rho in HALF_RHOS[half]]
 
     def prep(gi):
@@ -140,7 +153,7 @@ def asm_half(half, nkb, skip=False):
         for q in windows(rho):
             r = f(s, q, 0)
             assert r % 2 == 0
-            for grp in (0, 1):
+            for grp in ((0,) if packed else (0, 1)):
                 if skip and kb == 0 and grp == 1:
                     continue
                 c = 4 * q + rho + 7 + 8 * grp
@@ -160,7 +173,7 @@ def asm_half(half, nkb, skip=False):
         if rho == HALF_RHOS[half][0] and kb + 1 < nkb:
             # XB was consumed by this group's preparation and every MFMA of K-block kb - 1 (the last reader of the other A
             # buffers) has been issued: fetch K-block kb + 1
-            L += lds_loads(kb + 1, xs_op, as_op)
+            L += lds_loads(kb + 1, xs_op, as_op, packed)
         L += interleave(mfmas(gi), prep(gi + 1) if nxt else [])
         if nxt:
             L.append("s_nop 0")
@@ -183,6 +196,25 @@ def emit():
             lines, ncol = asm_half(half, nkb, skip)
             out.append(f"template <> struct Mm8Phase<{nkb}, {half}, {'true' if skip else 'false'}> {{")
             out.append("    static __device__ __forceinline__ void run(v4i (&acc)[24], uint32_t xs_addr, uint32_t as_addr, v4i biasv) {")
+            out.append("        asm volatile(")
+            for ln in lines:
+                out.append(f'            "{ln}\\n\\t"')
+            outs = ", ".join(f'"=&v"(acc[{i}])' for i in range(ncol))
+            out.append(f"            : {outs}")
+            out.append('            : "v"(xs_addr), "v"(as_addr), "v"(biasv)')
+            out.append(f'            : {clob}, "memory");')
+            out.append("    }")
+            out.append("};")
+    # the packed phases (k_mm8f's narrow last row tile): their own template, so that the text above stays what it was
+    assert packed_columns(0) == [c for c in range(NCP) if c % 4 in (0, 3)] and packed_columns(1) == [c for c in range(NCP) if c % 4 in (1, 2)]
+    out.append("// packed phases: accumulator i of a half is the virtual column (one per window) of the same two lists cut at 38")
+    out.append("template <int NKB, int HALF> struct Mm8PhasePacked;")
+    for nkb in range(1, MAXKB + 1):
+        for half in range(2):
+            lines, ncol = asm_half(half, nkb, packed=True)
+            assert sum("v_mfma" in ln for ln in lines) == len(windows(HALF_RHOS[half][0]) + windows(HALF_RHOS[half][1])) * nkb
+            out.append(f"template <> struct Mm8PhasePacked<{nkb}, {half}> {{")
+            out.append("    static __device__ __forceinline__ void run(v4i (&acc)[20], uint32_t xs_addr, uint32_t as_addr, v4i biasv) {")
             out.append("        asm volatile(")
             for ln in lines:
                 out.append(f'            "{ln}\\n\\t"')

@@ -528,6 +528,19 @@ int mm8_shared(hb_ctx *ctx, const Mm8Shared **out, hipStream_t s) {
     { Big bt(14, 0); for (int c = 0; c < MM8_NC; c++) { Big t(1, (uint32_t)MM8_BIAS); big_add(bt, big_shl(t, 8 * c, 14)); } biasmod = big_divmod(bt, p, nullptr); }
     { Big sft(shift8, shift8 + 8); if (!big_ge(biasmod, sft)) big_add(biasmod, p); big_sub(biasmod, sft); }
     digits9(biasmod, sh->biasmod);
+    for (int merged = 0; merged < 2; merged++) {      // the rows of a packed pass (hb_mfma_fused.hip)
+        Big bt(14, 0);
+        for (int c = 0; c < MM8_NCP; c++) {
+            Big t(1, (uint32_t)MM8_BIAS_PACK);
+            big_add(bt, big_shl(t, 8 * c, 14));
+            if (merged) big_add(bt, big_shl(t, 8 * (c + 8), 14));
+        }
+        Big bm = big_divmod(bt, p, nullptr);
+        Big sft(shift8, shift8 + 8);
+        if (!big_ge(bm, sft)) big_add(bm, p);
+        big_sub(bm, sft);
+        digits9(bm, merged ? sh->biasmod_pm : sh->biasmod_ps);
+    }
     {   // (0x80..80 * 2^261) mod p: mont_mul(row sum, .) = 0x80..80 * row sum
         Big c80(8, 0x80808080u);
         Big r261(9, 0); r261[8] = 1u << 5;

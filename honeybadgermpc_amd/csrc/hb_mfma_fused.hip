@@ -66,6 +66,44 @@ struct FsPick { const uint4 *cand; const uint32_t *cand_crow; int n_coef, nc; ui
 // that the two waves of a SIMD (w and w + 4) reach the unit's barrier together -- a wave that waits leaves its SIMD to ONE wave, and one
 // wave issues at 0.7 of the rate two reach (fs_split)
 struct FsSplit { uint32_t terms[FS_WAVES]; };
+// A narrow last row tile PACKED: the two digit groups of an output on M rows m and m + 8 of one sixteen-byte piece per K-block, so the
+// pass over it issues 39 NKB MFMAs instead of 78 NKB (Mm8PhasePacked).  Output `reg` of lane (n, g) is M row 4 reg + g, so the two partial
+// sums of a merged output are regs r and r + 2 of ONE lane: no lane of the tile ever needs another's.  nm merged outputs take M rows
+// 0 .. nm - 1 (and 8 .. 8 + nm - 1); ns rows whose digit group 1 is empty take one M row each, 4 .. 7 and 12 .. 15 (regs 1 and 3: only
+// with nm <= 4, so that every reg of the tile is of one kind in all its lanes).  Either nm <= 8 and ns = 0, or nm <= 4 and 5 <= ns <= 8
+// (the two forms k_mm8f is compiled for); nm = ns = 0: no packed tile.
+struct FsPack { int nm, ns; uint8_t single[8]; };
+// the image slot (16 row tile + M row) of matrix row i; kind 0: both digit groups in the slot's own two pieces, 1: merged, 2: single-group.
+// The single-group rows leave their places, the rows behind them move up, the last nm of the rest are the merged ones.
+__host__ __device__ inline int fs_slot(const FsPack &pk, int i, int n_out, int &kind) {
+    kind = 0;
+    if (!(pk.nm | pk.ns)) return i;
+    const int base = 16 * ((n_out + 15) / 16 - 1);
+    int before = 0;
+    for (int k = 0; k < pk.ns; k++) {
+        if (pk.single[k] == i) { kind = 2; return base + 4 + (k & 3) + 8 * (k >> 2); }
+        before += pk.single[k] < i;
+    }
+    const int pos = i - before;
+    if (pos >= base) kind = 1;
+    return pos;
+}
+// Does the last row tile pack?  rem = the rows of the ragged last tile, small[i]: coefficient row i has no digit above the eighth.  Up to
+// eight rows merge where they stand; more need single-group rows to trade places with (the LAST small coefficient rows, eight at most).
+static bool fs_pack_decide(int d, int n_coef, int nc, const uint8_t *small, FsPack *pk) {
+    memset(pk, 0, sizeof *pk);
+    const int n_out = n_coef + nc, rem = n_out - 16 * ((n_out + 15) / 16 - 1);
+    if ((int64_t)d * 8 * 128 * 128 > MM8_BIAS_PACK) return false;
+    if (rem <= 8) { pk->nm = rem; return true; }
+    if (rem == 16) return false;
+    int ns = 0;
+    for (int i = n_coef - 1; i >= 0 && ns < 8; i--)
+        if (small[i]) pk->single[ns++] = (uint8_t)i;
+    std::reverse(pk->single, pk->single + ns);
+    if (rem - ns > 4) { memset(pk, 0, sizeof *pk); return false; }      // (rem > 8: where this holds ns >= 5, and regs 1 and 3 both hold rows)
+    pk->nm = rem - ns; pk->ns = ns;
+    return true;
+}
 constexpr int FS_CAND_MAXN = 128;               // parties a candidate store is built for (n d 128-bit entries in the builder's LDS)
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -77,8 +115,115 @@ __host__ __device__ inline size_t fs_lds_bytes(int n_rt, int nkb) {
     return ((size_t)n_rt * 64 + (size_t)n_rt * nkb * 2 * 64 + (size_t)2 * FS_TPW * nkb * 4 * 64 + MM8_FOLD_Q) * 16 + (size_t)(32 + 16 * n_rt) * 4;
 }
 
+// The reduction of one output of lane (n, g) in k_mm8f, as TEXT (a lambda with this body costs the kernel registers it does not have: the
+// instance without a packed tile must stay the code it was).  I_: the image slot (its mode and constant); F_(k), k < 12: the output's columns
+// (4k+1, 4k+2) as lo + 256 hi; E_(k), k < 11: columns (4k+3, 4k+4) likewise; C0_: column 0.  A packed pass hands it the same 47 columns,
+// summed from its two digit groups.  Uses the kernel's locals (chunk, n, lane, the opaque constants, the tables in LDS).  Notes on the body:
+//   * the compared row is loaded unconditionally (from the buffer's first element when there is nothing to compare): a load under `cmp`
+//     makes hipcc wrap the whole reduction in that divergent branch, and the register copies at its join spill
+//   * glo / ghi are G_7 .. G_11; `top` is bit 256 of the remainder (r < 2p < 2^257)
+//   * the empty asm keeps the reduction outside the exec masks of the compare and the store (same reason as the load)
+//   * disagreements are reported once per wave and output (an adversary that corrupts everything would otherwise queue a million atomics
+//     on one word: 430 us instead of 55 for config 3's launch): lane (n, g) holds chunk tile_base + n, so the sixteen chunk bits of the
+//     wave are the OR of its four lane groups
+#define FS_REDUCE(I_, F_, E_, C0_) \
+    do { \
+        const int i = (I_); \
+        const int md = maskl[i]; \
+        const bool live = chunk < n_chunks; \
+        const bool cmp = live && md > 0, st = live && md < 0; \
+        uint32_t ew[8]; \
+        load_words<8>(ew, in_pk + (cmp ? (chunk * in_sc + (int64_t)(md - 1) * in_sl) * 8 : 0)); \
+        uint64_t pw[8]; \
+        { \
+            const uint4 *cr = reinterpret_cast<const uint4 *>(crl + (size_t)i * 16); \
+        _Pragma("unroll") \
+            for (int k = 0; k < 4; k++) { \
+                const uint4 c = cr[k]; \
+                pw[2 * k] = (uint64_t)c.x | ((uint64_t)c.y << 32); \
+                pw[2 * k + 1] = (uint64_t)c.z | ((uint64_t)c.w << 32); \
+            } \
+        } \
+        uint32_t glo[5], ghi[5]; \
+        _Pragma("unroll") \
+        for (int k = 0; k < 12; k++) { \
+            uint64_t gk = (uint64_t)F_(k) * k256 + (k < 7 ? pw[k] : 0ull); \
+            if (k < 11) gk += (uint64_t)E_(k) * k16m; \
+            if (k < 7) pw[k] = gk; \
+            else { glo[k - 7] = (uint32_t)gk; ghi[k - 7] = (uint32_t)(gk >> 32); } \
+        } \
+        pw[0] += (uint64_t)(C0_) * u1; \
+        pw[7] += (uint64_t)glo[0] * u1; \
+        uint32_t hw[5]; \
+        { \
+            unsigned cyw = 0; \
+        _Pragma("unroll") \
+            for (int k = 0; k < 4; k++) hw[k] = __builtin_addc(glo[k + 1], ghi[k], cyw, &cyw); \
+            hw[4] = ghi[4] + cyw; \
+        } \
+        v4i hb; \
+        _Pragma("unroll") \
+        for (int k = 0; k < 4; k++) hb[k] = (int)(hw[k] ^ 0x80808080u); \
+        v4i dcol[8]; \
+        _Pragma("unroll") \
+        for (int eb = 0; eb < 8; eb++) \
+            dcol[eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fold_lane[eb * (MM8_FOLD_ROW / 16)], hb, v4i{0, 0, 0, 0}, 0, 0, 0); \
+        _Pragma("unroll") \
+        for (int k = 0; k < 8; k++) pw[k] += (uint64_t)hw[4] * bp.c384[k]; \
+        _Pragma("unroll") \
+        for (int k = 0; k < 8; k++) { \
+            int64_t tt = (int64_t)pw[k] + (int64_t)dcol[k][0] * s1; \
+            tt += (int64_t)dcol[k][1] * s256; \
+            tt += (int64_t)dcol[k][2] * s64k; \
+            tt += (int64_t)dcol[k][3] * s16m; \
+            pw[k] = (uint64_t)tt; \
+        } \
+        const uint64_t tq = pw[7] + (pw[6] >> 32); \
+        const uint32_t qh = (uint32_t)(((uint64_t)(uint32_t)(tq >> 16) * bp.mu) >> 46); \
+        _Pragma("unroll") \
+        for (int k = 0; k < 8; k++) pw[k] += (uint64_t)qh * bp.pneg[k]; \
+        uint32_t ow[8]; \
+        uint32_t top; \
+        { \
+            unsigned cy = 0; \
+            ow[0] = (uint32_t)pw[0]; \
+        _Pragma("unroll") \
+            for (int k = 1; k < 8; k++) ow[k] = __builtin_addc((uint32_t)pw[k], (uint32_t)(pw[k - 1] >> 32), cy, &cy); \
+            top = (uint32_t)(pw[7] >> 32) + cy - qh; \
+        } \
+        if (__builtin_amdgcn_ballot_w64(top != 0 || ow[7] >= ~bp.pneg[7]) != 0) { \
+            uint32_t u[8]; \
+            unsigned cy2 = 0; \
+        _Pragma("unroll") \
+            for (int k = 0; k < 8; k++) u[k] = __builtin_addc(ow[k], bp.pneg[k], cy2, &cy2); \
+            const bool take = cy2 || top; \
+        _Pragma("unroll") \
+            for (int k = 0; k < 8; k++) ow[k] = take ? u[k] : ow[k]; \
+        } \
+        uint32_t diff = 0; \
+        _Pragma("unroll") \
+        for (int k = 0; k < 8; k++) diff |= ew[k] ^ ow[k]; \
+        asm volatile("" : "+v"(diff), "+v"(ow[0]), "+v"(ow[1]), "+v"(ow[2]), "+v"(ow[3]), "+v"(ow[4]), "+v"(ow[5]), "+v"(ow[6]), "+v"(ow[7])); \
+        const unsigned long long bad_lanes = __builtin_amdgcn_ballot_w64(cmp && diff); \
+        if (bad_lanes) { \
+            const uint32_t bits16 = (uint32_t)((bad_lanes | (bad_lanes >> 16) | (bad_lanes >> 32) | (bad_lanes >> 48)) & 0xffffull); \
+            if (lane == 0) { \
+                const int64_t tile_base = chunk - n; \
+                const int32_t cmin = (int32_t)tile_base + __builtin_ctz(bits16); \
+                if (*reinterpret_cast<volatile int32_t *>(mismatch) == 0) atomicOr(mismatch, 1); \
+                if (first_bad && *reinterpret_cast<volatile int32_t *>(first_bad) > cmin) atomicMin(first_bad, cmin); \
+                if (bad_map) atomicOr(bad_map + (tile_base >> 5), bits16 << (tile_base & 31)); \
+            } \
+        } \
+        const int64_t oidx = chunk * out_sc + (int64_t)(-md - 1) * out_sl; \
+        if (st && oidx < out_count) store_words<8>(out_pk + oidx * 8, ow); \
+    } while (0)
+
 // rowmode[i]: 0 = nothing, v > 0: compare the sum with row v - 1 of the input buffer, v < 0: store it as output row -v - 1
-template <int NKB>
+// PK: the last row tile is a packed one (FsPack) -- 1: merged outputs alone (regs 0 and 1, each with its partner two regs up), 2: up to four
+// merged outputs (reg 0) and five to eight single-group rows (regs 1 and 3); the image's rows are then its 16 n_rt slots, and no row is
+// picked.  PK = 0 is the kernel as it was: what a decoder launches, and every image whose last tile does not pack.
+template <int NKB, int PK>
 __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restrict__ a8, const uint32_t *__restrict__ crowd, const v4i *__restrict__ foldg,
                                                           const uint32_t *__restrict__ KT, const PrescaleParams PP,
                                                           const uint32_t *__restrict__ in_pk, int64_t in_sc, int64_t in_sl, const int32_t *__restrict__ in_rows,
@@ -87,6 +232,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                                                           int32_t *__restrict__ mismatch, int32_t *__restrict__ first_bad, uint32_t *__restrict__ bad_map,
                                                           int n_out, int n_rt, int64_t n_chunks, int64_t n_units, BarrettParams bp, const FsDone done, const FsPick pick,
                                                           const FsSplit split) {
+    constexpr bool PACKED = PK != 0;
+    const int n_slots = PACKED ? 16 * n_rt : n_out;      // rows of the image (PACKED: n_out goes unused)
     constexpr int NT = 64 * FS_WAVES, NL = 9, NW = 8;
     extern __shared__ uint4 fs_lds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -128,7 +275,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
     // dependent loads, the sender's number and then its row: they ride under the copy), and written over the image's empty rows behind it
     uint4 pk_piece = make_uint4(0, 0, 0, 0), pk_crow = make_uint4(0, 0, 0, 0);
     const int pk_e = threadIdx.x;
-    const bool pk_has_piece = pick.cand && pk_e < pick.nc * NKB * 8, pk_has_crow = pick.cand && pk_e < pick.nc * 4;
+    const bool pk_has_piece = !PACKED && pick.cand && pk_e < pick.nc * NKB * 8, pk_has_crow = !PACKED && pick.cand && pk_e < pick.nc * 4;
     // (one piece a thread ahead of the copy: config 3's 21 compared rows are 504 pieces for the 512 threads; what a larger launch has beyond
     // that is fetched behind the copy, below -- five pieces a thread in registers went to scratch memory)
     if (pk_has_piece) {
@@ -143,7 +290,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         const int tid = threadIdx.x, n_mask = n_rt * 16, n_crow = n_rt * 64, n_img = n_rt * NKB * 2 * 64;
         const int lc = tid < d ? tid : d - 1;
         int32_t rw = in_rows ? in_rows[lc] : lc;
-        int32_t mk = rowmode[tid < n_out ? tid : 0];
+        int32_t mk = rowmode[tid < n_slots ? tid : 0];
         v4i cr = reinterpret_cast<const v4i *>(crowd)[tid < n_crow ? tid : 0];
         v4i fo = foldg[tid < MM8_FOLD_Q ? tid : 0];
         v4i img[3];
@@ -152,14 +299,14 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         // (the words are wanted HERE: hipcc otherwise sinks each load into the branch of its write, one wait per load again)
         asm volatile("" : "+v"(rw), "+v"(mk), "+v"(cr), "+v"(fo), "+v"(img[0]), "+v"(img[1]), "+v"(img[2]));
         if (tid < 32) rowl[tid] = rw;
-        if (tid < n_mask) maskl[tid] = tid < n_out ? mk : 0;
+        if (tid < n_mask) maskl[tid] = tid < n_slots ? mk : 0;
         if (tid < n_crow) reinterpret_cast<v4i *>(fs_lds)[tid] = cr;
         if (tid < MM8_FOLD_Q) foldl[tid] = fo;
 #pragma unroll
         for (int k = 0; k < 3; k++)
             if (tid + k * NT < n_img) reinterpret_cast<v4i *>(abuf)[tid + k * NT] = img[k];
         // (what a larger launch has beyond one round)
-        for (int i = tid + NT; i < n_mask; i += NT) maskl[i] = i < n_out ? rowmode[i] : 0;
+        for (int i = tid + NT; i < n_mask; i += NT) maskl[i] = i < n_slots ? rowmode[i] : 0;
         for (int i = tid + NT; i < n_crow; i += NT) fs_lds[i] = reinterpret_cast<const uint4 *>(crowd)[i];
         for (int i = tid + 3 * NT; i < n_img; i += NT) abuf[i] = a8[i];
     }
@@ -258,7 +405,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
     // the first unit: every wave scales its share into buffer 0.  Nothing it touches depends on the tables (the padding slots are other
     // slots), so no barrier stands between the copy and this: the loop's first barrier covers both
     scale_unit(std::true_type{}, blockIdx.x, xbuf, first_terms);
-    if (pick.cand) {
+    if (!PACKED && pick.cand) {
         __syncthreads();      // (the image's copy is in LDS: the picked rows go over its empty rows)
         auto put = [&](int e, const uint4 &v) {
             const int j = e / (NKB * 8), pc = e - j * (NKB * 8);
@@ -304,9 +451,105 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
             uint32_t eap[4][11], c0p[4];     // half 0's column pairs, parked across the second MFMA block
             // output `reg` of lane (n, g) is row 16 rt + 4 reg + g: a ragged last tile fills its outputs from the top
             const int rows_here = n_out - 16 * rt < 16 ? n_out - 16 * rt : 16;
-            const int nreg = (rows_here + 3) >> 2;
+            const int nreg = PACKED ? 4 : (rows_here + 3) >> 2;      // (PACKED: the only tile that is not full takes the branch below)
             const uint32_t xs_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)xs;
             const uint32_t as_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)as;
+            if (PACKED && rt == n_rt - 1) {
+                // ---- the packed tile (FsPack): one MFMA a window.  Accumulator c' of reg r < 2 is column c' of the output on M row 4 r + g,
+                // of reg r + 2 column c' + 8 of the same output (merged), or both are columns c' of two single-group rows.  Reg 0 is always
+                // merged; reg 1 is merged with reg 3 (PK = 1), or regs 1 and 3 hold single-group rows (PK = 2).  The columns of a merged
+                // output are summed HERE, pair by pair, and go through the reduction of every other pass.
+                const v4i biaspv = v4i{MM8_BIAS_PACK, MM8_BIAS_PACK, MM8_BIAS_PACK, MM8_BIAS_PACK};
+                // half 0 holds c' = 0 in acc[0] and the pairs (4j+3, 4j+4), j < 9, in acc[1 + 2j], acc[2 + 2j]; half 1 the pairs (4k+1, 4k+2),
+                // k < 10, in acc[2k], acc[2k + 1]
+                auto park_merged = [&](auto rc, const v4i (&acc)[20]) __attribute__((always_inline)) {
+                    constexpr int r = decltype(rc)::value;
+                    c0p[r] = (uint32_t)acc[0][r];
+#pragma unroll
+                    for (int j = 0; j < 11; j++) {
+                        uint32_t lo = 0, hi = 0;
+                        if (j < 9) { lo = (uint32_t)acc[1 + 2 * j][r]; hi = (uint32_t)acc[2 + 2 * j][r]; }
+                        if (j >= 2) { lo += (uint32_t)acc[2 * j - 3][r + 2]; hi += (uint32_t)acc[2 * j - 2][r + 2]; }
+                        if (j == 1) hi += (uint32_t)acc[0][r + 2];
+                        eap[r][j] = lo + (hi << 8);
+                    }
+                };
+                auto park_single = [&](auto rc, const v4i (&acc)[20]) __attribute__((always_inline)) {
+                    constexpr int r = decltype(rc)::value;
+                    c0p[r] = (uint32_t)acc[0][r];
+#pragma unroll
+                    for (int j = 0; j < 11; j++) eap[r][j] = j < 9 ? (uint32_t)acc[1 + 2 * j][r] + ((uint32_t)acc[2 + 2 * j][r] << 8) : 0u;
+                };
+                auto keep = [&](auto rc) __attribute__((always_inline)) {
+                    constexpr int r = decltype(rc)::value;
+                    asm volatile("" ::"v"(c0p[r]), "v"(eap[r][0]), "v"(eap[r][1]), "v"(eap[r][2]), "v"(eap[r][3]), "v"(eap[r][4]), "v"(eap[r][5]),
+                                 "v"(eap[r][6]), "v"(eap[r][7]), "v"(eap[r][8]), "v"(eap[r][9]), "v"(eap[r][10]));
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                {
+                    v4i acc[20];
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_setprio(0);
+                    Mm8PhasePacked<NKB, 0>::run(acc, xs_addr, as_addr, biaspv);
+                    __builtin_amdgcn_s_setprio(2);
+                    __builtin_amdgcn_sched_barrier(0);
+                    FS_T(3);
+                    park_merged(std::integral_constant<int, 0>{}, acc);
+                    keep(std::integral_constant<int, 0>{});
+                    if constexpr (PK == 1) park_merged(std::integral_constant<int, 1>{}, acc);
+                    else park_single(std::integral_constant<int, 1>{}, acc);
+                    keep(std::integral_constant<int, 1>{});
+                    if constexpr (PK == 2) {
+                        park_single(std::integral_constant<int, 3>{}, acc);
+                        keep(std::integral_constant<int, 3>{});
+                    }
+                }
+                {
+                    v4i acc[20];
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                    FS_T(4);
+                    __builtin_amdgcn_s_setprio(0);
+                    Mm8PhasePacked<NKB, 1>::run(acc, xs_addr, as_addr, biaspv);
+                    __builtin_amdgcn_s_setprio(2);
+                    __builtin_amdgcn_sched_barrier(0);
+                    FS_T(5);
+                    // pair k of a merged output on regs r, r + 2 / of a single-group row on reg r
+                    auto pair_merged = [&](auto rc, int k) __attribute__((always_inline)) {
+                        constexpr int r = decltype(rc)::value;
+                        uint32_t lo = 0, hi = 0;
+                        if (k < 10) { lo = (uint32_t)acc[2 * k][r]; hi = (uint32_t)acc[2 * k + 1][r]; }
+                        if (k >= 2) { lo += (uint32_t)acc[2 * k - 4][r + 2]; hi += (uint32_t)acc[2 * k - 3][r + 2]; }
+                        return lo + (hi << 8);
+                    };
+                    auto pair_single = [&](auto rc, int k) __attribute__((always_inline)) {
+                        constexpr int r = decltype(rc)::value;
+                        return k < 10 ? (uint32_t)acc[2 * k][r] + ((uint32_t)acc[2 * k + 1][r] << 8) : 0u;
+                    };
+#define FS_FM0(k) pair_merged(std::integral_constant<int, 0>{}, k)
+#define FS_FM1(k) pair_merged(std::integral_constant<int, 1>{}, k)
+#define FS_FS1(k) pair_single(std::integral_constant<int, 1>{}, k)
+#define FS_FS3(k) pair_single(std::integral_constant<int, 3>{}, k)
+#define FS_E0(k) eap[0][k]
+#define FS_E1(k) eap[1][k]
+#define FS_E3(k) eap[3][k]
+                    // (reg 3 first: with its accumulators and parked pairs out of the way the other two fit the register file)
+                    if constexpr (PK == 2) { FS_REDUCE(16 * rt + 12 + g, FS_FS3, FS_E3, c0p[3]); __builtin_amdgcn_sched_barrier(0); }
+                    FS_REDUCE(16 * rt + g, FS_FM0, FS_E0, c0p[0]);
+                    if constexpr (PK == 1) FS_REDUCE(16 * rt + 4 + g, FS_FM1, FS_E1, c0p[1]);
+                    else FS_REDUCE(16 * rt + 4 + g, FS_FS1, FS_E1, c0p[1]);
+#undef FS_FM0
+#undef FS_FM1
+#undef FS_FS1
+#undef FS_FS3
+#undef FS_E0
+#undef FS_E1
+#undef FS_E3
+                }
+                FS_T(6);
+                continue;
+            }
             {   // ---- half 0: c = 0 and the pairs (4j+3, 4j+4)
                 v4i acc[24];
                 asm volatile("" ::: "memory");
@@ -340,103 +583,11 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 #pragma unroll
                 for (int reg = 0; reg < 4; reg++) {
                     if (reg >= 2 && reg >= nreg) break;
-                    const int i = 16 * rt + 4 * reg + g;
-                    const int md = maskl[i];
-                    const bool live = chunk < n_chunks;
-                    const bool cmp = live && md > 0, st = live && md < 0;
-                    uint32_t ew[8];
-                    // unconditional (from the buffer's first element when there is nothing to compare): a load under `cmp` makes hipcc wrap
-                    // the whole reduction in that divergent branch, and the register copies at its join spill
-                    load_words<8>(ew, in_pk + (cmp ? (chunk * in_sc + (int64_t)(md - 1) * in_sl) * 8 : 0));
-                    uint64_t pw[8];
-                    {
-                        const uint4 *cr = reinterpret_cast<const uint4 *>(crl + (size_t)i * 16);
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const uint4 c = cr[k];
-                            pw[2 * k] = (uint64_t)c.x | ((uint64_t)c.y << 32);
-                            pw[2 * k + 1] = (uint64_t)c.z | ((uint64_t)c.w << 32);
-                        }
-                    }
-                    uint32_t glo[5], ghi[5];       // G_7 .. G_11
-#pragma unroll
-                    for (int k = 0; k < 12; k++) {
-                        const uint32_t f = (uint32_t)acc[2 * k][reg] + ((uint32_t)acc[2 * k + 1][reg] << 8);
-                        uint64_t gk = (uint64_t)f * k256 + (k < 7 ? pw[k] : 0ull);
-                        if (k < 11) gk += (uint64_t)eap[reg][k] * k16m;
-                        if (k < 7) pw[k] = gk;
-                        else { glo[k - 7] = (uint32_t)gk; ghi[k - 7] = (uint32_t)(gk >> 32); }
-                    }
-                    pw[0] += (uint64_t)c0p[reg] * u1;
-                    pw[7] += (uint64_t)glo[0] * u1;
-                    uint32_t hw[5];
-                    {
-                        unsigned cyw = 0;
-#pragma unroll
-                        for (int k = 0; k < 4; k++) hw[k] = __builtin_addc(glo[k + 1], ghi[k], cyw, &cyw);
-                        hw[4] = ghi[4] + cyw;
-                    }
-                    v4i hb;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) hb[k] = (int)(hw[k] ^ 0x80808080u);
-                    v4i dcol[8];
-#pragma unroll
-                    for (int eb = 0; eb < 8; eb++)
-                        dcol[eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fold_lane[eb * (MM8_FOLD_ROW / 16)], hb, v4i{0, 0, 0, 0}, 0, 0, 0);
-#pragma unroll
-                    for (int k = 0; k < 8; k++) pw[k] += (uint64_t)hw[4] * bp.c384[k];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        int64_t tt = (int64_t)pw[k] + (int64_t)dcol[k][0] * s1;
-                        tt += (int64_t)dcol[k][1] * s256;
-                        tt += (int64_t)dcol[k][2] * s64k;
-                        tt += (int64_t)dcol[k][3] * s16m;
-                        pw[k] = (uint64_t)tt;
-                    }
-                    const uint64_t tq = pw[7] + (pw[6] >> 32);
-                    const uint32_t qh = (uint32_t)(((uint64_t)(uint32_t)(tq >> 16) * bp.mu) >> 46);
-#pragma unroll
-                    for (int k = 0; k < 8; k++) pw[k] += (uint64_t)qh * bp.pneg[k];
-                    uint32_t ow[8];
-                    uint32_t top;
-                    {
-                        unsigned cy = 0;
-                        ow[0] = (uint32_t)pw[0];
-#pragma unroll
-                        for (int k = 1; k < 8; k++) ow[k] = __builtin_addc((uint32_t)pw[k], (uint32_t)(pw[k - 1] >> 32), cy, &cy);
-                        top = (uint32_t)(pw[7] >> 32) + cy - qh;          // bit 256 of the remainder (r < 2p < 2^257)
-                    }
-                    if (__builtin_amdgcn_ballot_w64(top != 0 || ow[7] >= ~bp.pneg[7]) != 0) {
-                        uint32_t u[8];
-                        unsigned cy2 = 0;
-#pragma unroll
-                        for (int k = 0; k < 8; k++) u[k] = __builtin_addc(ow[k], bp.pneg[k], cy2, &cy2);
-                        const bool take = cy2 || top;
-#pragma unroll
-                        for (int k = 0; k < 8; k++) ow[k] = take ? u[k] : ow[k];
-                    }
-                    uint32_t diff = 0;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) diff |= ew[k] ^ ow[k];
-                    // keep the reduction outside the exec masks of the compare and the store (hipcc otherwise wraps the whole output in a
-                    // divergent branch, and the register copies at its join spill)
-                    asm volatile("" : "+v"(diff), "+v"(ow[0]), "+v"(ow[1]), "+v"(ow[2]), "+v"(ow[3]), "+v"(ow[4]), "+v"(ow[5]), "+v"(ow[6]), "+v"(ow[7]));
-                    // disagreements are reported once per wave and output (an adversary that corrupts everything would otherwise queue a
-                    // million atomics on one word: 430 us instead of 55 for config 3's launch): lane (n, g) holds chunk tile_base + n, so the
-                    // sixteen chunk bits of the wave are the OR of its four lane groups
-                    const unsigned long long bad_lanes = __builtin_amdgcn_ballot_w64(cmp && diff);
-                    if (bad_lanes) {
-                        const uint32_t bits16 = (uint32_t)((bad_lanes | (bad_lanes >> 16) | (bad_lanes >> 32) | (bad_lanes >> 48)) & 0xffffull);
-                        if (lane == 0) {
-                            const int64_t tile_base = chunk - n;
-                            const int32_t cmin = (int32_t)tile_base + __builtin_ctz(bits16);
-                            if (*reinterpret_cast<volatile int32_t *>(mismatch) == 0) atomicOr(mismatch, 1);
-                            if (first_bad && *reinterpret_cast<volatile int32_t *>(first_bad) > cmin) atomicMin(first_bad, cmin);
-                            if (bad_map) atomicOr(bad_map + (tile_base >> 5), bits16 << (tile_base & 31));
-                        }
-                    }
-                    const int64_t oidx = chunk * out_sc + (int64_t)(-md - 1) * out_sl;
-                    if (st && oidx < out_count) store_words<8>(out_pk + oidx * 8, ow);
+#define FS_F(k) ((uint32_t)acc[2 * (k)][reg] + ((uint32_t)acc[2 * (k) + 1][reg] << 8))
+#define FS_E(k) eap[reg][k]
+                    FS_REDUCE(16 * rt + 4 * reg + g, FS_F, FS_E, c0p[reg]);
+#undef FS_F
+#undef FS_E
                     if (reg & 1) __builtin_amdgcn_sched_barrier(0);   // two reductions at a time: ILP for the carry chains
                 }
             }
@@ -456,7 +607,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __int128 i128;
 
-struct FsConsts { uint32_t c80r[9], biasmod[9]; };
+struct FsConsts { uint32_t c80r[9], biasmod[9], biasmod_pm[9], biasmod_ps[9]; };     // (biasmod_p*: the rows of a packed tile, hb_mm8.hpp)
 constexpr int32_t FS_OVERFLOW = 0x40000000;       // OR-ed into the status word if an entry does not fit (the host's bound rules it out)
 
 // byte address of digit b (< 16) of entry (row i, term l) in the image (the layout of mm8_from_fast, hb_mfma.hip)
@@ -466,8 +617,9 @@ __device__ __forceinline__ size_t fs_digit_addr(int i, int l, int b, int nkb) {
     return ((((size_t)(i / 16) * nkb + l / 8) * 2 + grp) * 64 + (size_t)lane_) * 16 + 4 * (2 * hi + el) + bi;
 }
 
-// the constant of one matrix row from its d entries: (0x80..80 * sum - bias sum) mod p as eight pairs [bias of the fold's columns + word]
-__device__ __forceinline__ void fs_row_constant(const FpParams<9> &P, const FsConsts &cs, const i128 *row, int d, uint32_t *dst16) {
+// the constant of one matrix row from its d entries: (0x80..80 * sum - bias sum) mod p as eight pairs [bias of the fold's columns + word].
+// kind (fs_slot): the bias sum is over the columns the row's accumulators cover -- 47, or the 39 + 39 of a merged row, or 39
+__device__ __forceinline__ void fs_row_constant(const FpParams<9> &P, const FsConsts &cs, const i128 *row, int d, uint32_t *dst16, int kind = 0) {
     constexpr int NL = 9, NW = 8;
     uint32_t s5[5] = {0, 0, 0, 0, 0};                   // the row sum in 160 bits two's complement
     for (int l = 0; l < d; l++) {
@@ -487,7 +639,7 @@ __device__ __forceinline__ void fs_row_constant(const FpParams<9> &P, const FsCo
     unpack<NL, NW>(fe, w8);
     if (negs) fp_neg(fe, fe, P);
 #pragma unroll
-    for (int k = 0; k < NL; k++) { k80[k] = cs.c80r[k]; bm[k] = cs.biasmod[k]; }
+    for (int k = 0; k < NL; k++) { k80[k] = cs.c80r[k]; bm[k] = kind == 0 ? cs.biasmod[k] : kind == 1 ? cs.biasmod_pm[k] : cs.biasmod_ps[k]; }
     mont_mul(prod, fe, k80, P);
     fp_sub(corr, prod, bm, P);
     uint32_t cw[NW];
@@ -508,7 +660,7 @@ __device__ __forceinline__ void fs_row_constant(const FpParams<9> &P, const FsCo
 // Second phase: a thread per entry writes its 16 balanced digits; a thread per row its constant; 9 d threads the T tables.
 __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9> &P, const uint32_t *__restrict__ inv, int n, const FsIdx &ix, int d, int nc, int n_coef,
                                               int flags, const FsConsts &cs, uint8_t *__restrict__ a8, uint32_t *__restrict__ crow, uint32_t *__restrict__ KT,
-                                              int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status) {
+                                              int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status, const FsPack &pk) {
     constexpr int NL = 9, NW = 8;
     const int n_out = n_coef + nc, nkb = (d + 7) / 8, n_rt = (n_out + 15) / 16;
     i128 *ent = reinterpret_cast<i128 *>(fb_lds);                       // [n_out][d]
@@ -522,7 +674,7 @@ __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9>
         const size_t img = (size_t)n_rt * nkb * 2 * 64 * 16;
         for (size_t i = tid; i < img / 16; i += 1024) reinterpret_cast<uint4 *>(a8)[i] = make_uint4(0, 0, 0, 0);
         for (int i = tid; i < n_rt * 16 * 8; i += 1024) { crow[2 * i] = 0x10100000u; crow[2 * i + 1] = 0x1010u; }
-        for (int i = tid; i < n_rt * 16; i += 1024) rowmode[i] = i < n_coef ? -(i + 1) : 0;
+        for (int i = tid; i < n_rt * 16; i += 1024) rowmode[i] = 0;      // (the coefficient rows' modes: behind the barriers, by slot)
         if (tid < d) z_dev[tid] = ix.z[tid];
     }
     if (do_z && tid < 64) {
@@ -594,19 +746,27 @@ __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9>
         const int i = e / d, l = e - i * d;
         i128 v = ent[e];
         const bool negv = v < 0;
-        int carry = 0;
+        int carry = 0, kind;
+        const int sl = fs_slot(pk, i, n_out, kind);
+        bool lost = false;
 #pragma unroll
         for (int b = 0; b < 16; b++) {
             int t = (int)((uint32_t)(v >> (8 * b)) & 0xffu) + carry;
             if (t > 127) { t -= 256; carry = 1; } else carry = 0;
-            a8[fs_digit_addr(i, l, b, nkb)] = (uint8_t)(int8_t)t;
+            // a packed tile: digit group 1 of a merged row on M row + 8 of the piece of group 0; a single-group row has none
+            if (kind == 0) a8[fs_digit_addr(sl, l, b, nkb)] = (uint8_t)(int8_t)t;
+            else if (b < 8 || kind == 1) a8[fs_digit_addr(sl + (b < 8 ? 0 : 8), l, b & 7, nkb)] = (uint8_t)(int8_t)t;
+            else lost |= t != 0;
         }
-        if (carry != (negv ? 1 : 0) && status) atomicOr(status, FS_OVERFLOW);
+        if ((lost || carry != (negv ? 1 : 0)) && status) atomicOr(status, FS_OVERFLOW);
     }
     // ---- row constants: (0x80..80 * sum_l M[i][l] - bias sum) mod p as eight pairs [bias of the fold's columns + word] --------
-    for (int i = tid + row_lo; i < row_hi; i += 1024) fs_row_constant(P, cs, ent + (size_t)i * d, d, crow + (size_t)i * 16);
-    if (do_zc)
-        for (int i = tid; i < nc; i += 1024) rowmode[n_coef + i] = (int32_t)ix.zc[i] + 1;
+    for (int i = tid + row_lo; i < row_hi; i += 1024) {
+        int kind;
+        const int sl = fs_slot(pk, i, n_out, kind);
+        fs_row_constant(P, cs, ent + (size_t)i * d, d, crow + (size_t)sl * 16, kind);
+        rowmode[sl] = i < n_coef ? -(i + 1) : (int32_t)ix.zc[i - n_coef] + 1;
+    }
     if (do_z) {
         // T[l][q] = 2^(29 q) / den_l, canonical digits: mont_mul(w_l R, 2^(29 q)) = w_l 2^(29 q)
         for (int e = tid; e < d * NL; e += 1024) {
@@ -659,9 +819,9 @@ __device__ __forceinline__ void fs_cand_body(uint8_t *fc_lds, const FpParams<9> 
 
 __global__ void __launch_bounds__(1024) k_fs_build(const FpParams<9> P, const uint32_t *__restrict__ inv, int n, const FsIdx ix, int d, int nc, int n_coef,
                                                    int flags, const FsConsts cs, uint8_t *__restrict__ a8, uint32_t *__restrict__ crow, uint32_t *__restrict__ KT,
-                                                   int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status) {
+                                                   int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status, const FsPack pk) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fs_b_lds[];
-    fs_build_body(fs_b_lds, P, inv, n, ix, d, nc, n_coef, flags, cs, a8, crow, KT, rowmode, z_dev, status);
+    fs_build_body(fs_b_lds, P, inv, n, ix, d, nc, n_coef, flags, cs, a8, crow, KT, rowmode, z_dev, status, pk);
 }
 
 __global__ void __launch_bounds__(1024) k_fs_cand(const FpParams<9> P, int n, const uint16_t *__restrict__ xs, const FsIdx ix, int d, const FsConsts cs,
@@ -678,7 +838,7 @@ __global__ void __launch_bounds__(1024) k_fs_build_z_cand(const FpParams<9> P, c
                                                           int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, uint8_t *__restrict__ cand, uint32_t *__restrict__ cand_crow,
                                                           int32_t *__restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fs_zc_lds[];
-    if (blockIdx.x == 0) fs_build_body(fs_zc_lds, P, inv, n, ix, d, nc, n_coef, FS_BUILD_Z, cs, a8, crow, KT, rowmode, z_dev, status);
+    if (blockIdx.x == 0) fs_build_body(fs_zc_lds, P, inv, n, ix, d, nc, n_coef, FS_BUILD_Z, cs, a8, crow, KT, rowmode, z_dev, status, FsPack{});
     else fs_cand_body(fs_zc_lds, P, n, xs, ix, d, cs, cand, cand_crow, status);
 }
 
@@ -713,6 +873,8 @@ int fs_layout(hb_ctx *ctx, const PointTable *pt, int d, int nc, int n_coef, FsLa
     if (bits_n > 124.5 || bits_p > 124.5) return HB_ERR_UNSUPPORTED;
     L->n = pt->n; L->d = d; L->nc = nc; L->n_coef = n_coef; L->n_out = n_coef + nc;
     L->nkb = (d + 7) / 8; L->n_rt = (L->n_out + 15) / 16;
+    L->pk_nm = L->pk_ns = 0;
+    memset(L->pk_single, 0, sizeof L->pk_single);
     if (fs_lds_bytes(L->n_rt, L->nkb) > FS_LDS_LIMIT) return HB_ERR_UNSUPPORTED;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     L->o_a8 = 0;
@@ -728,6 +890,39 @@ int fs_layout(hb_ctx *ctx, const PointTable *pt, int d, int nc, int n_coef, FsLa
         L->need = L->o_cand_crow + al((size_t)pt->n * 16 * 4);
     }
     return HB_OK;
+}
+
+// which coefficient rows of N have no digit above the eighth: small[m] = 1 iff every |coeff_m(A_j)| < 2^62, from the integers themselves
+// (A(X) = prod (X - x_zq), then the synthetic divisions: the arithmetic of fs_build_body's first wave; the layout's bound keeps it in 128 bits)
+static void fs_small_rows(const uint16_t *xz, int d, int n_coef, uint8_t *small) {
+    i128 Ac[FS_MAXD + 1];
+    for (int k = 0; k <= d; k++) Ac[k] = k == 0 ? 1 : 0;
+    for (int q = 0; q < d; q++)
+        for (int k = q + 1; k >= 0; k--) Ac[k] = (k > 0 ? Ac[k - 1] : (i128)0) - (i128)xz[q] * Ac[k];
+    for (int m = 0; m < n_coef; m++) small[m] = 1;
+    const i128 lim = (i128)1 << 62;
+    for (int j = 0; j < d; j++) {
+        i128 cur = 1;
+        for (int m = d - 1; m >= 0; m--) {
+            if (m < n_coef && (cur >= lim || cur <= -lim)) small[m] = 0;
+            if (m > 0) cur = Ac[m] + (i128)xz[j] * cur;
+        }
+    }
+}
+
+bool fs_pack(const PointTable *pt, const int32_t *z, FsLayout *L) {
+    L->pk_nm = L->pk_ns = 0;
+    memset(L->pk_single, 0, sizeof L->pk_single);
+    if (env_hook(ENV_NO_FUSED_PACK)) return false;
+    uint16_t xz[FS_MAXD];
+    uint8_t small[FS_MAXD];
+    for (int i = 0; i < L->d; i++) { if (z[i] < 0 || z[i] >= L->n) return false; xz[i] = pt->xs[z[i]]; }
+    fs_small_rows(xz, L->d, L->n_coef, small);
+    FsPack pk;
+    if (!fs_pack_decide(L->d, L->n_coef, L->nc, small, &pk)) return false;
+    L->pk_nm = pk.nm; L->pk_ns = pk.ns;
+    memcpy(L->pk_single, pk.single, sizeof pk.single);
+    return true;
 }
 
 // enqueue the build into `base` (L.need bytes): FS_BUILD_Z needs z, FS_BUILD_ZC both (the rows of P depend on z too)
@@ -753,9 +948,18 @@ int fs_build(hb_ctx *ctx, const PointTable *pt, const int32_t *z, const int32_t 
     FsConsts cs;
     memcpy(cs.c80r, sh->c80r, sizeof cs.c80r);
     memcpy(cs.biasmod, sh->biasmod, sizeof cs.biasmod);
+    memcpy(cs.biasmod_pm, sh->biasmod_pm, sizeof cs.biasmod_pm);
+    memcpy(cs.biasmod_ps, sh->biasmod_ps, sizeof cs.biasmod_ps);
+    FsPack pk;
+    memset(&pk, 0, sizeof pk);
+    if (L.pk_nm) {
+        if (flags != (FS_BUILD_Z | FS_BUILD_ZC)) return fail(ctx, HB_ERR_BAD_ARG, "fused decode: a packed image is built in one piece");
+        pk.nm = L.pk_nm; pk.ns = L.pk_ns;
+        memcpy(pk.single, L.pk_single, sizeof pk.single);
+    }
     const size_t lds = ((size_t)L.n_out * d + d + 1) * 16 + ((size_t)d * 9 + (size_t)d * 4 * 9) * 4;
     k_fs_build<<<1, 1024, lds, s>>>(ctx->pw, pt->inv, n, ix, d, nc, L.n_coef, flags, cs, base + L.o_a8, (uint32_t *)(base + L.o_crow), (uint32_t *)(base + L.o_kt),
-                                    (int32_t *)(base + L.o_mode), (int32_t *)(base + L.o_z), status_dev);
+                                    (int32_t *)(base + L.o_mode), (int32_t *)(base + L.o_z), status_dev, pk);
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -781,6 +985,8 @@ int fs_build_cand(hb_ctx *ctx, PointTable *pt, const int32_t *z, const FsLayout 
     FsConsts cs;
     memcpy(cs.c80r, sh->c80r, sizeof cs.c80r);
     memcpy(cs.biasmod, sh->biasmod, sizeof cs.biasmod);
+    memset(cs.biasmod_pm, 0, sizeof cs.biasmod_pm);       // (no packed tile in an image whose compared rows are picked)
+    memset(cs.biasmod_ps, 0, sizeof cs.biasmod_ps);
     if (with_z) {
         const size_t lds_b = ((size_t)L.n_out * L.d + L.d + 1) * 16 + ((size_t)L.d * 9 + (size_t)L.d * 4 * 9) * 4, lds_c = (size_t)pt->n * L.d * 16;
         k_fs_build_z_cand<<<2, 1024, std::max(lds_b, lds_c), s>>>(ctx->pw, pt->inv, pt->n, pt->xs_dev, ix, L.d, L.nc, L.n_coef, cs, base + L.o_a8, (uint32_t *)(base + L.o_crow),
@@ -794,12 +1000,20 @@ int fs_build_cand(hb_ctx *ctx, PointTable *pt, const int32_t *z, const FsLayout 
     return HB_OK;
 }
 
+static std::atomic<int> g_fs_last_pack{-1};       // k_mm8f's PK at the last fs_launch of the process (hb_debug_fs_last_pack)
+
 // The terms of the next unit dealt to the waves.  A wave's load in a unit: its passes (wave w takes pairs w, w + 8, ... of the 4 n_rt; a pass
 // over a ragged last row tile with at most 8 rows reduces two of the four outputs a lane holds) plus its terms; measured on config 3's R2
 // launch (scratch/fs_phase_timing.py) a pass is 9.5 k cycles of a wave's time and a term 3.6 k when two waves share the SIMD.  Each term goes
 // to the wave with the least load so far (ties: the higher wave -- the older waves 0..3 win the issue arbitration anyway).
-static FsSplit fs_split(int d, int n_rt, int n_out) {
-    constexpr int PASS = 95, RAGGED = 70, TERM = 36;
+//
+// A packed pass: by the phase ticks of a timing build (profiles/fs_pack.txt) 0.63 of a full pass with two reductions (R1: 60) and 0.78 with
+// three (R2: 74) -- but at those weights the deal is the unpacked one, and the waves with a packed pass wait longest at the unit barrier
+// (the ticks of a pass include what its SIMD partner issues meanwhile).  A sweep of the weight on the benchmark put both at 57 or below,
+// where the waves with a packed pass take a term more and those with two full passes (or a full pass and three terms) one less.
+static FsSplit fs_split(int d, int n_rt, int n_out, int pk_nm, int pk_ns) {
+    constexpr int PASS = 95, RAGGED = 70, TERM = 36, PACKED2 = 50, PACKED3 = 55;
+    const int packed = pk_ns ? PACKED3 : PACKED2;
     FsSplit sp;
     int load[FS_WAVES];
     const int n_pairs = FS_TPW * n_rt;
@@ -810,7 +1024,7 @@ static FsSplit fs_split(int d, int n_rt, int n_out) {
         for (int pidx = w; pidx < n_pairs; pidx += FS_WAVES) {
             const int tl = n_rt == 2 ? (pidx >> 1) : pidx / n_rt;
             const int rt = n_rt == 2 ? ((pidx ^ (pidx >> 2)) & 1) : pidx - tl * n_rt;
-            load[w] += (ragged && rt == n_rt - 1) ? RAGGED : PASS;
+            load[w] += (pk_nm && rt == n_rt - 1) ? packed : (ragged && rt == n_rt - 1) ? RAGGED : PASS;
         }
     }
     for (int l = 0; l < d; l++) {
@@ -833,6 +1047,7 @@ int fs_launch(hb_ctx *ctx, const FsLayout &L, const uint8_t *base, const uint32_
     FsPick pick;
     memset(&pick, 0, sizeof pick);
     if (pick_zc) {
+        if (L.pk_nm) return fail(ctx, HB_ERR_BAD_ARG, "fused decode: a packed image has no rows to pick");
         if (!L.o_cand) return fail(ctx, HB_ERR_BAD_ARG, "fused decode: no candidate store to pick from");
         pick.cand = (const uint4 *)(base + L.o_cand); pick.cand_crow = (const uint32_t *)(base + L.o_cand_crow);
         pick.n_coef = L.n_coef; pick.nc = L.nc;
@@ -846,19 +1061,21 @@ int fs_launch(hb_ctx *ctx, const FsLayout &L, const uint8_t *base, const uint32_
     if (blocks > n_units) blocks = n_units;
     blocks = mm8_trimmed_grid(n_units, blocks);          // (config 3: 249 of 256 -- seven CUs stay free for what other streams launch meanwhile)
     const size_t lds = fs_lds_bytes(L.n_rt, L.nkb);
-    const FsSplit split = fs_split(L.d, L.n_rt, L.n_out);
-#define FS_LAUNCH(NKB)                                                                                                                     \
+    const FsSplit split = fs_split(L.d, L.n_rt, L.n_out, L.pk_nm, L.pk_ns);
+    const int pack = !L.pk_nm ? 0 : L.pk_ns ? 2 : 1;       // (k_mm8f's PK)
+    g_fs_last_pack.store(pack);
+#define FS_LAUNCH(NKB, PK)                                                                                                                   \
     do {                                                                                                                                   \
         static std::atomic<unsigned long long> attr_done{0};   /* one bit per device: the attribute is per device */                                                                                                     \
-        if (!((attr_done.load() >> (ctx->device & 63)) & 1ull)) { HB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm8f<NKB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done.fetch_or(1ull << (ctx->device & 63)); } \
-        k_mm8f<NKB><<<dim3((unsigned)blocks), dim3(64 * FS_WAVES), lds, s>>>((const int4 *)(base + L.o_a8), (const uint32_t *)(base + L.o_crow), sh->fold_dev,        \
+        if (!((attr_done.load() >> (ctx->device & 63)) & 1ull)) { HB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm8f<NKB, PK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done.fetch_or(1ull << (ctx->device & 63)); } \
+        k_mm8f<NKB, PK><<<dim3((unsigned)blocks), dim3(64 * FS_WAVES), lds, s>>>((const int4 *)(base + L.o_a8), (const uint32_t *)(base + L.o_crow), sh->fold_dev,        \
             (const uint32_t *)(base + L.o_kt), ctx->psc, cols, cv.stride_c, cv.stride_l, (const int32_t *)(base + L.o_z), INT64_MAX, L.d, (const int32_t *)(base + L.o_mode), \
             out, ov.stride_c, ov.stride_l, out_count, mismatch_dev, first_bad_dev, bad_map_dev, L.n_out, L.n_rt, C, n_units, sh->bp, done, pick, split); \
     } while (0)
     switch (L.nkb) {
-        case 1: FS_LAUNCH(1); break;
-        case 2: FS_LAUNCH(2); break;
-        case 3: FS_LAUNCH(3); break;
+        case 1: if (pack == 1) FS_LAUNCH(1, 1); else if (pack == 2) FS_LAUNCH(1, 2); else FS_LAUNCH(1, 0); break;
+        case 2: if (pack == 1) FS_LAUNCH(2, 1); else if (pack == 2) FS_LAUNCH(2, 2); else FS_LAUNCH(2, 0); break;
+        case 3: if (pack == 1) FS_LAUNCH(3, 1); else if (pack == 2) FS_LAUNCH(3, 2); else FS_LAUNCH(3, 0); break;
         default: return fail(ctx, HB_ERR_UNSUPPORTED, "fused decode: more than 24 terms");
     }
 #undef FS_LAUNCH
@@ -867,6 +1084,36 @@ int fs_launch(hb_ctx *ctx, const FsLayout &L, const uint8_t *base, const uint32_
 }
 
 }  // namespace hb
+
+// the packing decision on its own (include/hbmpc_hip_debug.h): host arithmetic, no device
+extern "C" int hb_debug_fs_pack_rows(int d, int n_coef, int nc, const uint8_t *small, int32_t *out) {
+    hb::FsPack pk;
+    const bool ok = d >= 1 && d <= hb::FS_MAXD && n_coef >= 1 && n_coef <= d && nc >= 0 && nc <= hb::FS_MAXC && hb::fs_pack_decide(d, n_coef, nc, small, &pk);
+    if (!ok) memset(&pk, 0, sizeof pk);
+    out[0] = pk.nm; out[1] = pk.ns;
+    for (int k = 0; k < 8; k++) out[2 + k] = pk.single[k];
+    return ok ? 1 : 0;
+}
+extern "C" int hb_debug_fs_pack_points(const int32_t *xz, int d, int n_coef, int nc, int32_t *out, uint8_t *small_out) {
+    if (d < 1 || d > hb::FS_MAXD || n_coef < 1 || n_coef > d) return 0;
+    uint16_t x16[hb::FS_MAXD];
+    uint8_t small[hb::FS_MAXD];
+    for (int i = 0; i < d; i++) x16[i] = (uint16_t)xz[i];
+    hb::fs_small_rows(x16, d, n_coef, small);
+    if (small_out) memcpy(small_out, small, (size_t)n_coef);
+    return hb_debug_fs_pack_rows(d, n_coef, nc, small, out);
+}
+extern "C" int hb_debug_fs_last_pack(void) { return hb::g_fs_last_pack.load(); }
+extern "C" int hb_debug_fs_slot(int nm, int ns, const int32_t *single, int i, int n_out, int32_t *kind) {
+    hb::FsPack pk;
+    memset(&pk, 0, sizeof pk);
+    pk.nm = nm; pk.ns = ns;
+    for (int k = 0; k < 8 && k < ns; k++) pk.single[k] = (uint8_t)single[k];
+    int kd = 0;
+    const int sl = hb::fs_slot(pk, i, n_out, kd);
+    *kind = kd;
+    return sl;
+}
 
 #ifdef HB_MM8_TIMING
 extern "C" int hb_debug_fs_timing(unsigned long long *out, int count) {

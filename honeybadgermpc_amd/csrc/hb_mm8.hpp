@@ -15,6 +15,9 @@ constexpr int MM8_CW = 13;       // 32-bit words of the per-row constant / the c
 constexpr int MM8_FOLD_ROW = 272;   // bytes per row of the fold table (hb_mfma_wide.hip: sixteen lanes' 16 digits, then 16 zero bytes)
 constexpr int MM8_FOLD_Q = 8 * MM8_FOLD_ROW / 16;   // eight rows (one byte half), in uint4
 constexpr int MM8_BIAS = 5800000;   // >= 128 * sum |digit| >= |column| (checked per matrix when it is built), and 2 * BIAS * 257 < 2^32
+constexpr int MM8_NCP = 39;         // virtual columns of a packed pass (k_mm8f's narrow last row tile): one per window
+constexpr int MM8_BIAS_PACK = MM8_BIAS / 2;   // an accumulator of a packed pass contracts 8 digits a term, not 16: half the bias covers it, and the
+                                              // sum of the two accumulators of a merged column stays below 2 * BIAS like a column of an unpacked pass
 
 struct BarrettParams {
     uint32_t pneg[8]; // 2^256 - p, 32-bit words
@@ -39,6 +42,9 @@ struct Mm8Matrix {
 struct Mm8Shared {
     BarrettParams bp;
     uint32_t c80r[9], biasmod[9];
+    // biasmod of the rows of a packed pass: merged (BIAS_PACK in the 39 virtual columns of both digit groups, the second group's 2^64 up)
+    // and single-group (BIAS_PACK in 39 columns)
+    uint32_t biasmod_pm[9], biasmod_ps[9];
     uint8_t fold_host[MM8_FOLD_Q * 16];
     v4i *fold_dev;
 };

@@ -44,6 +44,18 @@ void hb_debug_mat_split(int mode);
  * PEEL = out[4], K = out[1] / 4).  Builds the handle's int8 image if no launch has yet -- exactly as the first launch would, the
  * environment hooks of that moment included -- and launches no mat-vec.  out: int32[8], host. */
 int hb_debug_matvec_route(hb_ctx *ctx, const hb_matrix *m, int64_t C, int32_t *out);
+/* The packed last row tile of the fused decode + validate kernel (csrc/hb_mfma_fused.hip, FsPack), host arithmetic only.
+ * hb_debug_fs_pack_rows: the decision for an image of n_coef coefficient rows (small[i] != 0: row i has no digit above the eighth) and nc
+ * compared rows over d terms; returns 1 if the last tile packs, out[0] = merged rows, out[1] = single-group rows, out[2..9] = the
+ * coefficient rows that are the single-group ones.  hb_debug_fs_pack_points: the same from the arrival points themselves (xz: d distinct
+ * integers below 2^16); small_out (n_coef bytes, may be null) receives the flags it derived.  hb_debug_fs_slot: the image slot
+ * (16 row tile + M row) of matrix row i under such a decision, *kind = 0 unpacked, 1 merged (digit group 1 on M row + 8), 2 single-group.
+ * hb_debug_fs_last_pack: the form of the last row tile at the process's last launch of the kernel -- 0 unpacked, 1 merged outputs alone,
+ * 2 merged outputs and single-group rows; -1 before any launch. */
+int hb_debug_fs_pack_rows(int d, int n_coef, int nc, const uint8_t *small, int32_t *out);
+int hb_debug_fs_pack_points(const int32_t *xz, int d, int n_coef, int nc, int32_t *out, uint8_t *small_out);
+int hb_debug_fs_slot(int nm, int ns, const int32_t *single, int i, int n_out, int32_t *kind);
+int hb_debug_fs_last_pack(void);
 
 
 #ifdef __cplusplus
