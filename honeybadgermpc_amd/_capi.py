@@ -224,6 +224,7 @@ DEBUG_SYMBOLS = {
     "hb_debug_fs_pack_points": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "hb_debug_fs_slot": (_i, [_i, _i, _vp, _i, _i, _vp]),
     "hb_debug_fs_last_pack": (_i, []),
+    "hb_debug_fs_last_mscale": (_i, []),
 }
 
 _lib = None

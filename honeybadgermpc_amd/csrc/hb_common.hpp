@@ -116,6 +116,7 @@ enum EnvHook {
     ENV_MM8W_TILE16,
     ENV_MM8_NO_SKIP,
     ENV_NO_EVAL_FEW,
+    ENV_NO_FUSED_MSCALE,
     ENV_NO_FUSED_PACK,
     ENV_NO_FUSED_SMALL,
     ENV_NO_FUSED_VALIDATE,
@@ -429,6 +430,8 @@ struct FsLayout {
     size_t o_a8, o_crow, o_kt, o_mode, o_z, o_cand, o_cand_crow, need;      // o_cand: the per-party candidate rows (0 when the point set is too large for them)
     int pk_nm, pk_ns;            // the packed last row tile (hb_mfma_fused.hip, FsPack): merged rows, single-group rows; 0, 0: none
     uint8_t pk_single[8];        // the coefficient rows that are its single-group rows
+    size_t o_ms;                 // the tables of the division by den on the matrix cores ([d + 1][1024] bytes of A operands, [d][32] constants)
+    int mscale;                  // the image has them and its launches use them (fs_mscale)
 };
 constexpr int FS_BUILD_Z = 1, FS_BUILD_ZC = 2;
 int fs_layout(hb_ctx *ctx, const PointTable *pt, int d, int nc, int n_coef, FsLayout *L);
@@ -437,6 +440,9 @@ int fs_build(hb_ctx *ctx, const PointTable *pt, const int32_t *z, const int32_t 
 // pass, and record it in the layout (before fs_build with both flags; launches that pick candidate rows keep the unpacked image).  Returns
 // whether it packs; HB_NO_FUSED_PACK=1 keeps every image unpacked.
 bool fs_pack(const PointTable *pt, const int32_t *z, FsLayout *L);
+// Decide whether the image's launches divide the received columns by den on the matrix cores (before fs_build with both flags, as
+// fs_pack; never for an image whose rows are picked).  HB_NO_FUSED_MSCALE=1, or tables that do not fit the LDS: the T_q multiplication.
+bool fs_mscale(FsLayout *L);
 // completion signal of a launch whose caller waits for the verdict: a device counter of finished workgroups, the pinned (device-visible)
 // record the last one fills in, the sequence number it writes last
 int fs_launch(hb_ctx *ctx, const FsLayout &L, const uint8_t *base, const uint32_t *cols, hb_view cv, uint32_t *out, hb_view ov, int64_t out_count,

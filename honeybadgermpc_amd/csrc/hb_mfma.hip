@@ -546,6 +546,12 @@ int mm8_shared(hb_ctx *ctx, const Mm8Shared **out, hipStream_t s) {
         Big r261(9, 0); r261[8] = 1u << 5;
         digits9(big_divmod(big_mul(c80, r261), p, nullptr), sh->c80r);
     }
+    {   // k_mm8f's division by den on the matrix cores (hb_mfma_fused.hip): mont_mul(w R, c) = w c, so both constants are plain residues
+        digits9(big_divmod(Big(8, 0x80808080u), p, nullptr), sh->ms_c80);
+        Big bt(10, 0);
+        for (int c = 0; c < 32; c++) { Big t(1, 1u << 20); big_add(bt, big_shl(t, 8 * c, 10)); }
+        digits9(big_divmod(bt, p, nullptr), sh->ms_bias);
+    }
     if (hipMalloc(&sh->fold_dev, sizeof sh->fold_host) != hipSuccess) { delete sh; return fail(ctx, HB_ERR_HIP, "mm8: hipMalloc(fold table)"); }
     if (int rc = upload_table(ctx, sh->fold_dev, sh->fold_host, sizeof sh->fold_host, s)) { (void)hipFree(sh->fold_dev); delete sh; return rc; }
     ctx->mm8_shared = sh;

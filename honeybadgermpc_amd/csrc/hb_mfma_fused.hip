@@ -111,8 +111,11 @@ constexpr int FS_CAND_MAXN = 128;               // parties a candidate store is 
 // ---------------------------------------------------------------------------------------------------------------------
 // LDS: row constants [n_rt * 16][16] | matrix digits [n_rt][NKB][2][64] x 16 B | two element buffers [4 tiles][NKB][2][2][64] x 16 B |
 // rowl[32] | maskl[16 n_rt] | fold table
-__host__ __device__ inline size_t fs_lds_bytes(int n_rt, int nkb) {
-    return ((size_t)n_rt * 64 + (size_t)n_rt * nkb * 2 * 64 + (size_t)2 * FS_TPW * nkb * 4 * 64 + MM8_FOLD_Q) * 16 + (size_t)(32 + 16 * n_rt) * 4;
+// | (ms_d > 0: the launch divides by den on the matrix cores) the tables of fs_ms_q(ms_d)
+__host__ __device__ inline int fs_ms_q(int d) { return (d + 1) * 64 + d * 8; }      // in uint4
+__host__ __device__ inline size_t fs_lds_bytes(int n_rt, int nkb, int ms_d = 0) {
+    return ((size_t)n_rt * 64 + (size_t)n_rt * nkb * 2 * 64 + (size_t)2 * FS_TPW * nkb * 4 * 64 + MM8_FOLD_Q + (ms_d ? fs_ms_q(ms_d) : 0)) * 16 +
+           (size_t)(32 + 16 * n_rt) * 4;
 }
 
 // The reduction of one output of lane (n, g) in k_mm8f, as TEXT (a lambda with this body costs the kernel registers it does not have: the
@@ -223,7 +226,8 @@ __host__ __device__ inline size_t fs_lds_bytes(int n_rt, int nkb) {
 // PK: the last row tile is a packed one (FsPack) -- 1: merged outputs alone (regs 0 and 1, each with its partner two regs up), 2: up to four
 // merged outputs (reg 0) and five to eight single-group rows (regs 1 and 3); the image's rows are then its 16 n_rt slots, and no row is
 // picked.  PK = 0 is the kernel as it was: what a decoder launches, and every image whose last tile does not pack.
-template <int NKB, int PK>
+// MSC: the received columns are divided by den on the matrix cores (the tables MS; fs_mscale) instead of by the T_q multiplication (KT)
+template <int NKB, int PK, bool MSC>
 __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restrict__ a8, const uint32_t *__restrict__ crowd, const v4i *__restrict__ foldg,
                                                           const uint32_t *__restrict__ KT, const PrescaleParams PP,
                                                           const uint32_t *__restrict__ in_pk, int64_t in_sc, int64_t in_sl, const int32_t *__restrict__ in_rows,
@@ -231,7 +235,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                                                           uint32_t *__restrict__ out_pk, int64_t out_sc, int64_t out_sl, int64_t out_count,
                                                           int32_t *__restrict__ mismatch, int32_t *__restrict__ first_bad, uint32_t *__restrict__ bad_map,
                                                           int n_out, int n_rt, int64_t n_chunks, int64_t n_units, BarrettParams bp, const FsDone done, const FsPick pick,
-                                                          const FsSplit split) {
+                                                          const FsSplit split, const v4i *__restrict__ MS) {
     constexpr bool PACKED = PK != 0;
     const int n_slots = PACKED ? 16 * n_rt : n_out;      // rows of the image (PACKED: n_out goes unused)
     constexpr int NT = 64 * FS_WAVES, NL = 9, NW = 8;
@@ -245,6 +249,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
     int32_t *rowl = reinterpret_cast<int32_t *>(xbuf + 2 * bufsz);
     int32_t *maskl = rowl + 32;
     v4i *foldl = reinterpret_cast<v4i *>(maskl + 16 * n_rt);
+    v4i *msl = foldl + MM8_FOLD_Q;                  // (MS: the tables of the division by den on the matrix cores, fs_ms_q(d) pieces)
 
 #ifdef HB_MM8_TIMING
     unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
@@ -296,8 +301,16 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         v4i img[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) img[k] = reinterpret_cast<const v4i *>(a8)[tid + k * NT < n_img ? tid + k * NT : 0];
+        // (MSC: four pieces a thread are the 1648 of d = 22)
+        const int n_ms = MSC ? fs_ms_q(d) : 0;
+        v4i msv[4];
+        if constexpr (MSC) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) msv[k] = MS[tid + k * NT < n_ms ? tid + k * NT : 0];
+        }
         // (the words are wanted HERE: hipcc otherwise sinks each load into the branch of its write, one wait per load again)
         asm volatile("" : "+v"(rw), "+v"(mk), "+v"(cr), "+v"(fo), "+v"(img[0]), "+v"(img[1]), "+v"(img[2]));
+        if constexpr (MSC) asm volatile("" : "+v"(msv[0]), "+v"(msv[1]), "+v"(msv[2]), "+v"(msv[3]));
         if (tid < 32) rowl[tid] = rw;
         if (tid < n_mask) maskl[tid] = tid < n_slots ? mk : 0;
         if (tid < n_crow) reinterpret_cast<v4i *>(fs_lds)[tid] = cr;
@@ -305,10 +318,17 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 #pragma unroll
         for (int k = 0; k < 3; k++)
             if (tid + k * NT < n_img) reinterpret_cast<v4i *>(abuf)[tid + k * NT] = img[k];
+        if constexpr (MSC) {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (tid + k * NT < n_ms) msl[tid + k * NT] = msv[k];
+        }
         // (what a larger launch has beyond one round)
         for (int i = tid + NT; i < n_mask; i += NT) maskl[i] = i < n_slots ? rowmode[i] : 0;
         for (int i = tid + NT; i < n_crow; i += NT) fs_lds[i] = reinterpret_cast<const uint4 *>(crowd)[i];
         for (int i = tid + 3 * NT; i < n_img; i += NT) abuf[i] = a8[i];
+        if constexpr (MSC)
+            for (int i = tid + 4 * NT; i < n_ms; i += NT) msl[i] = MS[i];
     }
     // the slots [buffer][tile][half][column] of a padding term, 256 in all: no scaling task ever writes them, and they are all that is
     // zeroed -- every other slot is written by the unit's scaling tasks before a pass reads it
@@ -321,6 +341,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
     const int n_pairs = FS_TPW * n_rt;
     const uint32_t my_terms = (uint32_t)__builtin_amdgcn_readfirstlane((int)split.terms[wave]);
 
+    uint32_t ms64k = 1u << 16;                   // opaque: a word of the matrix-core division is one v_mad_u64_u32 over two shifted adds
+    if constexpr (MSC) asm volatile("" : "+s"(ms64k));
     // T_q of a task's term is wave-uniform (scalar loads).  first: the prologue's call -- its first term's words are already in registers
     // (x_first), and rowl is not in LDS yet
     auto scale_unit = [&](auto first, int64_t unit, uint4 *dst, uint32_t terms) {
@@ -346,38 +368,79 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
             uint32_t xn[NW];
             bool okn = false;
             fetch(ln < d ? ln : l, xn, okn);
-            const uint32_t *__restrict__ T = KT + (size_t)l * (NL * NL);
-            uint32_t xd[NL];
-            unpack<NL, NW>(xd, xw);
-            uint64_t col[NL + 1];
-#pragma unroll
-            for (int j = 0; j <= NL; j++) col[j] = 0;
-#pragma unroll
-            for (int q = 0; q < NL; q++)
-#pragma unroll
-                for (int j = 0; j < NL; j++) col[j] += (uint64_t)xd[q] * T[q * NL + j];
-            uint32_t v[NL + 1];
-#pragma unroll
-            for (int k = 0; k < NL; k++) { v[k] = (uint32_t)col[k] & DMASK; col[k + 1] += col[k] >> LB; }
-            v[NL] = (uint32_t)col[NL];
-            const uint64_t mid = (uint64_t)v[9] * PP.m0 + (uint64_t)v[8] * PP.m1 + (((uint64_t)v[8] * PP.m0) >> LB);
-            const uint64_t qh = (uint64_t)v[9] * PP.m1 + (mid >> LB);
-            const uint32_t q0 = (uint32_t)qh & DMASK, q1 = (uint32_t)(qh >> LB);
-            uint64_t dc[NL];
-#pragma unroll
-            for (int k = 0; k < NL; k++) {
-                dc[k] = v[k] + (uint64_t)q0 * PP.pbar[k];
-                if (k > 0) dc[k] += (uint64_t)q1 * PP.pbar[k - 1];
-            }
-            uint32_t r[NL];
-#pragma unroll
-            for (int k = 0; k < NL; k++) {
-                r[k] = (uint32_t)dc[k] & DMASK;
-                if (k < NL - 1) dc[k + 1] += dc[k] >> LB;
-            }
             uint32_t w[NW];
-            pack<NL, NW>(w, r);
-            if (PP.pneg[NW - 1] >> 31) {
+            bool over;                  // bit 256 of the representative r < 2p that w holds the low 256 bits of
+            if constexpr (MSC) {
+                // ---- on the matrix cores: x / den_l = sum_b x_b U_l[b] over the element's 32 bytes, U_l[b] = 256^b / den_l as 32 balanced digits.
+                // A lane's 16 bytes are its own K-block of the B operand; the A operand is block-diagonal (lane (m, m / 4) holds the digits of
+                // column 4 eb + (m & 3), every other lane zeros), so reg r of the accumulator is column 4 eb + r of the lane's OWN element; the
+                // second half of the bytes is chained on the same accumulator.  The C operand is 2^20 + the bytes of the term's constant
+                // (128 sum_b U_l[b] - the biases, mod p): every column arrives positive and below 2^21, a word is two shifted adds and one
+                // multiply-add, and the quotient is FS_REDUCE's.  tests/fs_mscale_model.py has the bounds.
+                //
+                // The first unit's tasks run before the tables are in LDS: they read the same operands from the tables in global memory
+                // (a lane of the diagonal its row, the others the block of zeros: five addresses a load).
+                const v4i *tab;
+                if constexpr (FIRST) tab = MS; else tab = msl;
+                const v4i *al = tab + (g == (n >> 2) ? l * 64 + (n & 3) : d * 64);
+                const v4i *cl = tab + (d + 1) * 64 + l * 8;
+                const v4i b0 = v4i{(int)(xw[0] ^ 0x80808080u), (int)(xw[1] ^ 0x80808080u), (int)(xw[2] ^ 0x80808080u), (int)(xw[3] ^ 0x80808080u)};
+                const v4i b1 = v4i{(int)(xw[4] ^ 0x80808080u), (int)(xw[5] ^ 0x80808080u), (int)(xw[6] ^ 0x80808080u), (int)(xw[7] ^ 0x80808080u)};
+                v4i mc[8];
+#pragma unroll
+                for (int eb = 0; eb < 8; eb++) mc[eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[eb * 4], b0, cl[eb], 0, 0, 0);
+#pragma unroll
+                for (int eb = 0; eb < 8; eb++) mc[eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[32 + eb * 4], b1, mc[eb], 0, 0, 0);
+                uint64_t mw[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const uint32_t lo = (uint32_t)mc[k][0] + ((uint32_t)mc[k][1] << 8), hi = (uint32_t)mc[k][2] + ((uint32_t)mc[k][3] << 8);
+                    mw[k] = (uint64_t)hi * ms64k + lo;
+                }
+                const uint64_t tq = mw[7] + (mw[6] >> 32);
+                const uint32_t mq = (uint32_t)(((uint64_t)(uint32_t)(tq >> 16) * bp.mu) >> 46);
+#pragma unroll
+                for (int k = 0; k < 8; k++) mw[k] += (uint64_t)mq * bp.pneg[k];
+                unsigned cyw = 0;
+                w[0] = (uint32_t)mw[0];
+#pragma unroll
+                for (int k = 1; k < 8; k++) w[k] = __builtin_addc((uint32_t)mw[k], (uint32_t)(mw[k - 1] >> 32), cyw, &cyw);
+                over = (uint32_t)(mw[7] >> 32) + cyw != mq;
+            } else {
+                const uint32_t *__restrict__ T = KT + (size_t)l * (NL * NL);
+                uint32_t xd[NL];
+                unpack<NL, NW>(xd, xw);
+                uint64_t col[NL + 1];
+#pragma unroll
+                for (int j = 0; j <= NL; j++) col[j] = 0;
+#pragma unroll
+                for (int q = 0; q < NL; q++)
+#pragma unroll
+                    for (int j = 0; j < NL; j++) col[j] += (uint64_t)xd[q] * T[q * NL + j];
+                uint32_t v[NL + 1];
+#pragma unroll
+                for (int k = 0; k < NL; k++) { v[k] = (uint32_t)col[k] & DMASK; col[k + 1] += col[k] >> LB; }
+                v[NL] = (uint32_t)col[NL];
+                const uint64_t mid = (uint64_t)v[9] * PP.m0 + (uint64_t)v[8] * PP.m1 + (((uint64_t)v[8] * PP.m0) >> LB);
+                const uint64_t qh = (uint64_t)v[9] * PP.m1 + (mid >> LB);
+                const uint32_t q0 = (uint32_t)qh & DMASK, q1 = (uint32_t)(qh >> LB);
+                uint64_t dc[NL];
+#pragma unroll
+                for (int k = 0; k < NL; k++) {
+                    dc[k] = v[k] + (uint64_t)q0 * PP.pbar[k];
+                    if (k > 0) dc[k] += (uint64_t)q1 * PP.pbar[k - 1];
+                }
+                uint32_t r[NL];
+#pragma unroll
+                for (int k = 0; k < NL; k++) {
+                    r[k] = (uint32_t)dc[k] & DMASK;
+                    if (k < NL - 1) dc[k + 1] += dc[k] >> LB;
+                }
+                pack<NL, NW>(w, r);
+                over = (r[NL - 1] >> 24) != 0;
+            }
+            const uint32_t *pneg = MSC ? bp.pneg : PP.pneg;       // (the same words: whichever the instance holds already)
+            if (pneg[NW - 1] >> 31) {
                 // p < 2^255: r < 2p < 2^256 is a 256-bit representative as it is, and the GEMM takes any
 #pragma unroll
                 for (int k = 0; k < NW; k++) w[k] = ok ? w[k] : 0u;
@@ -386,8 +449,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                 uint32_t u[NW];
                 unsigned cy = 0;
 #pragma unroll
-                for (int k = 0; k < NW; k++) u[k] = __builtin_addc(w[k], PP.pneg[k], cy, &cy);
-                const bool take = cy || (r[NL - 1] >> 24);
+                for (int k = 0; k < NW; k++) u[k] = __builtin_addc(w[k], pneg[k], cy, &cy);
+                const bool take = cy || over;
 #pragma unroll
                 for (int k = 0; k < NW; k++) w[k] = ok ? (take ? u[k] : w[k]) : 0u;
             }
@@ -607,7 +670,11 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __int128 i128;
 
-struct FsConsts { uint32_t c80r[9], biasmod[9], biasmod_pm[9], biasmod_ps[9]; };     // (biasmod_p*: the rows of a packed tile, hb_mm8.hpp)
+struct FsConsts {
+    uint32_t c80r[9], biasmod[9], biasmod_pm[9], biasmod_ps[9];     // (biasmod_p*: the rows of a packed tile, hb_mm8.hpp)
+    uint32_t ms_c80[9], ms_bias[9], pneg[8];                        // (the division by den on the matrix cores: fs_build_mscale)
+};
+constexpr int FS_MS_BIAS = 1 << 20;               // what a column of the division by den starts from: above 32 * 128 * 128, its largest sum
 constexpr int32_t FS_OVERFLOW = 0x40000000;       // OR-ed into the status word if an entry does not fit (the host's bound rules it out)
 
 // byte address of digit b (< 16) of entry (row i, term l) in the image (the layout of mm8_from_fast, hb_mfma.hip)
@@ -660,7 +727,8 @@ __device__ __forceinline__ void fs_row_constant(const FpParams<9> &P, const FsCo
 // Second phase: a thread per entry writes its 16 balanced digits; a thread per row its constant; 9 d threads the T tables.
 __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9> &P, const uint32_t *__restrict__ inv, int n, const FsIdx &ix, int d, int nc, int n_coef,
                                               int flags, const FsConsts &cs, uint8_t *__restrict__ a8, uint32_t *__restrict__ crow, uint32_t *__restrict__ KT,
-                                              int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status, const FsPack &pk) {
+                                              int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status, const FsPack &pk,
+                                              uint8_t *__restrict__ ms = nullptr) {
     constexpr int NL = 9, NW = 8;
     const int n_out = n_coef + nc, nkb = (d + 7) / 8, n_rt = (n_out + 15) / 16;
     i128 *ent = reinterpret_cast<i128 *>(fb_lds);                       // [n_out][d]
@@ -779,6 +847,49 @@ __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9>
             for (int k = 0; k < NL; k++) KT[((size_t)l * NL + q) * NL + k] = tq[k];
         }
     }
+    if (do_z && ms) {
+        // The division by den on the matrix cores (k_mm8f, MS): per term the A operands [half][column quad][column & 3] x 16 bytes -- byte k
+        // of column c in half h is digit c of U_l[16 h + k], U_l[b] = 256^b / den_l as 32 balanced digits (of U or of U - p: one of the two
+        // fits) -- then a block of zeros (what the lanes off the diagonal read), then per term its 32 accumulator constants
+        // 2^20 + byte c of (0x80..80 / den_l - sum_c 2^(20 + 8 c)) mod p
+        for (int i = tid; i < 64; i += 1024) reinterpret_cast<uint4 *>(ms)[d * 64 + i] = make_uint4(0, 0, 0, 0);
+        for (int e = tid; e < d * 32; e += 1024) {
+            const int l = e >> 5, b = e & 31;
+            uint32_t w[NL], two[NL], u[NL], uw[NW];
+#pragma unroll
+            for (int k = 0; k < NL; k++) { w[k] = wj[(size_t)l * NL + k]; two[k] = (k == (8 * b) / LB) ? 1u << ((8 * b) % LB) : 0u; }
+            mont_mul(u, w, two, P);
+            pack<NL, NW>(uw, u);
+            int8_t dg[32];
+            int carry = 0;
+            for (int pass = 0; pass < 2; pass++) {
+                // (second pass: U - p as the 256 bits of U + 2^256 - p, whose digits end in a carry)
+                carry = 0;
+                for (int c = 0; c < 32; c++) {
+                    int t = (int)((uw[c >> 2] >> (8 * (c & 3))) & 0xffu) + carry;
+                    if (t > 127) { t -= 256; carry = 1; } else carry = 0;
+                    dg[c] = (int8_t)t;
+                }
+                if (carry == pass) break;
+                if (pass == 0) {
+                    unsigned cy = 0;
+#pragma unroll
+                    for (int k = 0; k < NW; k++) uw[k] = __builtin_addc(uw[k], cs.pneg[k], cy, &cy);
+                } else if (status) atomicOr(status, FS_OVERFLOW);
+            }
+            for (int c = 0; c < 32; c++) ms[(size_t)(((l * 2 + (b >> 4)) * 8 + (c >> 2)) * 4 + (c & 3)) * 16 + (b & 15)] = (uint8_t)dg[c];
+        }
+        for (int l = tid; l < d; l += 1024) {
+            uint32_t w[NL], c80[NL], bm[NL], prod[NL], kk[NL], kw[NW];
+#pragma unroll
+            for (int k = 0; k < NL; k++) { w[k] = wj[(size_t)l * NL + k]; c80[k] = cs.ms_c80[k]; bm[k] = cs.ms_bias[k]; }
+            mont_mul(prod, w, c80, P);
+            fp_sub(kk, prod, bm, P);
+            pack<NL, NW>(kw, kk);
+            int32_t *ci = reinterpret_cast<int32_t *>(ms + (size_t)(d + 1) * 1024) + l * 32;
+            for (int c = 0; c < 32; c++) ci[c] = FS_MS_BIAS + (int32_t)((kw[c >> 2] >> (8 * (c & 3))) & 0xffu);
+        }
+    }
 }
 
 // The rows of the compared senders before anybody knows who they will be: P[i][j] = prod_{q != j} (x_i - x_zq) for EVERY party i, its 16
@@ -819,9 +930,10 @@ __device__ __forceinline__ void fs_cand_body(uint8_t *fc_lds, const FpParams<9> 
 
 __global__ void __launch_bounds__(1024) k_fs_build(const FpParams<9> P, const uint32_t *__restrict__ inv, int n, const FsIdx ix, int d, int nc, int n_coef,
                                                    int flags, const FsConsts cs, uint8_t *__restrict__ a8, uint32_t *__restrict__ crow, uint32_t *__restrict__ KT,
-                                                   int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status, const FsPack pk) {
+                                                   int32_t *__restrict__ rowmode, int32_t *__restrict__ z_dev, int32_t *__restrict__ status, const FsPack pk,
+                                                   uint8_t *__restrict__ ms) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fs_b_lds[];
-    fs_build_body(fs_b_lds, P, inv, n, ix, d, nc, n_coef, flags, cs, a8, crow, KT, rowmode, z_dev, status, pk);
+    fs_build_body(fs_b_lds, P, inv, n, ix, d, nc, n_coef, flags, cs, a8, crow, KT, rowmode, z_dev, status, pk, ms);
 }
 
 __global__ void __launch_bounds__(1024) k_fs_cand(const FpParams<9> P, int n, const uint16_t *__restrict__ xs, const FsIdx ix, int d, const FsConsts cs,
@@ -882,7 +994,9 @@ int fs_layout(hb_ctx *ctx, const PointTable *pt, int d, int nc, int n_coef, FsLa
     L->o_kt = L->o_crow + al((size_t)L->n_rt * 16 * 16 * 4);
     L->o_mode = L->o_kt + al((size_t)d * 81 * 4);
     L->o_z = L->o_mode + al((size_t)L->n_rt * 16 * 4);
-    L->need = L->o_z + al((size_t)FS_MAXD * 4);
+    L->o_ms = L->o_z + al((size_t)FS_MAXD * 4);
+    L->need = L->o_ms + al((size_t)fs_ms_q(d) * 16);
+    L->mscale = 0;
     L->o_cand = L->o_cand_crow = 0;
     if (pt->n <= FS_CAND_MAXN && nc > 0) {
         L->o_cand = L->need;
@@ -925,6 +1039,13 @@ bool fs_pack(const PointTable *pt, const int32_t *z, FsLayout *L) {
     return true;
 }
 
+// An image that is built in one piece (a plan's, the one-shot check's) divides the received columns by den on the matrix cores, where the
+// tables fit the LDS beside the rest; HB_NO_FUSED_MSCALE=1 keeps the T_q multiplication everywhere (what a decoder's launches do).
+bool fs_mscale(FsLayout *L) {
+    L->mscale = !env_hook(ENV_NO_FUSED_MSCALE) && fs_lds_bytes(L->n_rt, L->nkb, L->d) <= FS_LDS_LIMIT;
+    return L->mscale != 0;
+}
+
 // enqueue the build into `base` (L.need bytes): FS_BUILD_Z needs z, FS_BUILD_ZC both (the rows of P depend on z too)
 int fs_build(hb_ctx *ctx, const PointTable *pt, const int32_t *z, const int32_t *zc, const FsLayout &L, uint8_t *base, int flags, int32_t *status_dev, hipStream_t s) {
     const int n = L.n, d = L.d, nc = L.nc;
@@ -950,6 +1071,10 @@ int fs_build(hb_ctx *ctx, const PointTable *pt, const int32_t *z, const int32_t 
     memcpy(cs.biasmod, sh->biasmod, sizeof cs.biasmod);
     memcpy(cs.biasmod_pm, sh->biasmod_pm, sizeof cs.biasmod_pm);
     memcpy(cs.biasmod_ps, sh->biasmod_ps, sizeof cs.biasmod_ps);
+    memcpy(cs.ms_c80, sh->ms_c80, sizeof cs.ms_c80);
+    memcpy(cs.ms_bias, sh->ms_bias, sizeof cs.ms_bias);
+    memcpy(cs.pneg, sh->bp.pneg, sizeof cs.pneg);
+    if (L.mscale && flags != (FS_BUILD_Z | FS_BUILD_ZC)) return fail(ctx, HB_ERR_BAD_ARG, "fused decode: the matrix-core division's tables are built with the whole image");
     FsPack pk;
     memset(&pk, 0, sizeof pk);
     if (L.pk_nm) {
@@ -959,7 +1084,7 @@ int fs_build(hb_ctx *ctx, const PointTable *pt, const int32_t *z, const int32_t 
     }
     const size_t lds = ((size_t)L.n_out * d + d + 1) * 16 + ((size_t)d * 9 + (size_t)d * 4 * 9) * 4;
     k_fs_build<<<1, 1024, lds, s>>>(ctx->pw, pt->inv, n, ix, d, nc, L.n_coef, flags, cs, base + L.o_a8, (uint32_t *)(base + L.o_crow), (uint32_t *)(base + L.o_kt),
-                                    (int32_t *)(base + L.o_mode), (int32_t *)(base + L.o_z), status_dev, pk);
+                                    (int32_t *)(base + L.o_mode), (int32_t *)(base + L.o_z), status_dev, pk, L.mscale ? base + L.o_ms : nullptr);
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -985,8 +1110,11 @@ int fs_build_cand(hb_ctx *ctx, PointTable *pt, const int32_t *z, const FsLayout 
     FsConsts cs;
     memcpy(cs.c80r, sh->c80r, sizeof cs.c80r);
     memcpy(cs.biasmod, sh->biasmod, sizeof cs.biasmod);
-    memset(cs.biasmod_pm, 0, sizeof cs.biasmod_pm);       // (no packed tile in an image whose compared rows are picked)
+    memset(cs.biasmod_pm, 0, sizeof cs.biasmod_pm);       // (no packed tile in an image whose compared rows are picked, and no matrix-core division)
     memset(cs.biasmod_ps, 0, sizeof cs.biasmod_ps);
+    memset(cs.ms_c80, 0, sizeof cs.ms_c80);
+    memset(cs.ms_bias, 0, sizeof cs.ms_bias);
+    memset(cs.pneg, 0, sizeof cs.pneg);
     if (with_z) {
         const size_t lds_b = ((size_t)L.n_out * L.d + L.d + 1) * 16 + ((size_t)L.d * 9 + (size_t)L.d * 4 * 9) * 4, lds_c = (size_t)pt->n * L.d * 16;
         k_fs_build_z_cand<<<2, 1024, std::max(lds_b, lds_c), s>>>(ctx->pw, pt->inv, pt->n, pt->xs_dev, ix, L.d, L.nc, L.n_coef, cs, base + L.o_a8, (uint32_t *)(base + L.o_crow),
@@ -1001,6 +1129,7 @@ int fs_build_cand(hb_ctx *ctx, PointTable *pt, const int32_t *z, const FsLayout 
 }
 
 static std::atomic<int> g_fs_last_pack{-1};       // k_mm8f's PK at the last fs_launch of the process (hb_debug_fs_last_pack)
+static std::atomic<int> g_fs_last_mscale{-1};     // and whether it divided by den on the matrix cores (hb_debug_fs_last_mscale)
 
 // The terms of the next unit dealt to the waves.  A wave's load in a unit: its passes (wave w takes pairs w, w + 8, ... of the 4 n_rt; a pass
 // over a ragged last row tile with at most 8 rows reduces two of the four outputs a lane holds) plus its terms; measured on config 3's R2
@@ -1011,8 +1140,12 @@ static std::atomic<int> g_fs_last_pack{-1};       // k_mm8f's PK at the last fs_
 // three (R2: 74) -- but at those weights the deal is the unpacked one, and the waves with a packed pass wait longest at the unit barrier
 // (the ticks of a pass include what its SIMD partner issues meanwhile).  A sweep of the weight on the benchmark put both at 57 or below,
 // where the waves with a packed pass take a term more and those with two full passes (or a full pass and three terms) one less.
-static FsSplit fs_split(int d, int n_rt, int n_out, int pk_nm, int pk_ns) {
-    constexpr int PASS = 95, RAGGED = 70, TERM = 36, PACKED2 = 50, PACKED3 = 55;
+//
+// A term divided on the matrix cores (mscale): 2.4 k ticks against the multiplication's 3.6 k in the same waves of a timing build
+// (profiles/fs_mscale.txt: R2 wave 5, ten tasks, 36.0 k -> 23.7 k), so 24.  The benchmark does not tell 12 .. 36 apart (same file).
+static FsSplit fs_split(int d, int n_rt, int n_out, int pk_nm, int pk_ns, bool mscale) {
+    constexpr int PASS = 95, RAGGED = 70, PACKED2 = 50, PACKED3 = 55;
+    const int TERM = mscale ? 24 : 36;
     const int packed = pk_ns ? PACKED3 : PACKED2;
     FsSplit sp;
     int load[FS_WAVES];
@@ -1047,7 +1180,7 @@ int fs_launch(hb_ctx *ctx, const FsLayout &L, const uint8_t *base, const uint32_
     FsPick pick;
     memset(&pick, 0, sizeof pick);
     if (pick_zc) {
-        if (L.pk_nm) return fail(ctx, HB_ERR_BAD_ARG, "fused decode: a packed image has no rows to pick");
+        if (L.pk_nm || L.mscale) return fail(ctx, HB_ERR_BAD_ARG, "fused decode: an image built in one piece has no rows to pick");
         if (!L.o_cand) return fail(ctx, HB_ERR_BAD_ARG, "fused decode: no candidate store to pick from");
         pick.cand = (const uint4 *)(base + L.o_cand); pick.cand_crow = (const uint32_t *)(base + L.o_cand_crow);
         pick.n_coef = L.n_coef; pick.nc = L.nc;
@@ -1060,17 +1193,20 @@ int fs_launch(hb_ctx *ctx, const FsLayout &L, const uint8_t *base, const uint32_
     int64_t blocks = fs_num_cus();
     if (blocks > n_units) blocks = n_units;
     blocks = mm8_trimmed_grid(n_units, blocks);          // (config 3: 249 of 256 -- seven CUs stay free for what other streams launch meanwhile)
-    const size_t lds = fs_lds_bytes(L.n_rt, L.nkb);
-    const FsSplit split = fs_split(L.d, L.n_rt, L.n_out, L.pk_nm, L.pk_ns);
+    const size_t lds = fs_lds_bytes(L.n_rt, L.nkb, L.mscale ? L.d : 0);
+    const FsSplit split = fs_split(L.d, L.n_rt, L.n_out, L.pk_nm, L.pk_ns, L.mscale != 0);
     const int pack = !L.pk_nm ? 0 : L.pk_ns ? 2 : 1;       // (k_mm8f's PK)
     g_fs_last_pack.store(pack);
-#define FS_LAUNCH(NKB, PK)                                                                                                                   \
+    g_fs_last_mscale.store(L.mscale ? 1 : 0);
+#define FS_LAUNCH(NKB, PK) do { if (L.mscale) FS_LAUNCH_(NKB, PK, true); else FS_LAUNCH_(NKB, PK, false); } while (0)
+#define FS_LAUNCH_(NKB, PK, MSC)                                                                                                                   \
     do {                                                                                                                                   \
         static std::atomic<unsigned long long> attr_done{0};   /* one bit per device: the attribute is per device */                                                                                                     \
-        if (!((attr_done.load() >> (ctx->device & 63)) & 1ull)) { HB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm8f<NKB, PK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done.fetch_or(1ull << (ctx->device & 63)); } \
-        k_mm8f<NKB, PK><<<dim3((unsigned)blocks), dim3(64 * FS_WAVES), lds, s>>>((const int4 *)(base + L.o_a8), (const uint32_t *)(base + L.o_crow), sh->fold_dev,        \
+        if (!((attr_done.load() >> (ctx->device & 63)) & 1ull)) { HB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm8f<NKB, PK, MSC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done.fetch_or(1ull << (ctx->device & 63)); } \
+        k_mm8f<NKB, PK, MSC><<<dim3((unsigned)blocks), dim3(64 * FS_WAVES), lds, s>>>((const int4 *)(base + L.o_a8), (const uint32_t *)(base + L.o_crow), sh->fold_dev,        \
             (const uint32_t *)(base + L.o_kt), ctx->psc, cols, cv.stride_c, cv.stride_l, (const int32_t *)(base + L.o_z), INT64_MAX, L.d, (const int32_t *)(base + L.o_mode), \
-            out, ov.stride_c, ov.stride_l, out_count, mismatch_dev, first_bad_dev, bad_map_dev, L.n_out, L.n_rt, C, n_units, sh->bp, done, pick, split); \
+            out, ov.stride_c, ov.stride_l, out_count, mismatch_dev, first_bad_dev, bad_map_dev, L.n_out, L.n_rt, C, n_units, sh->bp, done, pick, split, \
+            L.mscale ? (const v4i *)(base + L.o_ms) : nullptr); \
     } while (0)
     switch (L.nkb) {
         case 1: if (pack == 1) FS_LAUNCH(1, 1); else if (pack == 2) FS_LAUNCH(1, 2); else FS_LAUNCH(1, 0); break;
@@ -1079,6 +1215,7 @@ int fs_launch(hb_ctx *ctx, const FsLayout &L, const uint8_t *base, const uint32_
         default: return fail(ctx, HB_ERR_UNSUPPORTED, "fused decode: more than 24 terms");
     }
 #undef FS_LAUNCH
+#undef FS_LAUNCH_
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
@@ -1104,6 +1241,7 @@ extern "C" int hb_debug_fs_pack_points(const int32_t *xz, int d, int n_coef, int
     return hb_debug_fs_pack_rows(d, n_coef, nc, small, out);
 }
 extern "C" int hb_debug_fs_last_pack(void) { return hb::g_fs_last_pack.load(); }
+extern "C" int hb_debug_fs_last_mscale(void) { return hb::g_fs_last_mscale.load(); }
 extern "C" int hb_debug_fs_slot(int nm, int ns, const int32_t *single, int i, int n_out, int32_t *kind) {
     hb::FsPack pk;
     memset(&pk, 0, sizeof pk);

@@ -45,6 +45,8 @@ struct Mm8Shared {
     // biasmod of the rows of a packed pass: merged (BIAS_PACK in the 39 virtual columns of both digit groups, the second group's 2^64 up)
     // and single-group (BIAS_PACK in 39 columns)
     uint32_t biasmod_pm[9], biasmod_ps[9];
+    // k_mm8f's division by den on the matrix cores: 0x80..80 (32 bytes) mod p and sum_c 2^(20 + 8 c) mod p, c < 32, as plain digits
+    uint32_t ms_c80[9], ms_bias[9];
     uint8_t fold_host[MM8_FOLD_Q * 16];
     v4i *fold_dev;
 };

@@ -111,7 +111,7 @@ static void build_fused_small(hb_open_plan *pl, hipStream_t s) {
         int qrc = HB_OK;
         if (hipMalloc(&b1, a.need) != hipSuccess || hipMalloc(&b2, b.need) != hipSuccess) qrc = HB_ERR_HIP;
         const int32_t *zcp = pl->n_check > 0 ? pl->zc.data() : pl->z.data();
-        if (!qrc) { (void)fs_pack(pt, pl->z.data(), &a); (void)fs_pack(pt, pl->z.data(), &b); }
+        if (!qrc) { (void)fs_pack(pt, pl->z.data(), &a); (void)fs_pack(pt, pl->z.data(), &b); (void)fs_mscale(&a); (void)fs_mscale(&b); }
         if (!qrc) qrc = fs_build(ctx, pt, pl->z.data(), zcp, a, b1, FS_BUILD_Z | FS_BUILD_ZC, pl->mismatch_dev, s);
         if (!qrc) qrc = fs_build(ctx, pt, pl->z.data(), zcp, b, b2, FS_BUILD_Z | FS_BUILD_ZC, pl->mismatch_dev, s);
         if (!qrc) { pl->fs1 = b1; pl->fs2 = b2; pl->fl1 = a; pl->fl2 = b; pl->fused_pending = 0; }

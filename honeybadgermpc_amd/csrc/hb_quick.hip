@@ -1292,6 +1292,7 @@ int hb_quick_interp_check_map(hb_ctx *ctx, const uint64_t *x_host, int n, const 
             rc = take_slot(F.need, &sl); if (rc) return rc;
             uint8_t *base = static_cast<uint8_t *>(sl->buf);
             (void)fs_pack(pt, z, &F);            // (built in one piece, no row picked: a narrow last row tile packs as a plan's does)
+            (void)fs_mscale(&F);                 // (and the columns are divided by den on the matrix cores)
             rc = fs_build(ctx, pt, z, zc, F, base, FS_BUILD_Z | FS_BUILD_ZC, status_dev, s); if (rc) return rc;
             uint32_t *out = coeffs_dev ? (uint32_t *)coeffs_dev + (size_t)chunk_lo * d * 8 : nullptr;
             rc = fs_launch(ctx, F, base, in, pm, out, dv, coeffs_dev ? cnt * (int64_t)d : 0, status_dev, (nc > 0 && status_dev) ? status_dev + 1 : nullptr,

@@ -51,11 +51,14 @@ int hb_debug_matvec_route(hb_ctx *ctx, const hb_matrix *m, int64_t C, int32_t *o
  * integers below 2^16); small_out (n_coef bytes, may be null) receives the flags it derived.  hb_debug_fs_slot: the image slot
  * (16 row tile + M row) of matrix row i under such a decision, *kind = 0 unpacked, 1 merged (digit group 1 on M row + 8), 2 single-group.
  * hb_debug_fs_last_pack: the form of the last row tile at the process's last launch of the kernel -- 0 unpacked, 1 merged outputs alone,
- * 2 merged outputs and single-group rows; -1 before any launch. */
+ * 2 merged outputs and single-group rows; -1 before any launch.
+ * hb_debug_fs_last_mscale: 1 if that launch divided the received columns by den on the matrix cores, 0 if by the T_q multiplication
+ * (HB_NO_FUSED_MSCALE=1, a decoder's launch, tables that do not fit the LDS); -1 before any launch. */
 int hb_debug_fs_pack_rows(int d, int n_coef, int nc, const uint8_t *small, int32_t *out);
 int hb_debug_fs_pack_points(const int32_t *xz, int d, int n_coef, int nc, int32_t *out, uint8_t *small_out);
 int hb_debug_fs_slot(int nm, int ns, const int32_t *single, int i, int n_out, int32_t *kind);
 int hb_debug_fs_last_pack(void);
+int hb_debug_fs_last_mscale(void);
 
 
 #ifdef __cplusplus
