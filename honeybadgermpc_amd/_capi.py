@@ -31,6 +31,10 @@ HB_MIMC_SELFTEST_PLAIN, HB_MIMC_SELFTEST_ROUND, HB_MIMC_SELFTEST_FIRST = 0, 1, 2
 HB_JJ_SCALAR_BROADCAST, HB_JJ_POINT_BROADCAST = 1, 2
 HB_JJ_SELFTEST_SCALAR_MUL, HB_JJ_SELFTEST_DOUBLE_TABLE, HB_JJ_SELFTEST_MASK, HB_JJ_SELFTEST_STAGE1 = 0, 1, 2, 3
 HB_JJ_SELFTEST_STAGE2, HB_JJ_SELFTEST_STAGE3, HB_JJ_SELFTEST_SCALE = 4, 5, 6
+HB_G1_SCALAR_BROADCAST, HB_G1_POINT_BROADCAST = 1, 2
+HB_G1_SUBTRACT, HB_G1_GENERAL, HB_G1_DOUBLE = 1, 2, 4
+HB_G1_SELFTEST_FQ_MUL, HB_G1_SELFTEST_SCALAR_MUL, HB_G1_SELFTEST_ADD, HB_G1_SELFTEST_CHECK = 0, 1, 2, 3
+HB_G1_SELFTEST_TABLE, HB_G1_SELFTEST_COMMIT, HB_G1_SELFTEST_EVAL, HB_G1_SELFTEST_VERIFY = 4, 5, 6, 7
 HB_FXP_MOD, HB_FXP_TRUNC, HB_FXP_NEG_TRUNC = 0, 1, 2
 HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
 HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
@@ -111,6 +115,14 @@ SYMBOLS = {
     "hb_jj_add_stage2": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_jj_add_stage3": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "hb_jj_add_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "hb_g1_scalar_mul": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i64, _vp]),
+    "hb_g1_add": (_i, [_vp, _vp, _vp, _i, _vp, _i64, _vp]),
+    "hb_g1_check": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "hb_g1_table_bytes": (_i64, [_i]),
+    "hb_g1_table": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "hb_g1_commit": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_g1_eval": (_i, [_vp, _vp, _i, ctypes.c_uint64, _vp, _i64, _vp]),
+    "hb_g1_verify": (_i, [_vp, _vp, _vp, _i, _vp, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_fxp_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hb_fxp_trunc_pr": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
     "hb_fxp_ltl_leaves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
@@ -200,6 +212,7 @@ SYMBOLS = {
     "hb_selftest_bf": (_i, [_vp, _i, _i, _vp, _i64, _i, _vp]),
     "hb_selftest_mimc": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i64, _vp, _i64]),
     "hb_selftest_jj": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _i64]),
+    "hb_selftest_g1": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_bd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_div": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),

@@ -277,6 +277,37 @@ int hb_jj_add_stage3(hb_ctx *ctx, const uint64_t *c_open_dev, const uint64_t *p_
 int hb_jj_add_finish(hb_ctx *ctx, const uint64_t *d_open_dev, const uint64_t *uv_dev, uint64_t *inv_dev, uint64_t *x3_dev, uint64_t *y3_dev,
                      int64_t m, int32_t *zeros_dev, void *stream);
 
+/* ---- BLS12-381 G1 and the linear polynomial commitment (hb_g1.hip) -----------------------------------------------------
+ * The group the reference's poly_commit_lin.py commits in (betterpairing.G1): E: y^2 = x^3 + 4 over the 381-bit field GF(Q), written
+ * additively here.  Every call takes a four-limb context whose modulus is the group order R = Subgroup.BLS12_381 (anything else:
+ * HB_ERR_BAD_ARG).  A point is 12 words: x then y, 6 little-endian words each, canonical residues below Q; the identity is all zeros.
+ * Scalars are the context's elements, read as plain 256-bit integers (any value).  Points are taken as they come: what is off the
+ * curve gives a meaningless result, never a fault; hb_g1_check tells.  NOTHING here tests membership of the subgroup of order R:
+ * hb_g1_scalar_mul by R (identity out <=> member) is that test.
+ * hb_g1_scalar_mul: out[i] = k_i P_i; k_broadcast / point_broadcast != 0: element 0 serves every i.  One launch.
+ * hb_g1_add: out[i] = P_i + Q_i, or P_i - Q_i with subtract != 0.  Complete: identity, equal and opposite operands included.
+ * hb_g1_check: flags[i] = 1 if P_i is the identity, or has both coordinates below Q and lies on the curve; else 0.
+ * hb_g1_table: the fixed-base window table of ONE base (12 words in HOST memory; the identity or a point off the curve:
+ *   HB_ERR_BAD_ARG) for window width 4 or 8, into table_dev, a device buffer of hb_g1_table_bytes(window) bytes (0 for another width)
+ *   aligned to 16 bytes.  Its layout is the library's own.  Synchronises the stream once (the base's upload), then one launch.
+ * hb_g1_commit: out[i] = a_i g + b_i h from the tables of g and h (built with the same window): the dealer's commitments.
+ * hb_g1_eval: out[b] = sum_j index^j cs[b][j] for `count` vectors of n_coef commitments (cs: count * n_coef points), by Horner's
+ *   rule; index < 2^32 (else HB_ERR_BAD_ARG); index = 0 gives cs[b][0].
+ * hb_g1_verify: verdict[b] = 1 if every commitment of item b passes hb_g1_check's test and sum_j index^j cs[b][j] = s_b g + w_b h,
+ *   else 0; *rejected_dev (an int32 the caller has zeroed) grows by the number of rejected items.  One launch, no inversion.
+ * All: asynchronous on `stream` (but hb_g1_table's upload), nothing allocated; count == 0 returns HB_OK and launches nothing. */
+int hb_g1_scalar_mul(hb_ctx *ctx, const uint64_t *k_dev, int k_broadcast, const uint64_t *p_dev, int point_broadcast, uint64_t *out_dev,
+                     int64_t count, void *stream);
+int hb_g1_add(hb_ctx *ctx, const uint64_t *p_dev, const uint64_t *q_dev, int subtract, uint64_t *out_dev, int64_t count, void *stream);
+int hb_g1_check(hb_ctx *ctx, const uint64_t *p_dev, int32_t *flags_dev, int64_t count, void *stream);
+int64_t hb_g1_table_bytes(int window);
+int hb_g1_table(hb_ctx *ctx, const uint64_t *base_host, int window, void *table_dev, void *stream);
+int hb_g1_commit(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int window, const uint64_t *a_dev, const uint64_t *b_dev,
+                 uint64_t *out_dev, int64_t count, void *stream);
+int hb_g1_eval(hb_ctx *ctx, const uint64_t *cs_dev, int n_coef, uint64_t index, uint64_t *out_dev, int64_t count, void *stream);
+int hb_g1_verify(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int window, const uint64_t *cs_dev, int n_coef, uint64_t index,
+                 const uint64_t *s_dev, const uint64_t *w_dev, int32_t *verdict_dev, int32_t *rejected_dev, int64_t count, void *stream);
+
 /* ---- fixed-point arithmetic on shares (hb_fxp.hip) --------------------------------------------------------------------
  * progs/fixedpoint.py ("Secure Computation With Fixed-Point Numbers", Catrina and Saxena): random2m (:91-98), trunc_pr (:108-120),
  * get_carry_bit / bit_ltl (:131-172), div2m (:184-193), trunc (:208-211) and FixedPoint.ltz (:266-268) for arrays of `count` values.
@@ -842,6 +873,33 @@ int hb_selftest_mimc(const uint64_t *p_limbs, int n_limbs, int what, const uint6
 #define HB_JJ_SELFTEST_SCALE 6
 int hb_selftest_jj(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const uint64_t *a, const uint64_t *d,
                    int flags, int64_t arg, uint64_t *out, int64_t count);
+/* host-side run of the G1 kernels' bodies (no GPU needed) over host memory, item by item; points, scalars and tables as the device
+ * calls take them (a table: hb_g1_table_bytes(window) bytes, 16-byte aligned); also checks the literal constants of Fq against Q:
+ *   what = HB_G1_SELFTEST_FQ_MUL      operands[0..1] = a, b: 6 words an element, below Q; out = a b mod Q, 6 words an element
+ *          HB_G1_SELFTEST_SCALAR_MUL  operands[0..1] = k, P; flags = HB_G1_SCALAR_BROADCAST | HB_G1_POINT_BROADCAST; out = points
+ *          HB_G1_SELFTEST_ADD         operands[0..1] = P, Q; flags = HB_G1_SUBTRACT, as hb_g1_add;
+ *                                     | HB_G1_GENERAL: through the Jacobian + Jacobian formula, both operands moved off Z = 1;
+ *                                     | HB_G1_DOUBLE: out = 2 P through the doubling formula (Q unused)
+ *          HB_G1_SELFTEST_CHECK       operands[0] = P; out = `count` int32 flags
+ *          HB_G1_SELFTEST_TABLE       operands[0] = the base; arg = window; count = 1; out = the table
+ *          HB_G1_SELFTEST_COMMIT      operands[0..3] = a, b, table of g, table of h; arg = window
+ *          HB_G1_SELFTEST_EVAL        operands[0] = cs; flags = n_coef; arg = index
+ *          HB_G1_SELFTEST_VERIFY      operands[0..4] = cs, s, w, table of g, table of h; flags = n_coef | window << 16; arg = index;
+ *                                     out = `count` int32 verdicts, then the int32 count of rejected items */
+#define HB_G1_SCALAR_BROADCAST 1
+#define HB_G1_POINT_BROADCAST 2
+#define HB_G1_SUBTRACT 1
+#define HB_G1_GENERAL 2
+#define HB_G1_DOUBLE 4
+#define HB_G1_SELFTEST_FQ_MUL 0
+#define HB_G1_SELFTEST_SCALAR_MUL 1
+#define HB_G1_SELFTEST_ADD 2
+#define HB_G1_SELFTEST_CHECK 3
+#define HB_G1_SELFTEST_TABLE 4
+#define HB_G1_SELFTEST_COMMIT 5
+#define HB_G1_SELFTEST_EVAL 6
+#define HB_G1_SELFTEST_VERIFY 7
+int hb_selftest_g1(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count);
 /* host-side run of the fixed-point kernels' bodies (no GPU needed) over host memory, element by element.  params = {k, m, kappa,
  * nodes or mode, root}; parameters are checked as the device calls check them:
  *   what = HB_FXP_SELFTEST_MASK     operands[0..1] = x (or NULL), bits [k + kappa][count]; outs[0..1] as hb_fxp_mask writes masked_dev, r1_dev
