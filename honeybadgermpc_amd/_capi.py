@@ -123,6 +123,8 @@ SYMBOLS = {
     "hb_g1_commit": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_g1_eval": (_i, [_vp, _vp, _i, ctypes.c_uint64, _vp, _i64, _vp]),
     "hb_g1_verify": (_i, [_vp, _vp, _vp, _i, _vp, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_g1_msm_workspace_bytes": (_i64, [_i64, _i64, _i, _i]),
+    "hb_g1_msm": (_i, [_vp, _vp, _vp, _i, _vp, _i64, _i64, _i, _i, _vp, _i64, _vp]),
     "hb_fxp_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hb_fxp_trunc_pr": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
     "hb_fxp_ltl_leaves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
@@ -213,6 +215,7 @@ SYMBOLS = {
     "hb_selftest_mimc": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i64, _vp, _i64]),
     "hb_selftest_jj": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_g1": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
+    "hb_selftest_g1_msm": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _i, _i]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_bd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_div": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),

@@ -18,6 +18,12 @@ identity is all zeros.  Scalars are the context's (count, 4) elements, read as p
     eval_commitments(ctx, cs, i, out=None)               cs (B, t + 1, 2, 6), 0 <= i < 2^32 -> (B, 2, 6): sum_j i^j cs[b][j] by Horner
     verify(ctx, tg, th, cs, i, shares, witnesses)        -> (verdict (B,) int32: 1 accepted, 0 rejected; counter (1,) int32: rejected
                                                          items).  One fused launch; an item with a commitment off the curve is rejected.
+    msm(ctx, scalars, points, out=None, method="auto", chunk=None)
+                                                         sum_k scalars[m][k] * points[m or 0][k] -> (M, 2, 6) (csrc/hb_msm.hip): the sum
+                                                         over a list of points everything above lacks
+    lagrange_scalars(xs, targets)                        host, Python ints mod R: the weights of interpolation at `targets`
+    interpolate_at(ctx, xs, points, targets, out=None)   interpolation in the exponent: msm of those weights over shared bases
+    interpolate_g1_at_x(coords, x, order=-1, ctx=None)   the reference's betterpairing.interpolate_g1_at_x on host objects
 
 Everything is asynchronous on torch's current stream and nothing synchronises, except download() and FixedBase() (the base's upload).
 """
@@ -250,3 +256,133 @@ def verify(ctx, tg, th, cs, i, shares, witnesses):
     ctx.check(ctx.lib.hb_g1_verify(ctx.h, ctx.ptr(tg.table), ctx.ptr(th.table), window, ctx.ptr(cs), n_coef, i, ctx.ptr(s), ctx.ptr(w), ctx.ptr(verdict),
                                    ctx.ptr(counter), B, ctx.stream()), "hb_g1_verify")
     return verdict, counter
+
+
+# ---- multi-scalar multiplication (csrc/hb_msm.hip)
+MSM_CHUNK = 4096
+# "auto": the bucket path from this many terms a row on (hb_msm.hip's MSM_AUTO_TERMS says the same for the C ABI's method 0).  The smallest
+# K of the M = 64 rows of profiles/g1_msm.txt at which bucket beats direct: it does at every K measured (22: 7.5 ms against 10.4 ms), so
+# the smallest one; below it nothing is measured and a row of a few terms keeps the direct path.
+MSM_CROSSOVER = 22
+_MSM_METHODS = {"direct": 1, "bucket": 2}
+
+
+def msm(ctx, scalars, points, out=None, method="auto", chunk=None):
+    """out[m] = sum_k scalars[m][k] * points[m or 0][k] -> (M, 2, 6).  scalars: (M, K, 4), or (K, 4) for M = 1, plain 256-bit
+    integers; points: (K, 2, 6) shared by every row, or (M, K, 2, 6).  method: "direct" (a full scalar multiplication a term and a
+    tree of additions), "bucket" (windows of 8 bits: one mixed addition a term a window) or "auto" (bucket from MSM_CROSSOVER terms
+    on); all return the same words.  chunk (tests): the terms a workgroup of the bucket path takes, a multiple of 64 in [64, 4096].
+    K = 0 gives identities.  A call is never faster than about one scalar_mul of a wave (the last step is 248 dependent doublings a
+    row): the gain over scalar_mul + add is throughput at sizes that fill the device, see profiles/g1_msm.txt."""
+    _ctx(ctx)
+    if method != "auto" and method not in _MSM_METHODS:
+        raise ValueError(f"method: 'auto', 'direct' or 'bucket', got {method!r}")
+    if chunk is None:
+        chunk = 0
+    elif isinstance(chunk, bool) or not isinstance(chunk, int) or not 64 <= chunk <= MSM_CHUNK or chunk % 64:
+        raise ValueError(f"chunk: a multiple of 64 in [64, {MSM_CHUNK}], got {chunk!r}")
+    pts = _points(ctx, points)
+    if pts.dim() not in (3, 4):
+        raise ValueError(f"points: expected a tensor of shape (K, 2, {LIMBS}) or (M, K, 2, {LIMBS}), got {tuple(pts.shape)}")
+    K = int(pts.shape[-3])
+    sc = ctx.elems(scalars, what="scalars")
+    if sc.dim() not in (2, 3) or sc.shape[-2] != K:
+        raise ValueError(f"scalars: expected a tensor of shape (K, 4) or (M, K, 4) with K = {K}, got {tuple(sc.shape)}")
+    M = int(sc.shape[0]) if sc.dim() == 3 else 1
+    if pts.dim() == 4 and pts.shape[0] != M:
+        raise ValueError(f"scalars and points: {M} rows of scalars against {int(pts.shape[0])} rows of points")
+    code = _MSM_METHODS[method] if method != "auto" else (1 if K < MSM_CROSSOVER else 2)
+    out = _out(ctx, out, M)
+    nbytes = int(ctx.lib.hb_g1_msm_workspace_bytes(M, K, code, chunk))
+    if nbytes <= 0:
+        raise ValueError(f"msm: {M} rows of {K} terms are beyond one call")
+    ws = ctx.torch.empty((nbytes // 8,), dtype=ctx.torch.int64, device=ctx.tdev)
+    ctx.check(ctx.lib.hb_g1_msm(ctx.h, ctx.ptr(sc), ctx.ptr(pts), 1 if pts.dim() == 4 else 0, ctx.ptr(out), M, K, code, chunk, ctx.ptr(ws), nbytes,
+                                ctx.stream()), "hb_g1_msm")
+    return out
+
+
+def _batch_inverse(values):
+    """1 / v mod R for every v (none zero) with ONE modular inversion: prefix products, then back"""
+    prefix, run = [], 1
+    for v in values:
+        prefix.append(run)
+        run = run * v % R
+    inv, out = pow(run, -1, R), [0] * len(values)
+    for k in range(len(values) - 1, -1, -1):
+        out[k] = inv * prefix[k] % R
+        inv = inv * values[k] % R
+    return out
+
+
+def lagrange_scalars(xs, targets, shortcut=True):
+    """-> rows[i][k] = prod_{j != k} (targets[i] - xs[j]) / (xs[k] - xs[j]) mod R, Python ints: sum_k rows[i][k] f(xs[k]) = f(targets[i])
+    for every polynomial f of degree below len(xs).  A target that is a node gives a unit row (its numerators vanish but one).
+    Nodes that are consecutive integers (the reference's 0 .. K - 1) take their denominators from factorials,
+    (xs[k] - xs[j]) over j != k = k! (K - 1 - k)! (-1)^(K - 1 - k): O(K); any other distinct nodes O(K^2) (shortcut=False forces this
+    path).  Either way one modular inversion.  Duplicate nodes (mod R) raise ValueError."""
+    raw = [int(x) for x in xs]
+    nodes = [x % R for x in raw]
+    K = len(nodes)
+    if len(set(nodes)) != K:
+        raise ValueError("xs: the nodes must be distinct mod R")
+    if K == 0:
+        return [[] for _ in targets]
+    if shortcut and K < R and all(raw[k] == raw[0] + k for k in range(K)):
+        fact = [1] * K
+        for k in range(1, K):
+            fact[k] = fact[k - 1] * k % R
+        dens = [fact[k] * fact[K - 1 - k] * (-1 if (K - 1 - k) & 1 else 1) % R for k in range(K)]
+    else:
+        dens = []
+        for k in range(K):
+            d = 1
+            for j in range(K):
+                if j != k:
+                    d = d * (nodes[k] - nodes[j]) % R
+            dens.append(d)
+    inv = _batch_inverse(dens)
+    rows = []
+    for t in targets:
+        t = int(t) % R
+        # numerator k = (the product before k) * (the product after k): no division by t - xs[k], which may be zero
+        before, run = [], 1
+        for k in range(K):
+            before.append(run)
+            run = run * (t - nodes[k]) % R
+        row, run = [0] * K, 1
+        for k in range(K - 1, -1, -1):
+            row[k] = before[k] * run % R * inv[k] % R
+            run = run * (t - nodes[k]) % R
+        rows.append(row)
+    return rows
+
+
+def interpolate_at(ctx, xs, points, targets, out=None):
+    """points[k] = f(xs[k]) * G for an unknown polynomial f of degree below K -> (len(targets), 2, 6): f(targets[i]) * G, as msm of
+    lagrange_scalars(xs, targets) over the shared bases `points` (K, 2, 6).  The n Lagrange combinations of HbAvssBatch's share
+    recovery (hbavss.py:499-512) are ONE call."""
+    _ctx(ctx)
+    xs, targets = list(xs), list(targets)
+    pts = _points(ctx, points, len(xs))
+    rows = lagrange_scalars(xs, targets)
+    sc = ctx.upload_ints([v for row in rows for v in row]).reshape(len(targets), len(xs), 4)
+    return msm(ctx, sc, pts.reshape(len(xs), 2, LIMBS), out=out)
+
+
+def interpolate_g1_at_x(coords, x, order=-1, ctx=None):
+    """The reference's betterpairing.interpolate_g1_at_x (:800) on host objects: coords = [(x_k, host G1)], sorted by x_k, the first
+    `order` of them (all by default) interpolated at x -> a host G1.  One msm of one row; download synchronises."""
+    if ctx is None:
+        from ._capi import Context
+
+        ctx = Context.get(R)
+    _ctx(ctx)
+    coords = sorted(((int(c[0]), c[1]) for c in coords), key=lambda c: c[0])
+    if order == -1:
+        order = len(coords)
+    coords = coords[:order]
+    if not coords:
+        return G1.one()
+    pts = upload([c[1] for c in coords], ctx)
+    return download(interpolate_at(ctx, [c[0] for c in coords], pts, [int(x)]))[0]

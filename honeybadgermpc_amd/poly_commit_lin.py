@@ -19,6 +19,9 @@ evaluated at 1..n -- the package's existing batched evaluation, not a kernel of 
     wit = ntl.vandermonde_batch_evaluate(list(range(1, n + 1)), hat_rows, R)  # wit[b][i - 1] = hat_b(i)
 
 and the shares phi_b(i) come from the same call on the coefficients.
+
+Sums over a list of commitments -- products of commitments, interpolation in the exponent (the reference's interpolate_g1_at_x) -- are
+not methods of this class: g1.msm, g1.interpolate_at and g1.interpolate_g1_at_x work on the same (..., 2, 6) tensors.
 """
 import secrets
 

@@ -307,6 +307,20 @@ int hb_g1_commit(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int window
 int hb_g1_eval(hb_ctx *ctx, const uint64_t *cs_dev, int n_coef, uint64_t index, uint64_t *out_dev, int64_t count, void *stream);
 int hb_g1_verify(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int window, const uint64_t *cs_dev, int n_coef, uint64_t index,
                  const uint64_t *s_dev, const uint64_t *w_dev, int32_t *verdict_dev, int32_t *rejected_dev, int64_t count, void *stream);
+/* Multi-scalar multiplication in G1 (hb_msm.hip): out[m] = sum_k s[m][k] P[m][k] for `rows` rows of `terms` terms; what the reference's
+ * interpolate_g1_at_x (betterpairing.py:800) computes with Lagrange weights for scalars.  s_dev: rows * terms scalars, plain 256-bit
+ * integers; p_dev: `terms` points shared by every row (points_per_row == 0) or rows * terms points; out_dev: `rows` affine points.
+ * method: 0 auto (by `terms`), 1 direct (a full scalar multiplication a term, summed by a tree in LDS), 2 bucket (windows of 8 bits:
+ *   one mixed addition a term a window; buckets summed without a serial chain; see hb_msm.hip).  All give the same words.
+ * chunk: the terms one workgroup of the bucket path takes: 0 = the default (4096), else a multiple of 64 in [64, 4096].
+ * workspace_dev: hb_g1_msm_workspace_bytes(rows, terms, method, chunk) bytes (0 for arguments hb_g1_msm refuses), aligned to 16 bytes,
+ *   the library's while the call's launches run; its content afterwards means nothing.
+ * HB_ERR_BAD_ARG: a null pointer, a negative count, another method or chunk, a workspace too small, out overlapping s, P or the
+ *   workspace.  rows == 0 launches nothing; terms == 0 fills out with identities.  Three launches on `stream`, nothing allocated.
+ *   A call on the bucket path ends in 248 dependent doublings a row: it is never faster than one hb_g1_scalar_mul of a wave. */
+int64_t hb_g1_msm_workspace_bytes(int64_t rows, int64_t terms, int method, int chunk);
+int hb_g1_msm(hb_ctx *ctx, const uint64_t *s_dev, const uint64_t *p_dev, int points_per_row, uint64_t *out_dev, int64_t rows, int64_t terms,
+              int method, int chunk, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* ---- fixed-point arithmetic on shares (hb_fxp.hip) --------------------------------------------------------------------
  * progs/fixedpoint.py ("Secure Computation With Fixed-Point Numbers", Catrina and Saxena): random2m (:91-98), trunc_pr (:108-120),
@@ -900,6 +914,11 @@ int hb_selftest_jj(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_G1_SELFTEST_EVAL 6
 #define HB_G1_SELFTEST_VERIFY 7
 int hb_selftest_g1(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count);
+/* host-side run of hb_g1_msm (no GPU needed) over host memory: the per-lane steps of its kernels (the digit of a term, the walk of a
+ * bucket's list, b * B_b, a tree step, the fold, the row's Horner end) driven lane by lane, workgroup by workgroup, with arrays in place
+ * of LDS.  Arguments as hb_g1_msm; method = 3 (here only): the bucket path with EVERY non-empty bucket summed by the whole workgroup. */
+int hb_selftest_g1_msm(const uint64_t *s, const uint64_t *p, int points_per_row, uint64_t *out, int64_t rows, int64_t terms, int method,
+                       int chunk);
 /* host-side run of the fixed-point kernels' bodies (no GPU needed) over host memory, element by element.  params = {k, m, kappa,
  * nodes or mode, root}; parameters are checked as the device calls check them:
  *   what = HB_FXP_SELFTEST_MASK     operands[0..1] = x (or NULL), bits [k + kappa][count]; outs[0..1] as hb_fxp_mask writes masked_dev, r1_dev
