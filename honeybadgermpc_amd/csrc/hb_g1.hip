@@ -83,54 +83,7 @@ HB_HD int32_t g1_check_elem(const uint32_t *p, const FpParams<QL> &P) {
     if (a.inf) return 1;
     return (below && g1_on_curve(a, P)) ? 1 : 0;
 }
-// window w of a base's table (the header's layout): entries, then scratch
-HB_HD void g1_table_window(uint32_t *table, const uint32_t *base, int c, int w, const FpParams<QL> &P) {
-    const int n = (1 << c) - 1, W = 256 / c;
-    uint32_t *ent = table + (int64_t)w * n * G1_ENT;
-    uint32_t *scr = table + (int64_t)W * n * G1_ENT + (int64_t)w * n * G1_SCR;
-    G1Aff a;
-    G1Jac bw, acc;
-    g1_load(a, base, P);
-    g1_from_affine(bw, a, P);
-#pragma unroll 1
-    for (int s = 0; s < c * w; s++) g1_double(bw, bw, P);
-    // entry j = j B_w, Jacobian: X, Y in the entry, Z and the product of the Zs before it in the scratch
-    uint32_t run[QL];
-    fp_set<QL>(run, P.one);
-    g1_set_identity(acc, P);
-#pragma unroll 1
-    for (int j = 0; j < n; j++) {
-        g1_add(acc, bw, P);
-        g1_store16(ent + j * G1_ENT, acc.X);
-        g1_store16(ent + j * G1_ENT + 16, acc.Y);
-        g1_store16(scr + j * G1_SCR, acc.Z);
-        g1_store16(scr + j * G1_SCR + 16, run);
-        if (!fp_is_zero<QL>(acc.Z)) fq_mul(run, run, acc.Z, P);
-    }
-    uint32_t inv[QL];
-    fq_inv(inv, run, P);
-#pragma unroll 1
-    for (int j = n - 1; j >= 0; j--) {
-        uint32_t z[QL], zi[QL], zi2[QL], x[QL], y[QL];
-        g1_load16(z, scr + j * G1_SCR);
-        g1_load16(zi, scr + j * G1_SCR + 16);
-        g1_load16(x, ent + j * G1_ENT);
-        g1_load16(y, ent + j * G1_ENT + 16);
-        if (fp_is_zero<QL>(z)) {                               // an identity entry (a base of small order): (0, 0)
-            fq_zero(x);
-            fq_zero(y);
-        } else {
-            fq_mul(zi, zi, inv, P);                            // 1 / Z_j
-            fq_mul(inv, inv, z, P);
-            fq_mul(zi2, zi, zi, P);
-            fq_mul(x, x, zi2, P);
-            fq_mul(y, y, zi2, P);
-            fq_mul(y, y, zi, P);
-        }
-        g1_store16(ent + j * G1_ENT, x);
-        g1_store16(ent + j * G1_ENT + 16, y);
-    }
-}
+// (g1_table_window, the body of k_g1_table, lives in hb_g1_elem.hpp: k_g1_crs_table of hb_crs.hip runs it a base a workgroup)
 // acc = ka g + kb h from the two tables
 HB_HD void g1_comb(G1Jac &acc, const uint32_t (&kaw)[SW], const uint32_t (&kbw)[SW], const uint32_t *tg, const uint32_t *th, int c, const FpParams<QL> &P) {
     const int n = (1 << c) - 1, W = 256 / c;

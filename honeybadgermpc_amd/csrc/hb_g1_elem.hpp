@@ -1,6 +1,6 @@
 // hb_g1_elem.hpp -- the field and point bodies of BLS12-381 G1 (fq_*, g1_double, g1_add_mixed, g1_add, g1_eq, g1_load, g1_store,
-// g1_mul_affine, fq_params and the non-inlined fq_mul_call) and the checks every G1 entry point makes (G1_ENTER), shared by hb_g1.hip and
-// hb_msm.hip.  Host and device: the kernels only load, call and store, and the host self tests run the same functions.  The head of
+// g1_mul_affine, g1_table_window, the tree nodes of the sums, fq_params and the non-inlined fq_mul_call) and the checks every G1 entry
+// point makes (G1_ENTER), shared by hb_g1.hip, hb_msm.hip and hb_crs.hip.  Host and device: the kernels only load, call and store, and the host self tests run the same functions.  The head of
 // hb_g1.hip derives the bounds (Field, LAZY SUMS) and states the formulas (Points).
 #pragma once
 #include "hb_common.hpp"
@@ -288,6 +288,80 @@ HB_HD void g1_mul_affine(G1Jac &acc, const uint32_t (&kw)[SW], const G1Aff &a, c
         if (started) g1_double(acc, acc, P);
         if (bit) { g1_add_mixed(acc, a, P); started = true; }
     }
+}
+
+// ---------------------------------------------------------------- fixed-base tables (k_g1_table of hb_g1.hip, k_g1_crs_table of hb_crs.hip)
+// window w of a base's table (the layout at the head of hb_g1.hip): entries, then scratch
+HB_HD void g1_table_window(uint32_t *table, const uint32_t *base, int c, int w, const FpParams<QL> &P) {
+    const int n = (1 << c) - 1, W = 256 / c;
+    uint32_t *ent = table + (int64_t)w * n * G1_ENT;
+    uint32_t *scr = table + (int64_t)W * n * G1_ENT + (int64_t)w * n * G1_SCR;
+    G1Aff a;
+    G1Jac bw, acc;
+    g1_load(a, base, P);
+    g1_from_affine(bw, a, P);
+#pragma unroll 1
+    for (int s = 0; s < c * w; s++) g1_double(bw, bw, P);
+    // entry j = j B_w, Jacobian: X, Y in the entry, Z and the product of the Zs before it in the scratch
+    uint32_t run[QL];
+    fp_set<QL>(run, P.one);
+    g1_set_identity(acc, P);
+#pragma unroll 1
+    for (int j = 0; j < n; j++) {
+        g1_add(acc, bw, P);
+        g1_store16(ent + j * G1_ENT, acc.X);
+        g1_store16(ent + j * G1_ENT + 16, acc.Y);
+        g1_store16(scr + j * G1_SCR, acc.Z);
+        g1_store16(scr + j * G1_SCR + 16, run);
+        if (!fp_is_zero<QL>(acc.Z)) fq_mul(run, run, acc.Z, P);
+    }
+    uint32_t inv[QL];
+    fq_inv(inv, run, P);
+#pragma unroll 1
+    for (int j = n - 1; j >= 0; j--) {
+        uint32_t z[QL], zi[QL], zi2[QL], x[QL], y[QL];
+        g1_load16(z, scr + j * G1_SCR);
+        g1_load16(zi, scr + j * G1_SCR + 16);
+        g1_load16(x, ent + j * G1_ENT);
+        g1_load16(y, ent + j * G1_ENT + 16);
+        if (fp_is_zero<QL>(z)) {                               // an identity entry (a base of small order): (0, 0)
+            fq_zero(x);
+            fq_zero(y);
+        } else {
+            fq_mul(zi, zi, inv, P);                            // 1 / Z_j
+            fq_mul(inv, inv, z, P);
+            fq_mul(zi2, zi, zi, P);
+            fq_mul(x, x, zi2, P);
+            fq_mul(y, y, zi2, P);
+            fq_mul(y, y, zi, P);
+        }
+        g1_store16(ent + j * G1_ENT, x);
+        g1_store16(ent + j * G1_ENT + 16, y);
+    }
+}
+
+// ---------------------------------------------------------------- the tree of hb_msm.hip and hb_crs.hip
+// a node: a Jacobian point of 3 x 14 digits at a stride of 43 words (odd: lanes of a step hit distinct banks)
+constexpr int MSM_NODE = 3 * QL + 1;                     // words a tree node: 42 digits, one of padding
+HB_HD void msm_node_store(uint32_t *nodes, int lane, const G1Jac &j) {
+    uint32_t *n = nodes + lane * MSM_NODE;
+#pragma unroll
+    for (int q = 0; q < QL; q++) { n[q] = j.X[q]; n[QL + q] = j.Y[q]; n[2 * QL + q] = j.Z[q]; }
+}
+HB_HD void msm_node_load(G1Jac &j, const uint32_t *nodes, int lane) {
+    const uint32_t *n = nodes + lane * MSM_NODE;
+#pragma unroll
+    for (int q = 0; q < QL; q++) { j.X[q] = n[q]; j.Y[q] = n[QL + q]; j.Z[q] = n[2 * QL + q]; }
+}
+// one step of the tree: node lane += node lane + half
+HB_HD void msm_tree_step(uint32_t *nodes, int lane, int half, const FpParams<QL> &P) {
+    if (lane >= half) return;
+    G1Jac a, b;
+    msm_node_load(b, nodes, lane + half);
+    if (fp_is_zero<QL>(b.Z)) return;
+    msm_node_load(a, nodes, lane);
+    g1_add(a, b, P);
+    msm_node_store(nodes, lane, a);
 }
 
 // ---------------------------------------------------------------- host side

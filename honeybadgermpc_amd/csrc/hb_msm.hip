@@ -31,6 +31,7 @@
 // 256-thread workgroups, every load bounded by K, nothing waits for another workgroup, the caller's stream, nothing allocated.
 // The per-lane steps (msm_digit, msm_walk, msm_scale, msm_tree_step, msm_fold_lane, msm_finish_row) are HB_HD: hb_selftest_g1_msm drives
 // the very same functions lane by lane over host arrays in place of LDS.  Compiler's report: profiles/g1_msm.txt.
+// (MSM_NODE, msm_node_store, msm_node_load and msm_tree_step live in hb_g1_elem.hpp: hb_crs.hip's split rows end in the same tree.)
 #include "hb_g1_elem.hpp"
 
 using namespace hb;
@@ -39,7 +40,6 @@ namespace hb {
 
 constexpr int MSM_WG = 256;                              // lanes a workgroup = buckets a window = tree nodes
 constexpr int MSM_W = 32;                                // windows of 8 bits
-constexpr int MSM_NODE = 3 * QL + 1;                     // words a tree node: 42 digits, one of padding
 constexpr int MSM_PART = 48;                             // words a partial in the workspace
 constexpr int MSM_HEAVY = 64;                             // heavy buckets a chunk can hold: fewer than chunk / thr <= 64
 constexpr int MSM_CHUNK = 4096;                          // terms a workgroup of the bucket path takes at most (16-bit list entries)
@@ -50,16 +50,6 @@ HB_HD int msm_threshold(int chunk) { return 4 * chunk / MSM_WG > 16 ? 4 * chunk 
 // window digit w of the scalar at s: its byte w
 HB_HD uint32_t msm_digit(const uint32_t *s, int w) { return (s[w >> 2] >> (8 * (w & 3))) & 255u; }
 
-HB_HD void msm_node_store(uint32_t *nodes, int lane, const G1Jac &j) {
-    uint32_t *n = nodes + lane * MSM_NODE;
-#pragma unroll
-    for (int q = 0; q < QL; q++) { n[q] = j.X[q]; n[QL + q] = j.Y[q]; n[2 * QL + q] = j.Z[q]; }
-}
-HB_HD void msm_node_load(G1Jac &j, const uint32_t *nodes, int lane) {
-    const uint32_t *n = nodes + lane * MSM_NODE;
-#pragma unroll
-    for (int q = 0; q < QL; q++) { j.X[q] = n[q]; j.Y[q] = n[QL + q]; j.Z[q] = n[2 * QL + q]; }
-}
 HB_HD void msm_part_store(uint32_t *p, const G1Jac &j) {
     g1_store16(p, j.X);
     g1_store16(p + 16, j.Y);
@@ -69,16 +59,6 @@ HB_HD void msm_part_load(G1Jac &j, const uint32_t *p) {
     g1_load16(j.X, p);
     g1_load16(j.Y, p + 16);
     g1_load16(j.Z, p + 32);
-}
-// one step of the tree: node lane += node lane + half
-HB_HD void msm_tree_step(uint32_t *nodes, int lane, int half, const FpParams<QL> &P) {
-    if (lane >= half) return;
-    G1Jac a, b;
-    msm_node_load(b, nodes, lane + half);
-    if (fp_is_zero<QL>(b.Z)) return;
-    msm_node_load(a, nodes, lane);
-    g1_add(a, b, P);
-    msm_node_store(nodes, lane, a);
 }
 // acc = the sum of the points list[from], list[from + step], ... (indices below `to`) of the chunk whose points start at pts
 HB_HD void msm_walk(G1Jac &acc, const uint16_t *list, int from, int to, int step, const uint32_t *pts, const FpParams<QL> &P) {

@@ -21,11 +21,19 @@ identity is all zeros.  Scalars are the context's (count, 4) elements, read as p
     msm(ctx, scalars, points, out=None, method="auto", chunk=None)
                                                          sum_k scalars[m][k] * points[m or 0][k] -> (M, 2, 6) (csrc/hb_msm.hip): the sum
                                                          over a list of points everything above lacks
+    FixedBases(ctx, bases, window=8)                     owns ONE buffer with the window tables of N bases (a list of host G1, none the
+                                                         identity): a common reference string.  .base(k): table k as a FixedBase
+    msm_fixed(ctx, tg, a, th=None, b=None, out=None, split=None)
+                                                         sum_k a[m][k] * G_k (+ b[m][k] * H_k) over the first K bases of one or two
+                                                         FixedBases -> (rows, 2, 6) (csrc/hb_crs.hip): table look-ups, no doubling
+    kzg_quotients(ctx, phi, xs) -> (q, rem)              phi (B, t + 1, 4), n points: q (B, n, t, 4) the coefficients of
+                                                         (phi_b(X) - phi_b(x_i)) / (X - x_i), rem (B, n, 4) = phi_b(x_i)
     lagrange_scalars(xs, targets)                        host, Python ints mod R: the weights of interpolation at `targets`
     interpolate_at(ctx, xs, points, targets, out=None)   interpolation in the exponent: msm of those weights over shared bases
     interpolate_g1_at_x(coords, x, order=-1, ctx=None)   the reference's betterpairing.interpolate_g1_at_x on host objects
 
-Everything is asynchronous on torch's current stream and nothing synchronises, except download() and FixedBase() (the base's upload).
+Everything is asynchronous on torch's current stream and nothing synchronises, except download(), FixedBase() and FixedBases() (the
+bases' upload).
 """
 import numpy as np
 
@@ -300,6 +308,103 @@ def msm(ctx, scalars, points, out=None, method="auto", chunk=None):
     ctx.check(ctx.lib.hb_g1_msm(ctx.h, ctx.ptr(sc), ctx.ptr(pts), 1 if pts.dim() == 4 else 0, ctx.ptr(out), M, K, code, chunk, ctx.ptr(ws), nbytes,
                                 ctx.stream()), "hb_g1_msm")
     return out
+
+
+# ---- fixed bases of a common reference string (csrc/hb_crs.hip)
+MAX_FIXED_BASES = 4096
+
+
+class FixedBases:
+    """The window tables of N fixed bases in one buffer, built by one launch (a base a workgroup): the gs or hs of a KZG common reference
+    string.  Table k has FixedBase's layout: .base(k) is a FixedBase on it for commit and verify (a view: it keeps the buffer alive)."""
+
+    def __init__(self, ctx, bases, window=8):
+        _ctx(ctx)
+        bases = list(bases)
+        for p in bases:
+            if not isinstance(p, G1):
+                raise TypeError(f"bases: expected host G1 elements, got {type(p).__name__}")
+        if isinstance(window, bool) or not isinstance(window, int) or window not in (4, 8):
+            raise ValueError(f"window: 4 or 8, got {window!r}")
+        if not 1 <= len(bases) <= MAX_FIXED_BASES:
+            raise ValueError(f"bases: between 1 and {MAX_FIXED_BASES} bases, got {len(bases)}")
+        if any(p.is_one() for p in bases):
+            raise ValueError("bases: the identity has no table")
+        self.ctx, self.bases, self.window, self.n = ctx, bases, window, len(bases)
+        self.table_words = int(ctx.lib.hb_g1_table_bytes(window)) // 8
+        self.tables = ctx.torch.empty((self.n * self.table_words,), dtype=ctx.torch.int64, device=ctx.tdev)
+        host = np.array([p.to_limbs() for p in bases], dtype=np.uint64).reshape(self.n, POINT_WORDS)
+        ctx.check(ctx.lib.hb_g1_crs_table(ctx.h, host.ctypes.data, self.n, window, ctx.ptr(self.tables), ctx.stream()), "hb_g1_crs_table")
+
+    def __len__(self):
+        return self.n
+
+    def base(self, k):
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < self.n:
+            raise IndexError(f"k: a base index in [0, {self.n}), got {k!r}")
+        fb = FixedBase.__new__(FixedBase)
+        fb.ctx, fb.base, fb.window = self.ctx, self.bases[k], self.window
+        fb.table = self.tables[k * self.table_words:(k + 1) * self.table_words]
+        return fb
+
+
+def msm_fixed(ctx, tg, a, th=None, b=None, out=None, split=None):
+    """out[m] = sum_k a[m][k] * tg[k] (+ b[m][k] * th[k]) -> (rows, 2, 6).  tg, th: FixedBases of one window width and one length N;
+    a, b: (rows, K, 4), or (K, 4) for one row, plain 256-bit integers, K <= N: the first K bases are used.  th and b come together or not
+    at all.  One mixed addition a non-zero window digit, no doubling.  split (tests, measurements): the lanes that share a row, a
+    power of two in [1, 256]; None: the library's rule.  Every split and both widths return the same words.  K = 0 gives identities."""
+    _ctx(ctx)
+    if (th is None) != (b is None):
+        raise ValueError("th and b: the second family needs both its tables and its scalars")
+    for t, w in ((tg, "tg"), (th, "th")):
+        if t is None:
+            continue
+        if not isinstance(t, FixedBases):
+            raise TypeError(f"{w}: expected a FixedBases, got {type(t).__name__}")
+        if t.ctx is not ctx:
+            raise ValueError(f"{w}: the tables belong to another context")
+    if th is not None and (tg.window != th.window or tg.n != th.n):
+        raise ValueError(f"tg and th: window widths {tg.window} and {th.window}, lengths {tg.n} and {th.n} differ")
+    if split is None:
+        split = 0
+    elif isinstance(split, bool) or not isinstance(split, int) or not 1 <= split <= 256 or split & (split - 1):
+        raise ValueError(f"split: a power of two in [1, 256], got {split!r}")
+    a = ctx.elems(a, what="a")
+    if a.dim() not in (2, 3):
+        raise ValueError(f"a: expected a tensor of shape (K, 4) or (rows, K, 4), got {tuple(a.shape)}")
+    rows, K = (int(a.shape[0]) if a.dim() == 3 else 1), int(a.shape[-2])
+    if K > tg.n:
+        raise ValueError(f"a: {K} terms a row against {tg.n} bases")
+    if b is not None:
+        b = ctx.elems(b, what="b")
+        if tuple(b.shape) != tuple(a.shape):
+            raise ValueError(f"a and b: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    out = _out(ctx, out, rows)
+    ctx.check(ctx.lib.hb_g1_crs_msm(ctx.h, ctx.ptr(tg.tables), ctx.ptr(th.tables) if th is not None else None, tg.n, tg.window, ctx.ptr(a),
+                                    ctx.ptr(b) if b is not None else None, K, split, ctx.ptr(out), rows, ctx.stream()), "hb_g1_crs_msm")
+    return out
+
+
+def kzg_quotients(ctx, phi, xs):
+    """phi (B, t + 1, 4): B polynomials' coefficients, canonical residues, lowest first; xs: n points, a tensor (n, 4) of canonical
+    residues or a list of ints (reduced mod R) -> (q (B, n, t, 4), rem (B, n, 4)): phi_b(X) - rem[b][i] = (X - xs[i]) sum_j q[b][i][j] X^j,
+    so rem[b][i] = phi_b(xs[i]) and q[b][i] are the exponents of the KZG witness at xs[i].  One launch, a lane a (b, i)."""
+    _ctx(ctx)
+    phi = ctx.elems(phi, what="phi")
+    if phi.dim() != 3 or phi.shape[1] < 1:
+        raise ValueError(f"phi: expected a tensor of shape (B, t + 1, {ctx.n_limbs}) with t + 1 >= 1, got {tuple(phi.shape)}")
+    if isinstance(xs, ctx.torch.Tensor):
+        xs = ctx.elems(xs, what="xs")
+        if xs.dim() != 2:
+            raise ValueError(f"xs: expected a tensor of shape (n, {ctx.n_limbs}), got {tuple(xs.shape)}")
+    else:
+        xs = ctx.upload_ints([int(x) % R for x in xs]).reshape(-1, ctx.n_limbs)
+    B, n_coef, n = int(phi.shape[0]), int(phi.shape[1]), int(xs.shape[0])
+    torch = ctx.torch
+    q = torch.empty((B, n, n_coef - 1, ctx.n_limbs), dtype=torch.int64, device=ctx.tdev)
+    rem = torch.empty((B, n, ctx.n_limbs), dtype=torch.int64, device=ctx.tdev)
+    ctx.check(ctx.lib.hb_kzg_quotient(ctx.h, ctx.ptr(phi), n_coef, ctx.ptr(xs), n, ctx.ptr(q), ctx.ptr(rem), B, ctx.stream()), "hb_kzg_quotient")
+    return q, rem
 
 
 def _batch_inverse(values):

@@ -321,6 +321,32 @@ int hb_g1_verify(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int window
 int64_t hb_g1_msm_workspace_bytes(int64_t rows, int64_t terms, int method, int chunk);
 int hb_g1_msm(hb_ctx *ctx, const uint64_t *s_dev, const uint64_t *p_dev, int points_per_row, uint64_t *out_dev, int64_t rows, int64_t terms,
               int method, int chunk, void *workspace_dev, int64_t workspace_bytes, void *stream);
+/* The prover of the constant-size (KZG) polynomial commitment in G1 (hb_crs.hip): the reference's poly_commit_const.py commit and
+ * create_witness, sums of powers of the FIXED bases gs[j] = alpha^j g, hs[j] = alpha^j h of a common reference string.  The verifier
+ * (verify_eval, batch_verify_eval) needs a pairing -- G2, Fq12 -- and is NOT in this library.
+ * hb_g1_crs_table: the window tables of n_bases bases (n_bases * 12 words in HOST memory; an identity or a point off the curve among
+ *   them: HB_ERR_BAD_ARG, as hb_g1_table) for window width 4 or 8 into tables_dev, n_bases * hb_g1_table_bytes(window) bytes aligned to
+ *   16: table k stands at byte k * hb_g1_table_bytes(window) in hb_g1_table's layout, so each is also a table for hb_g1_commit and
+ *   hb_g1_verify.  n_bases <= 4096.  Returns once bases_host is the caller's again (one synchronisation, for the upload); then ONE
+ *   launch, a base a workgroup, on `stream`.
+ * hb_kzg_quotient: synthetic division in GF(R) for count_polys polynomials of n_coef = t + 1 >= 1 coefficients (phi_dev: count_polys *
+ *   n_coef canonical residues, lowest first) by X - xs[i] for n_points points (xs_dev: canonical residues):
+ *   q[b][i][t-1] = phi[b][t], q[b][i][j-1] = phi[b][j] + xs[i] q[b][i][j], rem[b][i] = phi[b][0] + xs[i] q[b][i][0] = phi_b(xs[i]).
+ *   q_dev: count_polys * n_points * t elements (unused, and may be NULL, for t = 0), rem_dev: count_polys * n_points; canonical.
+ *   (phi_b(X) - rem[b][i]) = (X - xs[i]) sum_j q[b][i][j] X^j: q holds the exponents of the witness, rem the share.  One launch.
+ * hb_g1_crs_msm: out[m] = sum_{k < terms} a[m][k] G_k + b[m][k] H_k over the first `terms` of the n_bases tables at tg_dev and th_dev
+ *   (both built with `window`); th_dev and b_dev both NULL: one family.  a_dev, b_dev: rows * terms scalars, plain 256-bit integers.
+ *   One mixed addition a non-zero window digit, no doubling.  split: the lanes that share a row, a power of two in [1, 256] (1: a row a
+ *   lane, no LDS; above: a tree in LDS ends the row), or 0 for the library's rule (hb_crs.hip: CRS_FILL_LANES).  Every split and both
+ *   widths give the same words.  One launch.
+ * All three, HB_ERR_BAD_ARG: a null pointer, a negative count, a window other than 4 or 8, terms > n_bases, n_bases > 4096, another
+ *   split, an output overlapping an input.  A zero count returns HB_OK and launches nothing; terms == 0 fills out with identities.
+ *   Nothing is allocated; everything is asynchronous on `stream` but the table's upload.  A context over R in four limbs, as all of G1. */
+int hb_g1_crs_table(hb_ctx *ctx, const uint64_t *bases_host, int64_t n_bases, int window, void *tables_dev, void *stream);
+int hb_kzg_quotient(hb_ctx *ctx, const uint64_t *phi_dev, int n_coef, const uint64_t *xs_dev, int64_t n_points, uint64_t *q_dev,
+                    uint64_t *rem_dev, int64_t count_polys, void *stream);
+int hb_g1_crs_msm(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int64_t n_bases, int window, const uint64_t *a_dev,
+                  const uint64_t *b_dev, int64_t terms, int split, uint64_t *out_dev, int64_t rows, void *stream);
 
 /* ---- fixed-point arithmetic on shares (hb_fxp.hip) --------------------------------------------------------------------
  * progs/fixedpoint.py ("Secure Computation With Fixed-Point Numbers", Catrina and Saxena): random2m (:91-98), trunc_pr (:108-120),
@@ -919,6 +945,17 @@ int hb_selftest_g1(int what, const uint64_t *const *operands, int flags, int64_t
  * of LDS.  Arguments as hb_g1_msm; method = 3 (here only): the bucket path with EVERY non-empty bucket summed by the whole workgroup. */
 int hb_selftest_g1_msm(const uint64_t *s, const uint64_t *p, int points_per_row, uint64_t *out, int64_t rows, int64_t terms, int method,
                        int chunk);
+/* host-side run of the bodies of hb_crs.hip (no GPU needed) over host memory; arguments are checked as the device calls check them:
+ *   what = HB_G1_CRS_SELFTEST_TABLE     operands[0] = `count` bases; arg = window; out = `count` tables, as hb_g1_crs_table lays them out
+ *          HB_G1_CRS_SELFTEST_QUOTIENT  operands[0..1] = phi, xs; flags = n_coef; arg = n_points; count = polynomials;
+ *                                       out = q (count * n_points * (n_coef - 1) elements), then rem (count * n_points)
+ *          HB_G1_CRS_SELFTEST_MSM       operands[0..3] = tables of G, tables of H or NULL, a, b or NULL; flags = window | split << 8;
+ *                                       arg = terms | n_bases << 32; count = rows; out = points.  split > 1 drives a workgroup lane by
+ *                                       lane: every lane's units, the tree steps over an array in place of LDS, the first lanes' stores */
+#define HB_G1_CRS_SELFTEST_TABLE 0
+#define HB_G1_CRS_SELFTEST_QUOTIENT 1
+#define HB_G1_CRS_SELFTEST_MSM 2
+int hb_selftest_g1_crs(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count);
 /* host-side run of the fixed-point kernels' bodies (no GPU needed) over host memory, element by element.  params = {k, m, kappa,
  * nodes or mode, root}; parameters are checked as the device calls check them:
  *   what = HB_FXP_SELFTEST_MASK     operands[0..1] = x (or NULL), bits [k + kappa][count]; outs[0..1] as hb_fxp_mask writes masked_dev, r1_dev
