@@ -36,6 +36,12 @@ HB_G1_SUBTRACT, HB_G1_GENERAL, HB_G1_DOUBLE = 1, 2, 4
 HB_G1_SELFTEST_FQ_MUL, HB_G1_SELFTEST_SCALAR_MUL, HB_G1_SELFTEST_ADD, HB_G1_SELFTEST_CHECK = 0, 1, 2, 3
 HB_G1_SELFTEST_TABLE, HB_G1_SELFTEST_COMMIT, HB_G1_SELFTEST_EVAL, HB_G1_SELFTEST_VERIFY = 4, 5, 6, 7
 HB_G1_CRS_SELFTEST_TABLE, HB_G1_CRS_SELFTEST_QUOTIENT, HB_G1_CRS_SELFTEST_MSM = 0, 1, 2
+HB_PAIR_GT, HB_PAIR_VERDICT = 0, 1
+HB_PAIR_SELFTEST_TOWER, HB_PAIR_SELFTEST_PREPARE, HB_PAIR_SELFTEST_PRODUCT = 0, 1, 2
+HB_PAIR_OP_FQ2_MUL, HB_PAIR_OP_FQ2_SQR, HB_PAIR_OP_FQ2_MUL_NR, HB_PAIR_OP_FQ2_INV = 0, 1, 2, 3
+HB_PAIR_OP_FQ6_MUL, HB_PAIR_OP_FQ6_MUL_BY_01, HB_PAIR_OP_FQ6_MUL_BY_1, HB_PAIR_OP_FQ6_MUL_NR, HB_PAIR_OP_FQ6_INV = 4, 5, 6, 7, 8
+HB_PAIR_OP_FQ12_MUL, HB_PAIR_OP_FQ12_SQR, HB_PAIR_OP_FQ12_MUL_BY_014, HB_PAIR_OP_FQ12_CONJ = 9, 10, 11, 12
+HB_PAIR_OP_FQ12_FROBENIUS, HB_PAIR_OP_FQ12_INV, HB_PAIR_OP_FQ12_FINAL_EXP, HB_PAIR_OP_FQ12_CYCLO_SQR = 13, 14, 15, 16
 HB_FXP_MOD, HB_FXP_TRUNC, HB_FXP_NEG_TRUNC = 0, 1, 2
 HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
 HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
@@ -129,6 +135,9 @@ SYMBOLS = {
     "hb_g1_crs_table": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "hb_kzg_quotient": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
     "hb_g1_crs_msm": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _i, _vp, _i64, _vp]),
+    "hb_pair_table_bytes": (_i64, []),
+    "hb_pair_prepare": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "hb_pair_product": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_fxp_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hb_fxp_trunc_pr": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
     "hb_fxp_ltl_leaves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
@@ -221,6 +230,7 @@ SYMBOLS = {
     "hb_selftest_g1": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_g1_msm": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _i, _i]),
     "hb_selftest_g1_crs": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
+    "hb_selftest_pairing": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_bd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_div": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),

@@ -1,32 +1,43 @@
 """
-The PROVER of the reference's PolyCommitConst (poly_commit_const.py: the constant-size, KZG polynomial commitment HbAvssBatch uses) over
-the fixed-base kernels of g1.py (csrc/hb_crs.hip).  commit and create_witness are sums of powers of the bases of the common reference
-string, gs[j] = alpha^j g and hs[j] = alpha^j h, so they are pure G1; the reference-shaped methods keep its names and behaviour on host
-objects (bls12_381.G1, the package's polynomials and field elements) and marshal into the batch calls, which are what a dealer uses.
+The reference's PolyCommitConst (poly_commit_const.py: the constant-size, KZG polynomial commitment HbAvssBatch uses), prover and verifier,
+over the fixed-base kernels of g1.py (csrc/hb_crs.hip) and the pairing kernel of pairing.py (csrc/hb_pair.hip).  commit and
+create_witness are sums of powers of the bases of the common reference string, gs[j] = alpha^j g and hs[j] = alpha^j h, so they are pure
+G1; the reference-shaped methods keep its names and behaviour on host objects (bls12_381.G1, the package's polynomials and field
+elements) and marshal into the batch calls, which are what a dealer and a recipient use.
 
-The VERIFIER is not here.  verify_eval and batch_verify_eval compare pairings; this package has no G2 and no Fq12, so they raise
-NotImplementedError and never return a verdict.  `ghats` (the G2 half of a reference CRS) is stored untouched and may be None.
+The VERIFIER needs `ghats`, the G2 half of the CRS: [ghat, alpha ghat], host bls12_381_pairing.G2.  The reference's check
+    e(c, ghat0) == e(w, ghat1 - i ghat0) e(g0, ghat0)^share e(h0, ghat0)^aux
+is evaluated in the form
+    e(c - share g0 - aux h0 + i w, ghat0) e(-w, ghat1) == 1
+which needs no G2 operation and no power in GT: both G2 points are fixed by the CRS and PREPARED once on the host (pairing.PreparedG2),
+the left side is G1 work for the kernels already here (msm_fixed over gs[0] and hs[0], scalar_mul, sub, add, neg: five launches,
+each ending in an inversion an item: a tenth of a large batch's check), and one launch of k_pair_product runs two Miller loops that share their squarings and one final exponentiation.
+A CRS without ghats (None in the middle) keeps the prover; the three verifier methods then raise NotImplementedError.
 
 There is no CPU path: without a GPU every method that computes raises HbmpcBackendError, like the rest of the package.
 
-    crs = gen_pc_const_crs(t)                              [gs, None, hs], t + 1 bases a family
+    crs = gen_pc_const_crs(t, ghat=G2.generator())         [gs, ghats, hs], t + 1 bases a family; ghat=None: [gs, None, hs]
     pc = PolyCommitConst(crs)
     c, hat = pc.commit_batch(coeffs)                       coeffs (B, t + 1, 4) -> c (B, 2, 6), hat (B, t + 1, 4): ONE launch
     w, shares, aux = pc.witness_batch(coeffs, hat, xs)     n points -> w (B, n, 2, 6), shares (B, n, 4), aux (B, n, 4): THREE launches,
                                                            the whole double loop of HbAvssBatch._get_dealer_msg (hbavss.py:567-598)
+    ok = pc.verify_batch(c, xs, shares, aux, w)            one verdict an item -> bool tensor (B,); xs one index or one an item
 
-What is NOT checked: that the bases are powers of one alpha (a CRS is trusted), that they lie in the subgroup of order R
-(g1.in_subgroup tells), and that the coefficients handed in as tensors are canonical residues (ctx.reduce_ makes them so).
+What is NOT checked: that the bases are powers of one alpha and that ghats[1] = alpha ghats[0] for that same alpha (a CRS is trusted),
+that the bases, the commitments and the witnesses lie in the subgroup of order R (the rearranged equation equals the reference's only
+there; g1.in_subgroup tells, and it is the caller's call), and that the scalars handed in as tensors are canonical residues
+(ctx.reduce_ makes them so).
 """
 import secrets
 
-from . import g1
+from . import g1, pairing
 from ._capi import Context
 from .bls12_381 import G1, R
+from .bls12_381_pairing import G2
 from .field import GF
 from .polynomial import polynomials_over
 
-_NO_PAIRING = "needs a pairing (G2 and Fq12), which this package does not have: only the prover of PolyCommitConst runs here"
+_NO_PAIRING = "needs a pairing against ghats, and the G2 half of this CRS is missing (None): only the prover of PolyCommitConst runs on it"
 
 
 class PolyCommitConst(object):
@@ -38,6 +49,12 @@ class PolyCommitConst(object):
             for p in fam:
                 if not isinstance(p, G1):
                     raise TypeError(f"{w}: expected host G1 elements, got {type(p).__name__}")
+        if self.ghats is not None:
+            self.ghats = list(self.ghats)
+            if len(self.ghats) != 2 or not all(isinstance(p, G2) for p in self.ghats):
+                raise TypeError("ghats: expected two host G2 elements, [ghat, alpha ghat], or None")
+            if any(p.is_one() for p in self.ghats):
+                raise ValueError("ghats: the identity pairs to 1 with everything")
         self.t = len(self.gs) - 1
         self.field = GF(R) if field is None else field
         if getattr(self.field, "modulus", None) != R:
@@ -45,6 +62,8 @@ class PolyCommitConst(object):
         self._ctx = ctx
         self.window = window
         self._tables = None
+        self._vtables = None
+        self._prepared = None
 
     # ---- plumbing
     @property
@@ -129,19 +148,102 @@ class PolyCommitConst(object):
         w, _, _ = self.witness_batch(self._host_coeffs(phi, "phi"), self._host_coeffs(phi_hat, "phi_hat"), [int(i)])
         return g1.download(w)[0]
 
-    def verify_eval(self, c, i, phi_at_i, phi_hat_at_i, witness):
-        raise NotImplementedError(f"PolyCommitConst.verify_eval {_NO_PAIRING}")
-
-    def batch_verify_eval(self, commits, i, shares, auxes, witnesses):
-        raise NotImplementedError(f"PolyCommitConst.batch_verify_eval {_NO_PAIRING}")
+    # ---- the verifier
+    def _need_ghats(self, name):
+        if self.ghats is None:
+            raise NotImplementedError(f"PolyCommitConst.{name} {_NO_PAIRING}")
 
     def preprocess_verifier(self, level=4):
-        raise NotImplementedError(f"PolyCommitConst.preprocess_verifier {_NO_PAIRING}")
+        """prepare ghats[0] and ghats[1] for the Miller loop and build the tables of gs[0] and hs[0] now (the reference's
+        gg.preprocess(level), gh.preprocess(level)).  level: the window width of those two tables when it is 4 or 8, else ignored."""
+        self._need_ghats("preprocess_verifier")
+        if level in (4, 8) and level != self.window and self._tables is None:
+            self.window = level
+            self._vtables = None
+        self._verifier_state()
+
+    def _verifier_state(self):
+        """-> (tables with gs[0], tables with hs[0], prepared ghats[0], prepared ghats[1])"""
+        ctx = self.ctx
+        if self._prepared is None:
+            self._prepared = (pairing.PreparedG2(ctx, self.ghats[0]), pairing.PreparedG2(ctx, self.ghats[1]))
+        if self._tables is not None:
+            tg, th = self._tables
+        else:
+            if self._vtables is None:
+                self._vtables = (g1.FixedBases(ctx, self.gs[:1], self.window), g1.FixedBases(ctx, self.hs[:1], self.window))
+            tg, th = self._vtables
+        return tg, th, self._prepared[0], self._prepared[1]
+
+    def verify_lhs(self, commits, xs, shares, auxes, witnesses):
+        """-> (A, -w), (B, 2, 6) each: A[b] = c[b] - shares[b] g0 - auxes[b] h0 + xs[b] w[b], composed from msm_fixed, scalar_mul
+        and add.  Shapes as verify_batch."""
+        self._need_ghats("verify_lhs")
+        ctx = self.ctx
+        tg, th, _, _ = self._verifier_state()
+        c = g1._points(ctx, commits, what="commits")
+        B = g1._n(c)
+        w = g1._points(ctx, witnesses, B, what="witnesses")
+        sh = ctx.elems(shares, B, what="shares").reshape(B, 1, ctx.n_limbs)
+        au = ctx.elems(auxes, B, what="auxes").reshape(B, 1, ctx.n_limbs)
+        if isinstance(xs, ctx.torch.Tensor):
+            xs = ctx.elems(xs, what="xs")
+            if xs.numel() // ctx.n_limbs not in (1, B):
+                raise ValueError(f"xs: one index or {B}, got {xs.numel() // ctx.n_limbs}")
+        elif isinstance(xs, (list, tuple)):
+            if len(xs) not in (1, B):
+                raise ValueError(f"xs: one index or {B}, got {len(xs)}")
+            xs = ctx.upload_ints([int(x) % R for x in xs])
+        else:
+            xs = ctx.upload_ints([int(xs) % R])
+        c, w = c.reshape(B, 2, g1.LIMBS), w.reshape(B, 2, g1.LIMBS)
+        opened = g1.msm_fixed(ctx, tg, sh, th, au)
+        lhs = g1.add(ctx, g1.sub(ctx, c, opened), g1.scalar_mul(ctx, xs, w)) if B else c
+        return lhs, g1.neg(ctx, w)
+
+    def verify_batch(self, commits, xs, shares, auxes, witnesses):
+        """commits (B, 2, 6), shares and auxes (B, 4), witnesses (B, 2, 6); xs: ONE index (an int, or a tensor (1, 4)) or one an item
+        (a list of B ints, or a tensor (B, 4)) -> bool tensor (B,): verdict[b] = the reference's verify_eval(commits[b], xs[b],
+        shares[b], auxes[b], witnesses[b]) for points of the subgroup of order R (see the module's head for what is not checked).
+        Six launches: five for the left side in G1, one for two Miller loops and a final exponentiation an item."""
+        self._need_ghats("verify_batch")
+        ctx = self.ctx
+        _, _, p0, p1 = self._verifier_state()
+        lhs, nw = self.verify_lhs(commits, xs, shares, auxes, witnesses)
+        ok, _ = pairing.product_is_one(ctx, [(lhs, p0), (nw, p1)])
+        return ok
+
+    def verify_eval(self, c, i, phi_at_i, phi_hat_at_i, witness):
+        """-> bool, on host objects, as the reference's verify_eval"""
+        self._need_ghats("verify_eval")
+        ctx = self.ctx
+        ok = self.verify_batch(g1.upload([c], ctx), int(i), ctx.upload_ints([int(phi_at_i) % R]), ctx.upload_ints([int(phi_hat_at_i) % R]),
+                               g1.upload([witness], ctx))
+        return bool(ok[0].item())
+
+    def batch_verify_eval(self, commits, i, shares, auxes, witnesses):
+        """-> bool, with the reference's semantics EXACTLY: ONE check of the product of the commitments and the product of the witnesses
+        against the sums of the shares and of the auxes, all at index i.  There is NO random linear combination: errors that cancel
+        in the sums pass, as they do in the reference; verify_batch gives a verdict an item.  An empty batch is True."""
+        self._need_ghats("batch_verify_eval")
+        commits, shares, auxes, witnesses = list(commits), list(shares), list(auxes), list(witnesses)
+        assert len(commits) == len(shares) and len(commits) == len(witnesses) and len(commits) == len(auxes)
+        n = len(commits)
+        if n == 0:
+            return True
+        ctx = self.ctx
+        ones = ctx.upload_ints([1] * n).reshape(1, n, ctx.n_limbs)
+        cprod = g1.msm(ctx, ones, g1.upload(commits, ctx))
+        wprod = g1.msm(ctx, ones, g1.upload(witnesses, ctx))
+        ssum, asum = sum(int(v) for v in shares) % R, sum(int(v) for v in auxes) % R
+        ok = self.verify_batch(cprod, int(i), ctx.upload_ints([ssum]), ctx.upload_ints([asum]), wprod)
+        return bool(ok[0].item())
 
 
-def gen_pc_const_crs(t, alpha=None, g=None, h=None, ctx=None):
-    """-> [gs, None, hs]: gs[j] = alpha^j g, hs[j] = alpha^j h, j <= t, host G1; one batched g1.scalar_mul a family.  The middle entry is
-    the reference's ghats, two points of G2, which this package cannot make.  alpha=None is drawn with `secrets` and not kept: whoever
+def gen_pc_const_crs(t, alpha=None, g=None, h=None, ctx=None, ghat=None):
+    """-> [gs, ghats, hs]: gs[j] = alpha^j g, hs[j] = alpha^j h, j <= t, host G1; one batched g1.scalar_mul a family.  The middle entry is
+    the reference's ghats: [ghat, ghat ** alpha] for a host G2 `ghat` (computed by the host model; not the identity), or None for
+    ghat=None, which leaves a CRS for the prover alone.  alpha=None is drawn with `secrets` and not kept: whoever
     knows it can open a commitment to anything.  alpha = 0 mod R is refused: identity bases have no table.  g, h: default to two
     independent points derived from fixed seeds (the reference derives BOTH from one seed, so that h = g there)."""
     assert type(t) is int and t >= 0
@@ -157,6 +259,11 @@ def gen_pc_const_crs(t, alpha=None, g=None, h=None, ctx=None):
             raise TypeError(f"{w}: expected a host G1, got {type(p).__name__}")
         if p.is_one():
             raise ValueError(f"{w}: the identity has no table")
+    if ghat is not None:
+        if not isinstance(ghat, G2):
+            raise TypeError(f"ghat: expected a host G2, got {type(ghat).__name__}")
+        if ghat.is_one():
+            raise ValueError("ghat: the identity pairs to 1 with everything")
     if ctx is None:
         ctx = Context.get(R)
     powers, run = [], 1
@@ -164,4 +271,5 @@ def gen_pc_const_crs(t, alpha=None, g=None, h=None, ctx=None):
         powers.append(run)
         run = run * alpha % R
     ks = ctx.upload_ints(powers)
-    return [g1.download(g1.scalar_mul(ctx, ks, g)), None, g1.download(g1.scalar_mul(ctx, ks, h))]
+    ghats = None if ghat is None else [ghat, ghat ** alpha]
+    return [g1.download(g1.scalar_mul(ctx, ks, g)), ghats, g1.download(g1.scalar_mul(ctx, ks, h))]

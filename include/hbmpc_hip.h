@@ -348,6 +348,32 @@ int hb_kzg_quotient(hb_ctx *ctx, const uint64_t *phi_dev, int n_coef, const uint
 int hb_g1_crs_msm(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int64_t n_bases, int window, const uint64_t *a_dev,
                   const uint64_t *b_dev, int64_t terms, int split, uint64_t *out_dev, int64_t rows, void *stream);
 
+/* ---- pairings against prepared G2 points (hb_pair.hip) ------------------------------------------------------------------
+ * The verifier of the KZG commitment (poly_commit_const.py:28-44): products of BLS12-381 pairings whose G2 arguments are fixed.  A G2
+ * point is PREPARED on the host (bls12_381_pairing.prepare_g2: the 68 line-coefficient triples of the ate loop, 63 doublings and 5
+ * additions in the order the loop reads them) and uploaded once; the device does no G2 arithmetic.  A GT element is 72 words: twelve
+ * canonical residues below Q of 6 little-endian words each, in the order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1 of the tower
+ * Fq2 = Fq[u]/(u^2 + 1), Fq6 = Fq2[v]/(v^3 - 1 - u), Fq12 = Fq6[w]/(w^2 - v).  It is the reference crate's pairing value: the Miller
+ * value to the power 3 (Q^12 - 1) / R.
+ * hb_pair_table_bytes: the bytes of one prepared table (its layout belongs to the library).
+ * hb_pair_prepare: n_coeffs = 204 Fq2 coefficients in HOST memory (68 triples; an Fq2 is c0 then c1, 6 words each, below Q; another
+ *   count or a residue not below Q: HB_ERR_BAD_ARG) into table_dev, hb_pair_table_bytes() bytes.  Returns once coeffs_host is the caller's
+ *   again (one synchronisation, for the upload).
+ * hb_pair_product: out[m] = FE(prod_k ML(P[m][k], Q_k)) for k < K, 1 <= K <= 4: tables_dev a HOST array of K device tables, points_dev
+ *   (count, K, 12) words as all of G1 takes points; an identity point contributes 1.  mode = HB_PAIR_GT: out_dev receives the GT elements,
+ *   72 words an item (flags_dev and rejected_dev unused).  mode = HB_PAIR_VERDICT: flags_dev[m] = 1 if the product is 1 and every point
+ *   of the item passes hb_g1_check's test, else 0, and *rejected_dev is incremented once a rejected item (the caller zeroes it; out_dev
+ *   unused).  Membership of a point in the subgroup of order R is NOT checked.  One launch.
+ * HB_ERR_BAD_ARG: a null pointer, a negative count, K outside 1..4, another mode, an output overlapping an input.  A zero count returns
+ *   HB_OK and launches nothing.  Nothing is allocated on the device; everything is asynchronous on `stream` but the table's upload.  A
+ *   context over R in four limbs, as all of G1. */
+#define HB_PAIR_GT 0
+#define HB_PAIR_VERDICT 1
+int64_t hb_pair_table_bytes(void);
+int hb_pair_prepare(hb_ctx *ctx, const uint64_t *coeffs_host, int64_t n_coeffs, void *table_dev, void *stream);
+int hb_pair_product(hb_ctx *ctx, const void *const *tables_dev, int K, const uint64_t *points_dev, int mode, uint64_t *out_dev,
+                    int32_t *flags_dev, int32_t *rejected_dev, int64_t count, void *stream);
+
 /* ---- fixed-point arithmetic on shares (hb_fxp.hip) --------------------------------------------------------------------
  * progs/fixedpoint.py ("Secure Computation With Fixed-Point Numbers", Catrina and Saxena): random2m (:91-98), trunc_pr (:108-120),
  * get_carry_bit / bit_ltl (:131-172), div2m (:184-193), trunc (:208-211) and FixedPoint.ltz (:266-268) for arrays of `count` values.
@@ -956,6 +982,37 @@ int hb_selftest_g1_msm(const uint64_t *s, const uint64_t *p, int points_per_row,
 #define HB_G1_CRS_SELFTEST_QUOTIENT 1
 #define HB_G1_CRS_SELFTEST_MSM 2
 int hb_selftest_g1_crs(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count);
+/* host-side run of the bodies of hb_pair.hip and hb_fq12_elem.hpp (no GPU needed) over host memory, item by item; also derives the
+ * Frobenius constants from Q and compares them with the literals (a difference: HB_ERR_BAD_ARG whatever is asked):
+ *   what = HB_PAIR_SELFTEST_TOWER    operands[0..1] = a, b: 72 words an item, residues below Q; flags = HB_PAIR_OP_*; out = 72 words an
+ *                                    item.  An operation of Fq2 or Fq6 works on the leading coordinates and copies the rest of a.
+ *                                    MUL_BY_01 / MUL_BY_1 / MUL_BY_014 take their sparse factor's Fq2 coefficients from the head of b.
+ *                                    FROBENIUS: arg = 1, 2 or 3.  FINAL_EXP: out = a^(3 (Q^12 - 1) / R).
+ *                                    CYCLO_SQR: Granger and Scott's squaring, a square only for a in the cyclotomic subgroup.
+ *          HB_PAIR_SELFTEST_PREPARE  operands[0] = the 204 Fq2 coefficients hb_pair_prepare takes; count = 1; out = the table
+ *          HB_PAIR_SELFTEST_PRODUCT  operands[0] = points (count, K, 12), operands[1..K] = tables; flags = K; arg = mode; out = GT
+ *                                    elements, or `count` int32 verdicts then the int32 count of rejected items */
+#define HB_PAIR_SELFTEST_TOWER 0
+#define HB_PAIR_SELFTEST_PREPARE 1
+#define HB_PAIR_SELFTEST_PRODUCT 2
+#define HB_PAIR_OP_FQ2_MUL 0
+#define HB_PAIR_OP_FQ2_SQR 1
+#define HB_PAIR_OP_FQ2_MUL_NR 2
+#define HB_PAIR_OP_FQ2_INV 3
+#define HB_PAIR_OP_FQ6_MUL 4
+#define HB_PAIR_OP_FQ6_MUL_BY_01 5
+#define HB_PAIR_OP_FQ6_MUL_BY_1 6
+#define HB_PAIR_OP_FQ6_MUL_NR 7
+#define HB_PAIR_OP_FQ6_INV 8
+#define HB_PAIR_OP_FQ12_MUL 9
+#define HB_PAIR_OP_FQ12_SQR 10
+#define HB_PAIR_OP_FQ12_MUL_BY_014 11
+#define HB_PAIR_OP_FQ12_CONJ 12
+#define HB_PAIR_OP_FQ12_FROBENIUS 13
+#define HB_PAIR_OP_FQ12_INV 14
+#define HB_PAIR_OP_FQ12_FINAL_EXP 15
+#define HB_PAIR_OP_FQ12_CYCLO_SQR 16
+int hb_selftest_pairing(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count);
 /* host-side run of the fixed-point kernels' bodies (no GPU needed) over host memory, element by element.  params = {k, m, kappa,
  * nodes or mode, root}; parameters are checked as the device calls check them:
  *   what = HB_FXP_SELFTEST_MASK     operands[0..1] = x (or NULL), bits [k + kappa][count]; outs[0..1] as hb_fxp_mask writes masked_dev, r1_dev
