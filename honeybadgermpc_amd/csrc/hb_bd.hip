@@ -72,8 +72,7 @@ template <int NL, int NW> HB_HD void bd_fold_elem(uint32_t (&gw)[NW], uint32_t (
 template <int NL, int NW> HB_HD void bd_sum0_elem(uint32_t (&o)[NW], uint32_t a, const uint32_t (&bw)[NW], const FpParams<NL> &P) {
     uint32_t b[NL], one[NL], nb[NL];
     unpack<NL, NW>(b, bw);
-#pragma unroll
-    for (int q = 0; q < NL; q++) one[q] = q == 0 ? 1u : 0u;
+    small_digits<NL>(one, 1);
     fp_sub<NL>(nb, one, b, P);
 #pragma unroll
     for (int q = 0; q < NL; q++) nb[q] = a ? nb[q] : b[q];

@@ -196,7 +196,7 @@ template <int NL> struct DivProductArgs {
     const uint32_t *opened, *ta, *tb, *tab, *aux, *nxt_a, *nxt_b, *bits;
     uint32_t *out0, *out1;
     int mode, products, nbits, m;
-    FxpConst<NL> cst, half;
+    FpConst<NL> cst, half;
 };
 
 struct DivProductRow {
@@ -249,7 +249,7 @@ template <int NL> struct DivTruncArgs {
     const uint32_t *opened, *s, *x_in, *ext0, *ext1, *ta, *tb;
     uint32_t *out;
     int mode, rows, products, m;
-    FxpConst<NL> invm, alpha;
+    FpConst<NL> invm, alpha;
 };
 
 struct DivTruncRow {
@@ -315,28 +315,18 @@ static bool div_trunc_ok(int bits, int mode, int rows, int products, int m) {
     }
 }
 
-// one canonical element in host memory -> canonical digits; false if it is not below p
-template <int NL, int NW> static bool div_host_digits(uint32_t (&r)[NL], const FpParams<NL> &P, const uint64_t *host) {
-    uint32_t w[NW];
-    memcpy(w, host, NW * 4);
-    unpack<NL, NW>(r, w);
-    for (int i = NL - 1; i >= 0; i--)
-        if (r[i] != P.p[i]) return r[i] < P.p[i];
-    return false;
-}
-
 template <int NL>
 static bool div_product_consts(DivProductArgs<NL> &A, const FpParams<NL> &P, const uint64_t *cst_host, int width) {
     for (int q = 0; q < NL; q++) { A.cst.d[q] = 0; A.half.d[q] = 0; }
     if (A.mode == HB_DIV_FIRST || A.mode == HB_DIV_TRUNC) fxp_pow2<NL>(A.half.d, width - 1, false, P);
-    if (A.mode == HB_DIV_FIRST || (A.mode == HB_DIV_NORM && A.nxt_a)) return div_host_digits<NL, words_of(NL)>(A.cst.d, P, cst_host);
+    if (A.mode == HB_DIV_FIRST || (A.mode == HB_DIV_NORM && A.nxt_a)) return host_digits<NL, words_of(NL)>(A.cst.d, P, cst_host);
     return true;
 }
 template <int NL>
 static bool div_trunc_consts(DivTruncArgs<NL> &A, const FpParams<NL> &P, const uint64_t *inv2m_host, const uint64_t *alpha_host) {
     for (int q = 0; q < NL; q++) A.alpha.d[q] = 0;
-    if (!fxp_host_mont<NL, words_of(NL)>(A.invm.d, P, inv2m_host)) return false;
-    return A.mode == HB_DIV_T_GOLD ? div_host_digits<NL, words_of(NL)>(A.alpha.d, P, alpha_host) : true;
+    if (!host_mont<NL, words_of(NL)>(A.invm.d, P, inv2m_host)) return false;
+    return A.mode == HB_DIV_T_GOLD ? host_digits<NL, words_of(NL)>(A.alpha.d, P, alpha_host) : true;
 }
 
 // host: the same rows over `count` elements

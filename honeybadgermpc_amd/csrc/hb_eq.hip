@@ -7,24 +7,27 @@
 // three opens: (diff r, rp rp) together, then _b rp^2, then c itself.  Preprocessing arrives as planes: row j of a plane holds test
 // bit j's value of every element, so a wave's loads of a row cover consecutive elements.
 //
-// k_legendre     out[i] = legendre(a_i) in {-1, 0, 1} as int8: a^((p-1)/2) against one and minus one in Montgomery form.  The exponent
+// The steps are rows under the generic kernel k_rows (hb_rows.hpp):
+// EqLegendreRow  out[i] = legendre(a_i) in {-1, 0, 1} as int8: a^((p-1)/2) against one and minus one in Montgomery form.  The exponent
 //                is the same for every lane: the host derives ONE sliding-window schedule from p (window 3: the odd powers a, a^3, a^5,
 //                a^7 stay in registers) and hands it to the kernel by value, so its steps sit in SGPRs and the chain has no divergence.
 //                254 squarings and 64 + 4 products for the BLS12-381 scalar field against 254 + ~127 bit by bit.  A zero skips the chain.
-// k_eq_mask1     diff = x - y (y may be absent: a test against zero), then the four masked differences of the first two Beaver products
+// EqMask1Row     diff = x - y (y may be absent: a test against zero), then the four masked differences of the first two Beaver products
 //                of every test bit into ONE array to open, (4, rows, count): diff - pa, r - qa, rp - pb, rp - qb.
-// k_eq_mid       that array opened: [diff r] and [rp^2] by ew_beaver_elem, _b = nr - (nr - 1) [b] (one product by a public constant),
+// EqMidRow       that array opened: [diff r] and [rp^2] by ew_beaver_elem, _b = nr - (nr - 1) [b] (one product by a public constant),
 //                the next array to open (2, rows, count): _b - pc, [rp^2] - qc, and the plane [diff r].
-// k_eq_cshare    [c] = [diff r] + beaver(opened2, triple c): the third array to open.
-// k_eq_finish    c opened: the Legendre chain of k_legendre and the affine map of the mode in the same launch,
+// EqCshareRow    [c] = [diff r] + beaver(opened2, triple c): the third array to open.
+// EqFinishRow    c opened: the Legendre chain of EqLegendreRow and the affine map of the mode in the same launch,
 //                   HB_EQ_BIT        (1 - L) / 2 + L [b]                              a share of exactly 1 or 0
 //                   HB_EQ_REFERENCE  L (nr + L) / 2 - (L (nr - 1) / 2) [b]            the reference's expression (nr = 5 there)
 //                and zero_rows[row] = 1 where some c of the row is 0 (plain vector stores; every writer stores the same value).
 //
-// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions: the __global__ wrappers only
-// load, call them and store, and hb_selftest_eq runs the very same functions on the host.
+// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions; a step's row -- which operands it
+// loads, which body it calls, where it stores -- is an HB_HD function over a memory policy, so hb_selftest_eq runs on the host the very
+// rows, arithmetic and addressing, that k_rows runs on the device.  The int8 symbols and zero_rows are not packed elements: the rows
+// store them directly, which is the same statement on the host and on the device.
 //
-// Launch shape (all kernels): 256-thread workgroups, one element a thread in x, the test bit (row) in blockIdx.y.  No LDS, no grid
+// Launch shape (all steps): 256-thread workgroups, one element a thread in x, the test bit (row) in blockIdx.y.  No LDS, no grid
 // stride, one launch a call.  diff is one subtraction and is recomputed by each row's thread from x and y (which stay in L2) rather
 // than stored as a plane of its own.  Planes, triples and opened values are read once: the 32-byte width takes the non-temporal
 // loads, as k_ew_beaver.
@@ -88,8 +91,6 @@ template <int NL, int NW> HB_HD int eq_legendre_elem(const uint32_t (&aw)[NW], c
     unpack<NL, NW>(a, aw);
     return eq_legendre<NL>(a, S, P);
 }
-
-// o = v - a on packed words
 
 // the four masked differences of one test bit of one element; HAS_Y = false: diff = x
 template <int NL, int NW, bool HAS_Y>
@@ -160,92 +161,94 @@ HB_HD int eq_finish_elem(uint32_t (&o)[NW], const uint32_t (&cw)[NW], const uint
     return L;
 }
 
-// ---------------------------------------------------------------- kernels
-// read-once operands (planes, triples, what was just opened)
+// ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
+// Row y is test bit y: element e = y * count + i of a plane of rows * count elements.  Every row issues all its loads ahead of its
+// first store, so where the header allows an output to be an input a thread reads its element before it writes it.
+struct EqLegendreArgs { EqSched S; const uint32_t *a; int8_t *out; };
 
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_legendre(const FpParams<NL> P, const EqSched S, const uint32_t *__restrict__ a, int8_t *__restrict__ out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t aw[NW];
-    load_words<NW>(aw, a + i * NW);
-    out[i] = (int8_t)eq_legendre_elem<NL, NW>(aw, S, P);
-}
+struct EqLegendreRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const EqLegendreArgs &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t aw[NW];
+        mem.load(aw, A.a, i);
+        A.out[i] = (int8_t)eq_legendre_elem<NL, NW>(aw, A.S, P);              // one byte an element: a plain store, no packed element
+    }
+};
 
 // masked: (4, rows, count), an array of its own
-template <int NL, int NW, bool HAS_Y>
-__global__ void __launch_bounds__(256) k_eq_mask1(const FpParams<NL> P, const uint32_t *__restrict__ x, const uint32_t *__restrict__ y, const uint32_t *__restrict__ r,
-                                                  const uint32_t *__restrict__ rp, const uint32_t *__restrict__ pa, const uint32_t *__restrict__ qa,
-                                                  const uint32_t *__restrict__ pb, const uint32_t *__restrict__ qb, uint32_t *__restrict__ masked, int64_t rows,
-                                                  int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t e = ((int64_t)blockIdx.y * count + i) * NW, plane = rows * count * NW;
-    uint32_t xw[NW], yw[NW], rw[NW], rpw[NW], paw[NW], qaw[NW], pbw[NW], qbw[NW], o0[NW], o1[NW], o2[NW], o3[NW];
-    load_words<NW>(xw, x + i * NW);
-    if constexpr (HAS_Y) load_words<NW>(yw, y + i * NW);
-    else {
+struct EqMask1Args { const uint32_t *x, *y, *r, *rp, *pa, *qa, *pb, *qb; uint32_t *masked; int64_t rows; };
+
+template <bool HAS_Y> struct EqMask1Row {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const EqMask1Args &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t e = (int64_t)y * count + i, plane = A.rows * count;
+        uint32_t xw[NW], yw[NW], rw[NW], rpw[NW], paw[NW], qaw[NW], pbw[NW], qbw[NW], o0[NW], o1[NW], o2[NW], o3[NW];
+        mem.load(xw, A.x, i);
+        if constexpr (HAS_Y) mem.load(yw, A.y, i);
+        else {
 #pragma unroll
-        for (int q = 0; q < NW; q++) yw[q] = 0;
+            for (int q = 0; q < NW; q++) yw[q] = 0;
+        }
+        mem.once(rw, A.r, e); mem.once(rpw, A.rp, e);
+        mem.once(paw, A.pa, e); mem.once(qaw, A.qa, e); mem.once(pbw, A.pb, e); mem.once(qbw, A.qb, e);
+        eq_mask1_elem<NL, NW, HAS_Y>(o0, o1, o2, o3, xw, yw, rw, rpw, paw, qaw, pbw, qbw, P);
+        mem.store(A.masked, e, o0);
+        mem.store(A.masked, plane + e, o1);
+        mem.store(A.masked, 2 * plane + e, o2);
+        mem.store(A.masked, 3 * plane + e, o3);
     }
-    load_once<NW>(rw, r + e); load_once<NW>(rpw, rp + e);
-    load_once<NW>(paw, pa + e); load_once<NW>(qaw, qa + e); load_once<NW>(pbw, pb + e); load_once<NW>(qbw, qb + e);
-    eq_mask1_elem<NL, NW, HAS_Y>(o0, o1, o2, o3, xw, yw, rw, rpw, paw, qaw, pbw, qbw, P);
-    store_words<NW>(masked + e, o0);
-    store_words<NW>(masked + plane + e, o1);
-    store_words<NW>(masked + 2 * plane + e, o2);
-    store_words<NW>(masked + 3 * plane + e, o3);
-}
+};
 
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_eq_mid(const FpParams<NL> P, const uint32_t *__restrict__ opened, const uint32_t *__restrict__ pa, const uint32_t *__restrict__ qa,
-                                                const uint32_t *__restrict__ pqa, const uint32_t *__restrict__ pb, const uint32_t *__restrict__ qb,
-                                                const uint32_t *__restrict__ pqb, const uint32_t *__restrict__ bits, const uint32_t *__restrict__ pc,
-                                                const uint32_t *__restrict__ qc, const EqMidConsts<NL> K, uint32_t *__restrict__ masked2, uint32_t *__restrict__ dr,
-                                                int64_t rows, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t e = ((int64_t)blockIdx.y * count + i) * NW, plane = rows * count * NW;
-    uint32_t o0[NW], o1[NW], o2[NW], o3[NW], paw[NW], qaw[NW], pqaw[NW], pbw[NW], qbw[NW], pqbw[NW], bw[NW], pcw[NW], qcw[NW], m0[NW], m1[NW], drw[NW];
-    load_once<NW>(o0, opened + e); load_once<NW>(o1, opened + plane + e); load_once<NW>(o2, opened + 2 * plane + e); load_once<NW>(o3, opened + 3 * plane + e);
-    load_once<NW>(paw, pa + e); load_once<NW>(qaw, qa + e); load_once<NW>(pqaw, pqa + e);
-    load_once<NW>(pbw, pb + e); load_once<NW>(qbw, qb + e); load_once<NW>(pqbw, pqb + e);
-    load_words<NW>(bw, bits + e); load_once<NW>(pcw, pc + e); load_words<NW>(qcw, qc + e);
-    eq_mid_elem<NL, NW>(m0, m1, drw, o0, o1, o2, o3, paw, qaw, pqaw, pbw, qbw, pqbw, bw, pcw, qcw, K, P);
-    store_words<NW>(masked2 + e, m0);
-    store_words<NW>(masked2 + plane + e, m1);
-    store_words<NW>(dr + e, drw);
-}
+// opened: (4, rows, count); masked2: (2, rows, count)
+template <int NL> struct EqMidArgs { const uint32_t *opened, *pa, *qa, *pqa, *pb, *qb, *pqb, *bits, *pc, *qc; uint32_t *masked2, *dr; int64_t rows; EqMidConsts<NL> K; };
 
-// c may be dr (a thread reads its element before it writes it): no __restrict__ on the two
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_eq_cshare(const FpParams<NL> P, const uint32_t *__restrict__ opened2, const uint32_t *dr, const uint32_t *__restrict__ pc,
-                                                   const uint32_t *__restrict__ qc, const uint32_t *__restrict__ pqc, uint32_t *c, int64_t rows, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t e = ((int64_t)blockIdx.y * count + i) * NW, plane = rows * count * NW;
-    uint32_t dw[NW], ew[NW], drw[NW], pcw[NW], qcw[NW], pqcw[NW], ow[NW];
-    load_once<NW>(dw, opened2 + e); load_once<NW>(ew, opened2 + plane + e);
-    load_words<NW>(drw, dr + e);
-    load_once<NW>(pcw, pc + e); load_once<NW>(qcw, qc + e); load_once<NW>(pqcw, pqc + e);
-    eq_cshare_elem<NL, NW>(ow, drw, dw, ew, pcw, qcw, pqcw, P);
-    store_words<NW>(c + e, ow);
-}
+struct EqMidRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const EqMidArgs<NL> &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t e = (int64_t)y * count + i, plane = A.rows * count;
+        uint32_t o0[NW], o1[NW], o2[NW], o3[NW], paw[NW], qaw[NW], pqaw[NW], pbw[NW], qbw[NW], pqbw[NW], bw[NW], pcw[NW], qcw[NW], m0[NW], m1[NW], drw[NW];
+        mem.once(o0, A.opened, e); mem.once(o1, A.opened, plane + e); mem.once(o2, A.opened, 2 * plane + e); mem.once(o3, A.opened, 3 * plane + e);
+        mem.once(paw, A.pa, e); mem.once(qaw, A.qa, e); mem.once(pqaw, A.pqa, e);
+        mem.once(pbw, A.pb, e); mem.once(qbw, A.qb, e); mem.once(pqbw, A.pqb, e);
+        mem.load(bw, A.bits, e); mem.once(pcw, A.pc, e); mem.load(qcw, A.qc, e);
+        eq_mid_elem<NL, NW>(m0, m1, drw, o0, o1, o2, o3, paw, qaw, pqaw, pbw, qbw, pqbw, bw, pcw, qcw, A.K, P);
+        mem.store(A.masked2, e, m0);
+        mem.store(A.masked2, plane + e, m1);
+        mem.store(A.dr, e, drw);
+    }
+};
 
-// factor may be c or bits (a thread reads its element before it writes it)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_eq_finish(const FpParams<NL> P, const EqSched S, const EqFinishConsts<NL> K, const uint32_t *c, const uint32_t *bits,
-                                                   uint32_t *factor, int32_t *__restrict__ zero_rows, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t e = ((int64_t)blockIdx.y * count + i) * NW;
-    uint32_t cw[NW], bw[NW], ow[NW];
-    load_words<NW>(cw, c + e);
-    load_words<NW>(bw, bits + e);
-    const int L = eq_finish_elem<NL, NW>(ow, cw, bw, S, K, P);
-    store_words<NW>(factor + e, ow);
-    if (L == 0) zero_rows[blockIdx.y] = 1;
-}
+// opened2: (2, rows, count); c may be dr
+struct EqCshareArgs { const uint32_t *opened2, *dr, *pc, *qc, *pqc; uint32_t *c; int64_t rows; };
+
+struct EqCshareRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const EqCshareArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t e = (int64_t)y * count + i, plane = A.rows * count;
+        uint32_t dw[NW], ew[NW], drw[NW], pcw[NW], qcw[NW], pqcw[NW], ow[NW];
+        mem.once(dw, A.opened2, e); mem.once(ew, A.opened2, plane + e);
+        mem.load(drw, A.dr, e);
+        mem.once(pcw, A.pc, e); mem.once(qcw, A.qc, e); mem.once(pqcw, A.pqc, e);
+        eq_cshare_elem<NL, NW>(ow, drw, dw, ew, pcw, qcw, pqcw, P);
+        mem.store(A.c, e, ow);
+    }
+};
+
+// factor may be c or bits; zero_rows: one int32 a row
+template <int NL> struct EqFinishArgs { EqSched S; const uint32_t *c, *bits; uint32_t *factor; int32_t *zero_rows; EqFinishConsts<NL> K; };
+
+struct EqFinishRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const EqFinishArgs<NL> &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t e = (int64_t)y * count + i;
+        uint32_t cw[NW], bw[NW], ow[NW];
+        mem.load(cw, A.c, e);
+        mem.load(bw, A.bits, e);
+        const int L = eq_finish_elem<NL, NW>(ow, cw, bw, A.S, A.K, P);
+        mem.store(A.factor, e, ow);
+        if (L == 0) A.zero_rows[y] = 1;                                         // a plain store; every writer stores the same value
+    }
+};
 
 // ---------------------------------------------------------------- host side
 static bool eq_make_sched(EqSched &S, const uint64_t *p_limbs, int n_limbs) {
@@ -283,39 +286,28 @@ static bool eq_make_sched(EqSched &S, const uint64_t *p_limbs, int n_limbs) {
     return true;
 }
 
-// one canonical element in host memory -> digits; false if it is not below p
-template <int NL, int NW> static bool eq_host_digits(uint32_t (&d)[NL], const FpParams<NL> &P, const uint64_t *host) {
-    uint32_t w[NW];
-    memcpy(w, host, NW * 4);
-    unpack<NL, NW>(d, w);
-    for (int i = NL - 1; i >= 0; i--)
-        if (d[i] != P.p[i]) return d[i] < P.p[i];
-    return false;
-}
-template <int NL> static void eq_small(uint32_t (&r)[NL], uint32_t v) {
-    for (int q = 0; q < NL; q++) r[q] = q == 0 ? v : 0u;
-}
 // nr must be a residue class other than 0 and 1 (that it is a NON-residue is the caller's business: share_comparison.check_nonresidue)
-template <int NL, int NW> static bool eq_mid_consts(EqMidConsts<NL> &K, const FpParams<NL> &P, const uint64_t *nr_host) {
+template <int NL> static bool eq_mid_consts(EqMidConsts<NL> &K, const FpParams<NL> &P, const uint64_t *nr_host) {
     uint32_t one[NL], t[NL];
-    if (!eq_host_digits<NL, NW>(K.nr, P, nr_host)) return false;
-    eq_small<NL>(one, 1);
+    if (!host_digits<NL, words_of(NL)>(K.nr, P, nr_host)) return false;
+    small_digits<NL>(one, 1);
     if (fp_is_zero<NL>(K.nr) || fp_eq<NL>(K.nr, one)) return false;
     fp_sub<NL>(t, K.nr, one, P);
     to_mont<NL>(K.nm1m, t, P);
     return true;
 }
-template <int NL, int NW> static bool eq_finish_consts(EqFinishConsts<NL> &K, const FpParams<NL> &P, const uint64_t *p_limbs, int n_limbs, int mode, const uint64_t *nr_host) {
+template <int NL> static bool eq_finish_consts(EqFinishConsts<NL> &K, const FpParams<NL> &P, const uint64_t *p_limbs, int n_limbs, int mode, const uint64_t *nr_host) {
+    constexpr int NW = words_of(NL);
     uint32_t one[NL], zero[NL];
-    eq_small<NL>(one, 1);
-    eq_small<NL>(zero, 0);
+    small_digits<NL>(one, 1);
+    small_digits<NL>(zero, 0);
     if (mode == HB_EQ_BIT) {                                              // L = 1: [b];  L = -1: 1 - [b]
         fp_set<NL>(K.a_pos, zero); fp_set<NL>(K.b_pos, P.one);
         fp_set<NL>(K.a_neg, one); fp_neg<NL>(K.b_neg, P.one, P);
         return true;
     }
     EqMidConsts<NL> M;
-    if (!eq_mid_consts<NL, NW>(M, P, nr_host)) return false;
+    if (!eq_mid_consts(M, P, nr_host)) return false;
     // 1 / 2 = (p + 1) / 2 on the limbs (p < 2^256 is odd: p + 1 may carry out of the top limb, the shift brings the bit back)
     uint64_t h[4] = {0, 0, 0, 0};
     unsigned __int128 acc = 1;
@@ -338,95 +330,50 @@ template <int NL, int NW> static bool eq_finish_consts(EqFinishConsts<NL> &K, co
 
 static bool eq_rows_ok(int rows) { return rows >= 1 && rows <= 4096; }
 
-// host: the same element functions over `count` elements
+// host: the same rows over `count` elements
 template <int NL, int NW>
 static int selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, void *const *outs, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
-    const int64_t rows = params[0], plane = rows * count;
+    const int64_t rows = params[0];
     const int mode = (int)params[1];
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    auto O = [](void *base, int64_t i) -> uint32_t * { return reinterpret_cast<uint32_t *>(base) + i * NW; };
-    const uint32_t none[NW] = {};
-    uint32_t r0[NW], r1[NW], r2[NW], r3[NW];
     EqSched S;
     if (!eq_make_sched(S, p_limbs, n_limbs)) return HB_ERR_BAD_ARG;
     if (what == HB_EQ_SELFTEST_LEGENDRE) {
-        for (int64_t i = 0; i < count; i++) reinterpret_cast<int8_t *>(outs[0])[i] = (int8_t)eq_legendre_elem<NL, NW>(W(ops[0], i), S, P);
+        const EqLegendreArgs A = {S, u32(ops[0]), (int8_t *)outs[0]};
+        host_rows<EqLegendreRow, NL, NW>(A, 1, count, P);
     } else if (what == HB_EQ_SELFTEST_MASK1) {
-        for (int64_t j = 0; j < rows; j++)
-            for (int64_t i = 0; i < count; i++) {
-                const int64_t e = j * count + i;
-                if (ops[1]) eq_mask1_elem<NL, NW, true>(r0, r1, r2, r3, W(ops[0], i), W(ops[1], i), W(ops[2], e), W(ops[3], e), W(ops[4], e), W(ops[5], e), W(ops[6], e), W(ops[7], e), P);
-                else eq_mask1_elem<NL, NW, false>(r0, r1, r2, r3, W(ops[0], i), none, W(ops[2], e), W(ops[3], e), W(ops[4], e), W(ops[5], e), W(ops[6], e), W(ops[7], e), P);
-                memcpy(O(outs[0], e), r0, NW * 4); memcpy(O(outs[0], plane + e), r1, NW * 4);
-                memcpy(O(outs[0], 2 * plane + e), r2, NW * 4); memcpy(O(outs[0], 3 * plane + e), r3, NW * 4);
-            }
+        const EqMask1Args A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(outs[0]), rows};
+        if (A.y) host_rows<EqMask1Row<true>, NL, NW>(A, (int)rows, count, P);
+        else host_rows<EqMask1Row<false>, NL, NW>(A, (int)rows, count, P);
     } else if (what == HB_EQ_SELFTEST_MID) {
-        EqMidConsts<NL> K;
-        if (!eq_mid_consts<NL, NW>(K, P, ops[10])) return HB_ERR_BAD_ARG;
-        for (int64_t e = 0; e < plane; e++) {
-            eq_mid_elem<NL, NW>(r0, r1, r2, W(ops[0], e), W(ops[0], plane + e), W(ops[0], 2 * plane + e), W(ops[0], 3 * plane + e), W(ops[1], e), W(ops[2], e), W(ops[3], e),
-                                W(ops[4], e), W(ops[5], e), W(ops[6], e), W(ops[7], e), W(ops[8], e), W(ops[9], e), K, P);
-            memcpy(O(outs[0], e), r0, NW * 4); memcpy(O(outs[0], plane + e), r1, NW * 4); memcpy(O(outs[1], e), r2, NW * 4);
-        }
+        EqMidArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(ops[9]),
+                           u32(outs[0]), u32(outs[1]), rows};
+        if (!eq_mid_consts(A.K, P, ops[10])) return HB_ERR_BAD_ARG;
+        host_rows<EqMidRow, NL, NW>(A, (int)rows, count, P);
     } else if (what == HB_EQ_SELFTEST_CSHARE) {
-        for (int64_t e = 0; e < plane; e++) {
-            eq_cshare_elem<NL, NW>(r0, W(ops[1], e), W(ops[0], e), W(ops[0], plane + e), W(ops[2], e), W(ops[3], e), W(ops[4], e), P);
-            memcpy(O(outs[0], e), r0, NW * 4);
-        }
+        const EqCshareArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(outs[0]), rows};
+        host_rows<EqCshareRow, NL, NW>(A, (int)rows, count, P);
     } else {
-        EqFinishConsts<NL> K;
-        if (!eq_finish_consts<NL, NW>(K, P, p_limbs, n_limbs, mode, ops[2])) return HB_ERR_BAD_ARG;
-        int32_t *zr = reinterpret_cast<int32_t *>(outs[1]);
-        for (int64_t j = 0; j < rows; j++)
-            for (int64_t i = 0; i < count; i++) {
-                const int64_t e = j * count + i;
-                const int L = eq_finish_elem<NL, NW>(r0, W(ops[0], e), W(ops[1], e), S, K, P);
-                memcpy(O(outs[0], e), r0, NW * 4);
-                if (L == 0) zr[j] = 1;
-            }
+        EqFinishArgs<NL> A = {S, u32(ops[0]), u32(ops[1]), u32(outs[0]), (int32_t *)outs[1]};
+        if (!eq_finish_consts(A.K, P, p_limbs, n_limbs, mode, ops[2])) return HB_ERR_BAD_ARG;
+        host_rows<EqFinishRow, NL, NW>(A, (int)rows, count, P);
     }
     return HB_OK;
-}
-
-template <int NL, int NW>
-static bool launch_eq_mid(const FpParams<NL> &P, const uint64_t *opened, const uint64_t *pa, const uint64_t *qa, const uint64_t *pqa, const uint64_t *pb, const uint64_t *qb,
-                          const uint64_t *pqb, const uint64_t *bits, const uint64_t *pc, const uint64_t *qc, const uint64_t *nr_host, uint64_t *masked2, uint64_t *dr, int rows,
-                          int64_t count, unsigned blocks, hipStream_t s) {
-    EqMidConsts<NL> K;
-    if (!eq_mid_consts<NL, NW>(K, P, nr_host)) return false;
-    if (count)
-        k_eq_mid<NL, NW><<<dim3(blocks, (unsigned)rows), 256, 0, s>>>(P, u32(opened), u32(pa), u32(qa), u32(pqa), u32(pb), u32(qb), u32(pqb), u32(bits), u32(pc), u32(qc), K,
-                                                                      (uint32_t *)masked2, (uint32_t *)dr, rows, count);
-    return true;
-}
-
-template <int NL, int NW>
-static bool launch_eq_finish(const FpParams<NL> &P, const EqSched &S, const uint64_t *p_limbs, int n_limbs, const uint64_t *c, const uint64_t *bits, int mode,
-                             const uint64_t *nr_host, uint64_t *factor, int32_t *zero_rows, int rows, int64_t count, unsigned blocks, hipStream_t s) {
-    EqFinishConsts<NL> K;
-    if (!eq_finish_consts<NL, NW>(K, P, p_limbs, n_limbs, mode, nr_host)) return false;
-    if (count) k_eq_finish<NL, NW><<<dim3(blocks, (unsigned)rows), 256, 0, s>>>(P, S, K, u32(c), u32(bits), (uint32_t *)factor, zero_rows, count);
-    return true;
 }
 
 }  // namespace hb
 
 extern "C" {
 
-
 int hb_legendre(hb_ctx *ctx, const uint64_t *a_dev, int8_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!a_dev || !out_dev))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
-    EqSched S;
-    if (!eq_make_sched(S, ctx->p_limbs, ctx->n_limbs)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_legendre: no schedule for this modulus");
+    EqLegendreArgs A = {{}, u32(a_dev), out_dev};
+    if (!eq_make_sched(A.S, ctx->p_limbs, ctx->n_limbs)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_legendre: no schedule for this modulus");
     if (overlap(out_dev, count, a_dev, count * 8 * (int64_t)ctx->n_limbs)) return fail(ctx, HB_ERR_BAD_ARG, "hb_legendre: out overlaps a");
     HB_ROW_BLOCKS(ctx, "hb_legendre");
-    HB_DISPATCH(ctx, (k_legendre<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, S, u32(a_dev), out_dev, count)),
-                (k_legendre<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, S, u32(a_dev), out_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    return launch_rows<EqLegendreRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_eq_mask1(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *r_dev, const uint64_t *rp_dev, const uint64_t *pa_dev, const uint64_t *qa_dev,
@@ -434,49 +381,37 @@ int hb_eq_mask1(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const
     if (!ctx || count < 0 || (count > 0 && (!x_dev || !r_dev || !rp_dev || !pa_dev || !qa_dev || !pb_dev || !qb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
     if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: needs 1 <= rows <= 4096");
     if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, pb_ = rows * count * eb;
-    const uint64_t *planes[6] = {r_dev, rp_dev, pa_dev, qa_dev, pb_dev, qb_dev};
-    for (const uint64_t *in : planes)
-        if (overlap(masked_dev, 4 * pb_, in, pb_)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
-    if (overlap(masked_dev, 4 * pb_, x_dev, count * eb) || overlap(masked_dev, 4 * pb_, y_dev, count * eb))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
+    const RowSpan outs[1] = {{masked_dev, 4 * rows}},
+                 ins[8] = {{x_dev, 1}, {y_dev, 1}, {r_dev, rows}, {rp_dev, rows}, {pa_dev, rows}, {qa_dev, rows}, {pb_dev, rows}, {qb_dev, rows}};
+    if (!outputs_apart(outs, 1, ins, 8, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
     HB_ROW_BLOCKS(ctx, "hb_eq_mask1");
     const dim3 grid((unsigned)blocks, (unsigned)rows);
-#define EQ_MASK1(NL, NW, HAS_Y, P) \
-    k_eq_mask1<NL, NW, HAS_Y><<<grid, 256, 0, s>>>(P, u32(x_dev), u32(y_dev), u32(r_dev), u32(rp_dev), u32(pa_dev), u32(qa_dev), u32(pb_dev), u32(qb_dev), (uint32_t *)masked_dev, rows, count)
-    if (y_dev) HB_DISPATCH(ctx, (EQ_MASK1(9, 8, true, ctx->pw)), (EQ_MASK1(3, 2, true, ctx->pn)));
-    else HB_DISPATCH(ctx, (EQ_MASK1(9, 8, false, ctx->pw)), (EQ_MASK1(3, 2, false, ctx->pn)));
-#undef EQ_MASK1
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const EqMask1Args A = {u32(x_dev), u32(y_dev), u32(r_dev), u32(rp_dev), u32(pa_dev), u32(qa_dev), u32(pb_dev), u32(qb_dev), u32(masked_dev), rows};
+    if (y_dev) return launch_rows<EqMask1Row<true>>(ctx, A, grid, s, count);
+    return launch_rows<EqMask1Row<false>>(ctx, A, grid, s, count);
 }
 
 int hb_eq_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *pa_dev, const uint64_t *qa_dev, const uint64_t *pqa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev,
               const uint64_t *pqb_dev, const uint64_t *bits_dev, const uint64_t *pc_dev, const uint64_t *qc_dev, const uint64_t *nr_host, uint64_t *masked2_dev,
               uint64_t *dr_dev, int rows, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || !nr_host) return HB_ERR_BAD_ARG;
-    const uint64_t *ins[10] = {opened_dev, pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, bits_dev, pc_dev, qc_dev};
+    const uint64_t *planes[9] = {pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, bits_dev, pc_dev, qc_dev};
     if (count > 0) {
-        for (const uint64_t *in : ins) if (!in) return HB_ERR_BAD_ARG;
-        if (!masked2_dev || !dr_dev) return HB_ERR_BAD_ARG;
+        for (const uint64_t *in : planes) if (!in) return HB_ERR_BAD_ARG;
+        if (!opened_dev || !masked2_dev || !dr_dev) return HB_ERR_BAD_ARG;
     }
     if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: needs 1 <= rows <= 4096");
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, pb_ = rows * count * eb;
-    if (count > 0) {
-        for (int k = 0; k < 10; k++) {
-            const int64_t ib = k == 0 ? 4 * pb_ : pb_;
-            if (overlap(masked2_dev, 2 * pb_, ins[k], ib) || overlap(dr_dev, pb_, ins[k], ib)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: the outputs are arrays of their own");
-        }
-        if (overlap(masked2_dev, 2 * pb_, dr_dev, pb_)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: masked2 overlaps dr");
-    }
+    const RowSpan outs[2] = {{masked2_dev, 2 * rows}, {dr_dev, rows}};
+    RowSpan ins[10] = {{opened_dev, 4 * rows}};
+    for (int k = 0; k < 9; k++) ins[1 + k] = {planes[k], rows};
+    if (!outputs_apart(outs, 2, ins, 10, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: the outputs are arrays of their own");
     HB_ROW_BLOCKS(ctx, "hb_eq_mid");
-    bool ok;
-    HB_DISPATCH(ctx,
-        (ok = launch_eq_mid<9, 8>(ctx->pw, opened_dev, pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, bits_dev, pc_dev, qc_dev, nr_host, masked2_dev, dr_dev, rows, count, (unsigned)blocks, s)),
-        (ok = launch_eq_mid<3, 2>(ctx->pn, opened_dev, pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, bits_dev, pc_dev, qc_dev, nr_host, masked2_dev, dr_dev, rows, count, (unsigned)blocks, s)));
-    if (!ok) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: nr must be a residue class other than 0 and 1");
-    if (count) HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const int rc = launch_rows<EqMidRow, EqMidArgs>(ctx, [&](auto &A, const auto &P) {
+        A.opened = u32(opened_dev); A.pa = u32(pa_dev); A.qa = u32(qa_dev); A.pqa = u32(pqa_dev); A.pb = u32(pb_dev); A.qb = u32(qb_dev); A.pqb = u32(pqb_dev);
+        A.bits = u32(bits_dev); A.pc = u32(pc_dev); A.qc = u32(qc_dev); A.masked2 = u32(masked2_dev); A.dr = u32(dr_dev); A.rows = rows;
+        return eq_mid_consts(A.K, P, nr_host);
+    }, dim3((unsigned)blocks, (unsigned)rows), s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_eq_mid: nr must be a residue class other than 0 and 1") : rc;
 }
 
 int hb_eq_cshare(hb_ctx *ctx, const uint64_t *opened2_dev, const uint64_t *dr_dev, const uint64_t *pc_dev, const uint64_t *qc_dev, const uint64_t *pqc_dev, uint64_t *c_dev,
@@ -484,17 +419,13 @@ int hb_eq_cshare(hb_ctx *ctx, const uint64_t *opened2_dev, const uint64_t *dr_de
     if (!ctx || count < 0 || (count > 0 && (!opened2_dev || !dr_dev || !pc_dev || !qc_dev || !pqc_dev || !c_dev))) return HB_ERR_BAD_ARG;
     if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_cshare: needs 1 <= rows <= 4096");
     if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, pb_ = rows * count * eb;
-    if (overlap(c_dev, pb_, opened2_dev, 2 * pb_) || overlap(c_dev, pb_, pc_dev, pb_) || overlap(c_dev, pb_, qc_dev, pb_) || overlap(c_dev, pb_, pqc_dev, pb_) ||
-        (c_dev != dr_dev && overlap(c_dev, pb_, dr_dev, pb_)))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_cshare: c may be dr itself and no other input");
+    // c == dr is the permitted alias: dr is then left out of the inputs c must keep apart from
+    const RowSpan outs[1] = {{c_dev, rows}},
+                 ins[5] = {{opened2_dev, 2 * rows}, {c_dev == dr_dev ? nullptr : dr_dev, rows}, {pc_dev, rows}, {qc_dev, rows}, {pqc_dev, rows}};
+    if (!outputs_apart(outs, 1, ins, 5, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_cshare: c may be dr itself and no other input");
     HB_ROW_BLOCKS(ctx, "hb_eq_cshare");
-    const dim3 grid((unsigned)blocks, (unsigned)rows);
-    HB_DISPATCH(ctx,
-        (k_eq_cshare<9, 8><<<grid, 256, 0, s>>>(ctx->pw, u32(opened2_dev), u32(dr_dev), u32(pc_dev), u32(qc_dev), u32(pqc_dev), (uint32_t *)c_dev, rows, count)),
-        (k_eq_cshare<3, 2><<<grid, 256, 0, s>>>(ctx->pn, u32(opened2_dev), u32(dr_dev), u32(pc_dev), u32(qc_dev), u32(pqc_dev), (uint32_t *)c_dev, rows, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const EqCshareArgs A = {u32(opened2_dev), u32(dr_dev), u32(pc_dev), u32(qc_dev), u32(pqc_dev), u32(c_dev), rows};
+    return launch_rows<EqCshareRow>(ctx, A, dim3((unsigned)blocks, (unsigned)rows), s, count);
 }
 
 int hb_eq_finish(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int mode, const uint64_t *nr_host, uint64_t *factor_dev, int32_t *zero_rows_dev, int rows,
@@ -505,19 +436,19 @@ int hb_eq_finish(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, i
     if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_finish: needs 1 <= rows <= 4096");
     EqSched S;
     if (!eq_make_sched(S, ctx->p_limbs, ctx->n_limbs)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_eq_finish: no schedule for this modulus");
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs, pb_ = rows * count * eb;
-    if (count > 0 && (overlap(zero_rows_dev, 4 * (int64_t)rows, c_dev, pb_) || overlap(zero_rows_dev, 4 * (int64_t)rows, bits_dev, pb_) ||
-                      overlap(zero_rows_dev, 4 * (int64_t)rows, factor_dev, pb_) || (factor_dev != c_dev && overlap(factor_dev, pb_, c_dev, pb_)) ||
-                      (factor_dev != bits_dev && overlap(factor_dev, pb_, bits_dev, pb_))))
+    // factor == c and factor == bits are the permitted aliases: such an input is left out of those factor must keep apart from;
+    // zero_rows is 4 bytes a row, not rows of elements
+    const int64_t row_bytes = 8 * (int64_t)ctx->n_limbs * count, zb = 4 * (int64_t)rows;
+    const RowSpan outs[1] = {{factor_dev, rows}}, ins[2] = {{factor_dev == c_dev ? nullptr : c_dev, rows}, {factor_dev == bits_dev ? nullptr : bits_dev, rows}};
+    if (count > 0 && (!outputs_apart(outs, 1, ins, 2, row_bytes) || overlap(zero_rows_dev, zb, c_dev, rows * row_bytes) ||
+                      overlap(zero_rows_dev, zb, bits_dev, rows * row_bytes) || overlap(zero_rows_dev, zb, factor_dev, rows * row_bytes)))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_finish: factor may be c or bits themselves; zero_rows is an array of its own");
     HB_ROW_BLOCKS(ctx, "hb_eq_finish");
-    bool ok;
-    HB_DISPATCH(ctx,
-        (ok = launch_eq_finish<9, 8>(ctx->pw, S, ctx->p_limbs, ctx->n_limbs, c_dev, bits_dev, mode, nr_host, factor_dev, zero_rows_dev, rows, count, (unsigned)blocks, s)),
-        (ok = launch_eq_finish<3, 2>(ctx->pn, S, ctx->p_limbs, ctx->n_limbs, c_dev, bits_dev, mode, nr_host, factor_dev, zero_rows_dev, rows, count, (unsigned)blocks, s)));
-    if (!ok) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_finish: nr must be a residue class other than 0 and 1");
-    if (count) HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const int rc = launch_rows<EqFinishRow, EqFinishArgs>(ctx, [&](auto &A, const auto &P) {
+        A.S = S; A.c = u32(c_dev); A.bits = u32(bits_dev); A.factor = u32(factor_dev); A.zero_rows = zero_rows_dev;
+        return eq_finish_consts(A.K, P, ctx->p_limbs, ctx->n_limbs, mode, nr_host);
+    }, dim3((unsigned)blocks, (unsigned)rows), s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_eq_finish: nr must be a residue class other than 0 and 1") : rc;
 }
 
 int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, void *const *outs, int64_t count) {

@@ -48,8 +48,8 @@ namespace hb {
 template <int NL> struct FxpFinishConsts { uint32_t pow2[NL], pow2m[NL], inv2m[NL]; };
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-// (FxpConst, fxp_horner, fxp_mask_elem, fxp_low_bits, fxp_trunc_pr_elem, fxp_leaf_elem, fxp_node_g_elem and the host helpers
-// fxp_params_ok, fxp_pow2, fxp_host_mont: hb_fxp_elem.hpp, shared with hb_bd.hip and hb_div.hip; word_bit, diff_elem: hb_rows.hpp)
+// (fxp_horner, fxp_mask_elem, fxp_low_bits, fxp_trunc_pr_elem, fxp_leaf_elem, fxp_node_g_elem and the host helpers fxp_params_ok,
+// fxp_pow2: hb_fxp_elem.hpp, shared with hb_bd.hip and hb_div.hip; FpConst, host_mont, word_bit, diff_elem: hb_rows.hpp)
 
 // mode HB_FXP_MOD: a2 = c2 - r1 + 2^m (1 - carry);  HB_FXP_TRUNC: (x - a2) 2^(-m);  HB_FXP_NEG_TRUNC: (a2 - x) 2^(-m)
 template <int NL, int NW>
@@ -73,7 +73,7 @@ HB_HD void fxp_finish_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const ui
 
 // ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
 // Where the header allows an output to be an input, a thread reads its element before it writes it.
-template <int NL> struct FxpMaskArgs { const uint32_t *x, *bits; uint32_t *masked, *r1; int nbits, m; FxpConst<NL> half; };
+template <int NL> struct FxpMaskArgs { const uint32_t *x, *bits; uint32_t *masked, *r1; int nbits, m; FpConst<NL> half; };
 
 template <bool HAS_X> struct FxpMaskRow {
     template <int NL, int NW, class Mem>
@@ -86,7 +86,7 @@ template <bool HAS_X> struct FxpMaskRow {
     }
 };
 
-template <int NL> struct FxpTruncPrArgs { const uint32_t *x, *c, *r1; uint32_t *out; int m; FxpConst<NL> invm; };
+template <int NL> struct FxpTruncPrArgs { const uint32_t *x, *c, *r1; uint32_t *out; int m; FpConst<NL> invm; };
 
 struct FxpTruncPrRow {
     template <int NL, int NW, class Mem>
@@ -197,14 +197,14 @@ template <int NL> static bool fxp_mask_consts(FxpMaskArgs<NL> &A, const FpParams
 }
 template <int NL> static bool fxp_trunc_pr_consts(FxpTruncPrArgs<NL> &A, const FpParams<NL> &P, int m, const uint64_t *inv2m_host) {
     A.m = m;
-    return fxp_host_mont<NL, words_of(NL)>(A.invm.d, P, inv2m_host);
+    return host_mont<NL, words_of(NL)>(A.invm.d, P, inv2m_host);
 }
 template <int NL> static bool fxp_finish_consts(FxpFinishArgs<NL> &A, const FpParams<NL> &P, int m, int mode, const uint64_t *inv2m_host) {
     A.m = m; A.mode = mode;
     fxp_pow2<NL>(A.K.pow2, m, false, P);
     fxp_pow2<NL>(A.K.pow2m, m, true, P);
     for (int q = 0; q < NL; q++) A.K.inv2m[q] = 0;
-    return mode != HB_FXP_MOD ? fxp_host_mont<NL, words_of(NL)>(A.K.inv2m, P, inv2m_host) : true;
+    return mode != HB_FXP_MOD ? host_mont<NL, words_of(NL)>(A.K.inv2m, P, inv2m_host) : true;
 }
 
 // nodes planes of a level; root: the level of two planes whose p is not wanted

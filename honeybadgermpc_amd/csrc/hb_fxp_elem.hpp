@@ -16,8 +16,7 @@ template <int NL, int NW>
 HB_HD void fxp_leaf_elem(uint32_t (&gw)[NW], uint32_t (&pw)[NW], uint32_t a, const uint32_t (&bw)[NW], const FpParams<NL> &P) {
     uint32_t b[NL], one[NL], nb[NL], g[NL], p[NL];
     unpack<NL, NW>(b, bw);
-#pragma unroll
-    for (int q = 0; q < NL; q++) one[q] = q == 0 ? 1u : 0u;
+    small_digits<NL>(one, 1);
     fp_sub<NL>(nb, one, b, P);
 #pragma unroll
     for (int q = 0; q < NL; q++) { g[q] = a ? nb[q] : 0u; p[q] = a ? b[q] : nb[q]; }
@@ -36,9 +35,6 @@ HB_HD void fxp_node_g_elem(uint32_t (&o)[NW], const uint32_t (&g1w)[NW], const u
     fp_add<NL>(r, g1, mm, P);
     pack<NL, NW>(o, r);
 }
-
-// a field element as digits, handed to a kernel by value
-template <int NL> struct FxpConst { uint32_t d[NL]; };
 
 // acc = 2 acc + b: one Horner step over a bit plane
 template <int NL, int NW> HB_HD void fxp_horner(uint32_t (&acc)[NL], const uint32_t (&bw)[NW], const FpParams<NL> &P) {
@@ -146,20 +142,8 @@ static inline bool fxp_params_ok(int bits, int k, int m, int kappa) { return m >
 // 2^e mod p, canonical digits (mont: times R)
 template <int NL> static void fxp_pow2(uint32_t (&r)[NL], int e, bool mont, const FpParams<NL> &P) {
     if (mont) fp_set<NL>(r, P.one);
-    else for (int q = 0; q < NL; q++) r[q] = q == 0 ? 1u : 0u;
+    else small_digits<NL>(r, 1);
     for (int i = 0; i < e; i++) { uint32_t t[NL]; fp_add<NL>(t, r, r, P); fp_set<NL>(r, t); }
-}
-// one canonical element in host memory -> its Montgomery digits; false if it is not below p
-template <int NL, int NW> static bool fxp_host_mont(uint32_t (&r)[NL], const FpParams<NL> &P, const uint64_t *host) {
-    uint32_t w[NW], d[NL];
-    memcpy(w, host, NW * 4);
-    unpack<NL, NW>(d, w);
-    bool below = false;
-    for (int i = NL - 1; i >= 0; i--)
-        if (d[i] != P.p[i]) { below = d[i] < P.p[i]; break; }
-    if (!below) return false;
-    to_mont<NL>(r, d, P);
-    return true;
 }
 
 }  // namespace hb

@@ -9,11 +9,11 @@
 //                  (X', Y', T', Z') = (E F, G H, E H, F G)                                                           8 products
 //   jj_add_mixed   the second point affine (x2, y2, td2 = d x2 y2):  A = X x2, B = Y y2, C = T td2, E = (X + Y)(x2 + y2) - A - B,
 //                  F = Z - C, G = Z + C, H = B - a A;  (X', Y', T', Z') = (E F, G H, E H, F G)                       9 products
-// k_jj_scalar_mul    out_i = n_i P_i: the accumulator starts at (0 : 1 : 1 : 0) and takes the scalar's bits from the top, one
+// JjScalarMulRow     out_i = n_i P_i: the accumulator starts at (0 : 1 : 1 : 0) and takes the scalar's bits from the top, one
 //                    doubling a bit and one mixed addition a set bit, 32 NW bits in a loop that is not unrolled (the scalar's words are
 //                    shifted left a bit a round: no register array is indexed by the loop counter); one fp_inv at the end.  Everything
 //                    stays in registers.  n_i = 0 leaves (0, 1).  Scalar and point: one for all (element 0) or one an element.
-// k_jj_double_table  rows j < K of 2^j P_i, projective: the Montgomery residues X R, Y R, Z R of row j at [j][i] of three arrays.
+// JjDoubleTableRow   rows j < K of 2^j P_i, projective: the Montgomery residues X R, Y R, Z R of row j at [j][i] of three arrays.
 //                    hb_jj_double_table then makes them affine with ONE hb_ew_inv over the K count values of Z and two hb_ew_op
 //                    products ((X R) / (Z R) = x): no inversion an element and row.
 //
@@ -22,21 +22,22 @@
 // regrouped so that each numerator rides with the blinding of its denominator, num / den = (num r) / (den r) with den r opened:
 // 9 Beaver triples and 2 random shares (rx, ry) a pair.  Triple k multiplies:  0 x1 x2,  1 y1 y2,  2 x1 y2,  3 y1 x2,  4 xp yp,
 // 5 nx rx,  6 ny ry,  7 dx rx,  8 dy ry   (xp = x1 x2, yp = y1 y2, nx = x1 y2 + y1 x2, ny = yp + xp, dx = 1 + d xp yp, dy = 1 - d xp yp).
-//   k_jj_add_mask     A [8][m]: rows 2k, 2k + 1 the masked factors (first - p_k, second - q_k) of products 0..3
-//   k_jj_add_stage1   opened A -> xp, yp, x1 y2, y1 x2 (four Beaver steps) -> B [6][m]: the masked factors of products 4..6
-//   k_jj_add_stage2   opened B -> [xp yp], u = [nx rx], v = [ny ry] (three Beaver steps); u, v kept ([2][m]); C [4][m]: the masked
+//   JjMaskRow         A [8][m]: rows 2k, 2k + 1 the masked factors (first - p_k, second - q_k) of products 0..3
+//   JjStage1Row       opened A -> xp, yp, x1 y2, y1 x2 (four Beaver steps) -> B [6][m]: the masked factors of products 4..6
+//   JjStage2Row       opened B -> [xp yp], u = [nx rx], v = [ny ry] (three Beaver steps); u, v kept ([2][m]); C [4][m]: the masked
 //                     factors of products 7, 8.  A public 1 and d meet a share alike on every party.
-//   k_jj_add_stage3   opened C -> D [2][m]: the shares of sig_x = dx rx, sig_y = dy ry (two Beaver steps)
-//   hb_jj_add_finish  opened D -> hb_ew_inv over its 2 m values (batched), then k_jj_add_scale: x3 = u / sig_x, y3 = v / sig_y
+//   JjStage3Row       opened C -> D [2][m]: the shares of sig_x = dx rx, sig_y = dy ry (two Beaver steps)
+//   hb_jj_add_finish  opened D -> hb_ew_inv over its 2 m values (batched), then JjScaleRow: x3 = u / sig_x, y3 = v / sig_y
 // A zero sig (r = 0, or operands off the curve) is counted by hb_ew_inv's counter.  Six launches and four opens an addition.
 // Every Beaver step is ew_beaver_elem of hb_ew_elem.hpp, unchanged; everything between the steps is fp_add / fp_sub / mont_mul on
 // canonical residues: there is NO lazy sum in this file beyond ew_beaver_elem's own (bounds stated there), so every digit is below 2^29
 // and every value below p between two calls.  p = 2^256 - 189 with every operand p - 1 is the largest case (tests/test_jubjub_host.py).
 //
-// The per-element bodies are HB_HD functions on pointers and an index (as ew_inv_lane of hb_ew.hip): they load what they need when
-// they need it -- a stage reads up to 28 elements, more than a lane holds at once -- and store their rows; the __global__ wrappers
-// only find the index and call them, and hb_selftest_jj runs the very same functions over host memory.  Outputs are distinct arrays.
-// Launch shape (all kernels): 256-thread workgroups, one element (pair) a thread, grid = ceil(count / 256), no LDS, no grid stride,
+// The steps are rows under the generic kernel k_rows (hb_rows.hpp): a step's row -- which elements it loads, which body it calls,
+// where it stores -- is an HB_HD function over a memory policy, so hb_selftest_jj runs on the host the very rows, arithmetic and
+// addressing, that k_rows runs on the device.  A row loads what it needs when it needs it -- a stage reads up to 28 elements, more
+// than a lane holds at once -- and stores as it goes.  Outputs are distinct arrays.
+// Launch shape (all steps): 256-thread workgroups, one element (pair) a thread, grid = ceil(count / 256), no LDS, no grid stride,
 // the caller's stream.  What was just opened and the preprocessing are read once: the 32-byte width takes the non-temporal loads.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DESIGN.md section 3l and profiles/jubjub.txt.
 #include "hb_common.hpp"
@@ -47,19 +48,11 @@ using namespace hb;
 
 namespace hb {
 
-// a field element as digits, handed to a kernel by value (the curve's a and d in Montgomery form)
-template <int NL> struct JjConst { uint32_t d[NL]; };
 template <int NL> struct JjPoint { uint32_t X[NL], Y[NL], Z[NL], T[NL]; };
 // one party's triples: row k of a component starts k * stride elements behind its base
 struct JjTrip { const uint32_t *p, *q, *pq; int64_t stride; };
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-template <int NL, int NW> HB_HD void jj_digits_once(uint32_t (&d)[NL], const uint32_t *p) {
-    uint32_t w[NW];
-    load_once<NW>(w, p);
-    unpack<NL, NW>(d, w);
-}
-
 // r = 2 p (r may be p)
 template <int NL> HB_HD void jj_double(JjPoint<NL> &r, const JjPoint<NL> &p, const uint32_t (&am)[NL], const FpParams<NL> &P) {
     uint32_t A[NL], B[NL], C[NL], D[NL], E[NL], F[NL], G[NL], H[NL], t[NL];
@@ -137,272 +130,239 @@ HB_HD void jj_scalar_mul_elem(uint32_t (&ox)[NW], uint32_t (&oy)[NW], const uint
     pack<NL, NW>(oy, td2);
 }
 
-// rows j < K of 2^j (x, y), projective, as the Montgomery residues of X, Y, Z: row j of element i at [(j * count + i) * NW]
-template <int NL, int NW>
-HB_HD void jj_double_table_elem(uint32_t *xs, uint32_t *ys, uint32_t *zs, const uint32_t (&xw)[NW], const uint32_t (&yw)[NW], const uint32_t (&am)[NL], int K,
-                                int64_t i, int64_t count, const FpParams<NL> &P) {
-    uint32_t t[NL];
-    JjPoint<NL> acc;
-    unpack<NL, NW>(t, xw);
-    to_mont<NL>(acc.X, t, P);
-    unpack<NL, NW>(t, yw);
-    to_mont<NL>(acc.Y, t, P);
-    mont_mul<NL>(acc.T, acc.X, acc.Y, P);
-    fp_set<NL>(acc.Z, P.one);
-#pragma unroll 1
-    for (int j = 0; j < K; j++) {
-        const int64_t at = ((int64_t)j * count + i) * NW;
-        store_digits<NL, NW>(xs + at, acc.X);
-        store_digits<NL, NW>(ys + at, acc.Y);
-        store_digits<NL, NW>(zs + at, acc.Z);
-        if (j + 1 < K) jj_double<NL>(acc, acc, am, P);
-    }
+// ---------------------------------------------------------------- digits through a memory policy (hb_rows.hpp)
+template <int NL, int NW, class Mem> HB_HD void jj_get(uint32_t (&d)[NL], const Mem &mem, const uint32_t *base, int64_t e) {
+    uint32_t w[NW];
+    mem.load(w, base, e);
+    unpack<NL, NW>(d, w);
 }
-
-// out = v - mask[i]
-template <int NL, int NW> HB_HD void jj_sub_store(uint32_t *out, const uint32_t (&v)[NL], const uint32_t *mask, const FpParams<NL> &P) {
-    uint32_t k[NL], r[NL];
-    jj_digits_once<NL, NW>(k, mask);
-    fp_sub<NL>(r, v, k, P);
-    store_digits<NL, NW>(out, r);
+template <int NL, int NW, class Mem> HB_HD void jj_get_once(uint32_t (&d)[NL], const Mem &mem, const uint32_t *base, int64_t e) {
+    uint32_t w[NW];
+    mem.once(w, base, e);
+    unpack<NL, NW>(d, w);
 }
-// o = the Beaver step of triple k on the opened factors at dp, ep (element i of each)
-template <int NL, int NW>
-HB_HD void jj_beaver(uint32_t (&o)[NL], const uint32_t *dp, const uint32_t *ep, const JjTrip &t, int k, int64_t i, const FpParams<NL> &P) {
+template <int NL, int NW, class Mem> HB_HD void jj_put(const Mem &mem, uint32_t *base, int64_t e, const uint32_t (&d)[NL]) {
+    uint32_t w[NW];
+    pack<NL, NW>(w, d);
+    mem.store(base, e, w);
+}
+// out[e] = v - mask[k]
+template <int NL, int NW, class Mem>
+HB_HD void jj_put_diff(const Mem &mem, uint32_t *out, int64_t e, const uint32_t (&v)[NL], const uint32_t *mask, int64_t k, const FpParams<NL> &P) {
+    uint32_t kd[NL], r[NL];
+    jj_get_once<NL, NW>(kd, mem, mask, k);
+    fp_sub<NL>(r, v, kd, P);
+    jj_put<NL, NW>(mem, out, e, r);
+}
+// o = the Beaver step of triple k on the opened factors in rows r, r + 1 of `opened` (m elements a row)
+template <int NL, int NW, class Mem>
+HB_HD void jj_beaver(uint32_t (&o)[NL], const Mem &mem, const uint32_t *opened, int r, const JjTrip &t, int k, int64_t i, int64_t m, const FpParams<NL> &P) {
     uint32_t dw[NW], ew[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
-    const int64_t at = ((int64_t)k * t.stride + i) * NW;
-    load_once<NW>(dw, dp + i * NW);
-    load_once<NW>(ew, ep + i * NW);
-    load_once<NW>(pw, t.p + at);
-    load_once<NW>(qw, t.q + at);
-    load_once<NW>(pqw, t.pq + at);
+    const int64_t at = (int64_t)k * t.stride + i;
+    mem.once(dw, opened, (int64_t)r * m + i);
+    mem.once(ew, opened, (int64_t)(r + 1) * m + i);
+    mem.once(pw, t.p, at);
+    mem.once(qw, t.q, at);
+    mem.once(pqw, t.pq, at);
     ew_beaver_elem<NL, NW>(ow, dw, ew, pw, qw, pqw, P);
     unpack<NL, NW>(o, ow);
 }
-#define JJ_ROW(base, row) ((base) + ((int64_t)(row) * m + i) * NW)
-#define JJ_TRIP(comp, k) ((comp) + ((int64_t)(k) * t.stride + i) * NW)
+
+// ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
+// One row a step: `count` is the element count of the cleartext steps and the pair count m of the shared addition.  An array of
+// several rows of m elements is addressed at row * m + i, the triples at k * t.stride + i: they keep their own row stride.  A stage
+// reads up to 28 elements, more than a lane holds at once, so a row loads what it needs when it needs it.
+template <int NL> struct JjScalarMulArgs { const uint32_t *n, *x, *y; int n_bcast, p_bcast; uint32_t *ox, *oy; FpConst<NL> am, dm; };
+
+struct JjScalarMulRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const JjScalarMulArgs<NL> &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t nw[NW], xw[NW], yw[NW], rx[NW], ry[NW];
+        mem.load(nw, A.n, A.n_bcast ? 0 : i);
+        mem.load(xw, A.x, A.p_bcast ? 0 : i);
+        mem.load(yw, A.y, A.p_bcast ? 0 : i);
+        jj_scalar_mul_elem<NL, NW>(rx, ry, nw, xw, yw, A.am.d, A.dm.d, P);
+        mem.store(A.ox, i, rx);
+        mem.store(A.oy, i, ry);
+    }
+};
+
+// rows j < K of 2^j (x, y), projective, as the Montgomery residues of X, Y, Z: row j of element i at j * count + i.  The rows are
+// walked in the thread: each is the double of the one before.
+template <int NL> struct JjDoubleTableArgs { const uint32_t *x, *y; uint32_t *xs, *ys, *zs; int K; FpConst<NL> am; };
+
+struct JjDoubleTableRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const JjDoubleTableArgs<NL> &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t t[NL];
+        JjPoint<NL> acc;
+        jj_get<NL, NW>(t, mem, A.x, i);
+        to_mont<NL>(acc.X, t, P);
+        jj_get<NL, NW>(t, mem, A.y, i);
+        to_mont<NL>(acc.Y, t, P);
+        mont_mul<NL>(acc.T, acc.X, acc.Y, P);
+        fp_set<NL>(acc.Z, P.one);
+#pragma unroll 1
+        for (int j = 0; j < A.K; j++) {
+            const int64_t at = (int64_t)j * count + i;
+            jj_put<NL, NW>(mem, A.xs, at, acc.X);
+            jj_put<NL, NW>(mem, A.ys, at, acc.Y);
+            jj_put<NL, NW>(mem, A.zs, at, acc.Z);
+            if (j + 1 < A.K) jj_double<NL>(acc, acc, A.am.d, P);
+        }
+    }
+};
 
 // A[2k] = first_k - p_k, A[2k + 1] = second_k - q_k for the products 0 x1 x2, 1 y1 y2, 2 x1 y2, 3 y1 x2
-template <int NL, int NW>
-HB_HD void jj_mask_elem(uint32_t *A, const uint32_t *x1, const uint32_t *y1, const uint32_t *x2, const uint32_t *y2, const JjTrip &t, int64_t i, int64_t m,
-                        const FpParams<NL> &P) {
-    uint32_t xa[NL], ya[NL], xb[NL], yb[NL];
-    load_digits<NL, NW>(xa, x1 + i * NW);
-    load_digits<NL, NW>(ya, y1 + i * NW);
-    load_digits<NL, NW>(xb, x2 + i * NW);
-    load_digits<NL, NW>(yb, y2 + i * NW);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 0), xa, JJ_TRIP(t.p, 0), P);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 1), xb, JJ_TRIP(t.q, 0), P);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 2), ya, JJ_TRIP(t.p, 1), P);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 3), yb, JJ_TRIP(t.q, 1), P);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 4), xa, JJ_TRIP(t.p, 2), P);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 5), yb, JJ_TRIP(t.q, 2), P);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 6), ya, JJ_TRIP(t.p, 3), P);
-    jj_sub_store<NL, NW>(JJ_ROW(A, 7), xb, JJ_TRIP(t.q, 3), P);
-}
+struct JjMaskArgs { const uint32_t *x1, *y1, *x2, *y2; JjTrip t; uint32_t *A; };
+
+struct JjMaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const JjMaskArgs &A, int, int64_t i, int64_t m, const Mem &mem, const FpParams<NL> &P) {
+        const auto row = [&](int r) { return (int64_t)r * m + i; };
+        const auto trip = [&](int k) { return (int64_t)k * A.t.stride + i; };
+        uint32_t xa[NL], ya[NL], xb[NL], yb[NL];
+        jj_get<NL, NW>(xa, mem, A.x1, i);
+        jj_get<NL, NW>(ya, mem, A.y1, i);
+        jj_get<NL, NW>(xb, mem, A.x2, i);
+        jj_get<NL, NW>(yb, mem, A.y2, i);
+        jj_put_diff<NL, NW>(mem, A.A, row(0), xa, A.t.p, trip(0), P);
+        jj_put_diff<NL, NW>(mem, A.A, row(1), xb, A.t.q, trip(0), P);
+        jj_put_diff<NL, NW>(mem, A.A, row(2), ya, A.t.p, trip(1), P);
+        jj_put_diff<NL, NW>(mem, A.A, row(3), yb, A.t.q, trip(1), P);
+        jj_put_diff<NL, NW>(mem, A.A, row(4), xa, A.t.p, trip(2), P);
+        jj_put_diff<NL, NW>(mem, A.A, row(5), yb, A.t.q, trip(2), P);
+        jj_put_diff<NL, NW>(mem, A.A, row(6), ya, A.t.p, trip(3), P);
+        jj_put_diff<NL, NW>(mem, A.A, row(7), xb, A.t.q, trip(3), P);
+    }
+};
+
+// stages 1 and 3: `in` is the array just opened, `out` the next one (stage 3 takes no rx, ry)
+struct JjStageArgs { const uint32_t *in; JjTrip t; const uint32_t *rx, *ry; uint32_t *out; };
 
 // opened A -> B: xp - p4, yp - q4, nx - p5, rx - q5, ny - p6, ry - q6
-template <int NL, int NW>
-HB_HD void jj_stage1_elem(uint32_t *B, const uint32_t *A, const JjTrip &t, const uint32_t *rx, const uint32_t *ry, int64_t i, int64_t m, const FpParams<NL> &P) {
-    uint32_t xp[NL], yp[NL], a[NL], b[NL], n[NL];
-    jj_beaver<NL, NW>(xp, A, A + m * NW, t, 0, i, P);
-    jj_beaver<NL, NW>(yp, A + 2 * m * NW, A + 3 * m * NW, t, 1, i, P);
-    jj_sub_store<NL, NW>(JJ_ROW(B, 0), xp, JJ_TRIP(t.p, 4), P);
-    jj_sub_store<NL, NW>(JJ_ROW(B, 1), yp, JJ_TRIP(t.q, 4), P);
-    fp_add<NL>(n, yp, xp, P);
-    jj_sub_store<NL, NW>(JJ_ROW(B, 4), n, JJ_TRIP(t.p, 6), P);
-    jj_beaver<NL, NW>(a, A + 4 * m * NW, A + 5 * m * NW, t, 2, i, P);
-    jj_beaver<NL, NW>(b, A + 6 * m * NW, A + 7 * m * NW, t, 3, i, P);
-    fp_add<NL>(n, a, b, P);
-    jj_sub_store<NL, NW>(JJ_ROW(B, 2), n, JJ_TRIP(t.p, 5), P);
-    load_digits<NL, NW>(a, rx + i * NW);
-    jj_sub_store<NL, NW>(JJ_ROW(B, 3), a, JJ_TRIP(t.q, 5), P);
-    load_digits<NL, NW>(b, ry + i * NW);
-    jj_sub_store<NL, NW>(JJ_ROW(B, 5), b, JJ_TRIP(t.q, 6), P);
-}
+struct JjStage1Row {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const JjStageArgs &A, int, int64_t i, int64_t m, const Mem &mem, const FpParams<NL> &P) {
+        const auto row = [&](int r) { return (int64_t)r * m + i; };
+        const auto trip = [&](int k) { return (int64_t)k * A.t.stride + i; };
+        uint32_t xp[NL], yp[NL], a[NL], b[NL], n[NL];
+        jj_beaver<NL, NW>(xp, mem, A.in, 0, A.t, 0, i, m, P);
+        jj_beaver<NL, NW>(yp, mem, A.in, 2, A.t, 1, i, m, P);
+        jj_put_diff<NL, NW>(mem, A.out, row(0), xp, A.t.p, trip(4), P);
+        jj_put_diff<NL, NW>(mem, A.out, row(1), yp, A.t.q, trip(4), P);
+        fp_add<NL>(n, yp, xp, P);
+        jj_put_diff<NL, NW>(mem, A.out, row(4), n, A.t.p, trip(6), P);
+        jj_beaver<NL, NW>(a, mem, A.in, 4, A.t, 2, i, m, P);
+        jj_beaver<NL, NW>(b, mem, A.in, 6, A.t, 3, i, m, P);
+        fp_add<NL>(n, a, b, P);
+        jj_put_diff<NL, NW>(mem, A.out, row(2), n, A.t.p, trip(5), P);
+        jj_get<NL, NW>(a, mem, A.rx, i);
+        jj_put_diff<NL, NW>(mem, A.out, row(3), a, A.t.q, trip(5), P);
+        jj_get<NL, NW>(b, mem, A.ry, i);
+        jj_put_diff<NL, NW>(mem, A.out, row(5), b, A.t.q, trip(6), P);
+    }
+};
 
 // opened B -> uv = (u, v) = ([nx rx], [ny ry]) and C: dx - p7, rx - q7, dy - p8, ry - q8 with dx = 1 + d [xp yp], dy = 1 - d [xp yp]
-template <int NL, int NW>
-HB_HD void jj_stage2_elem(uint32_t *uv, uint32_t *C, const uint32_t *B, const JjTrip &t, const uint32_t *rx, const uint32_t *ry, const uint32_t (&dm)[NL], int64_t i,
-                          int64_t m, const FpParams<NL> &P) {
-    uint32_t w[NL], s[NL], one[NL];
-    jj_beaver<NL, NW>(w, B + 2 * m * NW, B + 3 * m * NW, t, 5, i, P);
-    store_digits<NL, NW>(JJ_ROW(uv, 0), w);
-    jj_beaver<NL, NW>(w, B + 4 * m * NW, B + 5 * m * NW, t, 6, i, P);
-    store_digits<NL, NW>(JJ_ROW(uv, 1), w);
-    jj_beaver<NL, NW>(s, B, B + m * NW, t, 4, i, P);
-    mont_mul<NL>(w, s, dm, P);                                  // d [xp yp]: a plain residue times d R
-#pragma unroll
-    for (int q = 0; q < NL; q++) one[q] = q == 0 ? 1u : 0u;
-    fp_add<NL>(s, one, w, P);
-    jj_sub_store<NL, NW>(JJ_ROW(C, 0), s, JJ_TRIP(t.p, 7), P);
-    fp_sub<NL>(s, one, w, P);
-    jj_sub_store<NL, NW>(JJ_ROW(C, 2), s, JJ_TRIP(t.p, 8), P);
-    load_digits<NL, NW>(w, rx + i * NW);
-    jj_sub_store<NL, NW>(JJ_ROW(C, 1), w, JJ_TRIP(t.q, 7), P);
-    load_digits<NL, NW>(w, ry + i * NW);
-    jj_sub_store<NL, NW>(JJ_ROW(C, 3), w, JJ_TRIP(t.q, 8), P);
-}
+template <int NL> struct JjStage2Args { const uint32_t *B; JjTrip t; const uint32_t *rx, *ry; uint32_t *uv, *C; FpConst<NL> dm; };
+
+struct JjStage2Row {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const JjStage2Args<NL> &A, int, int64_t i, int64_t m, const Mem &mem, const FpParams<NL> &P) {
+        const auto row = [&](int r) { return (int64_t)r * m + i; };
+        const auto trip = [&](int k) { return (int64_t)k * A.t.stride + i; };
+        uint32_t w[NL], s[NL], one[NL];
+        jj_beaver<NL, NW>(w, mem, A.B, 2, A.t, 5, i, m, P);
+        jj_put<NL, NW>(mem, A.uv, row(0), w);
+        jj_beaver<NL, NW>(w, mem, A.B, 4, A.t, 6, i, m, P);
+        jj_put<NL, NW>(mem, A.uv, row(1), w);
+        jj_beaver<NL, NW>(s, mem, A.B, 0, A.t, 4, i, m, P);
+        mont_mul<NL>(w, s, A.dm.d, P);                              // d [xp yp]: a plain residue times d R
+        small_digits<NL>(one, 1);
+        fp_add<NL>(s, one, w, P);
+        jj_put_diff<NL, NW>(mem, A.C, row(0), s, A.t.p, trip(7), P);
+        fp_sub<NL>(s, one, w, P);
+        jj_put_diff<NL, NW>(mem, A.C, row(2), s, A.t.p, trip(8), P);
+        jj_get<NL, NW>(w, mem, A.rx, i);
+        jj_put_diff<NL, NW>(mem, A.C, row(1), w, A.t.q, trip(7), P);
+        jj_get<NL, NW>(w, mem, A.ry, i);
+        jj_put_diff<NL, NW>(mem, A.C, row(3), w, A.t.q, trip(8), P);
+    }
+};
 
 // opened C -> D = ([dx rx], [dy ry])
-template <int NL, int NW> HB_HD void jj_stage3_elem(uint32_t *D, const uint32_t *C, const JjTrip &t, int64_t i, int64_t m, const FpParams<NL> &P) {
-    uint32_t s[NL];
-    jj_beaver<NL, NW>(s, C, C + m * NW, t, 7, i, P);
-    store_digits<NL, NW>(JJ_ROW(D, 0), s);
-    jj_beaver<NL, NW>(s, C + 2 * m * NW, C + 3 * m * NW, t, 8, i, P);
-    store_digits<NL, NW>(JJ_ROW(D, 1), s);
-}
+struct JjStage3Row {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const JjStageArgs &A, int, int64_t i, int64_t m, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t s[NL];
+        jj_beaver<NL, NW>(s, mem, A.in, 0, A.t, 7, i, m, P);
+        jj_put<NL, NW>(mem, A.out, i, s);
+        jj_beaver<NL, NW>(s, mem, A.in, 2, A.t, 8, i, m, P);
+        jj_put<NL, NW>(mem, A.out, m + i, s);
+    }
+};
 
 // x3 = u / sig_x, y3 = v / sig_y from the inverted sigs: a product of two plain residues is two Montgomery products (ew_binary_elem)
-template <int NL, int NW>
-HB_HD void jj_scale_elem(uint32_t *x3, uint32_t *y3, const uint32_t *inv, const uint32_t *uv, int64_t i, int64_t m, const FpParams<NL> &P) {
-    uint32_t a[NL], b[NL], r[NL];
-    jj_digits_once<NL, NW>(a, JJ_ROW(inv, 0));
-    jj_digits_once<NL, NW>(b, JJ_ROW(uv, 0));
-    mont_mul<NL>(r, a, b, P);
-    mont_mul<NL>(a, P.r2, r, P);
-    store_digits<NL, NW>(x3 + i * NW, a);
-    jj_digits_once<NL, NW>(a, JJ_ROW(inv, 1));
-    jj_digits_once<NL, NW>(b, JJ_ROW(uv, 1));
-    mont_mul<NL>(r, a, b, P);
-    mont_mul<NL>(a, P.r2, r, P);
-    store_digits<NL, NW>(y3 + i * NW, a);
-}
+struct JjScaleArgs { const uint32_t *inv, *uv; uint32_t *x3, *y3; };
 
-// ---------------------------------------------------------------- kernels
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_jj_scalar_mul(const FpParams<NL> P, const uint32_t *n, int n_bcast, const uint32_t *x, const uint32_t *y, int p_bcast,
-                                                       const JjConst<NL> am, const JjConst<NL> dm, uint32_t *ox, uint32_t *oy, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t nw[NW], xw[NW], yw[NW], rx[NW], ry[NW];
-    load_words<NW>(nw, n + (n_bcast ? 0 : i) * NW);
-    load_words<NW>(xw, x + (p_bcast ? 0 : i) * NW);
-    load_words<NW>(yw, y + (p_bcast ? 0 : i) * NW);
-    jj_scalar_mul_elem<NL, NW>(rx, ry, nw, xw, yw, am.d, dm.d, P);
-    store_words<NW>(ox + i * NW, rx);
-    store_words<NW>(oy + i * NW, ry);
-}
-
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_jj_double_table(const FpParams<NL> P, const uint32_t *x, const uint32_t *y, const JjConst<NL> am, int K, uint32_t *xs,
-                                                         uint32_t *ys, uint32_t *zs, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t xw[NW], yw[NW];
-    load_words<NW>(xw, x + i * NW);
-    load_words<NW>(yw, y + i * NW);
-    jj_double_table_elem<NL, NW>(xs, ys, zs, xw, yw, am.d, K, i, count, P);
-}
-
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_jj_add_mask(const FpParams<NL> P, const uint32_t *x1, const uint32_t *y1, const uint32_t *x2, const uint32_t *y2,
-                                                     const JjTrip t, uint32_t *A, int64_t m) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    jj_mask_elem<NL, NW>(A, x1, y1, x2, y2, t, i, m, P);
-}
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_jj_add_stage1(const FpParams<NL> P, const uint32_t *A, const JjTrip t, const uint32_t *rx, const uint32_t *ry, uint32_t *B,
-                                                       int64_t m) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    jj_stage1_elem<NL, NW>(B, A, t, rx, ry, i, m, P);
-}
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_jj_add_stage2(const FpParams<NL> P, const uint32_t *B, const JjTrip t, const uint32_t *rx, const uint32_t *ry,
-                                                       const JjConst<NL> dm, uint32_t *uv, uint32_t *C, int64_t m) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    jj_stage2_elem<NL, NW>(uv, C, B, t, rx, ry, dm.d, i, m, P);
-}
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_jj_add_stage3(const FpParams<NL> P, const uint32_t *C, const JjTrip t, uint32_t *D, int64_t m) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    jj_stage3_elem<NL, NW>(D, C, t, i, m, P);
-}
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_jj_add_scale(const FpParams<NL> P, const uint32_t *inv, const uint32_t *uv, uint32_t *x3, uint32_t *y3, int64_t m) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    jj_scale_elem<NL, NW>(x3, y3, inv, uv, i, m, P);
-}
+struct JjScaleRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const JjScaleArgs &A, int, int64_t i, int64_t m, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t a[NL], b[NL], r[NL];
+        jj_get_once<NL, NW>(a, mem, A.inv, i);
+        jj_get_once<NL, NW>(b, mem, A.uv, i);
+        mont_mul<NL>(r, a, b, P);
+        mont_mul<NL>(a, P.r2, r, P);
+        jj_put<NL, NW>(mem, A.x3, i, a);
+        jj_get_once<NL, NW>(a, mem, A.inv, m + i);
+        jj_get_once<NL, NW>(b, mem, A.uv, m + i);
+        mont_mul<NL>(r, a, b, P);
+        mont_mul<NL>(a, P.r2, r, P);
+        jj_put<NL, NW>(mem, A.y3, i, a);
+    }
+};
 
 // ---------------------------------------------------------------- host side
+static JjTrip jj_trip(const uint64_t *p, const uint64_t *q, const uint64_t *pq, int64_t stride) { return JjTrip{u32(p), u32(q), u32(pq), stride}; }
+
 // a curve constant from its packed words -> Montgomery digits; false if it is missing or not below p
-template <int NL, int NW> static bool jj_const(JjConst<NL> &c, const FpParams<NL> &P, const uint64_t *host) {
-    if (!host) return false;
-    uint32_t w[NW], v[NL];
-    memcpy(w, host, NW * 4);
-    unpack<NL, NW>(v, w);
-    bool below = false;
-    for (int i = NL - 1; i >= 0; i--)
-        if (v[i] != P.p[i]) { below = v[i] < P.p[i]; break; }
-    if (!below) return false;
-    to_mont<NL>(c.d, v, P);
-    return true;
-}
-struct JjConsts { JjConst<9> aw, dw; JjConst<3> an, dn; };
-static bool jj_consts(hb_ctx *ctx, JjConsts &c, const uint64_t *a_host, const uint64_t *d_host) {
-    if (ctx->n_limbs == 4) return (!a_host || jj_const<9, 8>(c.aw, ctx->pw, a_host)) && (!d_host || jj_const<9, 8>(c.dw, ctx->pw, d_host));
-    return (!a_host || jj_const<3, 2>(c.an, ctx->pn, a_host)) && (!d_host || jj_const<3, 2>(c.dn, ctx->pn, d_host));
-}
-static JjTrip jj_trip(const uint64_t *p, const uint64_t *q, const uint64_t *pq, int64_t stride) {
-    return JjTrip{(const uint32_t *)p, (const uint32_t *)q, (const uint32_t *)pq, stride};
+template <int NL> static bool jj_curve_const(FpConst<NL> &c, const FpParams<NL> &P, const uint64_t *host) {
+    return host && host_mont<NL, words_of(NL)>(c.d, P, host);
 }
 
-// host: the same element functions over `count` elements
+// host: the same rows over `count` elements.  `out` is ONE buffer: a step's second and third output start behind the first.
 template <int NL, int NW>
 static int selftest_jj(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const uint64_t *a_host, const uint64_t *d_host, int flags, int64_t arg,
                        uint64_t *out, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
-    JjConst<NL> am = {}, dm = {};
-    if (a_host && !jj_const<NL, NW>(am, P, a_host)) return HB_ERR_BAD_ARG;
-    if (d_host && !jj_const<NL, NW>(dm, P, d_host)) return HB_ERR_BAD_ARG;
-    auto U = [](const uint64_t *base) { return reinterpret_cast<const uint32_t *>(base); };
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    uint32_t *o = reinterpret_cast<uint32_t *>(out);
-    const int64_t m = count;
+    FpConst<NL> am = {}, dm = {};
+    if ((a_host && !jj_curve_const(am, P, a_host)) || (d_host && !jj_curve_const(dm, P, d_host))) return HB_ERR_BAD_ARG;
+    uint32_t *o = u32(out);
     if (what == HB_JJ_SELFTEST_SCALAR_MUL) {
-        const bool nb = (flags & HB_JJ_SCALAR_BROADCAST) != 0, pb = (flags & HB_JJ_POINT_BROADCAST) != 0;
-        for (int64_t i = 0; i < count; i++) {
-            uint32_t rx[NW], ry[NW];
-            jj_scalar_mul_elem<NL, NW>(rx, ry, W(ops[0], nb ? 0 : i), W(ops[1], pb ? 0 : i), W(ops[2], pb ? 0 : i), am.d, dm.d, P);
-            memcpy(o + i * NW, rx, NW * 4);
-            memcpy(o + (count + i) * NW, ry, NW * 4);
-        }
-        return HB_OK;
-    }
-    if (what == HB_JJ_SELFTEST_DOUBLE_TABLE) {
+        const JjScalarMulArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), (flags & HB_JJ_SCALAR_BROADCAST) != 0, (flags & HB_JJ_POINT_BROADCAST) != 0, o, o + count * NW, am, dm};
+        host_rows<JjScalarMulRow, NL, NW>(A, 1, count, P);
+    } else if (what == HB_JJ_SELFTEST_DOUBLE_TABLE) {
         const int K = (int)arg;
-        for (int64_t i = 0; i < count; i++)
-            jj_double_table_elem<NL, NW>(o, o + (int64_t)K * count * NW, o + 2 * (int64_t)K * count * NW, W(ops[0], i), W(ops[1], i), am.d, K, i, count, P);
-        return HB_OK;
-    }
-    if (what == HB_JJ_SELFTEST_SCALE) {
-        for (int64_t i = 0; i < m; i++) jj_scale_elem<NL, NW>(o, o + m * NW, U(ops[0]), U(ops[1]), i, m, P);
-        return HB_OK;
-    }
-    if (what == HB_JJ_SELFTEST_MASK) {
-        const JjTrip t = jj_trip(ops[4], ops[5], nullptr, arg);
-        for (int64_t i = 0; i < m; i++) jj_mask_elem<NL, NW>(o, U(ops[0]), U(ops[1]), U(ops[2]), U(ops[3]), t, i, m, P);
-        return HB_OK;
-    }
-    const JjTrip t = jj_trip(ops[1], ops[2], ops[3], arg);
-    for (int64_t i = 0; i < m; i++) {
-        if (what == HB_JJ_SELFTEST_STAGE1) jj_stage1_elem<NL, NW>(o, U(ops[0]), t, U(ops[4]), U(ops[5]), i, m, P);
-        else if (what == HB_JJ_SELFTEST_STAGE2) jj_stage2_elem<NL, NW>(o, o + 2 * m * NW, U(ops[0]), t, U(ops[4]), U(ops[5]), dm.d, i, m, P);
-        else jj_stage3_elem<NL, NW>(o, U(ops[0]), t, i, m, P);
+        const JjDoubleTableArgs<NL> A = {u32(ops[0]), u32(ops[1]), o, o + (int64_t)K * count * NW, o + 2 * (int64_t)K * count * NW, K, am};
+        host_rows<JjDoubleTableRow, NL, NW>(A, 1, count, P);
+    } else if (what == HB_JJ_SELFTEST_SCALE) {
+        const JjScaleArgs A = {u32(ops[0]), u32(ops[1]), o, o + count * NW};
+        host_rows<JjScaleRow, NL, NW>(A, 1, count, P);
+    } else if (what == HB_JJ_SELFTEST_MASK) {
+        const JjMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), jj_trip(ops[4], ops[5], nullptr, arg), o};
+        host_rows<JjMaskRow, NL, NW>(A, 1, count, P);
+    } else if (what == HB_JJ_SELFTEST_STAGE2) {
+        const JjStage2Args<NL> A = {u32(ops[0]), jj_trip(ops[1], ops[2], ops[3], arg), u32(ops[4]), u32(ops[5]), o, o + 2 * count * NW, dm};
+        host_rows<JjStage2Row, NL, NW>(A, 1, count, P);
+    } else {
+        const bool first = what == HB_JJ_SELFTEST_STAGE1;
+        const JjStageArgs A = {u32(ops[0]), jj_trip(ops[1], ops[2], ops[3], arg), first ? u32(ops[4]) : nullptr, first ? u32(ops[5]) : nullptr, o};
+        if (first) host_rows<JjStage1Row, NL, NW>(A, 1, count, P);
+        else host_rows<JjStage3Row, NL, NW>(A, 1, count, P);
     }
     return HB_OK;
-}
-
-static bool jj_blocks(int64_t count, unsigned *blocks) {
-    const int64_t b = (count + 255) / 256;
-    *blocks = (unsigned)b;
-    return b <= 0x7fffffffLL;
 }
 
 }  // namespace hb
@@ -416,17 +376,12 @@ int hb_jj_scalar_mul(hb_ctx *ctx, const uint64_t *n_dev, int n_broadcast, const 
     if (count > 1 && ((n_broadcast && (outx_dev == n_dev || outy_dev == n_dev)) ||
                       (point_broadcast && (outx_dev == x_dev || outx_dev == y_dev || outy_dev == x_dev || outy_dev == y_dev))))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_jj_scalar_mul: out aliases a broadcast operand");
-    JjConsts c;
-    if (!jj_consts(ctx, c, a_host, d_host)) return fail(ctx, HB_ERR_BAD_ARG, "hb_jj_scalar_mul: a curve constant is not below the modulus");
-    if (count == 0) return HB_OK;
-    unsigned blocks;
-    if (!jj_blocks(count, &blocks)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_jj_scalar_mul: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t *n = (const uint32_t *)n_dev, *x = (const uint32_t *)x_dev, *y = (const uint32_t *)y_dev;
-    HB_DISPATCH(ctx, (k_jj_scalar_mul<9, 8><<<blocks, 256, 0, s>>>(ctx->pw, n, n_broadcast != 0, x, y, point_broadcast != 0, c.aw, c.dw, (uint32_t *)outx_dev, (uint32_t *)outy_dev, count)),
-                (k_jj_scalar_mul<3, 2><<<blocks, 256, 0, s>>>(ctx->pn, n, n_broadcast != 0, x, y, point_broadcast != 0, c.an, c.dn, (uint32_t *)outx_dev, (uint32_t *)outy_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    HB_ROW_BLOCKS(ctx, "hb_jj_scalar_mul");
+    const int rc = launch_rows<JjScalarMulRow, JjScalarMulArgs>(ctx, [&](auto &A, const auto &P) {
+        A.n = u32(n_dev); A.x = u32(x_dev); A.y = u32(y_dev); A.n_bcast = n_broadcast != 0; A.p_bcast = point_broadcast != 0; A.ox = u32(outx_dev); A.oy = u32(outy_dev);
+        return jj_curve_const(A.am, P, a_host) && jj_curve_const(A.dm, P, d_host);
+    }, (unsigned)blocks, s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_jj_scalar_mul: a curve constant is not below the modulus") : rc;
 }
 
 int hb_jj_double_table(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *a_host, int rows, uint64_t *xs_dev, uint64_t *ys_dev, uint64_t *zs_dev,
@@ -434,71 +389,60 @@ int hb_jj_double_table(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev
     if (!ctx || count < 0 || !a_host || (count > 0 && (!x_dev || !y_dev || !xs_dev || !ys_dev || !zs_dev))) return HB_ERR_BAD_ARG;
     if (rows < 1) return fail(ctx, HB_ERR_BAD_ARG, "hb_jj_double_table: at least one row");
     if (count > 0 && (xs_dev == ys_dev || xs_dev == zs_dev || ys_dev == zs_dev)) return fail(ctx, HB_ERR_BAD_ARG, "hb_jj_double_table: the three arrays must be distinct");
-    JjConsts c;
-    if (!jj_consts(ctx, c, a_host, nullptr)) return fail(ctx, HB_ERR_BAD_ARG, "hb_jj_double_table: a is not below the modulus");
-    if (count == 0) return HB_OK;
-    unsigned blocks;
-    if (!jj_blocks(count, &blocks) || count > INT64_MAX / rows / 64) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_jj_double_table: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    HB_DISPATCH(ctx, (k_jj_double_table<9, 8><<<blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)x_dev, (const uint32_t *)y_dev, c.aw, rows, (uint32_t *)xs_dev, (uint32_t *)ys_dev, (uint32_t *)zs_dev, count)),
-                (k_jj_double_table<3, 2><<<blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)x_dev, (const uint32_t *)y_dev, c.an, rows, (uint32_t *)xs_dev, (uint32_t *)ys_dev, (uint32_t *)zs_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
+    HB_ROW_BLOCKS(ctx, "hb_jj_double_table");
+    if (count > INT64_MAX / rows / 64) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_jj_double_table: batch too large for one launch");
+    int rc = launch_rows<JjDoubleTableRow, JjDoubleTableArgs>(ctx, [&](auto &A, const auto &P) {
+        A.x = u32(x_dev); A.y = u32(y_dev); A.xs = u32(xs_dev); A.ys = u32(ys_dev); A.zs = u32(zs_dev); A.K = rows;
+        return jj_curve_const(A.am, P, a_host);
+    }, (unsigned)blocks, s, count);
+    if (rc == HB_ERR_BAD_ARG) return fail(ctx, rc, "hb_jj_double_table: a is not below the modulus");
+    if (rc != HB_OK || count == 0) return rc;
     // affine: (X R) / (Z R) = x -- one batched inversion over every row's Z, two element-wise products
     const int64_t all = (int64_t)rows * count;
-    int rc = hb_ew_inv(ctx, zs_dev, zs_dev, all, zeros_dev, stream);
+    rc = hb_ew_inv(ctx, zs_dev, zs_dev, all, zeros_dev, stream);
     if (rc == HB_OK) rc = hb_ew_op(ctx, HB_EW_MUL, xs_dev, zs_dev, 0, xs_dev, all, stream);
     if (rc == HB_OK) rc = hb_ew_op(ctx, HB_EW_MUL, ys_dev, zs_dev, 0, ys_dev, all, stream);
     return rc;
 }
 
+// what the five stages of the shared addition check alike; count = m for HB_ROW_BLOCKS
 #define JJ_STAGE_GUARD(name, nullcheck)                                                                                           \
     if (!ctx || m < 0 || (m > 0 && (nullcheck))) return HB_ERR_BAD_ARG;                                                           \
     if (trip_stride < m) return fail(ctx, HB_ERR_BAD_ARG, name ": the triples' row stride is below the pair count");              \
     if (m == 0) return HB_OK;                                                                                                     \
-    unsigned blocks;                                                                                                              \
-    if (!jj_blocks(m, &blocks) || trip_stride > INT64_MAX / 1024) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch"); \
-    hipStream_t s = (hipStream_t)stream
+    const int64_t count = m;                                                                                                      \
+    HB_ROW_BLOCKS(ctx, name);                                                                                                     \
+    if (trip_stride > INT64_MAX / 1024) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch")
 
 int hb_jj_add_mask(hb_ctx *ctx, const uint64_t *x1_dev, const uint64_t *y1_dev, const uint64_t *x2_dev, const uint64_t *y2_dev, const uint64_t *p_dev,
                    const uint64_t *q_dev, int64_t trip_stride, uint64_t *a_dev, int64_t m, void *stream) { HB_API_GUARD(ctx);
     JJ_STAGE_GUARD("hb_jj_add_mask", !x1_dev || !y1_dev || !x2_dev || !y2_dev || !p_dev || !q_dev || !a_dev);
-    const JjTrip t = jj_trip(p_dev, q_dev, nullptr, trip_stride);
-    HB_DISPATCH(ctx, (k_jj_add_mask<9, 8><<<blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)x1_dev, (const uint32_t *)y1_dev, (const uint32_t *)x2_dev, (const uint32_t *)y2_dev, t, (uint32_t *)a_dev, m)),
-                (k_jj_add_mask<3, 2><<<blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)x1_dev, (const uint32_t *)y1_dev, (const uint32_t *)x2_dev, (const uint32_t *)y2_dev, t, (uint32_t *)a_dev, m)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const JjMaskArgs A = {u32(x1_dev), u32(y1_dev), u32(x2_dev), u32(y2_dev), jj_trip(p_dev, q_dev, nullptr, trip_stride), u32(a_dev)};
+    return launch_rows<JjMaskRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_jj_add_stage1(hb_ctx *ctx, const uint64_t *a_open_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev, int64_t trip_stride,
                      const uint64_t *rx_dev, const uint64_t *ry_dev, uint64_t *b_dev, int64_t m, void *stream) { HB_API_GUARD(ctx);
     JJ_STAGE_GUARD("hb_jj_add_stage1", !a_open_dev || !p_dev || !q_dev || !pq_dev || !rx_dev || !ry_dev || !b_dev);
-    const JjTrip t = jj_trip(p_dev, q_dev, pq_dev, trip_stride);
-    HB_DISPATCH(ctx, (k_jj_add_stage1<9, 8><<<blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)a_open_dev, t, (const uint32_t *)rx_dev, (const uint32_t *)ry_dev, (uint32_t *)b_dev, m)),
-                (k_jj_add_stage1<3, 2><<<blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)a_open_dev, t, (const uint32_t *)rx_dev, (const uint32_t *)ry_dev, (uint32_t *)b_dev, m)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const JjStageArgs A = {u32(a_open_dev), jj_trip(p_dev, q_dev, pq_dev, trip_stride), u32(rx_dev), u32(ry_dev), u32(b_dev)};
+    return launch_rows<JjStage1Row>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_jj_add_stage2(hb_ctx *ctx, const uint64_t *b_open_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev, int64_t trip_stride,
                      const uint64_t *rx_dev, const uint64_t *ry_dev, const uint64_t *d_host, uint64_t *uv_dev, uint64_t *c_dev, int64_t m, void *stream) { HB_API_GUARD(ctx);
     JJ_STAGE_GUARD("hb_jj_add_stage2", !b_open_dev || !p_dev || !q_dev || !pq_dev || !rx_dev || !ry_dev || !uv_dev || !c_dev);
-    JjConsts c;
-    if (!d_host || !jj_consts(ctx, c, nullptr, d_host)) return fail(ctx, HB_ERR_BAD_ARG, "hb_jj_add_stage2: d is missing or not below the modulus");
-    const JjTrip t = jj_trip(p_dev, q_dev, pq_dev, trip_stride);
-    HB_DISPATCH(ctx, (k_jj_add_stage2<9, 8><<<blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)b_open_dev, t, (const uint32_t *)rx_dev, (const uint32_t *)ry_dev, c.dw, (uint32_t *)uv_dev, (uint32_t *)c_dev, m)),
-                (k_jj_add_stage2<3, 2><<<blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)b_open_dev, t, (const uint32_t *)rx_dev, (const uint32_t *)ry_dev, c.dn, (uint32_t *)uv_dev, (uint32_t *)c_dev, m)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const int rc = launch_rows<JjStage2Row, JjStage2Args>(ctx, [&](auto &A, const auto &P) {
+        A.B = u32(b_open_dev); A.t = jj_trip(p_dev, q_dev, pq_dev, trip_stride); A.rx = u32(rx_dev); A.ry = u32(ry_dev); A.uv = u32(uv_dev); A.C = u32(c_dev);
+        return jj_curve_const(A.dm, P, d_host);
+    }, (unsigned)blocks, s, count);
+    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_jj_add_stage2: d is missing or not below the modulus") : rc;
 }
 
 int hb_jj_add_stage3(hb_ctx *ctx, const uint64_t *c_open_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev, int64_t trip_stride,
                      uint64_t *d_dev, int64_t m, void *stream) { HB_API_GUARD(ctx);
     JJ_STAGE_GUARD("hb_jj_add_stage3", !c_open_dev || !p_dev || !q_dev || !pq_dev || !d_dev);
-    const JjTrip t = jj_trip(p_dev, q_dev, pq_dev, trip_stride);
-    HB_DISPATCH(ctx, (k_jj_add_stage3<9, 8><<<blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)c_open_dev, t, (uint32_t *)d_dev, m)),
-                (k_jj_add_stage3<3, 2><<<blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)c_open_dev, t, (uint32_t *)d_dev, m)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const JjStageArgs A = {u32(c_open_dev), jj_trip(p_dev, q_dev, pq_dev, trip_stride), nullptr, nullptr, u32(d_dev)};
+    return launch_rows<JjStage3Row>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_jj_add_finish(hb_ctx *ctx, const uint64_t *d_open_dev, const uint64_t *uv_dev, uint64_t *inv_dev, uint64_t *x3_dev, uint64_t *y3_dev, int64_t m,
@@ -507,16 +451,15 @@ int hb_jj_add_finish(hb_ctx *ctx, const uint64_t *d_open_dev, const uint64_t *uv
     if (m > 0 && (x3_dev == y3_dev || x3_dev == inv_dev || y3_dev == inv_dev || x3_dev == uv_dev || y3_dev == uv_dev))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_jj_add_finish: the outputs must be distinct from each other, from uv and from the inverses");
     if (m == 0) return HB_OK;
-    unsigned blocks;
-    if (!jj_blocks(m, &blocks)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_jj_add_finish: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
+    const int64_t count = m;
+    HB_ROW_BLOCKS(ctx, "hb_jj_add_finish");
     const int rc = hb_ew_inv(ctx, d_open_dev, inv_dev, 2 * m, zeros_dev, stream);
     if (rc != HB_OK) return rc;
-    HB_DISPATCH(ctx, (k_jj_add_scale<9, 8><<<blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)inv_dev, (const uint32_t *)uv_dev, (uint32_t *)x3_dev, (uint32_t *)y3_dev, m)),
-                (k_jj_add_scale<3, 2><<<blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)inv_dev, (const uint32_t *)uv_dev, (uint32_t *)x3_dev, (uint32_t *)y3_dev, m)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const JjScaleArgs A = {u32(inv_dev), u32(uv_dev), u32(x3_dev), u32(y3_dev)};
+    return launch_rows<JjScaleRow>(ctx, A, (unsigned)blocks, s, count);
 }
+
+#undef JJ_STAGE_GUARD
 
 int hb_selftest_jj(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const uint64_t *a, const uint64_t *d, int flags, int64_t arg,
                    uint64_t *out, int64_t count) {

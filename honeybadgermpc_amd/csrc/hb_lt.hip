@@ -7,32 +7,37 @@
 // are affine in [r_i], because c_i is public; its least significant bit is [r > c].  The same tree over the leaves of the comparison
 // itself gives [r > c] as a bit.  The tree's levels are FxpCarryMaskRow / FxpCarryCombineRow of hb_fxp.hip, unchanged.
 //
-// k_lt_mask        2 (a - b) + r, the array to open (b may be absent: 2 a + r).
-// k_lt_leaves      (g, p), L planes each, most significant bit first; bit i of c is taken from the packed words and selects:
+// The steps are rows under the generic kernel k_rows (hb_rows.hpp):
+// LtMaskRow        2 (a - b) + r, the array to open (b may be absent: 2 a + r).
+// LtLeavesRow      (g, p), L planes each, most significant bit first; bit i of c is taken from the packed words and selects:
 //                     HB_LT_DIRECT     c_i = 0 -> (r_i, 1 - r_i)   c_i = 1 -> (0, r_i)         g = [r_i > c_i], p = [r_i = c_i]: root g = [r > c]
 //                     HB_LT_REFERENCE  c_i = 0 -> (r_i, 1 + r_i)   c_i = 1 -> (0, 2 - r_i)     the reference's r_i (1 - c_i), 1 + (r_i xor c_i): root g = x
 //                  No triple, no open.  (The reference spends a product and an open on every bit, one after the other.)
-// k_lt_xor_mask    DIRECT, after the tree gave w = [r > c]: u = c_0 ? 1 - r_0 : r_0 and the array to open [u - pa, w - qa].
-// k_lt_dmask       REFERENCE, after the tree gave x: u, and ONE array of five planes [s + x, u - pa, s_0 - qa, s_1 - pb, s_2 - qb] with
+// LtXorMaskRow     DIRECT, after the tree gave w = [r > c]: u = c_0 ? 1 - r_0 : r_0 and the array to open [u - pa, w - qa].
+// LtDmaskRow       REFERENCE, after the tree gave x: u, and ONE array of five planes [s + x, u - pa, s_0 - qa, s_1 - pb, s_2 - qb] with
 //                  s_0, s_1, s_2 = planes 0, L - 1, L - 2 of the second mask's bit shares (:178-182): d = s + x and the masked operands of
 //                  the two products that do not depend on d travel in one open.
-// k_lt_mid         that array opened: v = u xor s_0 and s_1 s_2 by ew_beaver_elem, d_0 by the reference's four-way select (:186-199;
+// LtMidRow         that array opened: v = u xor s_0 and s_1 s_2 by ew_beaver_elem, d_0 by the reference's four-way select (:186-199;
 //                  d < p < 2^L, so the three comparisons of d read bits L - 1 and L - 2 of d alone), the array to open [v - pc, d_0 - qc].
-// k_lt_xor_finish  both modes: u + v - 2 [u v], the last xor.
+// LtXorFinishRow   both modes: u + v - 2 [u v], the last xor.
 //
-// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions: the __global__ wrappers only
-// load, call them and store, and hb_selftest_lt runs the very same functions on the host.
+// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions; a step's row -- which operands it
+// loads, which body it calls, where it stores -- is an HB_HD function over a memory policy, so hb_selftest_lt runs on the host the very
+// rows, arithmetic and addressing, that k_rows runs on the device.
 //
-// Launch shape (all kernels): 256-thread workgroups, one element a thread in x; k_lt_leaves takes the plane in blockIdx.y (c is
-// one element a thread and stays in L2 for the L planes).  No LDS, no grid stride, one launch a call.  Bit planes, triples and opened
+// Launch shape (all steps): 256-thread workgroups, one element a thread in x; LtLeavesRow takes the plane in blockIdx.y (c is one
+// element a thread and stays in L2 for the L planes).  No LDS, no grid stride, one launch a call.  Bit planes, triples and opened
 // values are read once: the 32-byte width takes the non-temporal loads, as k_ew_beaver.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
-//   k_lt_mask<9, 8>        29 VGPRs with b, 30 without: 8 waves a SIMD        k_lt_mask<3, 2>        12 VGPRs: 8 waves
-//   k_lt_leaves<9, 8>      41 VGPRs: 8 waves                                  k_lt_leaves<3, 2>      17 VGPRs: 8 waves
-//   k_lt_xor_mask<9, 8>    56 VGPRs: 8 waves                                  k_lt_xor_mask<3, 2>    24 VGPRs: 8 waves
-//   k_lt_dmask<9, 8>       68 VGPRs: 7 waves                                  k_lt_dmask<3, 2>       34 VGPRs: 8 waves
-//   k_lt_mid<9, 8>         83 VGPRs: 5 waves                                  k_lt_mid<3, 2>         56 VGPRs: 8 waves
-//   k_lt_xor_finish<9, 8>  73 VGPRs: 6 waves                                  k_lt_xor_finish<3, 2>  30 VGPRs: 8 waves
+//   LtMaskRow<9, 8>        29 VGPRs with b, 30 without: 8 waves a SIMD        LtMaskRow<3, 2>        12 VGPRs: 8 waves
+//   LtLeavesRow<9, 8>      41 VGPRs: 8 waves                                  LtLeavesRow<3, 2>      17 VGPRs: 8 waves
+//   LtXorMaskRow<9, 8>     56 VGPRs: 8 waves                                  LtXorMaskRow<3, 2>     24 VGPRs: 8 waves
+//   LtDmaskRow<9, 8>      101 VGPRs: 4 waves                                  LtDmaskRow<3, 2>       34 VGPRs: 8 waves
+//   LtMidRow<9, 8>         83 VGPRs: 5 waves                                  LtMidRow<3, 2>         56 VGPRs: 8 waves
+//   LtXorFinishRow<9, 8>   73 VGPRs: 6 waves                                  LtXorFinishRow<3, 2>   29 VGPRs: 8 waves
+// LtDmaskRow<9, 8> held 68 VGPRs (7 waves) while its pointers were __restrict__ kernel parameters; pointers in an argument struct
+// carry none and the compiler keeps more of the 21 loads' results live.  The launch streams 17 elements an element and took the same
+// time either way (profiles/less_than.txt), so it has no kernel of its own.
 // (DESIGN.md section 3p has the schedule and the counts.)
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
@@ -43,11 +48,6 @@ using namespace hb;
 namespace hb {
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-template <int NL> HB_HD void lt_small(uint32_t (&r)[NL], uint32_t v) {
-#pragma unroll
-    for (int q = 0; q < NL; q++) r[q] = q == 0 ? v : 0u;
-}
-
 // o = 2 (a - b) + r; HAS_B = false: 2 a + r
 template <int NL, int NW, bool HAS_B>
 HB_HD void lt_mask_elem(uint32_t (&o)[NW], const uint32_t (&aw)[NW], const uint32_t (&bw)[NW], const uint32_t (&rw)[NW], const FpParams<NL> &P) {
@@ -70,14 +70,14 @@ HB_HD void lt_leaf_elem(uint32_t (&gw)[NW], uint32_t (&pw)[NW], uint32_t a, cons
     uint32_t b[NL], k[NL], t[NL], w[NL], g[NL], p[NL];
     unpack<NL, NW>(b, bw);
     if (mode == HB_LT_DIRECT) {                        // mode is the same for every lane; the bit a selects
-        lt_small<NL>(k, 1);
+        small_digits<NL>(k, 1);
         fp_sub<NL>(t, k, b, P);                        // 1 - r_i
 #pragma unroll
         for (int q = 0; q < NL; q++) p[q] = a ? b[q] : t[q];
     } else {
-        lt_small<NL>(k, 2);
+        small_digits<NL>(k, 2);
         fp_sub<NL>(t, k, b, P);                        // 2 - r_i
-        lt_small<NL>(k, 1);
+        small_digits<NL>(k, 1);
         fp_add<NL>(w, k, b, P);                        // 1 + r_i
 #pragma unroll
         for (int q = 0; q < NL; q++) p[q] = a ? t[q] : w[q];
@@ -92,7 +92,7 @@ HB_HD void lt_leaf_elem(uint32_t (&gw)[NW], uint32_t (&pw)[NW], uint32_t a, cons
 template <int NL, int NW> HB_HD void lt_u_elem(uint32_t (&uw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r0w)[NW], const FpParams<NL> &P) {
     uint32_t b[NL], one[NL], t[NL];
     unpack<NL, NW>(b, r0w);
-    lt_small<NL>(one, 1);
+    small_digits<NL>(one, 1);
     fp_sub<NL>(t, one, b, P);
     const uint32_t c0 = cw[0] & 1u;
 #pragma unroll
@@ -160,7 +160,7 @@ HB_HD void lt_mid_elem(uint32_t (&vw)[NW], uint32_t (&d0w)[NW], uint32_t (&m0)[N
     const uint32_t d0 = o0[0] & 1u, t1 = word_bit<NW>(o0, L - 1), t2 = word_bit<NW>(o0, L - 2);
     const uint32_t dx1 = d0 ^ (t1 ^ 1u), dx2 = d0 ^ ((t1 | t2) ^ 1u), dx12 = d0 ^ ((t1 & t2) ^ 1u);
     // (1 - s_1 - s_2 + s_1 s_2) d0
-    lt_small<NL>(w, 1);
+    small_digits<NL>(w, 1);
     fp_sub<NL>(t, w, s1, P);
     fp_sub<NL>(w, t, s2, P);
     fp_add<NL>(t, w, sp, P);
@@ -182,168 +182,150 @@ HB_HD void lt_mid_elem(uint32_t (&vw)[NW], uint32_t (&d0w)[NW], uint32_t (&m0)[N
     diff_elem<NL, NW>(m1, d0w, qcw, P);
 }
 
-// ---------------------------------------------------------------- kernels
-// Every output is an array of its own: __restrict__ throughout.
-template <int NL, int NW, bool HAS_B>
-__global__ void __launch_bounds__(256) k_lt_mask(const FpParams<NL> P, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ r,
-                                                 uint32_t *__restrict__ masked, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t aw[NW], bw[NW], rw[NW], ow[NW];
-    load_words<NW>(aw, a + i * NW);
-    if constexpr (HAS_B) load_words<NW>(bw, b + i * NW);
-    else {
-#pragma unroll
-        for (int q = 0; q < NW; q++) bw[q] = 0;
-    }
-    load_words<NW>(rw, r + i * NW);
-    lt_mask_elem<NL, NW, HAS_B>(ow, aw, bw, rw, P);
-    store_words<NW>(masked + i * NW, ow);
-}
+// ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
+// Every output is an array of its own, and every row issues all its loads ahead of its first store.
+struct LtMaskArgs { const uint32_t *a, *b, *r; uint32_t *masked; };
 
-// plane j = blockIdx.y holds bit L - 1 - j
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_lt_leaves(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ r_bits, int L, int mode,
-                                                   uint32_t *__restrict__ g, uint32_t *__restrict__ p, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t j = blockIdx.y;
-    const int bit = L - 1 - (int)j;
-    uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
-    load_words<NW>(cw, c + i * NW);
-    load_once<NW>(bw, r_bits + ((int64_t)bit * count + i) * NW);
-    lt_leaf_elem<NL, NW>(gw, pw, word_bit<NW>(cw, bit), bw, mode, P);
-    store_words<NW>(g + (j * count + i) * NW, gw);
-    store_words<NW>(p + (j * count + i) * NW, pw);
-}
+template <bool HAS_B> struct LtMaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LtMaskArgs &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t aw[NW], bw[NW], rw[NW], ow[NW];
+        mem.load(aw, A.a, i);
+        if constexpr (HAS_B) mem.load(bw, A.b, i);
+        else {
+#pragma unroll
+            for (int q = 0; q < NW; q++) bw[q] = 0;
+        }
+        mem.load(rw, A.r, i);
+        lt_mask_elem<NL, NW, HAS_B>(ow, aw, bw, rw, P);
+        mem.store(A.masked, i, ow);
+    }
+};
+
+// g, p: L planes each; plane y holds bit L - 1 - y
+struct LtLeavesArgs { const uint32_t *c, *r_bits; uint32_t *g, *p; int L, mode; };
+
+struct LtLeavesRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LtLeavesArgs &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        const int64_t j = y;
+        const int bit = A.L - 1 - y;
+        uint32_t cw[NW], bw[NW], gw[NW], pw[NW];
+        mem.load(cw, A.c, i);
+        mem.once(bw, A.r_bits, (int64_t)bit * count + i);
+        lt_leaf_elem<NL, NW>(gw, pw, word_bit<NW>(cw, bit), bw, A.mode, P);
+        mem.store(A.g, j * count + i, gw);
+        mem.store(A.p, j * count + i, pw);
+    }
+};
 
 // masked: (2, count)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_lt_xor_mask(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ r0, const uint32_t *__restrict__ w,
-                                                     const uint32_t *__restrict__ pa, const uint32_t *__restrict__ qa, uint32_t *__restrict__ u,
-                                                     uint32_t *__restrict__ masked, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t cw[NW], rw[NW], ww[NW], paw[NW], qaw[NW], uw[NW], m0[NW], m1[NW];
-    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); load_once<NW>(ww, w + i * NW);
-    load_once<NW>(paw, pa + i * NW); load_once<NW>(qaw, qa + i * NW);
-    lt_xor_mask_elem<NL, NW>(uw, m0, m1, cw, rw, ww, paw, qaw, P);
-    store_words<NW>(u + i * NW, uw);
-    store_words<NW>(masked + i * NW, m0);
-    store_words<NW>(masked + (count + i) * NW, m1);
-}
+struct LtXorMaskArgs { const uint32_t *c, *r0, *w, *pa, *qa; uint32_t *u, *masked; };
 
-// masked: (5, count)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_lt_dmask(const FpParams<NL> P, const uint32_t *__restrict__ c, const uint32_t *__restrict__ r0, const uint32_t *__restrict__ x,
-                                                  const uint32_t *__restrict__ s, const uint32_t *__restrict__ s_bits, int L, const uint32_t *__restrict__ pa,
-                                                  const uint32_t *__restrict__ qa, const uint32_t *__restrict__ pb, const uint32_t *__restrict__ qb,
-                                                  uint32_t *__restrict__ u, uint32_t *__restrict__ masked, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t cw[NW], rw[NW], xw[NW], sw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pbw[NW], qbw[NW], uw[NW], m0[NW], m1[NW], m2[NW], m3[NW], m4[NW];
-    load_words<NW>(cw, c + i * NW); load_words<NW>(rw, r0 + i * NW); load_once<NW>(xw, x + i * NW); load_words<NW>(sw, s + i * NW);
-    load_words<NW>(s0w, s_bits + i * NW);
-    load_words<NW>(s1w, s_bits + ((int64_t)(L - 1) * count + i) * NW);
-    load_words<NW>(s2w, s_bits + ((int64_t)(L - 2) * count + i) * NW);
-    load_once<NW>(paw, pa + i * NW); load_once<NW>(qaw, qa + i * NW); load_once<NW>(pbw, pb + i * NW); load_once<NW>(qbw, qb + i * NW);
-    lt_dmask_elem<NL, NW>(uw, m0, m1, m2, m3, m4, cw, rw, xw, sw, s0w, s1w, s2w, paw, qaw, pbw, qbw, P);
-    store_words<NW>(u + i * NW, uw);
-    store_words<NW>(masked + i * NW, m0);
-    store_words<NW>(masked + (count + i) * NW, m1);
-    store_words<NW>(masked + (2 * count + i) * NW, m2);
-    store_words<NW>(masked + (3 * count + i) * NW, m3);
-    store_words<NW>(masked + (4 * count + i) * NW, m4);
-}
+struct LtXorMaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LtXorMaskArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t cw[NW], rw[NW], ww[NW], paw[NW], qaw[NW], uw[NW], m0[NW], m1[NW];
+        mem.load(cw, A.c, i); mem.load(rw, A.r0, i); mem.once(ww, A.w, i);
+        mem.once(paw, A.pa, i); mem.once(qaw, A.qa, i);
+        lt_xor_mask_elem<NL, NW>(uw, m0, m1, cw, rw, ww, paw, qaw, P);
+        mem.store(A.u, i, uw);
+        mem.store(A.masked, i, m0);
+        mem.store(A.masked, count + i, m1);
+    }
+};
+
+// masked: (5, count); s_0, s_1, s_2 are planes 0, L - 1, L - 2 of s_bits
+struct LtDmaskArgs { const uint32_t *c, *r0, *x, *s, *s_bits, *pa, *qa, *pb, *qb; uint32_t *u, *masked; int L; };
+
+struct LtDmaskRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LtDmaskArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t cw[NW], rw[NW], xw[NW], sw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pbw[NW], qbw[NW], uw[NW], m0[NW], m1[NW], m2[NW], m3[NW], m4[NW];
+        mem.load(cw, A.c, i); mem.load(rw, A.r0, i); mem.once(xw, A.x, i); mem.load(sw, A.s, i);
+        mem.load(s0w, A.s_bits, i);
+        mem.load(s1w, A.s_bits, (int64_t)(A.L - 1) * count + i);
+        mem.load(s2w, A.s_bits, (int64_t)(A.L - 2) * count + i);
+        mem.once(paw, A.pa, i); mem.once(qaw, A.qa, i); mem.once(pbw, A.pb, i); mem.once(qbw, A.qb, i);
+        lt_dmask_elem<NL, NW>(uw, m0, m1, m2, m3, m4, cw, rw, xw, sw, s0w, s1w, s2w, paw, qaw, pbw, qbw, P);
+        mem.store(A.u, i, uw);
+        mem.store(A.masked, i, m0);
+        mem.store(A.masked, count + i, m1);
+        mem.store(A.masked, 2 * count + i, m2);
+        mem.store(A.masked, 3 * count + i, m3);
+        mem.store(A.masked, 4 * count + i, m4);
+    }
+};
 
 // opened: (5, count); masked: (2, count)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_lt_mid(const FpParams<NL> P, const uint32_t *__restrict__ opened, const uint32_t *__restrict__ u, const uint32_t *__restrict__ s_bits,
-                                                int L, const uint32_t *__restrict__ pa, const uint32_t *__restrict__ qa, const uint32_t *__restrict__ pqa,
-                                                const uint32_t *__restrict__ pb, const uint32_t *__restrict__ qb, const uint32_t *__restrict__ pqb,
-                                                const uint32_t *__restrict__ pc, const uint32_t *__restrict__ qc, uint32_t *__restrict__ v, uint32_t *__restrict__ d0,
-                                                uint32_t *__restrict__ masked, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t o0[NW], o1[NW], o2[NW], o3[NW], o4[NW], uw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pqaw[NW], pbw[NW], qbw[NW], pqbw[NW], pcw[NW], qcw[NW];
-    uint32_t vw[NW], d0w[NW], m0[NW], m1[NW];
-    load_once<NW>(o0, opened + i * NW); load_once<NW>(o1, opened + (count + i) * NW); load_once<NW>(o2, opened + (2 * count + i) * NW);
-    load_once<NW>(o3, opened + (3 * count + i) * NW); load_once<NW>(o4, opened + (4 * count + i) * NW);
-    load_once<NW>(uw, u + i * NW);
-    load_words<NW>(s0w, s_bits + i * NW);
-    load_words<NW>(s1w, s_bits + ((int64_t)(L - 1) * count + i) * NW);
-    load_words<NW>(s2w, s_bits + ((int64_t)(L - 2) * count + i) * NW);
-    load_once<NW>(paw, pa + i * NW); load_once<NW>(qaw, qa + i * NW); load_once<NW>(pqaw, pqa + i * NW);
-    load_once<NW>(pbw, pb + i * NW); load_once<NW>(qbw, qb + i * NW); load_once<NW>(pqbw, pqb + i * NW);
-    load_words<NW>(pcw, pc + i * NW); load_words<NW>(qcw, qc + i * NW);
-    lt_mid_elem<NL, NW>(vw, d0w, m0, m1, o0, o1, o2, o3, o4, uw, s0w, s1w, s2w, paw, qaw, pqaw, pbw, qbw, pqbw, pcw, qcw, L, P);
-    store_words<NW>(v + i * NW, vw);
-    store_words<NW>(d0 + i * NW, d0w);
-    store_words<NW>(masked + i * NW, m0);
-    store_words<NW>(masked + (count + i) * NW, m1);
-}
+struct LtMidArgs { const uint32_t *opened, *u, *s_bits, *pa, *qa, *pqa, *pb, *qb, *pqb, *pc, *qc; uint32_t *v, *d0, *masked; int L; };
+
+struct LtMidRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LtMidArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t o0[NW], o1[NW], o2[NW], o3[NW], o4[NW], uw[NW], s0w[NW], s1w[NW], s2w[NW], paw[NW], qaw[NW], pqaw[NW], pbw[NW], qbw[NW], pqbw[NW], pcw[NW], qcw[NW];
+        uint32_t vw[NW], d0w[NW], m0[NW], m1[NW];
+        mem.once(o0, A.opened, i); mem.once(o1, A.opened, count + i); mem.once(o2, A.opened, 2 * count + i);
+        mem.once(o3, A.opened, 3 * count + i); mem.once(o4, A.opened, 4 * count + i);
+        mem.once(uw, A.u, i);
+        mem.load(s0w, A.s_bits, i);
+        mem.load(s1w, A.s_bits, (int64_t)(A.L - 1) * count + i);
+        mem.load(s2w, A.s_bits, (int64_t)(A.L - 2) * count + i);
+        mem.once(paw, A.pa, i); mem.once(qaw, A.qa, i); mem.once(pqaw, A.pqa, i);
+        mem.once(pbw, A.pb, i); mem.once(qbw, A.qb, i); mem.once(pqbw, A.pqb, i);
+        mem.load(pcw, A.pc, i); mem.load(qcw, A.qc, i);
+        lt_mid_elem<NL, NW>(vw, d0w, m0, m1, o0, o1, o2, o3, o4, uw, s0w, s1w, s2w, paw, qaw, pqaw, pbw, qbw, pqbw, pcw, qcw, A.L, P);
+        mem.store(A.v, i, vw);
+        mem.store(A.d0, i, d0w);
+        mem.store(A.masked, i, m0);
+        mem.store(A.masked, count + i, m1);
+    }
+};
 
 // opened: (2, count)
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_lt_xor_finish(const FpParams<NL> P, const uint32_t *__restrict__ opened, const uint32_t *__restrict__ u, const uint32_t *__restrict__ v,
-                                                       const uint32_t *__restrict__ tp, const uint32_t *__restrict__ tq, const uint32_t *__restrict__ tpq,
-                                                       uint32_t *__restrict__ out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t dw[NW], ew[NW], uw[NW], vw[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
-    load_once<NW>(dw, opened + i * NW); load_once<NW>(ew, opened + (count + i) * NW);
-    load_once<NW>(uw, u + i * NW); load_once<NW>(vw, v + i * NW);
-    load_once<NW>(pw, tp + i * NW); load_once<NW>(qw, tq + i * NW); load_once<NW>(pqw, tpq + i * NW);
-    lt_xor_elem<NL, NW>(ow, uw, vw, dw, ew, pw, qw, pqw, P);
-    store_words<NW>(out + i * NW, ow);
-}
+struct LtXorFinishArgs { const uint32_t *opened, *u, *v, *tp, *tq, *tpq; uint32_t *out; };
+
+struct LtXorFinishRow {
+    template <int NL, int NW, class Mem>
+    HB_HD static void run(const LtXorFinishArgs &A, int, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t dw[NW], ew[NW], uw[NW], vw[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
+        mem.once(dw, A.opened, i); mem.once(ew, A.opened, count + i);
+        mem.once(uw, A.u, i); mem.once(vw, A.v, i);
+        mem.once(pw, A.tp, i); mem.once(qw, A.tq, i); mem.once(pqw, A.tpq, i);
+        lt_xor_elem<NL, NW>(ow, uw, vw, dw, ew, pw, qw, pqw, P);
+        mem.store(A.out, i, ow);
+    }
+};
 
 // ---------------------------------------------------------------- host side
 static bool lt_mode_ok(int mode) { return mode == HB_LT_DIRECT || mode == HB_LT_REFERENCE; }
 
-// host: the same element functions over `count` elements
+// host: the same rows over `count` elements
 template <int NL, int NW>
 static int selftest_lt(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
     const int L = (int)params[0], mode = (int)params[1];
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    auto O = [](uint64_t *base, int64_t i) -> uint32_t * { return reinterpret_cast<uint32_t *>(base) + i * NW; };
-    const uint32_t none[NW] = {};
-    uint32_t r0[NW], r1[NW], r2[NW], r3[NW], r4[NW], r5[NW];
-    for (int64_t i = 0; i < count; i++) {
-        if (what == HB_LT_SELFTEST_MASK) {
-            if (ops[1]) lt_mask_elem<NL, NW, true>(r0, W(ops[0], i), W(ops[1], i), W(ops[2], i), P);
-            else lt_mask_elem<NL, NW, false>(r0, W(ops[0], i), none, W(ops[2], i), P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-        } else if (what == HB_LT_SELFTEST_LEAVES) {
-            for (int j = 0; j < L; j++) {
-                const int bit = L - 1 - j;
-                lt_leaf_elem<NL, NW>(r0, r1, word_bit<NW>(W(ops[0], i), bit), W(ops[1], (int64_t)bit * count + i), mode, P);
-                memcpy(O(outs[0], (int64_t)j * count + i), r0, NW * 4);
-                memcpy(O(outs[1], (int64_t)j * count + i), r1, NW * 4);
-            }
-        } else if (what == HB_LT_SELFTEST_XOR_MASK) {
-            lt_xor_mask_elem<NL, NW>(r0, r1, r2, W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), W(ops[4], i), P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-            memcpy(O(outs[1], i), r1, NW * 4); memcpy(O(outs[1], count + i), r2, NW * 4);
-        } else if (what == HB_LT_SELFTEST_DMASK) {
-            lt_dmask_elem<NL, NW>(r0, r1, r2, r3, r4, r5, W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), W(ops[4], i), W(ops[4], (int64_t)(L - 1) * count + i),
-                                  W(ops[4], (int64_t)(L - 2) * count + i), W(ops[5], i), W(ops[6], i), W(ops[7], i), W(ops[8], i), P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-            memcpy(O(outs[1], i), r1, NW * 4); memcpy(O(outs[1], count + i), r2, NW * 4); memcpy(O(outs[1], 2 * count + i), r3, NW * 4);
-            memcpy(O(outs[1], 3 * count + i), r4, NW * 4); memcpy(O(outs[1], 4 * count + i), r5, NW * 4);
-        } else if (what == HB_LT_SELFTEST_MID) {
-            lt_mid_elem<NL, NW>(r0, r1, r2, r3, W(ops[0], i), W(ops[0], count + i), W(ops[0], 2 * count + i), W(ops[0], 3 * count + i), W(ops[0], 4 * count + i), W(ops[1], i),
-                                W(ops[2], i), W(ops[2], (int64_t)(L - 1) * count + i), W(ops[2], (int64_t)(L - 2) * count + i), W(ops[3], i), W(ops[4], i), W(ops[5], i),
-                                W(ops[6], i), W(ops[7], i), W(ops[8], i), W(ops[9], i), W(ops[10], i), L, P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-            memcpy(O(outs[1], i), r1, NW * 4);
-            memcpy(O(outs[2], i), r2, NW * 4); memcpy(O(outs[2], count + i), r3, NW * 4);
-        } else {
-            lt_xor_elem<NL, NW>(r0, W(ops[1], i), W(ops[2], i), W(ops[0], i), W(ops[0], count + i), W(ops[3], i), W(ops[4], i), W(ops[5], i), P);
-            memcpy(O(outs[0], i), r0, NW * 4);
-        }
+    if (what == HB_LT_SELFTEST_MASK) {
+        const LtMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(outs[0])};
+        if (A.b) host_rows<LtMaskRow<true>, NL, NW>(A, 1, count, P);
+        else host_rows<LtMaskRow<false>, NL, NW>(A, 1, count, P);
+    } else if (what == HB_LT_SELFTEST_LEAVES) {
+        const LtLeavesArgs A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1]), L, mode};
+        host_rows<LtLeavesRow, NL, NW>(A, L, count, P);
+    } else if (what == HB_LT_SELFTEST_XOR_MASK) {
+        const LtXorMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(outs[0]), u32(outs[1])};
+        host_rows<LtXorMaskRow, NL, NW>(A, 1, count, P);
+    } else if (what == HB_LT_SELFTEST_DMASK) {
+        const LtDmaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(outs[0]), u32(outs[1]), L};
+        host_rows<LtDmaskRow, NL, NW>(A, 1, count, P);
+    } else if (what == HB_LT_SELFTEST_MID) {
+        const LtMidArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(ops[9]), u32(ops[10]),
+                             u32(outs[0]), u32(outs[1]), u32(outs[2]), L};
+        host_rows<LtMidRow, NL, NW>(A, 1, count, P);
+    } else {
+        const LtXorFinishArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(outs[0])};
+        host_rows<LtXorFinishRow, NL, NW>(A, 1, count, P);
     }
     return HB_OK;
 }
@@ -361,12 +343,9 @@ int hb_lt_mask(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const 
     const RowSpan outs[1] = {{masked_dev, 1}}, ins[3] = {{a_dev, 1}, {b_dev, 1}, {r_dev, 1}};
     if (!outputs_apart(outs, 1, ins, 3, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mask: masked is an array of its own");
     HB_ROW_BLOCKS(ctx, "hb_lt_mask");
-#define LT_MASK(NL, NW, HAS_B, P) k_lt_mask<NL, NW, HAS_B><<<(unsigned)blocks, 256, 0, s>>>(P, u32(a_dev), u32(b_dev), u32(r_dev), (uint32_t *)masked_dev, count)
-    if (b_dev) HB_DISPATCH(ctx, (LT_MASK(9, 8, true, ctx->pw)), (LT_MASK(3, 2, true, ctx->pn)));
-    else HB_DISPATCH(ctx, (LT_MASK(9, 8, false, ctx->pw)), (LT_MASK(3, 2, false, ctx->pn)));
-#undef LT_MASK
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const LtMaskArgs A = {u32(a_dev), u32(b_dev), u32(r_dev), u32(masked_dev)};
+    if (b_dev) return launch_rows<LtMaskRow<true>>(ctx, A, (unsigned)blocks, s, count);
+    return launch_rows<LtMaskRow<false>>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_lt_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r_bits_dev, int L, int mode, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream) {
@@ -379,12 +358,8 @@ int hb_lt_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r_bits_dev,
     const RowSpan outs[2] = {{g_dev, L}, {p_dev, L}}, ins[2] = {{c_dev, 1}, {r_bits_dev, L}};
     if (!outputs_apart(outs, 2, ins, 2, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: g and p are arrays of their own");
     HB_ROW_BLOCKS(ctx, "hb_lt_leaves");
-    const dim3 grid((unsigned)blocks, (unsigned)L);
-    HB_DISPATCH(ctx,
-        (k_lt_leaves<9, 8><<<grid, 256, 0, s>>>(ctx->pw, u32(c_dev), u32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)),
-        (k_lt_leaves<3, 2><<<grid, 256, 0, s>>>(ctx->pn, u32(c_dev), u32(r_bits_dev), L, mode, (uint32_t *)g_dev, (uint32_t *)p_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const LtLeavesArgs A = {u32(c_dev), u32(r_bits_dev), u32(g_dev), u32(p_dev), L, mode};
+    return launch_rows<LtLeavesRow>(ctx, A, dim3((unsigned)blocks, (unsigned)L), s, count);
 }
 
 int hb_lt_xor_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *w_dev, const uint64_t *pa_dev, const uint64_t *qa_dev, uint64_t *u_dev,
@@ -395,11 +370,8 @@ int hb_lt_xor_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, c
     const RowSpan outs[2] = {{u_dev, 1}, {masked_dev, 2}}, ins[5] = {{c_dev, 1}, {r0_dev, 1}, {w_dev, 1}, {pa_dev, 1}, {qa_dev, 1}};
     if (!outputs_apart(outs, 2, ins, 5, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_mask: u and masked are arrays of their own");
     HB_ROW_BLOCKS(ctx, "hb_lt_xor_mask");
-    HB_DISPATCH(ctx,
-        (k_lt_xor_mask<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, u32(c_dev), u32(r0_dev), u32(w_dev), u32(pa_dev), u32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)),
-        (k_lt_xor_mask<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, u32(c_dev), u32(r0_dev), u32(w_dev), u32(pa_dev), u32(qa_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const LtXorMaskArgs A = {u32(c_dev), u32(r0_dev), u32(w_dev), u32(pa_dev), u32(qa_dev), u32(u_dev), u32(masked_dev)};
+    return launch_rows<LtXorMaskRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_lt_dmask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *x_dev, const uint64_t *s_dev, const uint64_t *s_bits_dev, int L,
@@ -414,13 +386,8 @@ int hb_lt_dmask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, cons
                  ins[9] = {{c_dev, 1}, {r0_dev, 1}, {x_dev, 1}, {s_dev, 1}, {s_bits_dev, L}, {pa_dev, 1}, {qa_dev, 1}, {pb_dev, 1}, {qb_dev, 1}};
     if (!outputs_apart(outs, 2, ins, 9, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: u and masked are arrays of their own");
     HB_ROW_BLOCKS(ctx, "hb_lt_dmask");
-#define LT_DMASK(NL, NW, P)                                                                                                                                      \
-    k_lt_dmask<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, u32(c_dev), u32(r0_dev), u32(x_dev), u32(s_dev), u32(s_bits_dev), L, u32(pa_dev), u32(qa_dev), u32(pb_dev), \
-                                                        u32(qb_dev), (uint32_t *)u_dev, (uint32_t *)masked_dev, count)
-    HB_DISPATCH(ctx, (LT_DMASK(9, 8, ctx->pw)), (LT_DMASK(3, 2, ctx->pn)));
-#undef LT_DMASK
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const LtDmaskArgs A = {u32(c_dev), u32(r0_dev), u32(x_dev), u32(s_dev), u32(s_bits_dev), u32(pa_dev), u32(qa_dev), u32(pb_dev), u32(qb_dev), u32(u_dev), u32(masked_dev), L};
+    return launch_rows<LtDmaskRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_lt_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *s_bits_dev, int L, const uint64_t *pa_dev, const uint64_t *qa_dev,
@@ -440,13 +407,9 @@ int hb_lt_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, co
     for (int k = 0; k < 8; k++) ins[3 + k] = {trip[k], 1};
     if (!outputs_apart(outs, 3, ins, 11, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: the outputs are arrays of their own");
     HB_ROW_BLOCKS(ctx, "hb_lt_mid");
-#define LT_MID(NL, NW, P)                                                                                                                                       \
-    k_lt_mid<NL, NW><<<(unsigned)blocks, 256, 0, s>>>(P, u32(opened_dev), u32(u_dev), u32(s_bits_dev), L, u32(pa_dev), u32(qa_dev), u32(pqa_dev), u32(pb_dev),        \
-                                                      u32(qb_dev), u32(pqb_dev), u32(pc_dev), u32(qc_dev), (uint32_t *)v_dev, (uint32_t *)d0_dev, (uint32_t *)masked_dev, count)
-    HB_DISPATCH(ctx, (LT_MID(9, 8, ctx->pw)), (LT_MID(3, 2, ctx->pn)));
-#undef LT_MID
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const LtMidArgs A = {u32(opened_dev), u32(u_dev), u32(s_bits_dev), u32(pa_dev), u32(qa_dev), u32(pqa_dev), u32(pb_dev), u32(qb_dev), u32(pqb_dev), u32(pc_dev), u32(qc_dev),
+                         u32(v_dev), u32(d0_dev), u32(masked_dev), L};
+    return launch_rows<LtMidRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_lt_xor_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *v_dev, const uint64_t *p_dev, const uint64_t *q_dev,
@@ -457,11 +420,8 @@ int hb_lt_xor_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_
     const RowSpan outs[1] = {{out_dev, 1}}, ins[6] = {{opened_dev, 2}, {u_dev, 1}, {v_dev, 1}, {p_dev, 1}, {q_dev, 1}, {pq_dev, 1}};
     if (!outputs_apart(outs, 1, ins, 6, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_finish: out is an array of its own");
     HB_ROW_BLOCKS(ctx, "hb_lt_xor_finish");
-    HB_DISPATCH(ctx,
-        (k_lt_xor_finish<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, u32(opened_dev), u32(u_dev), u32(v_dev), u32(p_dev), u32(q_dev), u32(pq_dev), (uint32_t *)out_dev, count)),
-        (k_lt_xor_finish<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, u32(opened_dev), u32(u_dev), u32(v_dev), u32(p_dev), u32(q_dev), u32(pq_dev), (uint32_t *)out_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const LtXorFinishArgs A = {u32(opened_dev), u32(u_dev), u32(v_dev), u32(p_dev), u32(q_dev), u32(pq_dev), u32(out_dev)};
+    return launch_rows<LtXorFinishRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {

@@ -30,9 +30,6 @@ using namespace hb;
 
 namespace hb {
 
-// a field element as digits, handed to a kernel by value (the counter's start, the round constant c + 1)
-template <int NL> struct MimcConst { uint32_t d[NL]; };
-
 // ---------------------------------------------------------------- per-element bodies (host and device)
 // r = i mod p, canonical, for an index 0 <= i < 2^63 (p may be as small as 13).  The digits of i times R^2: T < R p (i < 2^87 <= R,
 // R^2 mod p < p), so REDC returns i R mod p below 2 p -- one conditional subtraction, as any mont_mul -- and a bare REDC takes the R off.
@@ -201,7 +198,7 @@ template <int NW, bool BCAST, bool UNIFORM = true> __device__ __forceinline__ vo
 // Thread t of block b owns elements b 256 E + t + 256 e, e < E.  A slot past `count` repeats the thread's first element and is not
 // stored.  No __restrict__: out may be x, addend or a per-element key (a thread reads all its elements before it writes any).
 template <int NL, int NW, int E, bool BCAST>
-__global__ void __launch_bounds__(256) k_mimc_plain(const FpParams<NL> P, const uint32_t *x, const MimcConst<NL> start, const uint32_t *key, const uint32_t *addend,
+__global__ void __launch_bounds__(256) k_mimc_plain(const FpParams<NL> P, const uint32_t *x, const FpConst<NL> start, const uint32_t *key, const uint32_t *addend,
                                                     int subtract, int rounds, uint32_t *out, int64_t count) {
     const int64_t first = (int64_t)blockIdx.x * (256 * E) + threadIdx.x;
     if (first >= count) return;
@@ -222,7 +219,7 @@ __global__ void __launch_bounds__(256) k_mimc_plain(const FpParams<NL> P, const 
 }
 
 template <int NL, int NW, bool BCAST>
-__global__ void __launch_bounds__(256) k_mimc_first(const FpParams<NL> P, const uint32_t *x, const MimcConst<NL> start, const uint32_t *key, const uint32_t *r0,
+__global__ void __launch_bounds__(256) k_mimc_first(const FpParams<NL> P, const uint32_t *x, const FpConst<NL> start, const uint32_t *key, const uint32_t *r0,
                                                     uint32_t *out, int64_t count) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
@@ -236,7 +233,7 @@ __global__ void __launch_bounds__(256) k_mimc_first(const FpParams<NL> P, const 
 
 template <int NL, int NW, bool LAST, bool BCAST>
 __global__ void __launch_bounds__(256) k_mimc_round(const FpParams<NL> P, const uint32_t *y, const uint32_t *r, const uint32_t *r2, const uint32_t *r3,
-                                                    const uint32_t *key, const MimcConst<NL> cst, const uint32_t *r_next, uint32_t *out, int64_t count) {
+                                                    const uint32_t *key, const FpConst<NL> cst, const uint32_t *r_next, uint32_t *out, int64_t count) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     uint32_t yw[NW], rw[NW], r2w[NW], r3w[NW], kw[NW], rnw[NW], ow[NW];
@@ -250,27 +247,23 @@ __global__ void __launch_bounds__(256) k_mimc_round(const FpParams<NL> P, const 
 
 // ---------------------------------------------------------------- host side
 // v mod p as digits (v < 2^63)
-template <int NL> static MimcConst<NL> mimc_small(const FpParams<NL> &P, uint64_t v) {
+template <int NL> static FpConst<NL> mimc_small(const FpParams<NL> &P, uint64_t v) {
     bool below_2_64 = (P.p[2] >> 6) == 0;
     for (int i = 3; i < NL; i++) below_2_64 = below_2_64 && P.p[i] == 0;
     if (below_2_64) v %= (uint64_t)P.p[0] | ((uint64_t)P.p[1] << LB) | ((uint64_t)P.p[2] << (2 * LB));
-    MimcConst<NL> c;
+    FpConst<NL> c;
     for (int q = 0; q < NL; q++) c.d[q] = (q < 3) ? ((uint32_t)(v >> (LB * q)) & DMASK) : 0u;
     return c;
 }
 // the counter's start from its packed words (NULL: 0); false if it is not below p
-template <int NL, int NW> static bool mimc_start(MimcConst<NL> &c, const FpParams<NL> &P, const uint64_t *start_host) {
-    uint32_t w[NW] = {};
-    if (start_host) memcpy(w, start_host, NW * 4);
-    unpack<NL, NW>(c.d, w);
-    static_assert(NL * LB >= 32 * NW, "the digits hold every bit of the packed words");
-    for (int i = NL - 1; i >= 0; i--)
-        if (c.d[i] != P.p[i]) return c.d[i] < P.p[i];
-    return false;
+template <int NL, int NW> static bool mimc_start(FpConst<NL> &c, const FpParams<NL> &P, const uint64_t *start_host) {
+    if (start_host) return host_digits<NL, NW>(c.d, P, start_host);
+    small_digits<NL>(c.d, 0);
+    return true;
 }
 
 template <int NL, int NW>
-static void launch_plain(const FpParams<NL> &P, const uint32_t *x, const MimcConst<NL> &start, const uint32_t *key, bool bcast, const uint32_t *addend, int subtract,
+static void launch_plain(const FpParams<NL> &P, const uint32_t *x, const FpConst<NL> &start, const uint32_t *key, bool bcast, const uint32_t *addend, int subtract,
                          int rounds, bool pair, uint32_t *out, int64_t count, unsigned blocks, hipStream_t s) {
     if (pair) {
         if (bcast) k_mimc_plain<NL, NW, 2, true><<<blocks, 256, 0, s>>>(P, x, start, key, addend, subtract, rounds, out, count);
@@ -281,7 +274,7 @@ static void launch_plain(const FpParams<NL> &P, const uint32_t *x, const MimcCon
     }
 }
 template <int NL, int NW>
-static void launch_first(const FpParams<NL> &P, const uint32_t *x, const MimcConst<NL> &start, const uint32_t *key, bool bcast, const uint32_t *r0, uint32_t *out,
+static void launch_first(const FpParams<NL> &P, const uint32_t *x, const FpConst<NL> &start, const uint32_t *key, bool bcast, const uint32_t *r0, uint32_t *out,
                          int64_t count, unsigned blocks, hipStream_t s) {
     if (bcast) k_mimc_first<NL, NW, true><<<blocks, 256, 0, s>>>(P, x, start, key, r0, out, count);
     else k_mimc_first<NL, NW, false><<<blocks, 256, 0, s>>>(P, x, start, key, r0, out, count);
@@ -289,7 +282,7 @@ static void launch_first(const FpParams<NL> &P, const uint32_t *x, const MimcCon
 template <int NL, int NW>
 static void launch_round(const FpParams<NL> &P, const uint32_t *y, const uint32_t *r, const uint32_t *r2, const uint32_t *r3, const uint32_t *key, bool bcast,
                          int64_t ctr, const uint32_t *r_next, uint32_t *out, int64_t count, unsigned blocks, hipStream_t s) {
-    const MimcConst<NL> cst = mimc_small<NL>(P, (uint64_t)ctr + 1);
+    const FpConst<NL> cst = mimc_small<NL>(P, (uint64_t)ctr + 1);
     if (r_next) {
         if (bcast) k_mimc_round<NL, NW, false, true><<<blocks, 256, 0, s>>>(P, y, r, r2, r3, key, cst, r_next, out, count);
         else k_mimc_round<NL, NW, false, false><<<blocks, 256, 0, s>>>(P, y, r, r2, r3, key, cst, r_next, out, count);
@@ -305,7 +298,7 @@ static int selftest_mimc(const uint64_t *p_limbs, int what, const uint64_t *cons
                          uint64_t *out, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
-    MimcConst<NL> start;
+    FpConst<NL> start;
     if (!mimc_start<NL, NW>(start, P, start_host)) return HB_ERR_BAD_ARG;
     auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
     uint32_t *o = reinterpret_cast<uint32_t *>(out);
@@ -338,7 +331,7 @@ static int selftest_mimc(const uint64_t *p_limbs, int what, const uint64_t *cons
         }
         return HB_OK;
     }
-    const MimcConst<NL> cst = mimc_small<NL>(P, (uint64_t)arg + 1);
+    const FpConst<NL> cst = mimc_small<NL>(P, (uint64_t)arg + 1);
     for (int64_t i = 0; i < count; i++) {
         uint32_t r[NW];
         if (what == HB_MIMC_SELFTEST_FIRST)
@@ -363,8 +356,8 @@ int hb_mimc_plain(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *start_host
     if (flags & ~(HB_MIMC_SUB | HB_MIMC_PAIR)) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_plain: unknown flag");
     if ((flags & HB_MIMC_SUB) && !addend_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_plain: HB_MIMC_SUB without an addend");
     if (key_broadcast && count > 1 && out_dev == key_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_plain: out aliases the broadcast key");
-    MimcConst<9> sw;
-    MimcConst<3> sn;
+    FpConst<9> sw;
+    FpConst<3> sn;
     if (!(ctx->n_limbs == 4 ? mimc_start<9, 8>(sw, ctx->pw, start_host) : mimc_start<3, 2>(sn, ctx->pn, start_host)))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_plain: start is not below the modulus");
     if (count == 0) return HB_OK;
@@ -384,8 +377,8 @@ int hb_mimc_first(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *start_host
                   uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!key_dev || !r0_dev || !out_dev))) return HB_ERR_BAD_ARG;
     if (key_broadcast && count > 1 && out_dev == key_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_first: out aliases the broadcast key");
-    MimcConst<9> sw;
-    MimcConst<3> sn;
+    FpConst<9> sw;
+    FpConst<3> sn;
     if (!(ctx->n_limbs == 4 ? mimc_start<9, 8>(sw, ctx->pw, start_host) : mimc_start<3, 2>(sn, ctx->pn, start_host)))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_first: start is not below the modulus");
     if (count == 0) return HB_OK;

@@ -1,6 +1,11 @@
-// hb_rows.hpp -- what the share-array step files (hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip, hb_eq.hip, hb_bf.hip, hb_mimc.hip,
-// hb_jj.hip, hb_off.hip, hb_mat.hip) share, one of each: the read-once load, the small element helpers, the argument checks of the
-// entry points, and the shape of a step.
+// hb_rows.hpp -- what the share-array step files share, one of each.
+//   The helpers -- the read-once load, the small element helpers (word_bit, diff_elem, small_digits, FpConst), the host's digits of a
+//   constant (host_digits, host_mont) and the argument checks of the entry points (u32, overlap, RowSpan / outputs_apart, modulus_bits,
+//   HB_ROW_BLOCKS) -- serve all of them: hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_mimc.hip, hb_bf.hip,
+//   hb_off.hip and hb_mat.hip.
+//   The shape of a step -- the memory policies, k_rows, host_rows, launch_rows -- serves hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip,
+//   hb_eq.hip and hb_jj.hip: every step of theirs is a row.  hb_mimc.hip (two elements a thread, a specialised key load), hb_bf.hip
+//   (two indices an element), hb_off.hip and hb_mat.hip (tiles) have kernels of other shapes and use the helpers alone.
 //
 // A step is a ROW: a type with
 //     template <int NL, int NW, class Mem> HB_HD static void run(const Args &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P)
@@ -30,6 +35,15 @@ template <int NW> HB_HD uint32_t word_bit(const uint32_t (&cw)[NW], int i) {
 #pragma unroll
     for (int q = 0; q < NW; q++) w = (q == (i >> 5)) ? cw[q] : w;
     return (w >> (i & 31)) & 1u;
+}
+
+// a field element as digits, handed to a kernel by value
+template <int NL> struct FpConst { uint32_t d[NL]; };
+
+// r = the small value v
+template <int NL> HB_HD void small_digits(uint32_t (&r)[NL], uint32_t v) {
+#pragma unroll
+    for (int q = 0; q < NL; q++) r[q] = q == 0 ? v : 0u;
 }
 
 // o = v - a: a masked difference
@@ -80,6 +94,23 @@ inline int modulus_bits(const uint64_t *p_limbs, int n_limbs) {
 inline bool overlap(const void *x, int64_t x_bytes, const void *y, int64_t y_bytes) {
     const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
     return x && y && a < b + (uintptr_t)y_bytes && b < a + (uintptr_t)x_bytes;
+}
+
+// one canonical element in host memory -> its digits; false if it is not below p
+template <int NL, int NW> bool host_digits(uint32_t (&d)[NL], const FpParams<NL> &P, const uint64_t *host) {
+    uint32_t w[NW];
+    memcpy(w, host, NW * 4);
+    unpack<NL, NW>(d, w);
+    for (int i = NL - 1; i >= 0; i--)
+        if (d[i] != P.p[i]) return d[i] < P.p[i];
+    return false;
+}
+// the same -> its Montgomery digits
+template <int NL, int NW> bool host_mont(uint32_t (&r)[NL], const FpParams<NL> &P, const uint64_t *host) {
+    uint32_t d[NL];
+    if (!host_digits<NL, NW>(d, P, host)) return false;
+    to_mont<NL>(r, d, P);
+    return true;
 }
 
 // `rows` rows of row_bytes each from p on; a null p is an operand the call does not take

@@ -1,0 +1,183 @@
+// A stand-alone HOST program over hb_selftest_lt, hb_selftest_eq and hb_selftest_jj for AddressSanitizer and UBSan: the rows of
+// csrc/hb_lt.hip, hb_eq.hip and hb_jj.hip (hb_rows.hpp: host_rows runs what k_rows runs) compiled WITH the sanitizers into this program;
+// the rest of the library comes from libhbmpc_hip.so as it is.  No GPU is touched.
+//
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
+//         scratch/asan_rows.cpp honeybadgermpc_amd/csrc/hb_lt.hip honeybadgermpc_amd/csrc/hb_eq.hip honeybadgermpc_amd/csrc/hb_jj.hip \
+//         -Lhoneybadgermpc_amd/lib -lhbmpc_hip -Wl,-rpath,$PWD/honeybadgermpc_amd/lib -o scratch/asan_rows && scratch/asan_rows
+//
+// Every step at count = 3, rows = 3 (hb_eq), a triples' row stride of count + 3 (hb_jj), both widths.  Every operand and output is a heap
+// buffer of exactly the documented size, so a row that reads or writes one row past an array is a report.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../include/hbmpc_hip.h"
+
+static int fails = 0;
+#define CHECK(cond) do { if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); fails++; } } while (0)
+
+static uint64_t lcg = 88172645463325252ull;
+static uint64_t next() { lcg ^= lcg << 13; lcg ^= lcg >> 7; lcg ^= lcg << 17; return lcg; }
+
+static int NL;                                                             // 64-bit limbs an element: 4 or 1
+// exactly `elems` elements of canonical residues (the top limb stays below the modulus')
+struct Elems {
+    uint64_t *p;
+    explicit Elems(size_t elems) : p((uint64_t *)malloc(elems * NL * 8)) {
+        for (size_t i = 0; i < elems * NL; i++) p[i] = (i % NL == (size_t)NL - 1) ? next() >> 4 : next();
+    }
+    ~Elems() { free(p); }
+    operator const uint64_t *() const { return p; }
+};
+template <class T> struct Raw {
+    T *p;
+    explicit Raw(size_t n) : p((T *)calloc(n, sizeof(T))) {}
+    ~Raw() { free(p); }
+};
+
+static const uint64_t BLS[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
+static const uint64_t P64[1] = {0xffffffffffffffc5ull};
+
+static void less_than(const uint64_t *p, int L, int64_t n) {
+    const int64_t prm[2][2] = {{L, HB_LT_DIRECT}, {L, HB_LT_REFERENCE}};
+    Elems a(n), b(n), r(n), c(n), w(n), x(n), s(n), u(n), v(n), bits((size_t)L * n), o5(5 * n), o2(2 * n);
+    Elems t0(n), t1(n), t2(n), t3(n), t4(n), t5(n), t6(n), t7(n);
+    for (int has_b = 0; has_b < 2; has_b++) {
+        Elems out(n);
+        const uint64_t *ops[3] = {a, has_b ? b.p : nullptr, r};
+        uint64_t *outs[1] = {out.p};
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_MASK, ops, prm[0], outs, n) == HB_OK);
+    }
+    for (int mode = 0; mode < 2; mode++) {
+        Elems g((size_t)L * n), q((size_t)L * n);
+        const uint64_t *ops[2] = {c, bits};
+        uint64_t *outs[2] = {g.p, q.p};
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_LEAVES, ops, prm[mode], outs, n) == HB_OK);
+    }
+    {
+        Elems ou(n), masked(2 * n);
+        const uint64_t *ops[5] = {c, r, w, t0, t1};
+        uint64_t *outs[2] = {ou.p, masked.p};
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_XOR_MASK, ops, prm[0], outs, n) == HB_OK);
+    }
+    {
+        Elems ou(n), masked(5 * n);
+        const uint64_t *ops[9] = {c, r, x, s, bits, t0, t1, t2, t3};
+        uint64_t *outs[2] = {ou.p, masked.p};
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_DMASK, ops, prm[1], outs, n) == HB_OK);
+    }
+    {
+        Elems ov(n), d0(n), masked(2 * n);
+        const uint64_t *ops[11] = {o5, u, bits, t0, t1, t2, t3, t4, t5, t6, t7};
+        uint64_t *outs[3] = {ov.p, d0.p, masked.p};
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_MID, ops, prm[1], outs, n) == HB_OK);
+    }
+    {
+        Elems out(n);
+        const uint64_t *ops[6] = {o2, u, v, t0, t1, t2};
+        uint64_t *outs[1] = {out.p};
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_XOR_FINISH, ops, prm[0], outs, n) == HB_OK);
+    }
+}
+
+static void equality(const uint64_t *p, int64_t rows, int64_t n) {
+    const int64_t rc = rows * n, prm[2][2] = {{rows, HB_EQ_BIT}, {rows, HB_EQ_REFERENCE}};
+    std::vector<uint64_t> nr(NL, 0);
+    nr[0] = 5;
+    Elems x(n), y(n), r(rc), rp(rc), bits(rc), o4(4 * rc), o2(2 * rc), c(rc);
+    Elems t0(rc), t1(rc), t2(rc), t3(rc), t4(rc), t5(rc), t6(rc), t7(rc);
+    memset(c.p + (size_t)(n + 1) * NL, 0, NL * 8);                         // one c of the middle row is 0
+    {
+        Raw<int8_t> out(n);
+        const uint64_t *ops[1] = {x};
+        void *outs[1] = {out.p};
+        CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_LEGENDRE, ops, prm[0], outs, n) == HB_OK);
+    }
+    for (int has_y = 0; has_y < 2; has_y++) {
+        Elems masked(4 * rc);
+        const uint64_t *ops[8] = {x, has_y ? y.p : nullptr, r, rp, t0, t1, t2, t3};
+        void *outs[1] = {masked.p};
+        CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_MASK1, ops, prm[0], outs, n) == HB_OK);
+    }
+    {
+        Elems masked2(2 * rc), dr(rc);
+        const uint64_t *ops[11] = {o4, t0, t1, t2, t3, t4, t5, bits, t6, t7, nr.data()};
+        void *outs[2] = {masked2.p, dr.p};
+        CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_MID, ops, prm[0], outs, n) == HB_OK);
+    }
+    for (int alias = 0; alias < 2; alias++) {                               // c a fresh array, then c = dr
+        Elems dr(rc), out(rc);
+        const uint64_t *ops[5] = {o2, dr, t0, t1, t2};
+        void *outs[1] = {alias ? dr.p : out.p};
+        CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_CSHARE, ops, prm[0], outs, n) == HB_OK);
+    }
+    for (int mode = 0; mode < 2; mode++) {
+        Elems factor(rc);
+        Raw<int32_t> zero_rows(rows);
+        const uint64_t *ops[3] = {c, bits, nr.data()};
+        void *outs[2] = {factor.p, zero_rows.p};
+        CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_FINISH, ops, prm[mode], outs, n) == HB_OK);
+        CHECK(zero_rows.p[0] == 0 && zero_rows.p[1] == 1 && zero_rows.p[2] == 0);
+        for (int l = 0; l < NL; l++) CHECK(factor.p[(size_t)(n + 1) * NL + l] == 0);
+    }
+}
+
+static void jubjub(const uint64_t *p, int64_t m) {
+    const int64_t stride = m + 3, K = 3;
+    std::vector<uint64_t> a(p, p + NL), d(NL, 0);
+    a[0] -= 1;                                                             // a = -1
+    d[0] = 2;
+    Elems x1(m), y1(m), x2(m), y2(m), rx(m), ry(m), one_n(1), one_x(1), one_y(1);
+    for (int flags = 0; flags < 4; flags++) {
+        Elems out(2 * m);
+        const uint64_t *ops[3] = {(flags & HB_JJ_SCALAR_BROADCAST) ? one_n.p : rx.p, (flags & HB_JJ_POINT_BROADCAST) ? one_x.p : x1.p,
+                                  (flags & HB_JJ_POINT_BROADCAST) ? one_y.p : y1.p};
+        CHECK(hb_selftest_jj(p, NL, HB_JJ_SELFTEST_SCALAR_MUL, ops, a.data(), d.data(), flags, 0, out.p, m) == HB_OK);
+    }
+    {
+        Elems out(3 * K * m);
+        const uint64_t *ops[2] = {x1, y1};
+        CHECK(hb_selftest_jj(p, NL, HB_JJ_SELFTEST_DOUBLE_TABLE, ops, a.data(), nullptr, 0, K, out.p, m) == HB_OK);
+    }
+    {                                                                      // rows 0..3 of the triples: the last row holds m elements, no more
+        Elems tp(3 * stride + m), tq(3 * stride + m), out(8 * m);
+        const uint64_t *ops[6] = {x1, y1, x2, y2, tp, tq};
+        CHECK(hb_selftest_jj(p, NL, HB_JJ_SELFTEST_MASK, ops, nullptr, nullptr, 0, stride, out.p, m) == HB_OK);
+    }
+    {                                                                      // rows 0..6
+        Elems A(8 * m), tp(6 * stride + m), tq(6 * stride + m), tpq(6 * stride + m), out(6 * m);
+        const uint64_t *ops[6] = {A, tp, tq, tpq, rx, ry};
+        CHECK(hb_selftest_jj(p, NL, HB_JJ_SELFTEST_STAGE1, ops, nullptr, nullptr, 0, stride, out.p, m) == HB_OK);
+    }
+    Elems tp(8 * stride + m), tq(8 * stride + m), tpq(8 * stride + m);       // rows 0..8
+    {
+        Elems B(6 * m), out(6 * m);
+        const uint64_t *ops[6] = {B, tp, tq, tpq, rx, ry};
+        CHECK(hb_selftest_jj(p, NL, HB_JJ_SELFTEST_STAGE2, ops, nullptr, d.data(), 0, stride, out.p, m) == HB_OK);
+    }
+    {
+        Elems C(4 * m), out(2 * m);
+        const uint64_t *ops[4] = {C, tp, tq, tpq};
+        CHECK(hb_selftest_jj(p, NL, HB_JJ_SELFTEST_STAGE3, ops, nullptr, nullptr, 0, stride, out.p, m) == HB_OK);
+    }
+    {
+        Elems inv(2 * m), uv(2 * m), out(2 * m);
+        const uint64_t *ops[2] = {inv, uv};
+        CHECK(hb_selftest_jj(p, NL, HB_JJ_SELFTEST_SCALE, ops, nullptr, nullptr, 0, 0, out.p, m) == HB_OK);
+    }
+}
+
+int main() {
+    for (int wide = 1; wide >= 0; wide--) {
+        NL = wide ? 4 : 1;
+        const uint64_t *p = wide ? BLS : P64;
+        less_than(p, wide ? 255 : 64, 3);
+        equality(p, 3, 3);
+        jubjub(p, 3);
+    }
+    printf(fails ? "asan_rows: %d check(s) FAILED\n" : "asan_rows ok\n", fails);
+    return fails ? 1 : 0;
+}

@@ -1,5 +1,5 @@
 """The Jubjub kernels timed on the device:
-   python scratch/time_jubjub.py [reps] [--label TEXT] [--level-only | --scalar-only | --protocol-only | --kernels] > profiles/jubjub.txt
+   python scratch/time_jubjub.py [reps] [--label TEXT] [--level-only | --scalar-only | --protocol-only | --kernels | --steps] > profiles/jubjub.txt
 
 (a) One level of shared additions, LOCAL launches only (no open: what a stage wrote is handed to the next as if it had been opened --
 the timing of the arithmetic, not of the protocol): fused = add_mask, add_stage1, add_stage2, add_stage3, add_finish of
@@ -20,6 +20,8 @@ in a synchronise) of a whole share_mul(K = 32) and of a whole mimc_decrypt (shar
 Opens, Python and the event loop included: it is NOT kernel time.
 
 --kernels runs two levels of each version at 2^20 over BLS12-381 and one scalar_mul at 2^16, and nothing else (for a kernel trace).
+--steps times every entry point alone at both widths (the stages at m = 2^20, scalar_mul and double_table at 2^16), HIP events around
+one launch with the host kept ahead of the device; run it against two builds of the library (HBMPC_HIP_LIB) in one visit to compare them.
 No GPU: fails (there is nothing to fall back to)."""
 import asyncio
 import socket
@@ -244,12 +246,54 @@ def time_protocol(reps):
               f": {res[0][0]} batches   {np.median(times):8.3f} s ({min(times):.3f} .. {max(times):.3f}), {reps} timed runs", flush=True)
 
 
+def one_launch(reps, fn, pad):
+    """HIP events around ONE call with the host kept ahead of the device: the device is still clearing `pad` when the call is enqueued"""
+    fn()
+    torch.cuda.synchronize()
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in evs:
+        pad.zero_()
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    return [e0.elapsed_time(e1) * 1e3 for e0, e1 in evs]
+
+
+def time_steps(reps):
+    """--steps: every entry point of csrc/hb_jj.hip alone, both widths: the stages of the shared addition at m = 2^20, scalar_mul and
+    double_table (8 rows) at 2^16 points.  add_finish and double_table are their row's launch and the batched inversion behind it."""
+    pad = torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    for p, name in ((BLS, "<9, 8>"), (P64, "<3, 2>")):
+        ctx, curve = Context.get(p), curve_of(p)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(11)
+        m, small = 1 << 20, 1 << 16
+        P, Q = (rnd(ctx, gen, m), rnd(ctx, gen, m)), (rnd(ctx, gen, m), rnd(ctx, gen, m))
+        trip = tuple(rnd(ctx, gen, 9 * m).reshape(9, m, ctx.n_limbs) for _ in range(3))
+        rs = rnd(ctx, gen, 2 * m).reshape(2, m, ctx.n_limbs)
+        A, B, C, D, uv = (rnd(ctx, gen, k * m) for k in (8, 6, 4, 2, 2))
+        pts, ns = some_points(ctx, curve, gen, small), rnd(ctx, gen, small)
+        steps = (("JjMaskRow", lambda: jubjub.add_mask(ctx, P, Q, trip)), ("JjStage1Row", lambda: jubjub.add_stage1(ctx, A, trip, rs)),
+                 ("JjStage2Row", lambda: jubjub.add_stage2(ctx, B, trip, rs, curve)), ("JjStage3Row", lambda: jubjub.add_stage3(ctx, C, trip)),
+                 ("add_finish (JjScaleRow)", lambda: jubjub.add_finish(ctx, D, uv, check=False)),
+                 ("JjScalarMulRow", lambda: jubjub.scalar_mul(ctx, ns, pts, curve)),
+                 ("double_table (JjDoubleTableRow)", lambda: jubjub.double_table(ctx, pts, 8, curve)))
+        for step, fn in steps:
+            print(f"step {step + ' ' + name:40s} {fmt(one_launch(reps, fn, pad))}", flush=True)
+        del P, Q, trip, rs, A, B, C, D, uv, pts, ns, steps
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     if not torch.cuda.is_available():
         raise SystemExit("scratch/time_jubjub.py needs the GPU")
     reps = int(args[0]) if args and args[0].isdigit() else 20
     label = args[args.index("--label") + 1] if "--label" in args else "working tree"
+    if "--steps" in args:
+        print(f"# scratch/time_jubjub.py --steps, {reps} runs a figure, HIP events around one launch: median (min .. max); {label}")
+        return time_steps(reps)
     if "--kernels" in args:
         ctx = Context.get(BLS)
         curve = curve_of(BLS)

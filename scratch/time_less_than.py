@@ -13,6 +13,10 @@ BLS12-381 Fr, L = 255.
     different preprocessing (508 | 510 triples and 255 | 510 bit shares against 125 triples and 96 bit shares an element); the figure
     says what the wider comparison costs.  Every opened result is checked against a < b.
 
+With --steps instead: every entry point alone at both widths (BLS12-381 Fr and 2^64 - 59), 2^20 elements (lt_leaves: L planes at
+2^16), HIP events around one launch with the host kept ahead of the device.  Run it against two builds of the library
+(HBMPC_HIP_LIB) in one visit to compare them.
+
 No GPU: fails (there is nothing to fall back to)."""
 import asyncio
 import random
@@ -31,6 +35,7 @@ from honeybadgermpc_amd.open_coalescer import OpenCoalescer  # noqa: E402
 from honeybadgermpc_amd.progs import fixedpoint as fx  # noqa: E402
 
 BLS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+P64 = (1 << 64) - 59
 N, T = 4, 1
 
 
@@ -147,12 +152,56 @@ def time_fixedpoint_lt(ctx, gen, count, runs, k=64, kappa=32):
     return [run_parties(p, body)[0] for _ in range(runs)], ok
 
 
+def one_launch(reps, fn, pad):
+    """HIP events around ONE call with the host kept ahead of the device: the device is still clearing `pad` when the call is enqueued"""
+    fn()
+    torch.cuda.synchronize()
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in evs:
+        pad.zero_()
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    return [e0.elapsed_time(e1) * 1e3 for e0, e1 in evs]
+
+
+def time_steps(reps):
+    """--steps: every entry point of csrc/hb_lt.hip alone, both widths: 2^20 elements (lt_leaves: L planes at 2^16)"""
+    pad = torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    for p, name in ((BLS, "<9, 8>"), (P64, "<3, 2>")):
+        ctx = Context.get(p)
+        L = p.bit_length()
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(29)
+        count = 1 << 20
+        a, b, r, c, w, x, s, u, v = (rnd(ctx, gen, count) for _ in range(9))
+        ta, tb, tc = (tuple(rnd(ctx, gen, count) for _ in range(3)) for _ in range(3))
+        s_bits = torch.zeros((L, count, ctx.n_limbs), dtype=torch.int64, device="cuda")           # planes 0, L - 1, L - 2 are read
+        o5, o2 = rnd(ctx, gen, count, 5), rnd(ctx, gen, count, 2)
+        small = 1 << 16
+        c16, bits16 = rnd(ctx, gen, small), rnd(ctx, gen, small, L)
+        steps = (("LtMaskRow<true>", lambda: sc.lt_mask(ctx, a, b, r)), ("LtMaskRow<false>", lambda: sc.lt_mask(ctx, a, None, r)),
+                 ("LtLeavesRow DIRECT", lambda: sc.lt_leaves(ctx, c16, bits16, sc.DIRECT)), ("LtLeavesRow REFERENCE", lambda: sc.lt_leaves(ctx, c16, bits16, sc.REFERENCE)),
+                 ("LtXorMaskRow", lambda: sc.lt_xor_mask(ctx, c, r, w, ta[0], ta[1])),
+                 ("LtDmaskRow", lambda: sc.lt_dmask(ctx, c, r, x, s, s_bits, ta[0], ta[1], tb[0], tb[1])),
+                 ("LtMidRow", lambda: sc.lt_mid(ctx, o5, u, s_bits, ta, tb, tc[0], tc[1])),
+                 ("LtXorFinishRow", lambda: sc.lt_xor_finish(ctx, o2, u, v, tc)))
+        for step, fn in steps:
+            print(f"step {step + ' ' + name:30s} {fmt(one_launch(reps, fn, pad))}", flush=True)
+        del a, b, r, c, w, x, s, u, v, ta, tb, tc, s_bits, o5, o2, c16, bits16, steps
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     if not torch.cuda.is_available():
         raise SystemExit("scratch/time_less_than.py needs the GPU")
     reps = max(20, int(args[0])) if args and args[0].isdigit() else 20
     label = args[args.index("--label") + 1] if "--label" in args else "working tree"
+    if "--steps" in args:
+        print(f"# scratch/time_less_than.py --steps, {reps} runs a figure, HIP events around one launch: median (min .. max); {label}")
+        return time_steps(reps)
     print(f"# scratch/time_less_than.py, {reps} runs a figure: median (min .. max); {torch.cuda.get_device_name(0)} on {socket.gethostname()}; {label}")
     p = BLS
     ctx = Context.get(p)

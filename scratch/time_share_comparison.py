@@ -11,7 +11,11 @@ BLS12-381 Fr.
     steps composed from share_arithmetic calls.  What a step "opens" is what the step before wrote (degree-0 shares): no open is timed.
 
 Each figure: HIP events around one group, `reps` (at least 20) runs after a warm-up, the two versions alternated run by run;
-median (min .. max).  Outputs are compared bit for bit.  No GPU: fails (there is nothing to fall back to)."""
+median (min .. max).  Outputs are compared bit for bit.  No GPU: fails (there is nothing to fall back to).
+
+With --steps instead: every entry point alone at both widths (BLS12-381 Fr and 2^64 - 59), 2^20 elements (rows = 4 at count = 2^18),
+HIP events around one launch with the host kept ahead of the device.  Run it against two builds of the library (HBMPC_HIP_LIB)
+in one visit to compare them."""
 import socket
 import sys
 
@@ -24,6 +28,7 @@ from honeybadgermpc_amd import share_comparison as sc  # noqa: E402
 from honeybadgermpc_amd._capi import Context  # noqa: E402
 
 BLS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+P64 = (1 << 64) - 59
 KAPPA = 32
 
 
@@ -68,12 +73,55 @@ def chain_multiplications(p):
     return sq + mul + 4 + 1
 
 
+def one_launch(reps, fn, pad):
+    """HIP events around ONE call with the host kept ahead of the device: the device is still clearing `pad` when the call is enqueued"""
+    fn()
+    torch.cuda.synchronize()
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in evs:
+        pad.zero_()
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    return [e0.elapsed_time(e1) * 1e3 for e0, e1 in evs]
+
+
+def time_steps(reps):
+    """--steps: every entry point of csrc/hb_eq.hip alone, both widths: 2^20 elements, rows = 4 at count = 2^18"""
+    pad = torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    rows, count = 4, 1 << 18
+    for p, name in ((BLS, "<9, 8>"), (P64, "<3, 2>")):
+        ctx = Context.get(p)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(19)
+        nr = sc.smallest_nonresidue(p)
+        a, x, y = rnd(ctx, gen, rows * count), rnd(ctx, gen, count), rnd(ctx, gen, count)
+        r, rp, bits, dr, c = (rnd(ctx, gen, count, rows) for _ in range(5))
+        ta, tb, tc = (tuple(rnd(ctx, gen, count, rows) for _ in range(3)) for _ in range(3))
+        o4, o2 = rnd(ctx, gen, 4 * rows * count), rnd(ctx, gen, 2 * rows * count)
+        steps = (("EqLegendreRow", lambda: sc.legendre(ctx, a)),
+                 ("EqMask1Row<true>", lambda: sc.eq_mask1(ctx, x, y, r, rp, ta[0], ta[1], tb[0], tb[1])),
+                 ("EqMask1Row<false>", lambda: sc.eq_mask1(ctx, x, None, r, rp, ta[0], ta[1], tb[0], tb[1])),
+                 ("EqMidRow", lambda: sc.eq_mid(ctx, o4, ta, tb, bits, tc[0], tc[1], nr)),
+                 ("EqCshareRow", lambda: sc.eq_cshare(ctx, o2, dr, tc)),
+                 ("EqFinishRow BIT", lambda: sc.eq_finish(ctx, c, bits, sc.BIT, nr)),
+                 ("EqFinishRow REFERENCE", lambda: sc.eq_finish(ctx, c, bits, sc.REFERENCE, nr)))
+        for step, fn in steps:
+            print(f"step {step + ' ' + name:30s} {fmt(one_launch(reps, fn, pad))}", flush=True)
+        del a, x, y, r, rp, bits, dr, c, ta, tb, tc, o4, o2, steps
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     if not torch.cuda.is_available():
         raise SystemExit("scratch/time_share_comparison.py needs the GPU")
     reps = max(20, int(args[0])) if args and args[0].isdigit() else 20
     label = args[args.index("--label") + 1] if "--label" in args else "working tree"
+    if "--steps" in args:
+        print(f"# scratch/time_share_comparison.py --steps, {reps} runs a figure, HIP events around one launch: median (min .. max); {label}")
+        return time_steps(reps)
     print(f"# scratch/time_share_comparison.py, {reps} runs a figure: median (min .. max); {torch.cuda.get_device_name(0)} on {socket.gethostname()}; {label}")
     p = BLS
     ctx = Context.get(p)

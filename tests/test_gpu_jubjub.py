@@ -614,3 +614,72 @@ def test_a_zero_random_share_raises_on_every_party():
 
     results, _ = _run_parties(p, n, t, set(), rnd, body)
     assert results == [4] * n
+
+
+@pytest.mark.parametrize("p", [BLS, P64], ids=["bls", "2^64-59"])
+@pytest.mark.parametrize("m", [1, 257])
+def test_every_step_equals_the_host_self_test(p, m):
+    """One row body: for every step of csrc/hb_jj.hip the device's output equals, bit for bit, what hb_selftest_jj computes on the host
+    from the same random inputs -- the self test runs the rows the kernels run, addressing included.  The triples' row stride is
+    m + 3, so it and m are different offsets; scalar_mul with each broadcast flag on and off; double_table with 3 rows, whose device
+    result is affine where the self test's is projective ((X R, Y R, Z R) -> X R / Z R, Y R / Z R: the division is done on ints here).
+    m = 1 is one partial workgroup, 257 a second workgroup that holds one element."""
+    import numpy as np
+    import selftest_cases as stc
+    from honeybadgermpc_amd.progs import jubjub
+
+    ctx, curve = _ctx(p), _curve(p)
+    torch, nl = ctx.torch, ctx.n_limbs
+    SCALAR_MUL, DOUBLE_TABLE, MASK, STAGE1, STAGE2, STAGE3, SCALE = range(7)
+    seeds = iter(range(700, 800))
+
+    def rnd(rows, cols=m):
+        limbs = np.random.default_rng(next(seeds)).integers(-(1 << 63), (1 << 63) - 1, size=(rows * cols, nl), dtype=np.int64, endpoint=True)
+        return ctx.reduce_(ctx.to_device(limbs)).view(rows, cols, nl)
+
+    def ints(t):
+        return ctx.download_ints(t.reshape(-1, nl))
+
+    def host(what, operands, out_rows, count=m, **kw):
+        rc, outs = stc.run_jj(p, nl, what, [o if isinstance(o, list) else ints(o) for o in operands], count, out_rows, **kw)
+        assert rc == 0
+        return outs
+
+    def same(dev, want_rows):
+        return ints(dev) == [v for row in want_rows for v in row]
+
+    # ---- cleartext
+    pool = _pool(p)
+    pts = [pool[(7 * i + 3) % len(pool)] for i in range(m)]
+    px, py = _upload_points(ctx, pts)
+    ns = rnd(1)[0]
+    a_h, d_h = ctx.host_elems([curve.a]), ctx.host_elems([curve.d])
+    for n_b, p_b in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        n_dev, x_dev, y_dev = ns[:1] if n_b else ns, px[:1] if p_b else px, py[:1] if p_b else py
+        ox, oy = ctx.empty(m), ctx.empty(m)
+        ctx.check(ctx.lib.hb_jj_scalar_mul(ctx.h, ctx.ptr(n_dev), n_b, ctx.ptr(x_dev), ctx.ptr(y_dev), p_b, a_h.ctypes.data, d_h.ctypes.data, ctx.ptr(ox), ctx.ptr(oy), m,
+                                           ctx.stream()), "hb_jj_scalar_mul")
+        h = host(SCALAR_MUL, [n_dev, x_dev, y_dev], 2, a=curve.a, d=curve.d, flags=n_b | 2 * p_b)
+        assert same(ox, h[:1]) and same(oy, h[1:]), (n_b, p_b)
+    K = 3
+    xs, ys = jubjub.double_table(ctx, (px, py), K, curve)
+    h = host(DOUBLE_TABLE, [px, py], 3 * K, a=curve.a, arg=K)
+    X, Y, Z = ([v for row in h[k * K:(k + 1) * K] for v in row] for k in range(3))
+    assert ints(xs) == [x * pow(z, -1, p) % p for x, z in zip(X, Z)] and ints(ys) == [y * pow(z, -1, p) % p for y, z in zip(Y, Z)]
+    # ---- the five stages of the shared addition
+    stride = m + 3
+    wide = tuple(rnd(9, stride) for _ in range(3))
+    trip = tuple(v[:, :m] for v in wide)                                   # a column slice: taken as it is, row stride m + 3
+    P, Q, rs = rnd(2), rnd(2), rnd(2)
+    assert same(jubjub.add_mask(ctx, (P[0], P[1]), (Q[0], Q[1]), trip), host(MASK, [P[0], P[1], Q[0], Q[1], wide[0], wide[1]], 8, arg=stride))
+    A, B, C, D = rnd(8), rnd(6), rnd(4), rnd(2)
+    assert same(jubjub.add_stage1(ctx, A, trip, rs), host(STAGE1, [A, *wide, rs[0], rs[1]], 6, arg=stride))
+    uv, c_out = jubjub.add_stage2(ctx, B, trip, rs, curve)
+    h = host(STAGE2, [B, *wide, rs[0], rs[1]], 6, d=curve.d, arg=stride)
+    assert same(uv, h[:2]) and same(c_out, h[2:])
+    assert same(jubjub.add_stage3(ctx, C, trip), host(STAGE3, [C, *wide], 2, arg=stride))
+    (x3, y3), zeros = jubjub.add_finish(ctx, D, uv, check=False)
+    assert int(zeros.item()) == 0
+    h = host(SCALE, [[pow(v, -1, p) for v in ints(D)], uv], 2)
+    assert same(x3, h[:1]) and same(y3, h[1:])
+    torch.cuda.synchronize()

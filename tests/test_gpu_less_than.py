@@ -407,3 +407,52 @@ def test_protocol_arguments_are_checked():
         assert tuple(empty.shape) == (0, ctx.n_limbs) and co.batches == 0 and co.opens == 0
 
     asyncio.run(main())
+
+
+@pytest.mark.parametrize("count", (1, 257))
+@pytest.mark.parametrize("p", (BLS, P64), ids=("bls", "2^64-59"))
+def test_every_step_equals_the_host_self_test(p, count):
+    """One row body: for every step of csrc/hb_lt.hip the device's output equals, bit for bit, what hb_selftest_lt computes on the host
+    from the same random inputs -- the self test runs the rows the kernels run, addressing included.  Both instantiations, L = 255 and
+    64; the mask with and without b, the leaves in both modes.  count 1 is one partial workgroup, 257 a second workgroup that holds
+    one element."""
+    import selftest_cases as stc
+    from honeybadgermpc_amd import share_comparison as sc
+
+    ctx = _ctx(p)
+    torch, nl, L = ctx.torch, ctx.n_limbs, p.bit_length()
+    MASK, LEAVES, XOR_MASK, DMASK, MID, XOR_FINISH = range(6)
+    seeds = iter(range(500, 600))
+
+    def rnd(rows=None):
+        return _random_tensor(ctx, next(seeds), count, rows)
+
+    def host(what, operands, out_rows, mode=sc.DIRECT):
+        rc, outs = stc.run_lt(p, nl, what, [None if o is None else _ints(ctx, o) for o in operands], mode, out_rows, count)
+        assert rc == 0
+        return [ctx.upload_ints(o) for o in outs]
+
+    def same(dev, want):
+        return torch.equal(dev.reshape(-1, nl), want)
+
+    a, b, r, c, w, x, s, u, v = (rnd() for _ in range(9))
+    r_bits, s_bits = rnd(L), rnd(L)                                       # a share of a bit is any residue
+    ta, tb, tc = ((rnd(), rnd(), rnd()) for _ in range(3))
+    assert same(sc.lt_mask(ctx, a, b, r), host(MASK, [a, b, r], [1])[0])
+    assert same(sc.lt_mask(ctx, a, None, r), host(MASK, [a, None, r], [1])[0])
+    for mode in (sc.DIRECT, sc.REFERENCE):
+        g, q = sc.lt_leaves(ctx, c, r_bits, mode)
+        h = host(LEAVES, [c, r_bits], [L, L], mode)
+        assert same(g, h[0]) and same(q, h[1]), mode
+    got = sc.lt_xor_mask(ctx, c, r_bits[0], w, ta[0], ta[1])
+    h = host(XOR_MASK, [c, r_bits[0], w, ta[0], ta[1]], [1, 2])
+    assert same(got[0], h[0]) and same(got[1], h[1])
+    got = sc.lt_dmask(ctx, c, r_bits[0], x, s, s_bits, ta[0], ta[1], tb[0], tb[1])
+    h = host(DMASK, [c, r_bits[0], x, s, s_bits, ta[0], ta[1], tb[0], tb[1]], [1, 5], sc.REFERENCE)
+    assert same(got[0], h[0]) and same(got[1], h[1])
+    opened = rnd(5)
+    got = sc.lt_mid(ctx, opened, u, s_bits, ta, tb, tc[0], tc[1])
+    h = host(MID, [opened, u, s_bits, *ta, *tb, tc[0], tc[1]], [1, 1, 2], sc.REFERENCE)
+    assert same(got[0], h[0]) and same(got[1], h[1]) and same(got[2], h[2])
+    opened = rnd(2)
+    assert same(sc.lt_xor_finish(ctx, opened, u, v, tc), host(XOR_FINISH, [opened, u, v, *tc], [1])[0])

@@ -407,3 +407,57 @@ def test_a_zero_c_is_drawn_again_from_the_spare_rows():
 
         for got in _run_parties(p, n, 1, body):
             assert got == (want, sc.equality_opens(kappa) + 3), mode
+
+
+@pytest.mark.parametrize("count", (1, 257))
+@pytest.mark.parametrize("p", (BLS, P64), ids=("bls", "2^64-59"))
+def test_every_step_equals_the_host_self_test(p, count):
+    """One row body: for every step of csrc/hb_eq.hip the device's output equals, bit for bit, what hb_selftest_eq computes on the host
+    from the same random inputs -- the self test runs the rows the kernels run, addressing included.  rows = 3, so a plane (rows *
+    count) and a row (count) are different offsets; the first mask with and without y; the c share into a fresh array and into dr;
+    the finish in both modes with one c of the middle row forced to 0: zero_rows = [0, 1, 0] and that element's factor is 0.
+    count 1 is one partial workgroup, 257 a second workgroup that holds one element."""
+    import selftest_cases as stc
+    from honeybadgermpc_amd import share_comparison as sc
+
+    ctx = _ctx(p)
+    torch, nl, rows = ctx.torch, ctx.n_limbs, 3
+    LEGENDRE, MASK1, MID, CSHARE, FINISH = range(5)
+    nr = sc.smallest_nonresidue(p)
+    seeds = iter(range(600, 700))
+
+    def rnd(n_rows=None):
+        return _random_tensor(ctx, next(seeds), count, n_rows)
+
+    def host(what, operands, out_rows, mode=sc.BIT):
+        rc, outs = stc.run_eq(p, nl, what, [o if o is None or isinstance(o, list) else _ints(ctx, o) for o in operands], rows, mode, out_rows, count)
+        assert rc == 0
+        return outs
+
+    def same(dev, want):
+        return torch.equal(dev.reshape(-1, nl), ctx.upload_ints(want))
+
+    x, y = rnd(), rnd()
+    assert sc.legendre(ctx, x).tolist() == host(LEGENDRE, [x], ["i8"])[0]
+    r, rp, bits = rnd(rows), rnd(rows), rnd(rows)
+    ta, tb, tc = ((rnd(rows), rnd(rows), rnd(rows)) for _ in range(3))
+    for yy in (y, None):
+        assert same(sc.eq_mask1(ctx, x, yy, r, rp, ta[0], ta[1], tb[0], tb[1]), host(MASK1, [x, yy, r, rp, ta[0], ta[1], tb[0], tb[1]], [4 * rows])[0])
+    opened = rnd(4 * rows)
+    masked2, dr = sc.eq_mid(ctx, opened, ta, tb, bits, tc[0], tc[1], nr)
+    h = host(MID, [opened, *ta, *tb, bits, tc[0], tc[1], [nr]], [2 * rows, rows])
+    assert same(masked2, h[0]) and same(dr, h[1])
+    opened2 = rnd(2 * rows)
+    want = host(CSHARE, [opened2, dr, *tc], [rows])[0]
+    assert same(sc.eq_cshare(ctx, opened2, dr, tc), want)
+    in_place = dr.clone()                                                 # c = dr, the permitted alias
+    ctx.check(ctx.lib.hb_eq_cshare(ctx.h, ctx.ptr(opened2.view(-1, nl)), ctx.ptr(in_place), *(ctx.ptr(t) for t in tc), ctx.ptr(in_place), rows, count, ctx.stream()),
+              "hb_eq_cshare")
+    assert same(in_place, want)
+    c = rnd(rows)
+    c[1, count // 2] = 0
+    for mode in (sc.BIT, sc.REFERENCE):
+        factor, zero_rows = sc.eq_finish(ctx, c, bits, mode, nr)
+        h = host(FINISH, [c, bits, [nr]], [rows, "zr"], mode)
+        assert same(factor, h[0]) and zero_rows.tolist() == h[1] == [0, 1, 0], mode
+        assert _ints(ctx, factor[1, count // 2]) == [0]

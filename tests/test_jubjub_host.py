@@ -1,18 +1,17 @@
 """CPU-only: the host model honeybadgermpc_amd.elliptic_curve against tests/golden/jubjub.json (written by scratch/gen_jubjub_golden.py
-from the reference's own Jubjub, Point and mimc_plain), and the per-element bodies of the Jubjub kernels (csrc/hb_jj.hip) run on the host
-through hb_selftest_jj -- the same HB_HD functions the kernels call -- against the golden file, the host model and Python ints.
+from the reference's own Jubjub, Point and mimc_plain), and the Jubjub steps (csrc/hb_jj.hip) run on the host through hb_selftest_jj
+-- the same rows, arithmetic and addressing, that the kernel runs -- against the golden file, the host model and Python ints.
 Exact equality."""
-import ctypes
 import itertools
 import json
 import os
 import random
 import re
 
-import numpy as np
 import pytest
 
 from conftest import BLS, REPO
+from selftest_cases import run_jj as run
 
 from honeybadgermpc_amd.elliptic_curve import Ideal, Jubjub, Point, Subgroup
 from honeybadgermpc_amd.progs.mimc import mimc_plain
@@ -34,21 +33,6 @@ def golden():
 
 def _xy(v):
     return int(v[0]), int(v[1])
-
-
-def run(p, nl, what, operands, count, out_rows, a=None, d=None, flags=0, arg=0):
-    """hb_selftest_jj over lists of ints (None: a NULL operand) -> (rc, [rows of `count` ints])"""
-    from honeybadgermpc_amd._capi import ints_to_limbs, limbs_to_ints, load_library, np_ptr
-
-    lib = load_library()
-    nb = 8 * nl
-    arrays = [None if o is None else ints_to_limbs(list(o) or [0], p, nb) for o in operands]
-    ptrs = (ctypes.c_void_p * 6)(*([None if x is None else x.ctypes.data for x in arrays] + [None] * (6 - len(arrays))))
-    consts = [None if v is None else ints_to_limbs([v], v + 1, nb) for v in (a, d)]
-    out = np.zeros((max(count * out_rows, 1), nl), dtype=np.uint64)
-    rc = lib.hb_selftest_jj(np_ptr(ints_to_limbs([p], p + 1, nb)), nl, what, ptrs, *[None if c is None else np_ptr(c) for c in consts], flags, arg, np_ptr(out), count)
-    flat = limbs_to_ints(out[:count * out_rows], nb)
-    return rc, [flat[r * count:(r + 1) * count] for r in range(out_rows)]
 
 
 # ---- Python-int models of the stages ------------------------------------------------------------------------------------------

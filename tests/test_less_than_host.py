@@ -1,18 +1,17 @@
 """CPU-only: the less-than half of honeybadgermpc_amd.share_comparison -- the host model against tests/golden/less_than.json (written by
 scratch/gen_less_than_golden.py from the reference's own LessThan mixin driven over cleartext shares with recorded draws) and against
-[a < b] itself, and the per-element bodies of csrc/hb_lt.hip run on the host through hb_selftest_lt -- the same HB_HD functions the
-kernels call -- against Python ints, singly and chained into the whole protocol with the tree's operator folded in Python.
+[a < b] itself, and the steps of csrc/hb_lt.hip run on the host through hb_selftest_lt -- the same rows, arithmetic and addressing,
+that the kernel runs -- against Python ints, singly and chained into the whole protocol with the tree's operator folded in Python.
 Exact equality."""
-import ctypes
 import json
 import os
 import random
 import re
 
-import numpy as np
 import pytest
 
 from conftest import BLS, REPO
+from selftest_cases import run_lt as run
 
 from honeybadgermpc_amd import share_comparison as sc
 
@@ -29,22 +28,6 @@ MODES = (sc.DIRECT, sc.REFERENCE)
 def golden():
     with open(os.path.join(REPO, "tests", "golden", "less_than.json")) as f:
         return json.load(f)
-
-
-def run(p, nl, what, operands, mode, out_rows, count, L=None):
-    """hb_selftest_lt over lists of ints (None: a NULL operand; arrays of several rows are flat, row-major).  out_rows: rows of
-    elements of each output -> (rc, [out lists])"""
-    from honeybadgermpc_amd._capi import ints_to_limbs, limbs_to_ints, load_library, np_ptr
-
-    lib = load_library()
-    nb = 8 * nl
-    arrays = [None if o is None else ints_to_limbs(list(o) or [0], p, nb) for o in operands]
-    ptrs = (ctypes.c_void_p * 12)(*([None if x is None else x.ctypes.data for x in arrays] + [None] * (12 - len(arrays))))
-    outs = [np.zeros((max(r * count, 1), nl), dtype=np.uint64) for r in out_rows]
-    optrs = (ctypes.c_void_p * 3)(*([o.ctypes.data for o in outs] + [None] * (3 - len(outs))))
-    prm = (ctypes.c_int64 * 2)(p.bit_length() if L is None else L, mode)
-    rc = lib.hb_selftest_lt(np_ptr(ints_to_limbs([p], p + 1, nb)), nl, what, ptrs, prm, optrs, count)
-    return rc, [limbs_to_ints(o[:r * count], nb) for o, r in zip(outs, out_rows)]
 
 
 def beaver(d, e, a, b, ab, p):

@@ -1,19 +1,18 @@
 """CPU-only: honeybadgermpc_amd.share_comparison -- the host functions and host models against tests/golden/share_comparison.json
 (written by scratch/gen_share_comparison_golden.py from the reference's own Equality mixin: legendre_mod_p, and _gen_test_bit /
-gen_test_bit / _prog driven over cleartext shares with recorded draws), the two finishing maps, and the per-element bodies of
-csrc/hb_eq.hip run on the host through hb_selftest_eq -- the same HB_HD functions the kernels call -- against Python ints.
+gen_test_bit / _prog driven over cleartext shares with recorded draws), the two finishing maps, and the steps of csrc/hb_eq.hip
+run on the host through hb_selftest_eq -- the same rows, arithmetic and addressing, that the kernel runs -- against Python ints.
 Exact equality."""
-import ctypes
 import itertools
 import json
 import os
 import random
 import re
 
-import numpy as np
 import pytest
 
 from conftest import BLS, REPO
+from selftest_cases import run_eq as run
 
 from honeybadgermpc_amd import share_comparison as sc
 
@@ -29,32 +28,6 @@ COUNTS = (0, 1, 257)
 def golden():
     with open(os.path.join(REPO, "tests", "golden", "share_comparison.json")) as f:
         return json.load(f)
-
-
-def run(p, nl, what, operands, rows, mode, out_rows, count):
-    """hb_selftest_eq over lists of ints (None: a NULL operand; arrays of several rows are flat, row-major).  out_rows: rows of
-    elements of each output, "i8" for the Legendre symbols, "zr" for zero_rows -> (rc, [out lists])"""
-    from honeybadgermpc_amd._capi import ints_to_limbs, limbs_to_ints, load_library, np_ptr
-
-    lib = load_library()
-    nb = 8 * nl
-    arrays = [None if o is None else ints_to_limbs(list(o) or [0], p, nb) for o in operands]
-    ptrs = (ctypes.c_void_p * 12)(*([None if x is None else x.ctypes.data for x in arrays] + [None] * (12 - len(arrays))))
-    outs = []
-    for r in out_rows:
-        if r == "i8":
-            outs.append(np.full(max(count, 1), 7, dtype=np.int8))
-        elif r == "zr":
-            outs.append(np.zeros(max(rows, 1), dtype=np.int32))
-        else:
-            outs.append(np.zeros((max(r * count, 1), nl), dtype=np.uint64))
-    optrs = (ctypes.c_void_p * 2)(*([o.ctypes.data for o in outs] + [None] * (2 - len(outs))))
-    prm = (ctypes.c_int64 * 2)(rows, mode)
-    rc = lib.hb_selftest_eq(np_ptr(ints_to_limbs([p], p + 1, nb)), nl, what, ptrs, prm, optrs, count)
-    res = []
-    for o, r in zip(outs, out_rows):
-        res.append(o[:count].tolist() if r == "i8" else (o[:rows].tolist() if r == "zr" else limbs_to_ints(o[:r * count], nb)))
-    return rc, res
 
 
 def beaver(d, e, a, b, ab, p):
