@@ -36,6 +36,10 @@ HB_G1_SUBTRACT, HB_G1_GENERAL, HB_G1_DOUBLE = 1, 2, 4
 HB_G1_SELFTEST_FQ_MUL, HB_G1_SELFTEST_SCALAR_MUL, HB_G1_SELFTEST_ADD, HB_G1_SELFTEST_CHECK = 0, 1, 2, 3
 HB_G1_SELFTEST_TABLE, HB_G1_SELFTEST_COMMIT, HB_G1_SELFTEST_EVAL, HB_G1_SELFTEST_VERIFY = 4, 5, 6, 7
 HB_G1_CRS_SELFTEST_TABLE, HB_G1_CRS_SELFTEST_QUOTIENT, HB_G1_CRS_SELFTEST_MSM = 0, 1, 2
+HB_G1_WIRE_OK, HB_G1_WIRE_NOT_COMPRESSED, HB_G1_WIRE_BAD_IDENTITY, HB_G1_WIRE_X_NOT_BELOW_Q = 0, 1, 2, 3
+HB_G1_WIRE_NOT_ON_CURVE, HB_G1_WIRE_NOT_IN_SUBGROUP = 4, 5
+HB_G1_WIRE_SELFTEST_SUBGROUP, HB_G1_WIRE_SELFTEST_DECOMPRESS, HB_G1_WIRE_SELFTEST_COMPRESS = 0, 1, 2
+HB_G1_WIRE_SELFTEST_SQRT, HB_G1_WIRE_SELFTEST_PHI = 3, 4
 HB_PAIR_GT, HB_PAIR_VERDICT = 0, 1
 HB_PAIR_SELFTEST_TOWER, HB_PAIR_SELFTEST_PREPARE, HB_PAIR_SELFTEST_PRODUCT = 0, 1, 2
 HB_PAIR_OP_FQ2_MUL, HB_PAIR_OP_FQ2_SQR, HB_PAIR_OP_FQ2_MUL_NR, HB_PAIR_OP_FQ2_INV = 0, 1, 2, 3
@@ -135,6 +139,9 @@ SYMBOLS = {
     "hb_g1_crs_table": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "hb_kzg_quotient": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
     "hb_g1_crs_msm": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _i, _vp, _i64, _vp]),
+    "hb_g1_subgroup": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "hb_g1_decompress": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_g1_compress": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "hb_pair_table_bytes": (_i64, []),
     "hb_pair_prepare": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "hb_pair_product": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
@@ -230,6 +237,7 @@ SYMBOLS = {
     "hb_selftest_g1": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_g1_msm": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _i, _i]),
     "hb_selftest_g1_crs": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
+    "hb_selftest_g1_wire": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_pairing": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_bd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),

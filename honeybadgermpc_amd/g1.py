@@ -11,7 +11,13 @@ identity is all zeros.  Scalars are the context's (count, 4) elements, read as p
                                                          tensor of 1 or `count` scalars; points: a host G1 or a tensor of 1 or `count`
     add(ctx, P, Q, out=None), sub(...), neg(ctx, P)      element-wise; complete (identity, equal and opposite operands)
     on_curve(ctx, points) -> bool tensor                 the identity, or coordinates below Q and y^2 = x^3 + 4
-    in_subgroup(ctx, points) -> bool tensor              R * P == identity, through scalar_mul's kernel.  NOTHING else checks this.
+    in_subgroup(ctx, points, method="order")             -> bool tensor.  "order": R * P == identity, through scalar_mul's kernel;
+                                                         "endomorphism": phi(P) == -[x^2] P in one launch, the same verdicts.  Nothing
+                                                         else checks this unless asked (decompress's and verify_batch's check_subgroup).
+    decompress(ctx, data, check_subgroup=False, out=None)
+                                                         48-byte encodings (device uint8 (count, 48), or host bytes) -> (points, status
+                                                         (count,) int32: STATUS_*, rejected (1,) int32) in one launch (csrc/hb_g1_wire.hip)
+    compress(ctx, points, out=None)                      -> uint8 (count, 48): the encodings, in one launch
     FixedBase(ctx, base, window=8)                       owns the window table of one base (a host G1, not the identity)
     commit(ctx, tg, th, a, b, out=None)                  a[i] * g + b[i] * h from two FixedBase of one window width: 2 * 256 / window
                                                          mixed additions at most, no doubling
@@ -37,7 +43,7 @@ bases' upload).
 """
 import numpy as np
 
-from .bls12_381 import G1, LIMBS, R
+from .bls12_381 import COMPRESSED_BYTES, G1, LIMBS, R
 
 POINT_WORDS = 2 * LIMBS
 
@@ -171,14 +177,90 @@ def on_curve(ctx, points):
     return flags != 0
 
 
-def in_subgroup(ctx, points):
-    """-> bool tensor (count,): on the curve and R * P the identity.  A full-width scalar multiplication an element: a recipient of
-    foreign commitments decides whether to pay for it (Pedersen binding holds in the subgroup)."""
+def in_subgroup(ctx, points, method="order"):
+    """-> bool tensor (count,): on the curve and in the subgroup of order R; both methods return the same tensor for every input.
+    "order": R * P the identity, a full-width scalar multiplication an element and two more launches.  "endomorphism": one launch of
+    hb_g1_subgroup, phi(P) == -[x^2] P (csrc/hb_g1_wire.hip): about a quarter of the field products, no inversion, and 3.5 times
+    faster at 2^16 points (profiles/g1_wire.txt): the one to use; "order" stays the default until the default is changed on its own."""
     _ctx(ctx)
+    if method not in ("order", "endomorphism"):
+        raise ValueError(f"method: 'order' or 'endomorphism', got {method!r}")
     p, n = _operand(ctx, points)
+    if method == "endomorphism":
+        flags = ctx.torch.empty((n,), dtype=ctx.torch.int32, device=ctx.tdev)
+        ctx.check(ctx.lib.hb_g1_subgroup(ctx.h, ctx.ptr(p), ctx.ptr(flags), n, ctx.stream()), "hb_g1_subgroup")
+        return flags != 0
     order = ctx.torch.from_numpy(np.array([[(R >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]], dtype=np.uint64).view(np.int64)).to(ctx.tdev)
     rp = scalar_mul(ctx, order, p)                           # the order itself is no canonical residue: uploaded as words
     return on_curve(ctx, p) & (rp.reshape(n, POINT_WORDS) == 0).all(dim=1)
+
+
+# ---- points from the wire (csrc/hb_g1_wire.hip): status[i] of decompress, as the header's HB_G1_WIRE_*
+STATUS_OK, STATUS_NOT_COMPRESSED, STATUS_BAD_IDENTITY, STATUS_X_NOT_BELOW_Q, STATUS_NOT_ON_CURVE, STATUS_NOT_IN_SUBGROUP = range(6)
+
+
+def _wire_bytes(ctx, data):
+    """-> (uint8 tensor on the device, contiguous, its storage aligned to 16 bytes; count)"""
+    torch = ctx.torch
+    if isinstance(data, torch.Tensor):
+        if data.dtype != torch.uint8:
+            raise TypeError(f"data: dtype must be uint8, got {data.dtype}")
+        if not data.is_cuda or data.device.index != ctx.device:
+            raise ValueError(f"data: must live on cuda:{ctx.device}, is on {data.device}")
+        if data.numel() % COMPRESSED_BYTES or (data.dim() >= 2 and data.shape[-1] != COMPRESSED_BYTES):
+            raise ValueError(f"data: expected a tensor of shape (count, {COMPRESSED_BYTES}), got {tuple(data.shape)}")
+        t = data if data.is_contiguous() else data.contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()                                       # a view into the middle of a buffer: the kernel reads 16 bytes a load
+    else:
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            arr = np.frombuffer(data, dtype=np.uint8)
+        elif isinstance(data, np.ndarray):
+            if data.dtype != np.uint8:
+                raise TypeError(f"data: dtype must be uint8, got {data.dtype}")
+            arr = data.reshape(-1)
+        else:
+            raise TypeError(f"data: expected a uint8 tensor, bytes, a bytearray or a numpy uint8 array, got {type(data).__name__}")
+        if arr.size % COMPRESSED_BYTES:
+            raise ValueError(f"data: {arr.size} bytes are no multiple of {COMPRESSED_BYTES}")
+        t = torch.from_numpy(np.array(arr, dtype=np.uint8, copy=True)).to(ctx.tdev)
+    return t, t.numel() // COMPRESSED_BYTES
+
+
+def decompress(ctx, data, check_subgroup=False, out=None):
+    """48-byte compressed encodings (bls12_381.G1.compress's format) -> (points (count, 2, 6), status (count,) int32, rejected (1,)
+    int32) in one launch.  data: a uint8 tensor (count, 48) on the context's device (copied when it is not contiguous or its storage
+    not aligned to 16 bytes), or host bytes / bytearray / numpy uint8 of 48 * count bytes, which is uploaded.  status[i] is STATUS_OK
+    or the first check the item fails, in the order G1.decompress makes them; STATUS_NOT_IN_SUBGROUP only with check_subgroup.  A
+    rejected item's point is all zeros (as the identity's: the status tells), rejected[0] counts them.  Nothing synchronises."""
+    _ctx(ctx)
+    enc, count = _wire_bytes(ctx, data)
+    torch = ctx.torch
+    out = _out(ctx, out, count)
+    status = torch.empty((count,), dtype=torch.int32, device=ctx.tdev)
+    rejected = torch.zeros((1,), dtype=torch.int32, device=ctx.tdev)
+    ctx.check(ctx.lib.hb_g1_decompress(ctx.h, ctx.ptr(enc), 1 if check_subgroup else 0, ctx.ptr(out), ctx.ptr(status), ctx.ptr(rejected), count, ctx.stream()),
+              "hb_g1_decompress")
+    return out, status, rejected
+
+
+def compress(ctx, points, out=None):
+    """points (count, 2, 6) -> uint8 (count, 48) in one launch: big-endian x with 0x80 set, 0x40 for the all-zero point, 0x20 iff
+    y > (Q - 1) / 2.  The coordinates are written as they stand: on_curve tells whether they are a point."""
+    _ctx(ctx)
+    p, n = _operand(ctx, points)
+    torch = ctx.torch
+    if out is None:
+        out = torch.empty((n, COMPRESSED_BYTES), dtype=torch.uint8, device=ctx.tdev)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8:
+            raise TypeError("out: expected a uint8 tensor")
+        if not out.is_cuda or out.device.index != ctx.device:
+            raise ValueError(f"out: must live on cuda:{ctx.device}, is on {out.device}")
+        if not out.is_contiguous() or out.numel() != n * COMPRESSED_BYTES or out.data_ptr() % 16:
+            raise ValueError(f"out: expected a contiguous tensor of {n} x {COMPRESSED_BYTES} bytes aligned to 16, got {tuple(out.shape)}")
+    ctx.check(ctx.lib.hb_g1_compress(ctx.h, ctx.ptr(p), ctx.ptr(out), n, ctx.stream()), "hb_g1_compress")
+    return out
 
 
 class FixedBase:

@@ -22,11 +22,14 @@ There is no CPU path: without a GPU every method that computes raises HbmpcBacke
     w, shares, aux = pc.witness_batch(coeffs, hat, xs)     n points -> w (B, n, 2, 6), shares (B, n, 4), aux (B, n, 4): THREE launches,
                                                            the whole double loop of HbAvssBatch._get_dealer_msg (hbavss.py:567-598)
     ok = pc.verify_batch(c, xs, shares, aux, w)            one verdict an item -> bool tensor (B,); xs one index or one an item
+    ok = pc.verify_wire(c48, xs, shares, aux, w48)         the same from 48-byte compressed encodings, membership in the subgroup
+                                                           checked: what a recipient runs on a dealer's message
 
 What is NOT checked: that the bases are powers of one alpha and that ghats[1] = alpha ghats[0] for that same alpha (a CRS is trusted),
-that the bases, the commitments and the witnesses lie in the subgroup of order R (the rearranged equation equals the reference's only
-there; g1.in_subgroup tells, and it is the caller's call), and that the scalars handed in as tensors are canonical residues
-(ctx.reduce_ makes them so).
+that the bases lie in the subgroup of order R, and that the scalars handed in as tensors are canonical residues (ctx.reduce_ makes
+them so).  Membership of the commitments and the witnesses in that subgroup (the rearranged equation equals the reference's only
+there) is checked when asked: verify_batch(..., check_subgroup=True) (off by default, as before) and verify_wire (on by default) run
+the endomorphism test of csrc/hb_g1_wire.hip, one launch an array.
 """
 import secrets
 
@@ -201,17 +204,36 @@ class PolyCommitConst(object):
         lhs = g1.add(ctx, g1.sub(ctx, c, opened), g1.scalar_mul(ctx, xs, w)) if B else c
         return lhs, g1.neg(ctx, w)
 
-    def verify_batch(self, commits, xs, shares, auxes, witnesses):
+    def verify_batch(self, commits, xs, shares, auxes, witnesses, check_subgroup=False):
         """commits (B, 2, 6), shares and auxes (B, 4), witnesses (B, 2, 6); xs: ONE index (an int, or a tensor (1, 4)) or one an item
         (a list of B ints, or a tensor (B, 4)) -> bool tensor (B,): verdict[b] = the reference's verify_eval(commits[b], xs[b],
         shares[b], auxes[b], witnesses[b]) for points of the subgroup of order R (see the module's head for what is not checked).
-        Six launches: five for the left side in G1, one for two Miller loops and a final exponentiation an item."""
+        Six launches: five for the left side in G1, one for two Miller loops and a final exponentiation an item.
+        check_subgroup=True: two more launches, and an item whose commitment or witness is outside the subgroup is False."""
         self._need_ghats("verify_batch")
         ctx = self.ctx
         _, _, p0, p1 = self._verifier_state()
         lhs, nw = self.verify_lhs(commits, xs, shares, auxes, witnesses)
         ok, _ = pairing.product_is_one(ctx, [(lhs, p0), (nw, p1)])
+        if check_subgroup:
+            B = int(ok.shape[0])
+            ok = ok & g1.in_subgroup(ctx, g1._points(ctx, commits, B, what="commits"), method="endomorphism") \
+                & g1.in_subgroup(ctx, g1._points(ctx, witnesses, B, what="witnesses"), method="endomorphism")
         return ok
+
+    def verify_wire(self, commits48, xs, shares, auxes, witnesses48, check_subgroup=True):
+        """verify_batch for commitments and witnesses as they come from another party: 48-byte compressed encodings (what
+        g1.decompress takes: uint8 (B, 48) on the device, or host bytes) -> bool tensor (B,).  Both arrays are decompressed with
+        check_subgroup (one launch each, the membership test inside it), verify_batch runs on the results, and its verdicts are ANDed
+        with status == 0 of both arrays: a malformed encoding or a point outside the subgroup is a False verdict, never an exception
+        (a rejected item enters verify_batch as the identity)."""
+        self._need_ghats("verify_wire")
+        ctx = self.ctx
+        c, cst, _ = g1.decompress(ctx, commits48, check_subgroup=check_subgroup)
+        w, wst, _ = g1.decompress(ctx, witnesses48, check_subgroup=check_subgroup)
+        if g1._n(c) != g1._n(w):
+            raise ValueError(f"commits48 and witnesses48: {g1._n(c)} encodings against {g1._n(w)}")
+        return self.verify_batch(c, xs, shares, auxes, w) & (cst == 0) & (wst == 0)
 
     def verify_eval(self, c, i, phi_at_i, phi_hat_at_i, witness):
         """-> bool, on host objects, as the reference's verify_eval"""

@@ -347,6 +347,32 @@ int hb_kzg_quotient(hb_ctx *ctx, const uint64_t *phi_dev, int n_coef, const uint
                     uint64_t *rem_dev, int64_t count_polys, void *stream);
 int hb_g1_crs_msm(hb_ctx *ctx, const void *tg_dev, const void *th_dev, int64_t n_bases, int window, const uint64_t *a_dev,
                   const uint64_t *b_dev, int64_t terms, int split, uint64_t *out_dev, int64_t rows, void *stream);
+/* G1 points from the wire (hb_g1_wire.hip): the 48-byte compressed encoding of the reference's Rust crate and a test of membership in
+ * the subgroup of order R that needs no full-width scalar multiplication.  An encoding is big-endian x; in byte 0, 0x80 always set
+ * (compressed), 0x40 the identity (x = 0, no sign), 0x20 set when y > (Q - 1) / 2.
+ * hb_g1_subgroup: flags[i] = 1 if P_i passes hb_g1_check's test AND (P_i is the identity or phi(P_i) = -[x^2] P_i), else 0;
+ *   phi(x, y) = (beta x, y) the curve's endomorphism, x = 0xd201000000010000 the curve's parameter: true exactly for the points of the
+ *   subgroup (Scott, eprint 2021/1130).  126 doublings and 10 additions an element in Jacobian coordinates, no inversion.  One launch.
+ * hb_g1_decompress: bytes_dev = count * 48 bytes, aligned to 16 (another alignment: HB_ERR_BAD_ARG) -> out_dev, `count` points as all
+ *   of G1 takes them, and status_dev[i], the FIRST check item i fails in the order of the codes below (HB_G1_WIRE_NOT_IN_SUBGROUP
+ *   only with check_subgroup != 0: hb_g1_subgroup's test in the same launch).  A rejected item's point is all zeros, as the
+ *   identity's is: the status tells them apart.  *rejected_dev is incremented once a rejected item (the caller zeroes it).  y is
+ *   rhs^((Q + 1) / 4) with rhs = x^3 + 4, accepted iff y^2 = rhs.  x = 0 with either sign IS a point ((0, +-2), of order 3).  One launch.
+ * hb_g1_compress: bytes_dev (count * 48 bytes, aligned to 16) = the encodings of `count` points.  The coordinates are written as they
+ *   stand (all zeros: the identity); hb_g1_check tells whether they are a point.  One launch.
+ * All: asynchronous on `stream`, nothing allocated; count == 0 returns HB_OK and launches nothing; an output overlapping an input:
+ *   HB_ERR_BAD_ARG.  The exponent (Q + 1) / 4, (Q - 1) / 2 and beta are derived from or checked against Q once a process (4 e = Q + 1,
+ *   beta^3 = 1, beta != 1, phi(G) = -[x^2] G on the generator, sqrt(4) = +-2); a failed check: HB_ERR_UNSUPPORTED from all three. */
+#define HB_G1_WIRE_OK 0
+#define HB_G1_WIRE_NOT_COMPRESSED 1
+#define HB_G1_WIRE_BAD_IDENTITY 2
+#define HB_G1_WIRE_X_NOT_BELOW_Q 3
+#define HB_G1_WIRE_NOT_ON_CURVE 4
+#define HB_G1_WIRE_NOT_IN_SUBGROUP 5
+int hb_g1_subgroup(hb_ctx *ctx, const uint64_t *p_dev, int32_t *flags_dev, int64_t count, void *stream);
+int hb_g1_decompress(hb_ctx *ctx, const void *bytes_dev, int check_subgroup, uint64_t *out_dev, int32_t *status_dev, int32_t *rejected_dev,
+                     int64_t count, void *stream);
+int hb_g1_compress(hb_ctx *ctx, const uint64_t *p_dev, void *bytes_dev, int64_t count, void *stream);
 
 /* ---- pairings against prepared G2 points (hb_pair.hip) ------------------------------------------------------------------
  * The verifier of the KZG commitment (poly_commit_const.py:28-44): products of BLS12-381 pairings whose G2 arguments are fixed.  A G2
@@ -982,6 +1008,21 @@ int hb_selftest_g1_msm(const uint64_t *s, const uint64_t *p, int points_per_row,
 #define HB_G1_CRS_SELFTEST_QUOTIENT 1
 #define HB_G1_CRS_SELFTEST_MSM 2
 int hb_selftest_g1_crs(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count);
+/* host-side run of the bodies of hb_g1_wire.hip (no GPU needed) over host memory, item by item; operands and out aligned to 16 bytes
+ * (else HB_ERR_BAD_ARG); arg = 0; the constants are derived and checked as for the device calls (a failed check: HB_ERR_UNSUPPORTED):
+ *   what = HB_G1_WIRE_SELFTEST_SUBGROUP    operands[0] = points; out = `count` int32 flags
+ *          HB_G1_WIRE_SELFTEST_DECOMPRESS  operands[0] = count * 48 bytes; flags = check_subgroup; out = `count` points (12 words each),
+ *                                          then `count` int32 statuses, then the int32 count of rejected items
+ *          HB_G1_WIRE_SELFTEST_COMPRESS    operands[0] = points; out = count * 48 bytes
+ *          HB_G1_WIRE_SELFTEST_SQRT        operands[0] = a: 6 words an element, below Q; out = `count` roots a^((Q + 1) / 4) (6 words
+ *                                          each, zeros where a is no square), then `count` int32 flags: 1 a square, 0 not
+ *          HB_G1_WIRE_SELFTEST_PHI         operands[0] = points; out = (beta x, y) of each */
+#define HB_G1_WIRE_SELFTEST_SUBGROUP 0
+#define HB_G1_WIRE_SELFTEST_DECOMPRESS 1
+#define HB_G1_WIRE_SELFTEST_COMPRESS 2
+#define HB_G1_WIRE_SELFTEST_SQRT 3
+#define HB_G1_WIRE_SELFTEST_PHI 4
+int hb_selftest_g1_wire(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count);
 /* host-side run of the bodies of hb_pair.hip and hb_fq12_elem.hpp (no GPU needed) over host memory, item by item; also derives the
  * Frobenius constants from Q and compares them with the literals (a difference: HB_ERR_BAD_ARG whatever is asked):
  *   what = HB_PAIR_SELFTEST_TOWER    operands[0..1] = a, b: 72 words an item, residues below Q; flags = HB_PAIR_OP_*; out = 72 words an
