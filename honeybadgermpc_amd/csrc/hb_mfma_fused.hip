@@ -267,11 +267,16 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
     };
     // ---- prologue: the first unit's first loads, tables, zeros for the terms d .. 8 NKB - 1 (never written again) ---------
     // every wave takes its share of the first unit (terms wave, wave + 8, wave + 16): the loads of its first term are issued ahead of the
-    // tables' copy and return under it
+    // tables' copy and return under it (the T_q multiplication; MSC: below)
     const uint32_t first_terms = (0x01010101u << wave) & (d < 32 ? (1u << d) - 1u : ~0u);
     uint32_t x_first[NW] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool ok_first = false;
-    if (first_terms) {
+    // MSC: the words of ALL of the wave's terms (NKB at most: d <= 8 NKB), loaded BEHIND the tables' loads below (the copy then waits for the
+    // tables alone, not for HBM).  A term the wave does not have (l >= d) loads term d - 1's words and is masked: a load under a branch is
+    // waited for where the branch joins
+    uint32_t xf[MSC ? NKB : 1][NW];
+    bool okf[MSC ? NKB : 1];
+    if (!MSC && first_terms) {
         const int l0 = __builtin_ctz(first_terms);
         fetch_row(unit_chunk(blockIdx.x), in_rows ? in_rows[l0] : l0, x_first, ok_first);
     }
@@ -301,16 +306,33 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         v4i img[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) img[k] = reinterpret_cast<const v4i *>(a8)[tid + k * NT < n_img ? tid + k * NT : 0];
-        // (MSC: four pieces a thread are the 1648 of d = 22)
-        const int n_ms = MSC ? fs_ms_q(d) : 0;
-        v4i msv[4];
+        // MSC: the division's tables go to LDS by OWNER -- a wave copies the rows of its own terms wave, wave + 8, ... (64 pieces a row: one
+        // piece a lane) and their constants (8 pieces a term: lanes 0 .. 8 NKB - 1), and writes the block of zeros itself.  So the first
+        // unit's tasks read their operands from LDS that their own wave wrote: no barrier, and no second fetch of the same rows from
+        // global memory.  A term the wave does not have (l >= d) copies row d - 1 again (the same words as its owner writes).
+        const int ms_lj = wave + 8 * (lane >> 3), ms_cq = (d + 1) * 64 + (ms_lj < d ? ms_lj : d - 1) * 8 + (lane & 7);
+        v4i msv[MSC ? NKB + 1 : 1];
         if constexpr (MSC) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) msv[k] = MS[tid + k * NT < n_ms ? tid + k * NT : 0];
+            for (int j = 0; j < NKB; j++) {
+                const int l = wave + 8 * j, lc = l < d ? l : d - 1;
+                msv[j] = MS[lc * 64 + lane];
+            }
+            msv[NKB] = MS[ms_cq];
+            const int64_t chunk0 = unit_chunk(blockIdx.x);
+#pragma unroll
+            for (int j = 0; j < NKB; j++) {
+                const int l = wave + 8 * j, lc = l < d ? l : d - 1;
+                fetch_row(chunk0, in_rows ? in_rows[lc] : lc, xf[j], okf[j]);
+                okf[j] = okf[j] && l < d;
+            }
         }
         // (the words are wanted HERE: hipcc otherwise sinks each load into the branch of its write, one wait per load again)
         asm volatile("" : "+v"(rw), "+v"(mk), "+v"(cr), "+v"(fo), "+v"(img[0]), "+v"(img[1]), "+v"(img[2]));
-        if constexpr (MSC) asm volatile("" : "+v"(msv[0]), "+v"(msv[1]), "+v"(msv[2]), "+v"(msv[3]));
+        if constexpr (MSC) {
+#pragma unroll
+            for (int j = 0; j <= NKB; j++) asm volatile("" : "+v"(msv[j]));
+        }
         if (tid < 32) rowl[tid] = rw;
         if (tid < n_mask) maskl[tid] = tid < n_slots ? mk : 0;
         if (tid < n_crow) reinterpret_cast<v4i *>(fs_lds)[tid] = cr;
@@ -320,15 +342,17 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
             if (tid + k * NT < n_img) reinterpret_cast<v4i *>(abuf)[tid + k * NT] = img[k];
         if constexpr (MSC) {
 #pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (tid + k * NT < n_ms) msl[tid + k * NT] = msv[k];
+            for (int j = 0; j < NKB; j++) {
+                const int l = wave + 8 * j, lc = l < d ? l : d - 1;
+                msl[lc * 64 + lane] = msv[j];
+            }
+            if (lane < 8 * NKB) msl[ms_cq] = msv[NKB];
+            msl[d * 64 + lane] = v4i{0, 0, 0, 0};
         }
         // (what a larger launch has beyond one round)
         for (int i = tid + NT; i < n_mask; i += NT) maskl[i] = i < n_slots ? rowmode[i] : 0;
         for (int i = tid + NT; i < n_crow; i += NT) fs_lds[i] = reinterpret_cast<const uint4 *>(crowd)[i];
         for (int i = tid + 3 * NT; i < n_img; i += NT) abuf[i] = a8[i];
-        if constexpr (MSC)
-            for (int i = tid + 4 * NT; i < n_ms; i += NT) msl[i] = MS[i];
     }
     // the slots [buffer][tile][half][column] of a padding term, 256 in all: no scaling task ever writes them, and they are all that is
     // zeroed -- every other slot is written by the unit's scaling tasks before a pass reads it
@@ -378,10 +402,9 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                 // (128 sum_b U_l[b] - the biases, mod p): every column arrives positive and below 2^21, a word is two shifted adds and one
                 // multiply-add, and the quotient is FS_REDUCE's.  tests/fs_mscale_model.py has the bounds.
                 //
-                // The first unit's tasks run before the tables are in LDS: they read the same operands from the tables in global memory
-                // (a lane of the diagonal its row, the others the block of zeros: five addresses a load).
-                const v4i *tab;
-                if constexpr (FIRST) tab = MS; else tab = msl;
+                // The first unit's tasks are a block of their own, below, where this lambda's `first` call stands for the T_q multiplication.
+                static_assert(!FIRST, "the first unit's matrix-core tasks are the block at the call site");
+                const v4i *tab = msl;
                 const v4i *al = tab + (g == (n >> 2) ? l * 64 + (n & 3) : d * 64);
                 const v4i *cl = tab + (d + 1) * 64 + l * 8;
                 const v4i b0 = v4i{(int)(xw[0] ^ 0x80808080u), (int)(xw[1] ^ 0x80808080u), (int)(xw[2] ^ 0x80808080u), (int)(xw[3] ^ 0x80808080u)};
@@ -467,7 +490,76 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 
     // the first unit: every wave scales its share into buffer 0.  Nothing it touches depends on the tables (the padding slots are other
     // slots), so no barrier stands between the copy and this: the loop's first barrier covers both
-    scale_unit(std::true_type{}, blockIdx.x, xbuf, first_terms);
+    if constexpr (MSC) {
+        // All eight waves only scale here: the wave's terms wave, wave + 8, ... as ONE straight-line block (scale_unit's arithmetic term by
+        // term).  What the head waits for is the first unit's words from HBM, every workgroup's at once, and vector loads return in order:
+        // so the words' loads are the LAST vector loads of the prologue, the operands are LDS reads (the rows this wave copied itself,
+        // above), and term j's MFMAs wait for term j's words alone -- its words, quotient and carries then run in one block with the
+        // MFMAs of term j + 1, under the arrival of the later words.  (Operands from the tables in global memory, as before: each task's
+        // sixteen loads queue behind every word load that was issued ahead of them, and the whole block waits for the last word.)
+        const int t = lane >> 4;
+        const bool diag = g == (n >> 2);
+        auto first_block = [&](auto canon_c) __attribute__((always_inline)) {
+            constexpr bool CANON = decltype(canon_c)::value;      // p >= 2^255: r < 2p may pass 2^256, made canonical (scale_unit)
+            v4i mc[NKB][8];
+#pragma unroll
+            for (int s = 0; s <= NKB; s++) {
+                if (s < NKB) {
+                    // the MFMAs of term s: they wait for ITS words alone (the loads return in order), the operands are LDS reads
+                    const int j = s, l = wave + 8 * j, lc = l < d ? l : d - 1;
+                    const v4i *al = msl + (diag ? lc * 64 + (n & 3) : d * 64);
+                    const v4i *cl = msl + (d + 1) * 64 + lc * 8;
+                    const v4i b0 = v4i{(int)(xf[j][0] ^ 0x80808080u), (int)(xf[j][1] ^ 0x80808080u), (int)(xf[j][2] ^ 0x80808080u), (int)(xf[j][3] ^ 0x80808080u)};
+                    const v4i b1 = v4i{(int)(xf[j][4] ^ 0x80808080u), (int)(xf[j][5] ^ 0x80808080u), (int)(xf[j][6] ^ 0x80808080u), (int)(xf[j][7] ^ 0x80808080u)};
+#pragma unroll
+                    for (int eb = 0; eb < 8; eb++) mc[j][eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[eb * 4], b0, cl[eb], 0, 0, 0);
+#pragma unroll
+                    for (int eb = 0; eb < 8; eb++) mc[j][eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[32 + eb * 4], b1, mc[j][eb], 0, 0, 0);
+                }
+                if (s > 0) {
+                    // the words, the quotient and the carries of term s - 1, in one block with the next term's MFMAs
+                    const int j = s - 1, l = wave + 8 * j;
+                    uint64_t mw[8];
+#pragma unroll
+                    for (int k = 0; k < 8; k++) {
+                        const uint32_t lo = (uint32_t)mc[j][k][0] + ((uint32_t)mc[j][k][1] << 8), hi = (uint32_t)mc[j][k][2] + ((uint32_t)mc[j][k][3] << 8);
+                        mw[k] = (uint64_t)hi * ms64k + lo;
+                    }
+                    const uint64_t tq = mw[7] + (mw[6] >> 32);
+                    const uint32_t mq = (uint32_t)(((uint64_t)(uint32_t)(tq >> 16) * bp.mu) >> 46);
+#pragma unroll
+                    for (int k = 0; k < 8; k++) mw[k] += (uint64_t)mq * bp.pneg[k];
+                    uint32_t w[NW];
+                    unsigned cyw = 0;
+                    w[0] = (uint32_t)mw[0];
+#pragma unroll
+                    for (int k = 1; k < 8; k++) w[k] = __builtin_addc((uint32_t)mw[k], (uint32_t)(mw[k - 1] >> 32), cyw, &cyw);
+                    if constexpr (CANON) {
+                        const bool over = (uint32_t)(mw[7] >> 32) + cyw != mq;
+                        uint32_t u[NW];
+                        unsigned cy = 0;
+#pragma unroll
+                        for (int k = 0; k < NW; k++) u[k] = __builtin_addc(w[k], bp.pneg[k], cy, &cy);
+                        const bool take = cy || over;
+#pragma unroll
+                        for (int k = 0; k < NW; k++) w[k] = okf[j] ? (take ? u[k] : w[k]) : 0u;
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < NW; k++) w[k] = okf[j] ? w[k] : 0u;
+                    }
+                    // (a term the wave does not have is a padding term of K-block j: its slot takes the zeros it must hold)
+                    const int gg = (l & 7) >> 1, e = l & 1;
+                    uint4 *slot = xbuf + (size_t)(((t * NKB + j) * 2 + e) * 2) * 64 + (n + 16 * gg);
+                    slot[0] = make_uint4(w[0], w[1], w[2], w[3]);
+                    slot[64] = make_uint4(w[4], w[5], w[6], w[7]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        if (bp.pneg[NW - 1] >> 31) first_block(std::false_type{});
+        else first_block(std::true_type{});
+    } else
+        scale_unit(std::true_type{}, blockIdx.x, xbuf, first_terms);
     if (!PACKED && pick.cand) {
         __syncthreads();      // (the image's copy is in LDS: the picked rows go over its empty rows)
         auto put = [&](int e, const uint4 &v) {
