@@ -430,7 +430,7 @@ struct FsLayout {
     size_t o_a8, o_crow, o_kt, o_mode, o_z, o_cand, o_cand_crow, need;      // o_cand: the per-party candidate rows (0 when the point set is too large for them)
     int pk_nm, pk_ns;            // the packed last row tile (hb_mfma_fused.hip, FsPack): merged rows, single-group rows; 0, 0: none
     uint8_t pk_single[8];        // the coefficient rows that are its single-group rows
-    size_t o_ms;                 // the tables of the division by den on the matrix cores ([d + 1][1024] bytes of A operands, [d][32] constants)
+    size_t o_ms;                 // the tables of the division by den on the matrix cores ([d][1024] bytes of A operands, [d][32] constants)
     int mscale;                  // the image has them and its launches use them (fs_mscale)
 };
 constexpr int FS_BUILD_Z = 1, FS_BUILD_ZC = 2;

@@ -112,7 +112,7 @@ constexpr int FS_CAND_MAXN = 128;               // parties a candidate store is 
 // LDS: row constants [n_rt * 16][16] | matrix digits [n_rt][NKB][2][64] x 16 B | two element buffers [4 tiles][NKB][2][2][64] x 16 B |
 // rowl[32] | maskl[16 n_rt] | fold table
 // | (ms_d > 0: the launch divides by den on the matrix cores) the tables of fs_ms_q(ms_d)
-__host__ __device__ inline int fs_ms_q(int d) { return (d + 1) * 64 + d * 8; }      // in uint4
+__host__ __device__ inline int fs_ms_q(int d) { return d * 64 + d * 8; }      // in uint4: per term a 1 KB row of digits, then per term 128 B of constants
 __host__ __device__ inline size_t fs_lds_bytes(int n_rt, int nkb, int ms_d = 0) {
     return ((size_t)n_rt * 64 + (size_t)n_rt * nkb * 2 * 64 + (size_t)2 * FS_TPW * nkb * 4 * 64 + MM8_FOLD_Q + (ms_d ? fs_ms_q(ms_d) : 0)) * 16 +
            (size_t)(32 + 16 * n_rt) * 4;
@@ -260,6 +260,23 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         const int64_t chunk = unit * 64 + lane;
         return chunk >= n_chunks ? n_chunks - 1 : chunk;          // (results of padding chunks are never stored or compared)
     };
+    // MSC: a task is two dense 32x32x32 products (32 columns x 32 chunks x 32 bytes), so lane (r, h) = (lane & 31, lane >> 5) loads bytes
+    // 16 h .. 16 h + 15 of chunk r of the unit (w[0 .. 3]) and of chunk 32 + r (w[4 .. 7]): the row, the clamp and the bound as fetch_row
+    // has them, per source chunk.  okk is the test of the lane's OWN chunk (chunk = lane, as everywhere behind the half swap)
+    auto fetch_halves = [&](int64_t unit, int row, uint32_t (&w)[NW], bool &okk) {
+        const int r = lane & 31, h = lane >> 5;
+        bool oks[2];
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            int64_t chunk = unit * 64 + 32 * s + r;
+            chunk = chunk >= n_chunks ? n_chunks - 1 : chunk;
+            const int64_t idx = chunk * in_sc + (int64_t)row * in_sl;
+            oks[s] = idx < in_count;
+            const uint4 v = *reinterpret_cast<const uint4 *>(in_pk + (oks[s] ? idx : 0) * NW + 4 * h);
+            w[4 * s] = v.x; w[4 * s + 1] = v.y; w[4 * s + 2] = v.z; w[4 * s + 3] = v.w;
+        }
+        okk = h ? oks[1] : oks[0];
+    };
     auto fetch_row = [&](int64_t chunk, int row, uint32_t (&w)[NW], bool &okk) {
         const int64_t idx = chunk * in_sc + (int64_t)row * in_sl;
         okk = idx < in_count;
@@ -307,10 +324,10 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 #pragma unroll
         for (int k = 0; k < 3; k++) img[k] = reinterpret_cast<const v4i *>(a8)[tid + k * NT < n_img ? tid + k * NT : 0];
         // MSC: the division's tables go to LDS by OWNER -- a wave copies the rows of its own terms wave, wave + 8, ... (64 pieces a row: one
-        // piece a lane) and their constants (8 pieces a term: lanes 0 .. 8 NKB - 1), and writes the block of zeros itself.  So the first
+        // piece a lane) and their constants (8 pieces a term: lanes 0 .. 8 NKB - 1).  So the first
         // unit's tasks read their operands from LDS that their own wave wrote: no barrier, and no second fetch of the same rows from
         // global memory.  A term the wave does not have (l >= d) copies row d - 1 again (the same words as its owner writes).
-        const int ms_lj = wave + 8 * (lane >> 3), ms_cq = (d + 1) * 64 + (ms_lj < d ? ms_lj : d - 1) * 8 + (lane & 7);
+        const int ms_lj = wave + 8 * (lane >> 3), ms_cq = d * 64 + (ms_lj < d ? ms_lj : d - 1) * 8 + (lane & 7);
         v4i msv[MSC ? NKB + 1 : 1];
         if constexpr (MSC) {
 #pragma unroll
@@ -319,11 +336,10 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                 msv[j] = MS[lc * 64 + lane];
             }
             msv[NKB] = MS[ms_cq];
-            const int64_t chunk0 = unit_chunk(blockIdx.x);
 #pragma unroll
             for (int j = 0; j < NKB; j++) {
                 const int l = wave + 8 * j, lc = l < d ? l : d - 1;
-                fetch_row(chunk0, in_rows ? in_rows[lc] : lc, xf[j], okf[j]);
+                fetch_halves(blockIdx.x, in_rows ? in_rows[lc] : lc, xf[j], okf[j]);
                 okf[j] = okf[j] && l < d;
             }
         }
@@ -347,7 +363,6 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                 msl[lc * 64 + lane] = msv[j];
             }
             if (lane < 8 * NKB) msl[ms_cq] = msv[NKB];
-            msl[d * 64 + lane] = v4i{0, 0, 0, 0};
         }
         // (what a larger launch has beyond one round)
         for (int i = tid + NT; i < n_mask; i += NT) maskl[i] = i < n_slots ? rowmode[i] : 0;
@@ -367,6 +382,52 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 
     uint32_t ms64k = 1u << 16;                   // opaque: a word of the matrix-core division is one v_mad_u64_u32 over two shifted adds
     if constexpr (MSC) asm volatile("" : "+s"(ms64k));
+    // ---- the division by den on the matrix cores: x / den_l = sum_b x_b U_l[b] over the element's 32 bytes, U_l[b] = 256^b / den_l as 32
+    // balanced digits.  U_l is the same for every chunk, so a task is the dense product [32 columns] x [32 bytes] x [64 chunks]: two
+    // independent v_mfma_i32_32x32x32_i8, chunks 0 .. 31 and 32 .. 63 of the unit.  Lane (r, h):
+    //   B  its 16 bytes 16 h .. 16 h + 15 of chunk r (and of chunk 32 + r), XOR 0x80 (fetch_halves)
+    //   A  byte j = digit r of U_l[16 h + j]: piece l * 64 + lane of the tables, the same for both products (whatever order the hardware
+    //      gives the 32 values of K, element j of A's lane (m, h) meets element j of B's lane (n, h): the sum over K is all that counts)
+    //   C  2^20 + byte c of the term's constant (128 sum_b U_l[b] - the biases, mod p), c = (i & 3) + 8 (i >> 2) + 4 h for register i
+    //      (the 32x32 accumulator map: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)): pieces d * 64 + l * 8 + 4 h ..
+    // Every column arrives positive and below 2^21 (tests/fs_mscale_model.py has the bounds; tests/fs_mscale32_model.py these maps).
+    typedef int v16i __attribute__((ext_vector_type(16)));
+    const v4i *ms_al = msl + lane, *ms_cl = msl + d * 64 + 4 * (lane >> 5);
+    auto ms_products = [&](int l, const uint32_t (&x)[NW], v16i &acc0, v16i &acc1) __attribute__((always_inline)) {
+        const v4i a = ms_al[l * 64];
+        const v4i *cl = ms_cl + l * 8;
+        v16i c;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const v4i cq = cl[q];
+#pragma unroll
+            for (int k = 0; k < 4; k++) c[4 * q + k] = cq[k];
+        }
+        const v4i b0 = v4i{(int)(x[0] ^ 0x80808080u), (int)(x[1] ^ 0x80808080u), (int)(x[2] ^ 0x80808080u), (int)(x[3] ^ 0x80808080u)};
+        const v4i b1 = v4i{(int)(x[4] ^ 0x80808080u), (int)(x[5] ^ 0x80808080u), (int)(x[6] ^ 0x80808080u), (int)(x[7] ^ 0x80808080u)};
+        acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b0, c, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b1, c, 0, 0, 0);
+    };
+    // The words: lane (r, h) holds the columns of the 32-bit-word addends 2 q + h, q < 4, of chunk r in acc0 and of chunk 32 + r in acc1
+    // (an addend is two shifted adds and one multiply-add, below 2^46).  The half swap (lanes 32 .. 63 of the destination against lanes
+    // 0 .. 31 of the source) with acc0's addends as destination and acc1's as source leaves the even addends of chunk = lane in the
+    // destination and the odd ones in the source, in every lane: from there on lane = chunk again
+    auto ms_words = [&](const v16i &acc0, const v16i &acc1, uint64_t (&mw)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            uint64_t ad[2];
+#pragma unroll
+            for (int s = 0; s < 2; s++) {
+                const v16i &m = s ? acc1 : acc0;
+                const uint32_t lo = (uint32_t)m[4 * q] + ((uint32_t)m[4 * q + 1] << 8), hi = (uint32_t)m[4 * q + 2] + ((uint32_t)m[4 * q + 3] << 8);
+                ad[s] = (uint64_t)hi * ms64k + lo;
+            }
+            const auto slo = __builtin_amdgcn_permlane32_swap((uint32_t)ad[0], (uint32_t)ad[1], false, false);
+            const auto shi = __builtin_amdgcn_permlane32_swap((uint32_t)(ad[0] >> 32), (uint32_t)(ad[1] >> 32), false, false);
+            mw[2 * q] = (uint64_t)slo[0] | ((uint64_t)shi[0] << 32);
+            mw[2 * q + 1] = (uint64_t)slo[1] | ((uint64_t)shi[1] << 32);
+        }
+    };
     // T_q of a task's term is wave-uniform (scalar loads).  first: the prologue's call -- its first term's words are already in registers
     // (x_first), and rowl is not in LDS yet
     auto scale_unit = [&](auto first, int64_t unit, uint4 *dst, uint32_t terms) {
@@ -375,7 +436,10 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         const int t = lane >> 4;
         uint32_t xw[NW];
         bool ok = false;
-        auto fetch = [&](int l, uint32_t (&w)[NW], bool &okk) { fetch_row(chunk, FIRST ? (in_rows ? in_rows[l] : l) : rowl[l], w, okk); };
+        auto fetch = [&](int l, uint32_t (&w)[NW], bool &okk) {
+            if constexpr (MSC) fetch_halves(unit, rowl[l], w, okk);
+            else fetch_row(chunk, FIRST ? (in_rows ? in_rows[l] : l) : rowl[l], w, okk);
+        };
         terms &= d < 32 ? (1u << d) - 1u : ~0u;
         int l = terms ? __builtin_ctz(terms) : d;
         if constexpr (FIRST) {
@@ -395,31 +459,15 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
             uint32_t w[NW];
             bool over;                  // bit 256 of the representative r < 2p that w holds the low 256 bits of
             if constexpr (MSC) {
-                // ---- on the matrix cores: x / den_l = sum_b x_b U_l[b] over the element's 32 bytes, U_l[b] = 256^b / den_l as 32 balanced digits.
-                // A lane's 16 bytes are its own K-block of the B operand; the A operand is block-diagonal (lane (m, m / 4) holds the digits of
-                // column 4 eb + (m & 3), every other lane zeros), so reg r of the accumulator is column 4 eb + r of the lane's OWN element; the
-                // second half of the bytes is chained on the same accumulator.  The C operand is 2^20 + the bytes of the term's constant
-                // (128 sum_b U_l[b] - the biases, mod p): every column arrives positive and below 2^21, a word is two shifted adds and one
-                // multiply-add, and the quotient is FS_REDUCE's.  tests/fs_mscale_model.py has the bounds.
+                // ---- on the matrix cores (ms_products, ms_words above): two independent 32x32x32 products of the term's digits with the
+                // halves this lane loaded, the words' addends, the half swap -- and the quotient is FS_REDUCE's, with lane = chunk.
                 //
                 // The first unit's tasks are a block of their own, below, where this lambda's `first` call stands for the T_q multiplication.
                 static_assert(!FIRST, "the first unit's matrix-core tasks are the block at the call site");
-                const v4i *tab = msl;
-                const v4i *al = tab + (g == (n >> 2) ? l * 64 + (n & 3) : d * 64);
-                const v4i *cl = tab + (d + 1) * 64 + l * 8;
-                const v4i b0 = v4i{(int)(xw[0] ^ 0x80808080u), (int)(xw[1] ^ 0x80808080u), (int)(xw[2] ^ 0x80808080u), (int)(xw[3] ^ 0x80808080u)};
-                const v4i b1 = v4i{(int)(xw[4] ^ 0x80808080u), (int)(xw[5] ^ 0x80808080u), (int)(xw[6] ^ 0x80808080u), (int)(xw[7] ^ 0x80808080u)};
-                v4i mc[8];
-#pragma unroll
-                for (int eb = 0; eb < 8; eb++) mc[eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[eb * 4], b0, cl[eb], 0, 0, 0);
-#pragma unroll
-                for (int eb = 0; eb < 8; eb++) mc[eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[32 + eb * 4], b1, mc[eb], 0, 0, 0);
+                v16i acc0, acc1;
+                ms_products(l, xw, acc0, acc1);
                 uint64_t mw[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const uint32_t lo = (uint32_t)mc[k][0] + ((uint32_t)mc[k][1] << 8), hi = (uint32_t)mc[k][2] + ((uint32_t)mc[k][3] << 8);
-                    mw[k] = (uint64_t)hi * ms64k + lo;
-                }
+                ms_words(acc0, acc1, mw);
                 const uint64_t tq = mw[7] + (mw[6] >> 32);
                 const uint32_t mq = (uint32_t)(((uint64_t)(uint32_t)(tq >> 16) * bp.mu) >> 46);
 #pragma unroll
@@ -495,36 +543,24 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
         // term).  What the head waits for is the first unit's words from HBM, every workgroup's at once, and vector loads return in order:
         // so the words' loads are the LAST vector loads of the prologue, the operands are LDS reads (the rows this wave copied itself,
         // above), and term j's MFMAs wait for term j's words alone -- its words, quotient and carries then run in one block with the
-        // MFMAs of term j + 1, under the arrival of the later words.  (Operands from the tables in global memory, as before: each task's
-        // sixteen loads queue behind every word load that was issued ahead of them, and the whole block waits for the last word.)
+        // MFMAs of term j + 1, under the arrival of the later words.  (Operands from the tables in global memory: their loads queue
+        // behind every word load that was issued ahead of them, and the whole block waits for the last word.)
         const int t = lane >> 4;
-        const bool diag = g == (n >> 2);
         auto first_block = [&](auto canon_c) __attribute__((always_inline)) {
             constexpr bool CANON = decltype(canon_c)::value;      // p >= 2^255: r < 2p may pass 2^256, made canonical (scale_unit)
-            v4i mc[NKB][8];
+            v16i mc[NKB][2];
 #pragma unroll
             for (int s = 0; s <= NKB; s++) {
                 if (s < NKB) {
-                    // the MFMAs of term s: they wait for ITS words alone (the loads return in order), the operands are LDS reads
+                    // the two products of term s: they wait for ITS words alone (the loads return in order), the operands are LDS reads
                     const int j = s, l = wave + 8 * j, lc = l < d ? l : d - 1;
-                    const v4i *al = msl + (diag ? lc * 64 + (n & 3) : d * 64);
-                    const v4i *cl = msl + (d + 1) * 64 + lc * 8;
-                    const v4i b0 = v4i{(int)(xf[j][0] ^ 0x80808080u), (int)(xf[j][1] ^ 0x80808080u), (int)(xf[j][2] ^ 0x80808080u), (int)(xf[j][3] ^ 0x80808080u)};
-                    const v4i b1 = v4i{(int)(xf[j][4] ^ 0x80808080u), (int)(xf[j][5] ^ 0x80808080u), (int)(xf[j][6] ^ 0x80808080u), (int)(xf[j][7] ^ 0x80808080u)};
-#pragma unroll
-                    for (int eb = 0; eb < 8; eb++) mc[j][eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[eb * 4], b0, cl[eb], 0, 0, 0);
-#pragma unroll
-                    for (int eb = 0; eb < 8; eb++) mc[j][eb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al[32 + eb * 4], b1, mc[j][eb], 0, 0, 0);
+                    ms_products(lc, xf[j], mc[j][0], mc[j][1]);
                 }
                 if (s > 0) {
-                    // the words, the quotient and the carries of term s - 1, in one block with the next term's MFMAs
+                    // the words, the half swap, the quotient and the carries of term s - 1, in one block with the next term's MFMAs
                     const int j = s - 1, l = wave + 8 * j;
                     uint64_t mw[8];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        const uint32_t lo = (uint32_t)mc[j][k][0] + ((uint32_t)mc[j][k][1] << 8), hi = (uint32_t)mc[j][k][2] + ((uint32_t)mc[j][k][3] << 8);
-                        mw[k] = (uint64_t)hi * ms64k + lo;
-                    }
+                    ms_words(mc[j][0], mc[j][1], mw);
                     const uint64_t tq = mw[7] + (mw[6] >> 32);
                     const uint32_t mq = (uint32_t)(((uint64_t)(uint32_t)(tq >> 16) * bp.mu) >> 46);
 #pragma unroll
@@ -940,11 +976,11 @@ __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9>
         }
     }
     if (do_z && ms) {
-        // The division by den on the matrix cores (k_mm8f, MS): per term the A operands [half][column quad][column & 3] x 16 bytes -- byte k
-        // of column c in half h is digit c of U_l[16 h + k], U_l[b] = 256^b / den_l as 32 balanced digits (of U or of U - p: one of the two
-        // fits) -- then a block of zeros (what the lanes off the diagonal read), then per term its 32 accumulator constants
-        // 2^20 + byte c of (0x80..80 / den_l - sum_c 2^(20 + 8 c)) mod p
-        for (int i = tid; i < 64; i += 1024) reinterpret_cast<uint4 *>(ms)[d * 64 + i] = make_uint4(0, 0, 0, 0);
+        // The division by den on the matrix cores (k_mm8f, MS): per term the A operand of the 32x32x32 products, [half][column] x 16 bytes
+        // -- byte k of column c in half h is digit c of U_l[16 h + k], U_l[b] = 256^b / den_l as 32 balanced digits (of U or of U - p: one
+        // of the two fits): piece h * 32 + c is what lane (c, h) reads -- then per term its 32 accumulator constants
+        // 2^20 + byte c of (0x80..80 / den_l - sum_c 2^(20 + 8 c)) mod p, in the accumulators' order [half][register]: register i of a
+        // lane of half h is column (i & 3) + 8 (i >> 2) + 4 h
         for (int e = tid; e < d * 32; e += 1024) {
             const int l = e >> 5, b = e & 31;
             uint32_t w[NL], two[NL], u[NL], uw[NW];
@@ -969,7 +1005,7 @@ __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9>
                     for (int k = 0; k < NW; k++) uw[k] = __builtin_addc(uw[k], cs.pneg[k], cy, &cy);
                 } else if (status) atomicOr(status, FS_OVERFLOW);
             }
-            for (int c = 0; c < 32; c++) ms[(size_t)(((l * 2 + (b >> 4)) * 8 + (c >> 2)) * 4 + (c & 3)) * 16 + (b & 15)] = (uint8_t)dg[c];
+            for (int c = 0; c < 32; c++) ms[(size_t)((l * 2 + (b >> 4)) * 32 + c) * 16 + (b & 15)] = (uint8_t)dg[c];
         }
         for (int l = tid; l < d; l += 1024) {
             uint32_t w[NL], c80[NL], bm[NL], prod[NL], kk[NL], kw[NW];
@@ -978,8 +1014,8 @@ __device__ __forceinline__ void fs_build_body(uint8_t *fb_lds, const FpParams<9>
             mont_mul(prod, w, c80, P);
             fp_sub(kk, prod, bm, P);
             pack<NL, NW>(kw, kk);
-            int32_t *ci = reinterpret_cast<int32_t *>(ms + (size_t)(d + 1) * 1024) + l * 32;
-            for (int c = 0; c < 32; c++) ci[c] = FS_MS_BIAS + (int32_t)((kw[c >> 2] >> (8 * (c & 3))) & 0xffu);
+            int32_t *ci = reinterpret_cast<int32_t *>(ms + (size_t)d * 1024) + l * 32;
+            for (int c = 0; c < 32; c++) ci[16 * ((c >> 2) & 1) + 4 * (c >> 3) + (c & 3)] = FS_MS_BIAS + (int32_t)((kw[c >> 2] >> (8 * (c & 3))) & 0xffu);
         }
     }
 }
@@ -1234,10 +1270,12 @@ static std::atomic<int> g_fs_last_mscale{-1};     // and whether it divided by d
 // where the waves with a packed pass take a term more and those with two full passes (or a full pass and three terms) one less.
 //
 // A term divided on the matrix cores (mscale): 2.4 k ticks against the multiplication's 3.6 k in the same waves of a timing build
-// (profiles/fs_mscale.txt: R2 wave 5, ten tasks, 36.0 k -> 23.7 k), so 24.  The benchmark does not tell 12 .. 36 apart (same file).
+// (profiles/fs_mscale.txt: R2 wave 5, ten tasks, 36.0 k -> 23.7 k), so 24 while a task was sixteen 16x16x64 MFMAs; as two 32x32x32 products
+// the same ten tasks are 26.8 k -> 20.9 k in one session (profiles/fs_mscale32.txt), 2.1 k a task, so 20.  The benchmark does not tell
+// 12 .. 36 apart (both files).
 static FsSplit fs_split(int d, int n_rt, int n_out, int pk_nm, int pk_ns, bool mscale) {
     constexpr int PASS = 95, RAGGED = 70, PACKED2 = 50, PACKED3 = 55;
-    const int TERM = mscale ? 24 : 36;
+    const int TERM = mscale ? 20 : 36;
     const int packed = pk_ns ? PACKED3 : PACKED2;
     FsSplit sp;
     int load[FS_WAVES];
