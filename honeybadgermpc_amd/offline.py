@@ -19,7 +19,10 @@ The protocol that makes preprocessing among the parties (reference offline_rando
 * generate_triples  -- k Beaver triples by degree reduction (:154-191)
 * generate_bits     -- k shared random bits, as +-1 or as 0 / 1 (:194-232)
 * generate_matrix_triples -- matrix triples (P, Q, P Q) for linalg.beaver_matmul: generate_triples with a matrix product in the middle
+* generate_powers   -- shares of b, b^2, .., b^k of random b, by doubling: ceil(log2 k) opens (csrc/hb_offpow.hip; not in the reference)
+* generate_cubes    -- shares of (r, r^2, r^3) for MiMC's rounds: the same chain with k = 3, two opens
 * mul_add, invsqrt_scale, degree_check -- the three kernels on tensors; invsqrt_model, degree_check_model -- on Python ints
+* pow_mask, pow_finish -- the two launches of a doubling level on tensors; power_levels, powers_model -- the levels, and on Python ints
 
 Element layout as in honeybadgermpc_amd.device: int64 tensors (count, 4), little-endian limbs.
 """
@@ -478,3 +481,115 @@ async def generate_bits(co, k, encoding=PM1, tag="bits", generator=None):
     opened = await co.open_share_array(mul_add(ctx, u, u, r_2t[k:2 * k]), degree=2 * co.t)
     squares = await co.open_share_array(sub(ctx, opened, r, out=opened))
     return invsqrt_scale(ctx, squares, u, encoding, check=True)
+
+
+# ---- shared powers and cubes (csrc/hb_offpow.hip; the reference deals both, preprocessing.py) --------------------------------------
+def power_levels(k):
+    """The doubling levels that grow b^1 into b^1 .. b^k: a list of (m, w), w = min(m, k - m).  With powers 1 .. m held, level (m, w)
+    makes b^(m+1+j) = b^m b^(j+1) for j < w.  ceil(log2 k) levels, k - 1 products; k = 1 -> []."""
+    if not (isinstance(k, int) and not isinstance(k, bool) and k >= 1):
+        raise ValueError("power_levels: k >= 1")
+    levels, m = [], 1
+    while m < k:
+        w = min(m, k - m)
+        levels.append((m, w))
+        m += w
+    return levels
+
+
+def powers_model(b, k, p):
+    """[b^1 .. b^k] mod p on Python ints, by the products the levels make"""
+    out = [b % p]
+    for m, w in power_levels(k):
+        out += [out[m - 1] * out[j] % p for j in range(w)]
+    return out
+
+
+_LAYOUTS = ("item", "power")
+
+
+def _pow_operands(ctx, powers, m, w, layout):
+    """-> (count, k, item_stride, power_stride) of a contiguous (count, k, limbs) ("item") or (k, count, limbs) ("power") tensor"""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout: one of {_LAYOUTS}, got {layout!r}")
+    if not isinstance(powers, ctx.torch.Tensor) or powers.dim() != 3:
+        raise ValueError(f"powers: expected a tensor of shape (count, k, {ctx.n_limbs}) or (k, count, {ctx.n_limbs})")
+    if not powers.is_contiguous():
+        raise ValueError("powers: must be contiguous")
+    ctx.elems(powers, what="powers")
+    count, k = (int(powers.shape[0]), int(powers.shape[1])) if layout == "item" else (int(powers.shape[1]), int(powers.shape[0]))
+    for v in (m, w):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise ValueError("m, w: integers")
+    if not (1 <= w <= m and m + w <= k):
+        raise ValueError(f"level ({m}, {w}): 1 <= w <= m and m + w <= k = {k}")
+    return (count, k, k, 1) if layout == "item" else (count, k, 1, count)
+
+
+def pow_mask(ctx, powers, r2t, m, w, layout="item", out=None):
+    """One level's masked products in one launch: out[c w + j] = P[c][m] P[c][j+1] + r2t[c w + j], (count w, limbs), contiguous.
+    powers: (count, k, limbs) for layout "item", (k, count, limbs) for "power"; it is only read."""
+    count, _, item_stride, power_stride = _pow_operands(ctx, powers, m, w, layout)
+    r2t = ctx.elems(r2t, count * w, what="r2t")
+    out = ctx.empty(count * w) if out is None else _out_like(ctx, out, r2t, count * w)
+    rc = ctx.lib.hb_off_pow_mask(ctx.h, ctx.ptr(powers), item_stride, power_stride, ctx.ptr(r2t), m, w, ctx.ptr(out), count, ctx.stream())
+    ctx.check(rc, "hb_off_pow_mask")
+    return out
+
+
+def pow_finish(ctx, opened, rt, powers, m, w, layout="item"):
+    """One level's finish in one launch: P[c][m+1+j] = opened[c w + j] - rt[c w + j], written into `powers` in place (columns m .. m+w-1
+    alone) -> powers."""
+    count, _, item_stride, power_stride = _pow_operands(ctx, powers, m, w, layout)
+    opened, rt = ctx.elems(opened, count * w, what="opened"), ctx.elems(rt, count * w, what="rt")
+    rc = ctx.lib.hb_off_pow_finish(ctx.h, ctx.ptr(opened), ctx.ptr(rt), ctx.ptr(powers), item_stride, power_stride, m, w, count, ctx.stream())
+    ctx.check(rc, "hb_off_pow_finish")
+    return powers
+
+
+def _positive_int(v, what):
+    if not (isinstance(v, int) and not isinstance(v, bool) and v >= 1):
+        raise ValueError(f"{what} >= 1")
+
+
+async def _powers(co, count, k, tag, generator, layout):
+    """the chain of generate_powers over `count` items -> the (count, k, limbs) or (k, count, limbs) tensor"""
+    ctx, good, L = co.ctx, co.n - 2 * co.t, co.ctx.n_limbs
+    r_t, r_2t = await randousha(co, -(-count * k // good), tag=(tag, "randousha"), generator=generator)
+    torch = ctx.torch
+    powers = torch.empty((count, k, L) if layout == "item" else (k, count, L), dtype=torch.int64, device=ctx.tdev)
+    (powers[:, 0] if layout == "item" else powers[0]).copy_(r_t[:count])
+    levels = power_levels(k)
+    masked = ctx.empty(count * max((w for _, w in levels), default=0))       # an open is over before the next level writes here
+    at = count
+    for m, w in levels:
+        size = count * w
+        pow_mask(ctx, powers, r_2t[at:at + size], m, w, layout, out=masked[:size])
+        opened = await co.open_share_array(masked[:size], degree=2 * co.t)
+        pow_finish(ctx, opened, r_t[at:at + size], powers, m, w, layout)
+        at += size
+    return powers
+
+
+async def generate_powers(co, count, k, tag="powers", generator=None, layout="item"):
+    """Shares of b_c, b_c^2, .., b_c^k for `count` random b_c nobody knows: (count, k, limbs) for layout "item" (what
+    power_mixing.power_mix and solver.mix take), (k, count, limbs) for "power".  One randousha(ceil(count k / (n - 2t))) supplies the
+    b (its first count t-sharings) and a mask pair (r_t, r_2t) for each of the count (k - 1) products; the powers grow by doubling
+    (power_levels): a level is one launch that masks b^m b^(j+1) + r_2t for every item and j, ONE coalesced open at degree 2t, and one
+    launch that writes opened - r_t into the powers array in place -- ceil(log2 k) opens in all, none for k = 1.  Aborts are
+    randousha's: anything but 2t successes raises HoneyBadgerMPCError in every party."""
+    _positive_int(count, "generate_powers: count")
+    _positive_int(k, "generate_powers: k")
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout: one of {_LAYOUTS}, got {layout!r}")
+    return await _powers(co, count, k, tag, generator, layout)
+
+
+async def generate_cubes(co, rounds, count, tag="cubes", generator=None):
+    """(r, r2, r3), (rounds, count, limbs) each: shares of random r, r^2, r^3, what progs.mimc.mimc_mpc_batch and mimc_decrypt take.
+    The chain of generate_powers with k = 3 over rounds count items in the power-major layout: two opens, and the three results are
+    views of one (3, rounds count, limbs) buffer -- nothing is transposed."""
+    _positive_int(rounds, "generate_cubes: rounds")
+    _positive_int(count, "generate_cubes: count")
+    powers = await _powers(co, rounds * count, 3, tag, generator, "power")
+    return tuple(powers[e].view(rounds, count, co.ctx.n_limbs) for e in range(3))

@@ -628,6 +628,19 @@ int hb_off_mul_add(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, co
 int hb_off_invsqrt_scale(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *u_dev, int mode, uint64_t *out_dev, int64_t count, int32_t *status_dev,
                          void *stream);
 int hb_off_degree_check(hb_ctx *ctx, const uint64_t *coeffs_dev, int n, int64_t k, int t, int32_t *counters_dev, void *stream);
+/* Shared powers and cubes (hb_offpow.hip; offline.py generate_powers, generate_cubes): the two launches of one doubling level.
+ * powers_dev holds the powers of `count` items: power e (1-based) of item c is element c item_stride + (e - 1) power_stride, strides
+ * in elements and >= 1 -- (k, 1) is item-major, (1, count) power-major.  With powers 1 .. m held, level (m, w), 1 <= w <= m, makes
+ * powers m + 1 .. m + w.  The masked, opened and mask arrays are contiguous, element c w + j for item c and product j < w.
+ * hb_off_pow_mask:   out[c w + j] = P[c][m] P[c][j + 1] + r2t[c w + j]; powers_dev is only read.
+ * hb_off_pow_finish: P[c][m + 1 + j] = opened[c w + j] - rt[c w + j]; nothing else of powers_dev is written.
+ * HB_ERR_BAD_ARG before any launch: a null operand with count w > 0, count < 0, m < 1, w < 1, w > m, a stride below 1, strides under
+ * which two cells of the count x (m + w) block share an element, out_dev over the block or over r2t_dev, opened_dev or rt_dev over
+ * the written columns.  count == 0 returns HB_OK and launches nothing. */
+int hb_off_pow_mask(hb_ctx *ctx, const uint64_t *powers_dev, int64_t item_stride, int64_t power_stride, const uint64_t *r2t_dev, int m, int w,
+                    uint64_t *out_dev, int64_t count, void *stream);
+int hb_off_pow_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *rt_dev, uint64_t *powers_dev, int64_t item_stride, int64_t power_stride,
+                      int m, int w, int64_t count, void *stream);
 
 /* ---- products of share matrices (hb_mat.hip) --------------------------------------------------------------------------------
  * hb_mat_mul: out[b] = A[b] B[b] (op) C[b] for b < batch; A is m x k, B is k x n, C and out are m x n, all row-major packed canonical
@@ -1144,6 +1157,14 @@ int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_OFF_SELFTEST_INVSQRT 1
 #define HB_OFF_SELFTEST_DEGREE_CHECK 2
 int hb_selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, uint64_t *out, int64_t count);
+/* host-side run of the two rows of hb_offpow.hip (no GPU needed) over host memory, with the index arithmetic and the argument checks of
+ * the entry points:
+ *   what = HB_OFF_POWERS_SELFTEST_MASK    as hb_off_pow_mask: r = r2t, out = the masked products; x is not read
+ *          HB_OFF_POWERS_SELFTEST_FINISH  as hb_off_pow_finish: x = opened, r = rt; out is not written */
+#define HB_OFF_POWERS_SELFTEST_MASK 0
+#define HB_OFF_POWERS_SELFTEST_FINISH 1
+int hb_selftest_off_powers(const uint64_t *p_limbs, int n_limbs, int what, uint64_t *powers, int64_t item_stride, int64_t power_stride, const uint64_t *x,
+                           const uint64_t *r, int m, int w, uint64_t *out, int64_t count);
 /* host-side run of the root-finding kernels' bodies (no GPU needed) over host memory, phase by phase as the kernels' workgroups walk
  * them.  For tests only: not a fallback.
  *   what = HB_RF_SELFTEST_NEWTON  operands[0] = sums [k]; params = {k}; out [k + 1] as hb_rf_newton writes coeffs_dev
