@@ -49,6 +49,7 @@ HB_PAIR_OP_FQ12_FROBENIUS, HB_PAIR_OP_FQ12_INV, HB_PAIR_OP_FQ12_FINAL_EXP, HB_PA
 HB_FXP_MOD, HB_FXP_TRUNC, HB_FXP_NEG_TRUNC = 0, 1, 2
 HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
 HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
+HB_SORT_SELFTEST_CMP_MASK, HB_SORT_SELFTEST_SWAP_MASK, HB_SORT_SELFTEST_SWAP_FINISH = 0, 1, 2
 HB_BD_SELFTEST_LEAVES, HB_BD_SELFTEST_PREFIX_MASK, HB_BD_SELFTEST_PREFIX_COMBINE, HB_BD_SELFTEST_SUM_MASK, HB_BD_SELFTEST_SUM_COMBINE = 0, 1, 2, 3, 4
 HB_DIV_SIGN, HB_DIV_NORM, HB_DIV_FIRST, HB_DIV_TRUNC = 0, 1, 2, 3
 HB_DIV_T_RESULT, HB_DIV_T_RECIP, HB_DIV_T_GOLD = 0, 1, 2
@@ -152,6 +153,9 @@ SYMBOLS = {
     "hb_fxp_carry_mask": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_fxp_carry_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_fxp_div2m_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i64, _vp]),
+    "hb_sort_cmp_mask": (_i, [_vp, _vp, _i64, _i64, _i, _i64, _i64, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    "hb_sort_swap_mask": (_i, [_vp, _vp, _i, _i64, _i64, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "hb_sort_swap_finish": (_i, [_vp, _vp, _i, _i64, _i64, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "hb_bd_leaves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
     "hb_bd_prefix_mask": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_bd_prefix_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
@@ -251,6 +255,7 @@ SYMBOLS = {
     "hb_selftest_off_powers": (_i, [_vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _i64]),
     "hb_selftest_rf": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "hb_selftest_mat": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "hb_selftest_sort": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
 }
 # include/hbmpc_hip_debug.h: diagnostics for scratch/ scripts and white-box tests, not part of the drop-in surface
 DEBUG_SYMBOLS = {

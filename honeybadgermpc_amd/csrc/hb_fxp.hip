@@ -44,32 +44,10 @@ using namespace hb;
 
 namespace hb {
 
-// what the finish needs: 2^m (canonical), 2^m and 2^(-m) (Montgomery)
-template <int NL> struct FxpFinishConsts { uint32_t pow2[NL], pow2m[NL], inv2m[NL]; };
-
 // ---------------------------------------------------------------- per-element bodies (host and device)
-// (fxp_horner, fxp_mask_elem, fxp_low_bits, fxp_trunc_pr_elem, fxp_leaf_elem, fxp_node_g_elem and the host helpers fxp_params_ok,
-// fxp_pow2: hb_fxp_elem.hpp, shared with hb_bd.hip and hb_div.hip; FpConst, host_mont, word_bit, diff_elem: hb_rows.hpp)
-
-// mode HB_FXP_MOD: a2 = c2 - r1 + 2^m (1 - carry);  HB_FXP_TRUNC: (x - a2) 2^(-m);  HB_FXP_NEG_TRUNC: (a2 - x) 2^(-m)
-template <int NL, int NW>
-HB_HD void fxp_finish_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r1w)[NW], const uint32_t (&carryw)[NW], int m,
-                           int mode, const FxpFinishConsts<NL> &K, const FpParams<NL> &P) {
-    uint32_t c2w[NW], a[NL], b[NL], t[NL], a2[NL];
-    fxp_low_bits<NW>(c2w, cw, m);
-    unpack<NL, NW>(a, c2w);
-    fp_add<NL>(t, a, K.pow2, P);
-    unpack<NL, NW>(b, r1w);
-    fp_sub<NL>(a, t, b, P);
-    unpack<NL, NW>(b, carryw);
-    mont_mul<NL>(t, K.pow2m, b, P);
-    fp_sub<NL>(a2, a, t, P);
-    if (mode == HB_FXP_MOD) { pack<NL, NW>(o, a2); return; }
-    unpack<NL, NW>(b, xw);
-    if (mode == HB_FXP_TRUNC) fp_sub<NL>(t, b, a2, P); else fp_sub<NL>(t, a2, b, P);
-    mont_mul<NL>(a, K.inv2m, t, P);
-    pack<NL, NW>(o, a);
-}
+// (fxp_horner, fxp_mask_elem, fxp_low_bits, fxp_trunc_pr_elem, fxp_leaf_elem, fxp_node_g_elem, fxp_finish_elem with FxpFinishConsts
+// and the host helpers fxp_params_ok, fxp_pow2, fxp_finish_fill: hb_fxp_elem.hpp, shared with hb_bd.hip, hb_div.hip and hb_sort.hip;
+// FpConst, host_mont, word_bit, diff_elem: hb_rows.hpp)
 
 // ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
 // Where the header allows an output to be an input, a thread reads its element before it writes it.
@@ -201,10 +179,7 @@ template <int NL> static bool fxp_trunc_pr_consts(FxpTruncPrArgs<NL> &A, const F
 }
 template <int NL> static bool fxp_finish_consts(FxpFinishArgs<NL> &A, const FpParams<NL> &P, int m, int mode, const uint64_t *inv2m_host) {
     A.m = m; A.mode = mode;
-    fxp_pow2<NL>(A.K.pow2, m, false, P);
-    fxp_pow2<NL>(A.K.pow2m, m, true, P);
-    for (int q = 0; q < NL; q++) A.K.inv2m[q] = 0;
-    return mode != HB_FXP_MOD ? host_mont<NL, words_of(NL)>(A.K.inv2m, P, inv2m_host) : true;
+    return fxp_finish_fill<NL>(A.K, P, m, mode, inv2m_host);
 }
 
 // nodes planes of a level; root: the level of two planes whose p is not wanted

@@ -1,7 +1,8 @@
 // hb_fxp_elem.hpp -- the per-element bodies of the fixed-point steps, shared by hb_fxp.hip (masks, truncation, and the carry tree of
-// div2m / ltz: only the root is kept), hb_bd.hip (the prefix network of the bit decomposition: every carry is kept) and hb_div.hip
-// (division: the prefix OR and the fused Goldschmidt steps), with the Sklansky wiring the two networks share and the argument checks
-// the files' entry points make, and the leaves' kernel k_leaves.  Host and device: a step's row (hb_rows.hpp) loads, calls these and
+// div2m / ltz: only the root is kept), hb_bd.hip (the prefix network of the bit decomposition: every carry is kept), hb_div.hip
+// (division: the prefix OR and the fused Goldschmidt steps) and hb_sort.hip (the comparison of a compare-exchange: the mask and the
+// finish), with the Sklansky wiring the two networks share and the argument checks the files' entry points make, and the leaves'
+// kernel k_leaves.  Host and device: a step's row (hb_rows.hpp) loads, calls these and
 // stores, and the host self tests run the same rows.
 #pragma once
 #include <cstdint>
@@ -95,6 +96,30 @@ HB_HD void fxp_trunc_pr_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const 
     pack<NL, NW>(o, t);
 }
 
+// what the finish needs: 2^m (canonical), 2^m and 2^(-m) (Montgomery)
+template <int NL> struct FxpFinishConsts { uint32_t pow2[NL], pow2m[NL], inv2m[NL]; };
+
+// mode HB_FXP_MOD: a2 = c2 - r1 + 2^m (1 - carry);  HB_FXP_TRUNC: (x - a2) 2^(-m);  HB_FXP_NEG_TRUNC: (a2 - x) 2^(-m)
+// (hb_fxp.hip's finish; hb_sort.hip's swap mask takes the NEG_TRUNC result, the comparison's bit, without storing it)
+template <int NL, int NW>
+HB_HD void fxp_finish_elem(uint32_t (&o)[NW], const uint32_t (&xw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r1w)[NW], const uint32_t (&carryw)[NW], int m,
+                           int mode, const FxpFinishConsts<NL> &K, const FpParams<NL> &P) {
+    uint32_t c2w[NW], a[NL], b[NL], t[NL], a2[NL];
+    fxp_low_bits<NW>(c2w, cw, m);
+    unpack<NL, NW>(a, c2w);
+    fp_add<NL>(t, a, K.pow2, P);
+    unpack<NL, NW>(b, r1w);
+    fp_sub<NL>(a, t, b, P);
+    unpack<NL, NW>(b, carryw);
+    mont_mul<NL>(t, K.pow2m, b, P);
+    fp_sub<NL>(a2, a, t, P);
+    if (mode == HB_FXP_MOD) { pack<NL, NW>(o, a2); return; }
+    unpack<NL, NW>(b, xw);
+    if (mode == HB_FXP_TRUNC) fp_sub<NL>(t, b, a2, P); else fp_sub<NL>(t, a2, b, P);
+    mont_mul<NL>(a, K.inv2m, t, P);
+    pack<NL, NW>(o, a);
+}
+
 // ---------------------------------------------------------------- the Sklansky wiring of hb_bd.hip and hb_div.hip (host and device)
 // plane of node y of level l, and its partner
 HB_HD int bd_node(int y, int l) { return ((y >> l) << (l + 1)) | (1 << l) | (y & ((1 << l) - 1)); }
@@ -144,6 +169,14 @@ template <int NL> static void fxp_pow2(uint32_t (&r)[NL], int e, bool mont, cons
     if (mont) fp_set<NL>(r, P.one);
     else small_digits<NL>(r, 1);
     for (int i = 0; i < e; i++) { uint32_t t[NL]; fp_add<NL>(t, r, r, P); fp_set<NL>(r, t); }
+}
+// the finish's constants from m; inv2m_host (one canonical element in host memory) is read unless mode is HB_FXP_MOD: false if it is
+// not below the modulus
+template <int NL> static bool fxp_finish_fill(FxpFinishConsts<NL> &K, const FpParams<NL> &P, int m, int mode, const uint64_t *inv2m_host) {
+    fxp_pow2<NL>(K.pow2, m, false, P);
+    fxp_pow2<NL>(K.pow2m, m, true, P);
+    for (int q = 0; q < NL; q++) K.inv2m[q] = 0;
+    return mode != HB_FXP_MOD ? host_mont<NL, words_of(NL)>(K.inv2m, P, inv2m_host) : true;
 }
 
 }  // namespace hb

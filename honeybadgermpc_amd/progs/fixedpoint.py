@@ -50,7 +50,8 @@ Protocol level, coroutines over an OpenCoalescer (every party runs the same coro
                                                         matmul_width(k, inner) = 2 k + ceil(log2(inner)): 2 batches, m n truncation opens
 
 div2m and its kin take 3 + 2 carry_levels(m) launches for any count.  FixedPointArray wraps a share array with +, -, neg(), mul,
-div by a public number, divide by a shared one and reciprocal (progs/fixedpoint_division.py), ltz, lt and open() -> list[float].
+div by a public number, divide by a shared one and reciprocal (progs/fixedpoint_division.py), ltz, lt, sort (progs/sorting.py) and
+open() -> list[float].
 """
 from .._capi import HB_FXP_MOD, HB_FXP_NEG_TRUNC, HB_FXP_TRUNC
 from ..share_arithmetic import add, beaver_multiply_arrays, neg, sub
@@ -553,6 +554,28 @@ class FixedPointArray:
     async def lt(self, x, bits, triples):
         """-> shares of [self < x]"""
         return await lt(self.co, self.shares, self._other(x), bits, triples, self.k, self.kappa)
+
+    async def sort(self, plan, bits, carry_triples, swap_triples, payload=None):
+        """-> (sorted, payload): every one of the plan's `batch` arrays of n values sorted ascending (progs/sorting.py), `payload`,
+        a (plan.width - 1, count, limbs) tensor of columns (None for plan.width == 1), moved with the values.  The values must lie in
+        [-2^(k-2-f), 2^(k-2-f)); equal values come out in the network's order, not the input's.  self and payload are left untouched."""
+        from . import sorting
+
+        if not isinstance(plan, sorting.SortPlan) or (plan.k, plan.kappa) != (self.k, self.kappa):
+            raise ValueError(f"plan: expected a SortPlan with (k, kappa) = ({self.k}, {self.kappa})")
+        L, count = self.ctx.n_limbs, self.shares.numel() // self.ctx.n_limbs
+        if count != plan.batch * plan.n:
+            raise ValueError(f"plan: {plan.batch} arrays of {plan.n} rows, but the array holds {count} values")
+        if (payload is None) != (plan.width == 1):
+            raise ValueError(f"payload: plan.width = {plan.width} takes {plan.width - 1} columns")
+        columns = [self.shares.view(1, count, L)]
+        if payload is not None:
+            payload = self.ctx.elems(payload, what="payload")
+            if payload.dim() != 3 or payload.shape[0] != plan.width - 1 or payload.shape[1] != count:
+                raise ValueError(f"payload: expected shape ({plan.width - 1}, {count}, {L}), got {tuple(payload.shape)}")
+            columns.append(payload)
+        table = await sorting.sort(self.co, self.ctx.torch.cat(columns), plan, bits, carry_triples, swap_triples)
+        return self._like(table[0]), (table[1:] if payload is not None else None)
 
     async def bits(self, m, bits, triples):
         """-> an (m, count, limbs) tensor of shares of the low m bits of int(a * 2**f), least significant first

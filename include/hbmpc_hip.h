@@ -443,6 +443,35 @@ int hb_fxp_carry_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t
 int hb_fxp_div2m_finish(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, const uint64_t *carry_dev, int m,
                         const uint64_t *inv2m_host, int mode, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- oblivious sort of shared values: one layer of compare-exchanges (hb_sort.hip) --------------------------------------------
+ * The three fused steps between the opens of a layer of Batcher's merge exchange (Knuth 5.2.2, Algorithm M).  table_dev holds
+ * `width` columns (1..256) of `batch` arrays of n rows, column-major: element w (batch n) + b n + i is row i of array b in column w;
+ * column 0 is the key.  A layer (a, r, d, cnt) compares, in every array, rows lo(e) and lo(e) + d for e < cnt with
+ * lo(e) = ((e >> a) << (a + 1)) | (e & (2^a - 1)) | r, and leaves the smaller key in row lo(e).  Slot s of the layer is comparator
+ * s % cnt of array s / cnt; every other array has rows of `slots` = batch cnt elements, row-major.  HB_ERR_BAD_ARG unless
+ * 2 <= n <= 2^31, batch >= 1, 0 <= a <= 30, r is 0 or 2^a, d is a positive odd multiple of 2^a (which makes the layer a matching:
+ * no row belongs to two comparators), lo(cnt - 1) + d < n, and batch n <= 2^40.  The comparison is that of hb_fxp_* with m = k - 1: the
+ * difference of two keys is a signed k-bit value.
+ * hb_sort_cmp_mask: d = key[lo] - key[hi] and the mask of hb_fxp_mask over the slot's k + kappa rows of bits_dev:
+ *   masked_dev[s] = d + 2^(k-1) + r1 + 2^(k-1) r2, the array to open, and r1_dev[s] = r1.  k >= 2, kappa >= 0, k + kappa + 1 <= bits(p) - 1.
+ *   masked_dev and r1_dev are arrays of their own.  The table is not written.
+ * hb_sort_swap_mask, after the carry tree's root (hb_fxp_ltl_leaves, hb_fxp_carry_mask / hb_fxp_carry_combine over the opened c):
+ *   u = 1 - [key_lo < key_hi], the HB_FXP_NEG_TRUNC result of hb_fxp_div2m_finish on (d, c, r1, carry) at m = k - 1 mapped to 1 - b and
+ *   not stored; out_dev rows 2w, 2w + 1 = u - p_w, (table[w][lo] - table[w][hi]) - q_w for w < width: the layer's second array to open,
+ *   [2 width][slots].  p_dev, q_dev [width][slots]: the first and second factors of one triple a slot and column.  inv2m_host: ONE
+ *   canonical element in host memory, 2^(-(k-1)) mod p.  Equal keys give u = 1.  out_dev is an array of its own; the table is not written.
+ * hb_sort_swap_finish: opened_dev = that array opened; for every slot and column m = de + dq + ep + pq (hb_ew_beaver), then
+ *   table[w][lo] -= m and table[w][hi] += m IN PLACE (safe: the layer is a matching).  Rows outside the layer's comparators are not
+ *   written.  The table does not overlap the other arrays.
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  cnt == 0 returns HB_OK and launches nothing. */
+int hb_sort_cmp_mask(hb_ctx *ctx, const uint64_t *table_dev, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt,
+                     const uint64_t *bits_dev, int k, int kappa, uint64_t *masked_dev, uint64_t *r1_dev, void *stream);
+int hb_sort_swap_mask(hb_ctx *ctx, const uint64_t *table_dev, int width, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt,
+                      const uint64_t *c_dev, const uint64_t *r1_dev, const uint64_t *carry_dev, const uint64_t *p_dev, const uint64_t *q_dev,
+                      int k, const uint64_t *inv2m_host, uint64_t *out_dev, void *stream);
+int hb_sort_swap_finish(hb_ctx *ctx, uint64_t *table_dev, int width, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt,
+                        const uint64_t *opened_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev, void *stream);
+
 /* ---- bit decomposition of shared values (hb_bd.hip) ------------------------------------------------------------------------
  * Shares of the low m bits of a signed k-bit value (Catrina and de Hoogh's BitDec on the masks above), for arrays of `count` values:
  * after the open of c = x + 2^(k-1) + r1 + 2^m r2 (hb_fxp_mask) they are the bits of c2 + (2^m - 1 - r1) + 1 mod 2^m, c2 = c mod 2^m
@@ -1191,6 +1220,16 @@ int hb_selftest_rf(const uint64_t *p_limbs, int n_limbs, int what, const uint64_
 #define HB_MAT_SELFTEST_AUTO 0x200
 int hb_selftest_mat(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands,
                     const int64_t *params, uint64_t *out);
+/* host-side run of the sorting kernels' rows (no GPU needed) over host memory, slot by slot, with the index arithmetic and the
+ * argument checks of the entry points.  params = {n, batch, width, a, r, d, cnt, k, kappa}; slots = batch cnt:
+ *   what = HB_SORT_SELFTEST_CMP_MASK     operands[0..1] = table (column 0 is read), bits [k + kappa][slots]; outs[0..1] = masked, r1
+ *          HB_SORT_SELFTEST_SWAP_MASK    operands[0..6] = table, c, r1, carry, p [width][slots], q, inv2m (one element); outs[0] [2 width][slots]
+ *          HB_SORT_SELFTEST_SWAP_FINISH  operands[0..3] = opened [2 width][slots], p, q, pq; outs[0] = the table, updated in place */
+#define HB_SORT_SELFTEST_CMP_MASK 0
+#define HB_SORT_SELFTEST_SWAP_MASK 1
+#define HB_SORT_SELFTEST_SWAP_FINISH 2
+int hb_selftest_sort(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                     uint64_t *const *outs);
 
 #ifdef __cplusplus
 }
