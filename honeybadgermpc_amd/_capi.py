@@ -62,6 +62,7 @@ HB_LT_SELFTEST_MASK, HB_LT_SELFTEST_LEAVES, HB_LT_SELFTEST_XOR_MASK, HB_LT_SELFT
 HB_OFF_PM1, HB_OFF_01 = 0, 1
 HB_OFF_SELFTEST_MUL_ADD, HB_OFF_SELFTEST_INVSQRT, HB_OFF_SELFTEST_DEGREE_CHECK = 0, 1, 2
 HB_OFF_POWERS_SELFTEST_MASK, HB_OFF_POWERS_SELFTEST_FINISH = 0, 1
+HB_OFF_SB_SELFTEST_LEAVES, HB_OFF_SB_SELFTEST_FINISH = 0, 1
 HB_MAT_NONE, HB_MAT_ADD, HB_MAT_SUB, HB_MAT_CONSTANTS = 0, 1, 2, 8
 HB_MAT_SELFTEST_SPLIT, HB_MAT_SELFTEST_AUTO = 0x100, 0x200
 HB_RF_MAX_K, HB_RF_SMALL_DEGREE = 1024, 32
@@ -183,6 +184,8 @@ SYMBOLS = {
     "hb_off_degree_check": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp]),
     "hb_off_pow_mask": (_i, [_vp, _vp, _i64, _i64, _vp, _i, _i, _vp, _i64, _vp]),
     "hb_off_pow_finish": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i64, _vp]),
+    "hb_off_sb_leaves": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_off_sb_finish": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _i64, _vp]),
     "hb_mat_mul": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp]),
     "hb_mat_constants": (_i, [_i, _vp]),
     "hb_quick_interp_check": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
@@ -253,6 +256,7 @@ SYMBOLS = {
     "hb_selftest_lt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_off": (_i, [_vp, _i, _i, _vp, _vp, _i64]),
     "hb_selftest_off_powers": (_i, [_vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _i64]),
+    "hb_selftest_off_share_bits": (_i, [_vp, _i, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp, _i64]),
     "hb_selftest_rf": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "hb_selftest_mat": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "hb_selftest_sort": (_i, [_vp, _i, _i, _vp, _vp, _vp]),

@@ -41,6 +41,7 @@
 // (DESIGN.md section 3p has the schedule and the counts.)
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
+#include "hb_lt_elem.hpp"
 #include "hb_rows.hpp"
 
 using namespace hb;
@@ -64,29 +65,7 @@ HB_HD void lt_mask_elem(uint32_t (&o)[NW], const uint32_t (&aw)[NW], const uint3
     pack<NL, NW>(o, u);
 }
 
-// the leaf of the public bit a of c against the share bw of the same bit of r
-template <int NL, int NW>
-HB_HD void lt_leaf_elem(uint32_t (&gw)[NW], uint32_t (&pw)[NW], uint32_t a, const uint32_t (&bw)[NW], int mode, const FpParams<NL> &P) {
-    uint32_t b[NL], k[NL], t[NL], w[NL], g[NL], p[NL];
-    unpack<NL, NW>(b, bw);
-    if (mode == HB_LT_DIRECT) {                        // mode is the same for every lane; the bit a selects
-        small_digits<NL>(k, 1);
-        fp_sub<NL>(t, k, b, P);                        // 1 - r_i
-#pragma unroll
-        for (int q = 0; q < NL; q++) p[q] = a ? b[q] : t[q];
-    } else {
-        small_digits<NL>(k, 2);
-        fp_sub<NL>(t, k, b, P);                        // 2 - r_i
-        small_digits<NL>(k, 1);
-        fp_add<NL>(w, k, b, P);                        // 1 + r_i
-#pragma unroll
-        for (int q = 0; q < NL; q++) p[q] = a ? t[q] : w[q];
-    }
-#pragma unroll
-    for (int q = 0; q < NL; q++) g[q] = a ? 0u : b[q];
-    pack<NL, NW>(gw, g);
-    pack<NL, NW>(pw, p);
-}
+// (the leaf of the public bit of c against the share of the same bit of r, lt_leaf_elem, is hb_lt_elem.hpp's: hb_offsb.hip makes the same leaves)
 
 // u = c_0 xor [r_0]: c_0 ? 1 - r_0 : r_0
 template <int NL, int NW> HB_HD void lt_u_elem(uint32_t (&uw)[NW], const uint32_t (&cw)[NW], const uint32_t (&r0w)[NW], const FpParams<NL> &P) {

@@ -2,9 +2,9 @@
 //   The helpers -- the read-once load, the small element helpers (word_bit, diff_elem, small_digits, FpConst), the host's digits of a
 //   constant (host_digits, host_mont) and the argument checks of the entry points (u32, overlap, RowSpan / outputs_apart, modulus_bits,
 //   HB_ROW_BLOCKS) -- serve all of them: hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_mimc.hip, hb_bf.hip,
-//   hb_off.hip, hb_mat.hip and hb_sort.hip.
+//   hb_off.hip, hb_offsb.hip, hb_mat.hip and hb_sort.hip.
 //   The shape of a step -- the memory policies, k_rows, host_rows, launch_rows -- serves hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip,
-//   hb_eq.hip, hb_jj.hip, hb_offpow.hip and hb_sort.hip: every step of theirs is a row.  hb_mimc.hip (two elements a thread, a specialised key load), hb_bf.hip
+//   hb_eq.hip, hb_jj.hip, hb_offpow.hip, hb_offsb.hip and hb_sort.hip: every step of theirs is a row.  hb_mimc.hip (two elements a thread, a specialised key load), hb_bf.hip
 //   (two indices an element), hb_off.hip and hb_mat.hip (tiles) have kernels of other shapes and use the helpers alone.
 //
 // A step is a ROW: a type with

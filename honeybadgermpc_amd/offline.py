@@ -23,16 +23,23 @@ The protocol that makes preprocessing among the parties (reference offline_rando
 * generate_cubes    -- shares of (r, r^2, r^3) for MiMC's rounds: the same chain with k = 3, two opens
 * mul_add, invsqrt_scale, degree_check -- the three kernels on tensors; invsqrt_model, degree_check_model -- on Python ints
 * pow_mask, pow_finish -- the two launches of a doubling level on tensors; power_levels, powers_model -- the levels, and on Python ints
+* generate_share_bits -- random residues shared together with their bit planes (the reference's get_share_bits, which it deals), by
+                       rejection of bitwise-shared candidates: bits, triples, one carry tree and one open a round (csrc/hb_offsb.hip)
+* generate_less_than_preprocessing -- (r, r_bits, triples, s, s_bits) as share_comparison.less_than takes them, no dealer
+* share_bits_round  -- one round over given bit planes and triples -> (r, r_bits, verdicts)
+* sb_leaves, sb_finish -- the two launches of a round on tensors; share_bits_model, share_bits_candidates -- a candidate on Python ints,
+                       and the number of candidates a round draws
 
 Element layout as in honeybadgermpc_amd.device: int64 tensors (count, 4), little-endian limbs.
 """
 import asyncio
+import collections
 import ctypes
 
 import numpy as np
 
 from . import wire
-from ._capi import HB_OFF_01, HB_OFF_PM1, Context, HbView, np_ptr
+from ._capi import HB_LT_DIRECT, HB_OFF_01, HB_OFF_PM1, Context, HbView, np_ptr
 from .device import BatchOpen
 from .exceptions import HoneyBadgerMPCError
 
@@ -593,3 +600,224 @@ async def generate_cubes(co, rounds, count, tag="cubes", generator=None):
     _positive_int(count, "generate_cubes: count")
     powers = await _powers(co, rounds * count, 3, tag, generator, "power")
     return tuple(powers[e].view(rounds, count, co.ctx.n_limbs) for e in range(3))
+
+
+# ---- share bits: a random residue with its bit planes (csrc/hb_offsb.hip; the reference deals them, preprocessing.py get_share_bits) --
+def share_bits_model(bits, p):
+    """One candidate on Python ints: bits b_0 .. b_{L-1}, least significant first, L = bit_length(p) -> (r, accepted) with
+    r = sum_i 2^i b_i, an integer below 2^L, and accepted = r < p.  A kept r is uniform in [0, p) when the bits are uniform."""
+    L = p.bit_length()
+    bits = list(bits)
+    if len(bits) != L or any(b not in (0, 1) or isinstance(b, bool) for b in bits):
+        raise ValueError(f"bits: expected {L} values 0 or 1")
+    r = sum(b << i for i, b in enumerate(bits))
+    return r, r < p
+
+
+def share_bits_candidates(p, count):
+    """The number m of candidates one round draws for `count` residues.  With a = p / 2^L the number kept among m candidates is
+    binomial, of mean m a and variance m a (1 - a); m is the smallest number whose mean lies four standard deviations above the
+    count: m a - 4 sqrt(m a (1 - a)) > count - 1.  The number kept is an integer, so a lower bound above count - 1 is a lower bound
+    of count -- with ">= count" instead, a field like 2^64 - 59, where a candidate is rejected with probability 2^-58, would ask for
+    one spare candidate whatever the count.  Evaluated on integers (X = m p - (count - 1) 2^L > 0 and X^2 > 16 m p (2^L - p)), so
+    every party gets the same m.  A round that keeps fewer is followed by another: m decides cost, never correctness."""
+    if not (isinstance(p, int) and not isinstance(p, bool) and p >= 3):
+        raise ValueError("share_bits_candidates: p >= 3")
+    if not (isinstance(count, int) and not isinstance(count, bool) and count >= 0):
+        raise ValueError("share_bits_candidates: count >= 0")
+    if count == 0:
+        return 0
+    N = 1 << p.bit_length()
+
+    def enough(m):
+        x = m * p - (count - 1) * N
+        return x > 0 and x * x > 16 * m * p * (N - p)
+
+    lo, hi = count - 1, count                     # enough(lo) is false: m a < m; the left side grows with m once it is positive
+    while not enough(hi):
+        lo, hi = hi, 2 * hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if enough(mid) else (mid, hi)
+    return hi
+
+
+def _sb_planes(ctx, bits):
+    """the candidates' bit planes: a contiguous (L, m, limbs) tensor -> (bits, L, m)"""
+    L = ctx.modulus.bit_length()
+    if not isinstance(bits, ctx.torch.Tensor) or bits.dim() != 3 or bits.shape[0] != L:
+        raise ValueError(f"bits: expected a tensor of shape ({L}, count, {ctx.n_limbs})")
+    if not bits.is_contiguous():
+        raise ValueError("bits: must be contiguous")
+    return ctx.elems(bits, what="bits"), L, int(bits.shape[1])
+
+
+def sb_leaves(ctx, bits, bound=None):
+    """-> (g, p), (L, count, limbs) each: the leaves of the carry tree for [r > bound] over candidates given as bit planes
+    (L, count, limbs), least significant first; the leaves are ordered most significant bit first.  bound: a public integer below
+    2^L, None for p - 1 (the root is then [r >= p]).  One launch, no triple, no open, and no array of the bound."""
+    bits, L, count = _sb_planes(ctx, bits)
+    if bound is None:
+        host = None
+    else:
+        if not (isinstance(bound, int) and not isinstance(bound, bool) and 0 <= bound < 1 << L):
+            raise ValueError(f"bound: an integer in [0, 2^{L})")
+        host = np.array([(bound >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(ctx.n_limbs)], dtype=np.uint64)
+    g, p = ctx.torch.empty_like(bits), ctx.torch.empty_like(bits)
+    rc = ctx.lib.hb_off_sb_leaves(ctx.h, ctx.ptr(bits), L, None if host is None else host.ctypes.data, ctx.ptr(g), ctx.ptr(p), count, ctx.stream())
+    ctx.check(rc, "hb_off_sb_leaves")
+    return g, p
+
+
+def sb_finish(ctx, bits, index, check=True):
+    """-> (r, r_bits), (len(index), limbs) and (L, len(index), limbs): slot j holds the planes of candidate index[j] and the residue
+    r = sum_q 2^q b_q they compose, in one launch and one pass over the planes.  index: a contiguous int64 device tensor (k,), every
+    entry in [0, count); anything else raises ValueError before any launch (the range check reads two words back: one
+    synchronisation; check=False leaves it out for an index that torch.nonzero made)."""
+    bits, L, count = _sb_planes(ctx, bits)
+    t = ctx.torch
+    if not isinstance(index, t.Tensor) or index.dtype != t.int64 or index.dim() != 1 or not index.is_cuda or index.device.index != ctx.device:
+        raise ValueError(f"index: expected an int64 tensor of shape (k,) on cuda:{ctx.device}")
+    if not index.is_contiguous():
+        raise ValueError("index: must be contiguous")
+    k = int(index.shape[0])
+    if check and k and (int(index.min()) < 0 or int(index.max()) >= count):
+        raise ValueError(f"index: every entry must lie in [0, {count})")
+    r = ctx.empty(k)
+    r_bits = t.empty((L, k, ctx.n_limbs), dtype=t.int64, device=ctx.tdev)
+    rc = ctx.lib.hb_off_sb_finish(ctx.h, ctx.ptr(bits), L, count, ctx.ptr(index), ctx.ptr(r), ctx.ptr(r_bits), k, ctx.stream())
+    ctx.check(rc, "hb_off_sb_finish")
+    return r, r_bits
+
+
+async def share_bits_round(co, bits, triples):
+    """One round of rejection over given candidates: bits (L, m, limbs), this party's shares of m L random bits, least significant
+    first, and triples = (p, q, pq), each (2 L - 3, m, limbs).  The leaves of [r > p - 1] (sb_leaves: affine, the bound is public),
+    progs.fixedpoint.carry_tree over them -- carry_levels(L - 1) opens, carry_triples(L - 1) = 2 L - 3 rows of triples -- and ONE open
+    of the root, the verdict w = [r >= p]: it tells of a discarded candidate that it was discarded, nothing else.  Every party sees
+    the same verdicts, so torch.nonzero gives every party the same kept candidates in the same order, and sb_finish gathers their
+    planes and composes r.  -> (r, r_bits, verdicts): (kept, limbs), (L, kept, limbs) and the public bool tensor [r_i < p], (m,).
+    An opened verdict that is neither 0 nor 1 (a plane that was no bit) raises HoneyBadgerMPCError on every party.  m = 0 returns
+    empty tensors without a launch.  The inputs are left untouched."""
+    from .progs.fixedpoint import carry_tree
+
+    ctx = co.ctx
+    bits, L, m = _sb_planes(ctx, bits)
+    t = ctx.torch
+    if m == 0:
+        return ctx.empty(0), t.empty((L, 0, ctx.n_limbs), dtype=t.int64, device=ctx.tdev), t.empty((0,), dtype=t.bool, device=ctx.tdev)
+    g, p = sb_leaves(ctx, bits)
+    root = await carry_tree(co, g, p, triples)
+    w = await co.open_share_array(root)
+    high_zero = (w[:, 1:] == 0).all(dim=1)
+    verdicts = high_zero & (w[:, 0] == 0)
+    rejected = high_zero & (w[:, 0] == 1)
+    if not bool((verdicts | rejected).all()):
+        raise HoneyBadgerMPCError("share bits: an opened verdict is neither 0 nor 1 (a bit plane did not hold a bit)")
+    index = t.nonzero(verdicts).view(-1)
+    r, r_bits = sb_finish(ctx, bits, index, check=False)
+    return r, r_bits, verdicts
+
+
+def _branch(co, name):
+    """A coalescer of its own for one of several coroutines that run concurrently: OpenCoalescer numbers its batches in the order they
+    are cut, and between concurrent coroutines that order depends on when messages arrive, which differs from party to party.  A
+    branch has its own channels ((name, tag) on the parent's network) and its own numbering, in its own program order."""
+    from .open_coalescer import OpenCoalescer
+
+    parent = co.get_send_recv
+    return OpenCoalescer(co.ctx.modulus, co.n, co.t, co.myid, lambda tag: parent((name, tag)), use_omega_powers=getattr(co, "use_omega_powers", False),
+                         device=co.ctx.device)
+
+
+async def _branches(co, tag, named):
+    """named: [(name, f)] with f(branch) a coroutine -> the results, run concurrently, each on its own branch of co.  The first
+    branch that raises ends the others: an abort of one randousha is an abort of the call, and nothing is left running."""
+    kids = [_branch(co, (tag, name)) for name, _ in named]
+    tasks = [asyncio.ensure_future(f(kid)) for kid, (_, f) in zip(kids, named)]
+    try:
+        return await asyncio.gather(*tasks)
+    finally:
+        for task in tasks:
+            if not task.done():
+                task.cancel()
+        for kid in kids:                           # the parent's diagnostics count what ran on its behalf
+            co.opens, co.batches = co.opens + kid.opens, co.batches + kid.batches
+
+
+async def generate_share_bits(co, count, tag="share_bits", generator=None, chunk=1 << 14, bit_source=None, triple_source=None):
+    """count random residues nobody knows, each shared together with its bit planes: (r, r_bits), (count, limbs) and (L, count, limbs),
+    least significant first -- what share_comparison.less_than takes as r, r_bits (and s, s_bits), made among the parties.  Rejection
+    sampling of a bitwise-shared value (share_bits_round): a round draws m = min(chunk, share_bits_candidates(p, still missing))
+    candidates -- L m shared bits from bit_source(co, k, tag) (default generate_bits, ZERO_ONE) and (2 L - 3) m triples from
+    triple_source(co, k, tag) (default generate_triples; its three (k, limbs) results are viewed as rows), the two running
+    concurrently, each on a branch of co with its own channels and batch numbering -- keeps the candidates below p, and rounds repeat
+    under the tags (tag, 0), (tag, 1), .. until there are enough; the surplus is dropped.  Over BLS12-381 (p / 2^255 = 0.9057) a kept
+    residue costs about 282 bits and 560 triples; a round of any size is the two opens of generate_bits, the open of
+    generate_triples, carry_levels(L - 1) tree levels and the verdicts' open.  Aborts are randousha's: anything but 2t successes
+    raises HoneyBadgerMPCError in every party."""
+    _positive_int(count, "generate_share_bits: count")
+    _positive_int(chunk, "generate_share_bits: chunk")
+    ctx = co.ctx
+    p, L, nl = ctx.modulus, ctx.modulus.bit_length(), ctx.n_limbs
+    if bit_source is None:
+        def bit_source(co, k, tag):
+            return generate_bits(co, k, encoding=ZERO_ONE, tag=tag, generator=generator)
+    if triple_source is None:
+        def triple_source(co, k, tag):
+            return generate_triples(co, k, tag=tag, generator=generator)
+    rows = 2 * L - 3
+    kept_r, kept_bits, missing, rnd = [], [], count, 0
+    while missing > 0:
+        m = min(chunk, share_bits_candidates(p, missing))
+        rtag = (tag, rnd)
+        bits, trip = await _branches(co, rtag, [("bits", lambda kid: bit_source(kid, L * m, (rtag, "bits"))),
+                                                ("triples", lambda kid: triple_source(kid, rows * m, (rtag, "triples")))])
+        bits = ctx.elems(bits, L * m, what="bit_source's result").view(L, m, nl)
+        try:
+            tp, tq, tpq = trip
+        except (TypeError, ValueError):
+            raise ValueError("triple_source: expected (p, q, pq)") from None
+        trip = tuple(ctx.elems(v, rows * m, what="triple_source's result").view(rows, m, nl) for v in (tp, tq, tpq))
+        r, r_bits, _ = await share_bits_round(co, bits, trip)
+        take = min(missing, int(r.shape[0]))
+        kept_r.append(r[:take])
+        kept_bits.append(r_bits[:, :take])
+        missing -= take
+        rnd += 1
+    if len(kept_r) == 1 and kept_bits[0].is_contiguous():                     # one round that kept exactly count: nothing is copied
+        return kept_r[0], kept_bits[0]
+    return ctx.torch.cat(kept_r, dim=0).contiguous(), ctx.torch.cat(kept_bits, dim=1).contiguous()
+
+
+LessThanPreprocessing = collections.namedtuple("LessThanPreprocessing", "r r_bits triples s s_bits")
+
+
+async def generate_less_than_preprocessing(co, count, mode=HB_LT_DIRECT, tag="less_than_preprocessing", generator=None, chunk=1 << 14, bit_source=None,
+                                           triple_source=None):
+    """Everything share_comparison.less_than(co, a, b, r, r_bits, triples, s, s_bits, mode) consumes for `count` pairs, laid out as it
+    takes it: r (count, limbs) and r_bits (L, count, limbs) from generate_share_bits; triples = (p, q, pq), each
+    (less_than_triples(L, mode), count, limbs); s, s_bits a second pair in mode REFERENCE, None in DIRECT.  The generators run
+    concurrently, each on a branch of co."""
+    from .share_comparison import REFERENCE, _check_lt_mode, less_than_triples
+
+    _check_lt_mode(mode)
+    _positive_int(count, "generate_less_than_preprocessing: count")
+    ctx = co.ctx
+    L, nl = ctx.modulus.bit_length(), ctx.n_limbs
+    rows = less_than_triples(L, mode)
+    if triple_source is None:
+        def triple_source(co, k, tag):
+            return generate_triples(co, k, tag=tag, generator=generator)
+
+    def share_bits(name):
+        return lambda kid: generate_share_bits(kid, count, tag=(tag, name), generator=generator, chunk=chunk, bit_source=bit_source, triple_source=triple_source)
+
+    named = [("r", share_bits("r")), ("triples", lambda kid: triple_source(kid, rows * count, (tag, "triples")))]
+    if mode == REFERENCE:
+        named.append(("s", share_bits("s")))
+    got = await _branches(co, tag, named)
+    (r, r_bits), trip = got[0], got[1]
+    trip = tuple(ctx.elems(v, rows * count, what="triple_source's result").view(rows, count, nl) for v in trip)
+    s, s_bits = got[2] if mode == REFERENCE else (None, None)
+    return LessThanPreprocessing(r, r_bits, trip, s, s_bits)

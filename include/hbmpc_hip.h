@@ -670,6 +670,23 @@ int hb_off_pow_mask(hb_ctx *ctx, const uint64_t *powers_dev, int64_t item_stride
                     uint64_t *out_dev, int64_t count, void *stream);
 int hb_off_pow_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *rt_dev, uint64_t *powers_dev, int64_t item_stride, int64_t power_stride,
                       int m, int w, int64_t count, void *stream);
+/* Share bits (hb_offsb.hip; offline.py share_bits_round, generate_share_bits): a random residue shared with its bit planes, by rejection
+ * of bitwise-shared candidates.  L is the bit length of the modulus; bits_dev holds planes [L][candidates], row i this party's shares
+ * of bit i (least significant first) of every candidate r = sum_i 2^i b_i < 2^L.
+ * hb_off_sb_leaves: g_dev, p_dev [L][count], row y for bit i = L - 1 - y of a PUBLIC bound against row i of bits_dev (count candidates),
+ *   the HB_LT_DIRECT leaves of hb_lt_leaves: bound bit 0: (b, 1 - b); 1: (0, b).  The root's g of the carry tree over them is
+ *   [r > bound].  bound_limbs: n_limbs limbs in HOST memory, below 2^L; NULL: p - 1, so that the root is [r >= p].  No array of the
+ *   bound is read or made.
+ * hb_off_sb_finish: for every output slot j < count with c = index_dev[j] (int64, device): r_bits_dev[q][j] = bits_dev[q][c] for every
+ *   plane q, and r_dev[j] = sum_q 2^q bits_dev[q][c] mod p, in one pass over the planes.  An index outside [0, candidates) is never
+ *   used as an address: that slot gets zeros in r_dev and in every plane.  Indices may repeat and come in any order.
+ * One launch each, asynchronous on `stream`, no allocation.  HB_ERR_BAD_ARG before any launch: a null operand where there is work,
+ * a negative count or candidates, L not the bit length of the modulus, a bound of 2^L or more, an output over an input or over the
+ * other output.  count == 0 returns HB_OK and launches nothing. */
+int hb_off_sb_leaves(hb_ctx *ctx, const uint64_t *bits_dev, int L, const uint64_t *bound_limbs, uint64_t *g_dev, uint64_t *p_dev, int64_t count,
+                     void *stream);
+int hb_off_sb_finish(hb_ctx *ctx, const uint64_t *bits_dev, int L, int64_t candidates, const int64_t *index_dev, uint64_t *r_dev, uint64_t *r_bits_dev,
+                     int64_t count, void *stream);
 
 /* ---- products of share matrices (hb_mat.hip) --------------------------------------------------------------------------------
  * hb_mat_mul: out[b] = A[b] B[b] (op) C[b] for b < batch; A is m x k, B is k x n, C and out are m x n, all row-major packed canonical
@@ -1194,6 +1211,16 @@ int hb_selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 #define HB_OFF_POWERS_SELFTEST_FINISH 1
 int hb_selftest_off_powers(const uint64_t *p_limbs, int n_limbs, int what, uint64_t *powers, int64_t item_stride, int64_t power_stride, const uint64_t *x,
                            const uint64_t *r, int m, int w, uint64_t *out, int64_t count);
+/* host-side run of the two rows of hb_offsb.hip (no GPU needed) over host memory, with the index arithmetic and the argument checks of
+ * the entry points:
+ *   what = HB_OFF_SB_SELFTEST_LEAVES  as hb_off_sb_leaves: bits [L][count], bound_limbs (or NULL: p - 1); out0, out1 = g, p [L][count];
+ *                                     candidates and index are not read
+ *          HB_OFF_SB_SELFTEST_FINISH  as hb_off_sb_finish: bits [L][candidates], index [count]; out0 = r [count], out1 = r_bits [L][count];
+ *                                     bound_limbs is not read */
+#define HB_OFF_SB_SELFTEST_LEAVES 0
+#define HB_OFF_SB_SELFTEST_FINISH 1
+int hb_selftest_off_share_bits(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *bits, int L, const uint64_t *bound_limbs, int64_t candidates,
+                               const int64_t *index, uint64_t *out0, uint64_t *out1, int64_t count);
 /* host-side run of the root-finding kernels' bodies (no GPU needed) over host memory, phase by phase as the kernels' workgroups walk
  * them.  For tests only: not a fallback.
  *   what = HB_RF_SELFTEST_NEWTON  operands[0] = sums [k]; params = {k}; out [k + 1] as hb_rf_newton writes coeffs_dev
