@@ -7,25 +7,26 @@
 // (blocks of s inputs go alternately to the x side and the y side), a shared sign b_j in {1, -1} and one Beaver triple:
 //     m = b_j (x - y),   out[2j] = (x + y + m) / 2,   out[2j + 1] = (x + y - m) / 2        (interleaved, not in place).
 // The multiplication opens b_j - p_j and (x - y) - q_j, so a layer is two local passes around one open:
-//   k_bf_mask    gather + both masked differences, written to ONE buffer [b - p (k/2) | (x - y) - q (k/2)] -- the layer's open
+//   BfMaskRow    gather + both masked differences, written to ONE buffer [b - p (k/2) | (x - y) - q (k/2)] -- the layer's open
 //                is one array; with the signs' half opened in advance (bits == nullptr) only the second half (k/2 elements)
-//   k_bf_switch  gather again + the Beaver step (ew_beaver_elem, the body of k_ew_beaver) + both sums halved + the interleave
+//   BfSwitchRow  gather again + the Beaver step (ew_beaver_elem, the body of EwBeaverRow) + both sums halved + the interleave
 // 16 element reads and writes a switch (mask 5 + 2, switch 7 + 2) against 36 for the same layer composed from hb_ew_op /
 // hb_ew_beaver launches and gathers.
 //
 // Halving needs no product: v / 2 = (v + (v odd ? p : 0)) >> 1, taken on the digits, where v + p < 2p has headroom (nine
 // 29-bit digits hold 261 bits, three hold 87) -- bf_halve.
 //
-// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions: the __global__ wrappers
-// only compute the two indices, load, call them and store, and hb_selftest_bf runs the very same functions on the host.
+// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions; both steps are rows
+// (hb_rows.hpp): the two indices, the loads, the body and the stores are an HB_HD function over a memory policy, so hb_selftest_bf
+// runs on the host the very rows, arithmetic and addressing, that k_rows runs on the device.
 //
-// Launch shape (both kernels): 256-thread workgroups, one switch a thread, grid = ceil(k / 2 / 256), no LDS, no grid stride,
-// one launch a call.  The index arithmetic is shifts and masks on the kernel argument `a`.  8-byte elements at stride 1
-// (a == 0): x and y are neighbours and one 16-byte load serves both -- an instantiation of its own (ADJ), picked by the host
-// when the stride is 1 and `in` is 16-byte aligned: as a wave-uniform branch inside one kernel the compiler if-converted it
+// Launch shape (both steps): k_rows -- 256-thread workgroups, one switch a thread, grid = ceil(k / 2 / 256), no LDS, no grid stride,
+// one launch a call.  The index arithmetic is shifts and masks on the argument `a`.  8-byte elements at stride 1
+// (a == 0): x and y are neighbours and one 16-byte load serves both (the policy's pair) -- a row of its own (ADJ), picked by the
+// host when the stride is 1 and `in` is 16-byte aligned: as a wave-uniform branch inside one kernel the compiler if-converted it
 // back into 8- and 4-byte loads.  The two outputs of a switch are always neighbours: the compiler merges their two 8-byte
 // stores into one dwordx4 by itself (32-byte elements: two dwordx4 each).  The triple, the sign and the opened values are read once and take
-// the non-temporal loads in the 32-byte width, as in k_ew_beaver; `in` is read by both kernels of a layer and loaded plainly.
+// the non-temporal loads in the 32-byte width, as in EwBeaverRow; `in` is read by both kernels of a layer and loaded plainly.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DESIGN.md section 3j.
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
@@ -90,95 +91,79 @@ HB_HD void bf_switch_elem(uint32_t (&o0)[NW], uint32_t (&o1)[NW], const uint32_t
     pack<NL, NW>(o1, r);
 }
 
-// ---------------------------------------------------------------- kernels
-// the two inputs of switch j.  ADJ (8-byte elements, a == 0, `in` 16-byte aligned): they sit side by side, one dwordx4.
-template <int NW, bool ADJ>
-__device__ __forceinline__ void bf_load_pair(uint32_t (&x)[NW], uint32_t (&y)[NW], const uint32_t *__restrict__ in, int64_t j, int a) {
+// ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
+// Element j of a row is switch j, `count` = k / 2.  The two inputs of switch j; ADJ (stride 1): the neighbours 2j and 2j + 1, mem.pair's.
+template <bool ADJ, int NW, class Mem> HB_HD void bf_inputs(uint32_t (&x)[NW], uint32_t (&y)[NW], const uint32_t *in, int64_t j, int a, const Mem &mem) {
     if constexpr (ADJ) {
-        static_assert(NW == 2, "two 8-byte elements in one 16-byte access");
-        const uint4 v = *reinterpret_cast<const uint4 *>(in + 4 * j);
-        x[0] = v.x; x[1] = v.y; y[0] = v.z; y[1] = v.w;
+        mem.pair(x, y, in, 2 * j);
     } else {
         const int64_t xi = bf_xi(j, a);
-        load_words<NW>(x, in + xi * NW);
-        load_words<NW>(y, in + (xi | ((int64_t)1 << a)) * NW);
+        mem.load(x, in, xi);
+        mem.load(y, in, xi | ((int64_t)1 << a));
     }
 }
-// out[2j], out[2j + 1]: 2 NW adjacent words
-template <int NW> __device__ __forceinline__ void bf_store_pair(uint32_t *__restrict__ out, int64_t j, const uint32_t (&o0)[NW], const uint32_t (&o1)[NW]) {
-    uint32_t *dst = out + 2 * j * NW;
-    store_words<NW>(dst, o0);
-    store_words<NW>(dst + NW, o1);
-}
-static bool bf_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-// read-once operands (the triple, the sign, the opened values)
 
 // masked[(BITS ? half : 0) + j] = in[xi] - in[yi] - q[j];  BITS: masked[j] = bits[j] - p[j].  `masked` does not overlap `in`.
-template <int NL, int NW, bool BITS, bool ADJ>
-__global__ void __launch_bounds__(256) k_bf_mask(const FpParams<NL> P, const uint32_t *in, const uint32_t *bits, const uint32_t *p, const uint32_t *q,
-                                                 int64_t half, int a, uint32_t *masked) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= half) return;
-    uint32_t xw[NW], yw[NW], qw[NW], ow[NW];
-    bf_load_pair<NW, ADJ>(xw, yw, in, j, a);
-    load_once<NW>(qw, q + j * NW);
-    if constexpr (BITS) {
-        uint32_t bw[NW], pw[NW], mw[NW];
-        load_once<NW>(bw, bits + j * NW);
-        load_once<NW>(pw, p + j * NW);
-        bf_mask_bit<NL, NW>(mw, bw, pw, P);
-        store_words<NW>(masked + j * NW, mw);
+struct BfMaskArgs { const uint32_t *in, *bits, *p, *q; uint32_t *masked; int a; };
+
+template <bool BITS, bool ADJ> struct BfMaskRow {
+    template <int NL, int NW, class Mem> HB_HD static void run(const BfMaskArgs &A, int, int64_t j, int64_t half, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t xw[NW], yw[NW], qw[NW], ow[NW];
+        bf_inputs<ADJ>(xw, yw, A.in, j, A.a, mem);
+        mem.once(qw, A.q, j);
+        if constexpr (BITS) {
+            uint32_t bw[NW], pw[NW], mw[NW];
+            mem.once(bw, A.bits, j);
+            mem.once(pw, A.p, j);
+            bf_mask_bit<NL, NW>(mw, bw, pw, P);
+            mem.store(A.masked, j, mw);
+        }
+        bf_mask_diff<NL, NW>(ow, xw, yw, qw, P);
+        mem.store(A.masked, (BITS ? half : 0) + j, ow);
     }
-    bf_mask_diff<NL, NW>(ow, xw, yw, qw, P);
-    store_words<NW>(masked + ((BITS ? half : 0) + j) * NW, ow);
-}
+};
 
 // out[2j], out[2j + 1] from in[xi], in[yi], the opened d[j], e[j] and the triple.  `out` does not overlap `in`: switch j writes
 // positions other switches read.
-template <int NL, int NW, bool ADJ>
-__global__ void __launch_bounds__(256) k_bf_switch(const FpParams<NL> P, const uint32_t *in, const uint32_t *d, const uint32_t *e, const uint32_t *p,
-                                                   const uint32_t *q, const uint32_t *pq, int64_t half, int a, uint32_t *out) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= half) return;
-    uint32_t xw[NW], yw[NW], dw[NW], ew[NW], pw[NW], qw[NW], pqw[NW], o0[NW], o1[NW];
-    bf_load_pair<NW, ADJ>(xw, yw, in, j, a);
-    load_once<NW>(dw, d + j * NW); load_once<NW>(ew, e + j * NW); load_once<NW>(qw, q + j * NW);
-    load_once<NW>(pw, p + j * NW); load_once<NW>(pqw, pq + j * NW);
-    bf_switch_elem<NL, NW>(o0, o1, xw, yw, dw, ew, pw, qw, pqw, P);
-    bf_store_pair<NW>(out, j, o0, o1);
-}
+struct BfSwitchArgs { const uint32_t *in, *d, *e, *p, *q, *pq; uint32_t *out; int a; };
+
+template <bool ADJ> struct BfSwitchRow {
+    template <int NL, int NW, class Mem> HB_HD static void run(const BfSwitchArgs &A, int, int64_t j, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t xw[NW], yw[NW], dw[NW], ew[NW], pw[NW], qw[NW], pqw[NW], o0[NW], o1[NW];
+        bf_inputs<ADJ>(xw, yw, A.in, j, A.a, mem);
+        mem.once(dw, A.d, j); mem.once(ew, A.e, j); mem.once(qw, A.q, j);
+        mem.once(pw, A.p, j); mem.once(pqw, A.pq, j);
+        bf_switch_elem<NL, NW>(o0, o1, xw, yw, dw, ew, pw, qw, pqw, P);
+        mem.store(A.out, 2 * j, o0);
+        mem.store(A.out, 2 * j + 1, o1);
+    }
+};
 
 // k a power of two >= 2 and 0 <= a < log2(k)
 static bool bf_shape_ok(int64_t k, int a) { return k >= 2 && (k & (k - 1)) == 0 && a >= 0 && a < 62 && ((int64_t)1 << a) < k; }
 
-template <int NL, int NW, bool BITS>
-static void launch_mask(const FpParams<NL> &P, const uint32_t *in, const uint32_t *b, const uint32_t *p, const uint32_t *q, int64_t half, int a, uint32_t *o,
-                        unsigned blocks, hipStream_t s) {
-    if constexpr (NW == 2) {
-        if (a == 0 && bf_aligned16(in)) { k_bf_mask<NL, NW, BITS, true><<<blocks, 256, 0, s>>>(P, in, b, p, q, half, a, o); return; }
+// AdjRow exactly when the elements are 8 bytes, the stride is 1 and `in` is 16-byte aligned (the narrow width alone has that row), else Row
+template <class AdjRow, class Row, class Args> static int bf_launch(hb_ctx *ctx, const Args &A, unsigned blocks, hipStream_t s, int64_t half) {
+    if (ctx->n_limbs != 4 && A.a == 0 && ((uintptr_t)A.in & 15) == 0) {
+        k_rows<AdjRow, 3, 2><<<blocks, 256, 0, s>>>(ctx->pn, A, half);
+        HB_LAUNCH_CHECK(ctx);
+        return HB_OK;
     }
-    k_bf_mask<NL, NW, BITS, false><<<blocks, 256, 0, s>>>(P, in, b, p, q, half, a, o);
-}
-template <int NL, int NW>
-static void launch_switch(const FpParams<NL> &P, const uint32_t *in, const uint32_t *d, const uint32_t *e, const uint32_t *p, const uint32_t *q, const uint32_t *pq,
-                          int64_t half, int a, uint32_t *o, unsigned blocks, hipStream_t s) {
-    if constexpr (NW == 2) {
-        if (a == 0 && bf_aligned16(in)) { k_bf_switch<NL, NW, true><<<blocks, 256, 0, s>>>(P, in, d, e, p, q, pq, half, a, o); return; }
-    }
-    k_bf_switch<NL, NW, false><<<blocks, 256, 0, s>>>(P, in, d, e, p, q, pq, half, a, o);
+    return launch_rows<Row>(ctx, A, blocks, s, half);
 }
 
-// host: the same element functions, switch by switch
+// host: the same rows, switch by switch.  MASK and SWITCH run the general row (two loads at bf_xi); at stride 1 in the 8-byte width
+// the ADJ row then runs too and writes the same outputs over them, so the host walks mem.pair as well.
 template <int NL, int NW>
 static int selftest_bf(const uint64_t *p_limbs, int what, const uint64_t *const *ops, int64_t k, int a, uint64_t *out) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    uint32_t *o = reinterpret_cast<uint32_t *>(out);
+    uint32_t *o = u32(out);
     if (what == HB_BF_SELFTEST_HALVE) {
         for (int64_t i = 0; i < k; i++) {
             uint32_t v[NL], r[NL], w[NW];
-            unpack<NL, NW>(v, W(ops[0], i));
+            memcpy(w, u32(ops[0]) + i * NW, NW * 4);
+            unpack<NL, NW>(v, w);
             bf_halve<NL>(r, v, P);
             pack<NL, NW>(w, r);
             memcpy(o + i * NW, w, NW * 4);
@@ -186,19 +171,20 @@ static int selftest_bf(const uint64_t *p_limbs, int what, const uint64_t *const 
         return HB_OK;
     }
     const int64_t half = k / 2;
-    for (int64_t j = 0; j < half; j++) {
-        const int64_t xi = bf_xi(j, a), yi = xi | ((int64_t)1 << a);
-        if (what == HB_BF_SELFTEST_MASK) {
-            uint32_t r[NW];
-            if (ops[1]) { bf_mask_bit<NL, NW>(r, W(ops[1], j), W(ops[2], j), P); memcpy(o + j * NW, r, NW * 4); }
-            bf_mask_diff<NL, NW>(r, W(ops[0], xi), W(ops[0], yi), W(ops[3], j), P);
-            memcpy(o + ((ops[1] ? half : 0) + j) * NW, r, NW * 4);
+    const bool adj = NW == 2 && a == 0;
+    if (what == HB_BF_SELFTEST_MASK) {
+        const BfMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), o, a};
+        if (A.bits) {
+            host_rows<BfMaskRow<true, false>, NL, NW>(A, 1, half, P);
+            if (adj) host_rows<BfMaskRow<true, true>, NL, NW>(A, 1, half, P);
         } else {
-            uint32_t r0[NW], r1[NW];
-            bf_switch_elem<NL, NW>(r0, r1, W(ops[0], xi), W(ops[0], yi), W(ops[1], j), W(ops[2], j), W(ops[3], j), W(ops[4], j), W(ops[5], j), P);
-            memcpy(o + 2 * j * NW, r0, NW * 4);
-            memcpy(o + (2 * j + 1) * NW, r1, NW * 4);
+            host_rows<BfMaskRow<false, false>, NL, NW>(A, 1, half, P);
+            if (adj) host_rows<BfMaskRow<false, true>, NL, NW>(A, 1, half, P);
         }
+    } else {
+        const BfSwitchArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), o, a};
+        host_rows<BfSwitchRow<false>, NL, NW>(A, 1, half, P);
+        if (adj) host_rows<BfSwitchRow<true>, NL, NW>(A, 1, half, P);
     }
     return HB_OK;
 }
@@ -216,16 +202,9 @@ int hb_bf_mask(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *bits_dev, co
     const int64_t blocks = (half + 255) / 256;
     if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_bf_mask: layer too large for one launch");
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t *in = (const uint32_t *)in_dev, *b = (const uint32_t *)bits_dev, *p = (const uint32_t *)p_dev, *q = (const uint32_t *)q_dev;
-    uint32_t *o = (uint32_t *)masked_dev;
-    if (bits_dev)
-        HB_DISPATCH(ctx, (launch_mask<9, 8, true>(ctx->pw, in, b, p, q, half, log2_stride, o, (unsigned)blocks, s)),
-                    (launch_mask<3, 2, true>(ctx->pn, in, b, p, q, half, log2_stride, o, (unsigned)blocks, s)));
-    else
-        HB_DISPATCH(ctx, (launch_mask<9, 8, false>(ctx->pw, in, nullptr, nullptr, q, half, log2_stride, o, (unsigned)blocks, s)),
-                    (launch_mask<3, 2, false>(ctx->pn, in, nullptr, nullptr, q, half, log2_stride, o, (unsigned)blocks, s)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const BfMaskArgs A = {u32(in_dev), u32(bits_dev), u32(p_dev), u32(q_dev), u32(masked_dev), log2_stride};
+    if (bits_dev) return bf_launch<BfMaskRow<true, true>, BfMaskRow<true, false>>(ctx, A, (unsigned)blocks, s, half);
+    return bf_launch<BfMaskRow<false, true>, BfMaskRow<false, false>>(ctx, A, (unsigned)blocks, s, half);
 }
 
 int hb_bf_switch(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *d_dev, const uint64_t *e_dev, const uint64_t *p_dev, const uint64_t *q_dev,
@@ -237,13 +216,8 @@ int hb_bf_switch(hb_ctx *ctx, const uint64_t *in_dev, const uint64_t *d_dev, con
     const int64_t blocks = (half + 255) / 256;
     if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_bf_switch: layer too large for one launch");
     hipStream_t s = (hipStream_t)stream;
-    HB_DISPATCH(ctx,
-        (launch_switch<9, 8>(ctx->pw, (const uint32_t *)in_dev, (const uint32_t *)d_dev, (const uint32_t *)e_dev, (const uint32_t *)p_dev, (const uint32_t *)q_dev,
-                             (const uint32_t *)pq_dev, half, log2_stride, (uint32_t *)out_dev, (unsigned)blocks, s)),
-        (launch_switch<3, 2>(ctx->pn, (const uint32_t *)in_dev, (const uint32_t *)d_dev, (const uint32_t *)e_dev, (const uint32_t *)p_dev, (const uint32_t *)q_dev,
-                             (const uint32_t *)pq_dev, half, log2_stride, (uint32_t *)out_dev, (unsigned)blocks, s)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    const BfSwitchArgs A = {u32(in_dev), u32(d_dev), u32(e_dev), u32(p_dev), u32(q_dev), u32(pq_dev), u32(out_dev), log2_stride};
+    return bf_launch<BfSwitchRow<true>, BfSwitchRow<false>>(ctx, A, (unsigned)blocks, s, half);
 }
 
 int hb_selftest_bf(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, int64_t k, int log2_stride, uint64_t *out) {

@@ -30,7 +30,7 @@
 // Launch shape (all steps): 256-thread workgroups, one element a thread in x, the test bit (row) in blockIdx.y.  No LDS, no grid
 // stride, one launch a call.  diff is one subtraction and is recomputed by each row's thread from x and y (which stay in L2) rather
 // than stored as a plane of its own.  Planes, triples and opened values are read once: the 32-byte width takes the non-temporal
-// loads, as k_ew_beaver.
+// loads, as EwBeaverRow.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DESIGN.md section 3n.
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"

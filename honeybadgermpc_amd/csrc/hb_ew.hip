@@ -4,23 +4,25 @@
 // progs/mixins/dataflow.py ShareArray.__add__ / __sub__ / __mul__) -- restated on fp29.hpp, not translated.
 //
 // Operands and results are packed canonical residues (what every other entry point of the library writes).  The per-element
-// bodies are HB_HD functions: the __global__ wrappers below only load, call them and store, and hb_selftest_ew runs the very
-// same functions on the host.
+// bodies are HB_HD functions.  The binary ops and the Beaver step are rows (hb_rows.hpp): which operands a step loads, which body it
+// calls and where it stores is an HB_HD function over a memory policy, so hb_selftest_ew runs on the host the very rows, arithmetic
+// and addressing, that k_rows runs on the device.  The inversion keeps a kernel of its own (a wave sums its zeros: no lane may leave
+// early); its self test walks the kernel's lane function tile by tile.
 //
 // Launch shapes (all kernels: 256-thread workgroups, no LDS, no grid stride, one launch per call):
-//   k_ew_binary   one element a thread; grid = ceil(count / 256)
-//   k_ew_beaver   one element a thread; grid = ceil(count / 256)
+//   k_rows<EwBinaryRow<OP, BCAST>>, k_rows<EwBeaverRow>   one element a thread; grid = ceil(count / 256)
 //   k_ew_inv      one tile of 64 E elements a wave, four tiles a workgroup; lane l owns elements l, l + 64, ... of its tile
 //                 (E = 8 for 32-byte elements, 16 for 8-byte ones)
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
-//   k_ew_binary<9, 8>  MUL 52 VGPRs (broadcast 46), ADD / SUB / NEG 20-22: 8 waves a SIMD     k_ew_binary<3, 2>  8-18 VGPRs: 8 waves
-//   k_ew_beaver<9, 8>  70 VGPRs: 7 waves a SIMD                                              k_ew_beaver<3, 2>  26 VGPRs: 8 waves
+//   k_rows<EwBinaryRow, 9, 8>  MUL 52 VGPRs (broadcast 46), ADD / SUB / NEG 20-22: 8 waves a SIMD     k_rows<EwBinaryRow, 3, 2>  8-18 VGPRs: 8 waves
+//   k_rows<EwBeaverRow, 9, 8>  70 VGPRs: 7 waves a SIMD                                              k_rows<EwBeaverRow, 3, 2>  25 VGPRs: 8 waves
 //   k_ew_inv<9, 8, 8>  255 VGPRs + 72 accumulation registers: 1 wave a SIMD                  k_ew_inv<3, 2, 16> 234 VGPRs: 2 waves
 // (asked for two waves a SIMD the wide inversion spills 292 bytes a lane; DESIGN.md section 3h has the findings and the timings)
 #include <type_traits>
 
 #include "hb_common.hpp"
 #include "hb_ew_elem.hpp"
+#include "hb_rows.hpp"
 
 using namespace hb;
 
@@ -102,52 +104,56 @@ HB_HD int ew_inv_lane(const uint32_t *in, uint32_t *out, int64_t first, int64_t 
     return zeros;
 }
 
-// ---------------------------------------------------------------- kernels
-// out[i] = a[i] OP b[BCAST ? 0 : i].  No __restrict__: out may be a or b (a thread reads its element before it writes it).
-// The broadcast element is read by every lane from one address (one transaction a wave) and made wave-uniform with
-// readfirstlane, so its digits live in SGPRs (the `a` operand of mac, fp29.hpp:72) and its unpack is scalar work.
-template <int NL, int NW, int OP, bool BCAST>
-__global__ void __launch_bounds__(256) k_ew_binary(const FpParams<NL> P, const uint32_t *a, const uint32_t *b, uint32_t *out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t aw[NW], bw[NW], ow[NW];
-    load_words<NW>(aw, a + i * NW);
-    if constexpr (OP == EW_NEG) {
+// ---------------------------------------------------------------- the steps' rows (host and device, over a memory policy: hb_rows.hpp)
+// out[i] = a[i] OP b[BCAST ? 0 : i].  out may be a or b: a row reads its operands before it stores.  The broadcast element is
+// mem.same's: on the device its digits live in SGPRs (the `a` operand of mac, fp29.hpp:72) and its unpack is scalar work.
+struct EwBinaryArgs { const uint32_t *a, *b; uint32_t *out; };
+
+template <int OP, bool BCAST> struct EwBinaryRow {
+    template <int NL, int NW, class Mem> HB_HD static void run(const EwBinaryArgs &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t aw[NW], bw[NW], ow[NW];
+        mem.load(aw, A.a, i);
+        if constexpr (OP == EW_NEG) {
 #pragma unroll
-        for (int q = 0; q < NW; q++) bw[q] = 0;
-    } else if constexpr (BCAST) {
-        load_words<NW>(bw, b);
-#pragma unroll
-        for (int q = 0; q < NW; q++) bw[q] = __builtin_amdgcn_readfirstlane(bw[q]);
-    } else {
-        load_words<NW>(bw, b + i * NW);
+            for (int q = 0; q < NW; q++) bw[q] = 0;
+        } else if constexpr (BCAST) {
+            mem.same(bw, A.b);
+        } else {
+            mem.load(bw, A.b, i);
+        }
+        ew_binary_elem<NL, NW, OP>(ow, aw, bw, P);
+        mem.store(A.out, i, ow);
     }
-    ew_binary_elem<NL, NW, OP>(ow, aw, bw, P);
-    store_words<NW>(out + i * NW, ow);
-}
+};
 
 // The fused Beaver step: five reads and one write an element, nothing in between goes to memory.  d and e are values just
-// opened and the triple is consumed: every byte is read once, so the 32-byte elements take the non-temporal loads
+// opened and the triple is consumed: every byte is read once (mem.once), so the 32-byte elements take the non-temporal loads
 // (load_words_nt: they pass the CU's vector L1, where no line of this launch is ever asked for twice, and are served by L2 as
 // plain loads are).  The result is stored plainly: a plain or non-temporal store leaves the line in L2 alike, and the next
 // launch of the program reads it.  8-byte elements use the plain dwordx2 forms (the _nt helpers move whole dwordx4).
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_ew_beaver(const FpParams<NL> P, const uint32_t *d, const uint32_t *e, const uint32_t *p, const uint32_t *q,
-                                                   const uint32_t *pq, uint32_t *out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t dw[NW], ew[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
-    if constexpr (NW % 4 == 0) {
-        load_words_nt<NW>(dw, d + i * NW); load_words_nt<NW>(ew, e + i * NW); load_words_nt<NW>(qw, q + i * NW);
-        load_words_nt<NW>(pw, p + i * NW); load_words_nt<NW>(pqw, pq + i * NW);
-    } else {
-        load_words<NW>(dw, d + i * NW); load_words<NW>(ew, e + i * NW); load_words<NW>(qw, q + i * NW);
-        load_words<NW>(pw, p + i * NW); load_words<NW>(pqw, pq + i * NW);
+struct EwBeaverArgs { const uint32_t *d, *e, *p, *q, *pq; uint32_t *out; };
+
+struct EwBeaverRow {
+    template <int NL, int NW, class Mem> HB_HD static void run(const EwBeaverArgs &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t dw[NW], ew[NW], pw[NW], qw[NW], pqw[NW], ow[NW];
+        mem.once(dw, A.d, i); mem.once(ew, A.e, i); mem.once(qw, A.q, i);
+        mem.once(pw, A.p, i); mem.once(pqw, A.pq, i);
+        ew_beaver_elem<NL, NW>(ow, dw, ew, pw, qw, pqw, P);
+        mem.store(A.out, i, ow);
     }
-    ew_beaver_elem<NL, NW>(ow, dw, ew, pw, qw, pqw, P);
-    store_words<NW>(out + i * NW, ow);
+};
+
+// f(the row of (op, broadcast)): the one switch of the launch and of the self test
+template <class F> static int with_binary_row(int op, bool bcast, F &&f) {
+    switch (op) {
+    case EW_ADD: return bcast ? f(EwBinaryRow<EW_ADD, true>{}) : f(EwBinaryRow<EW_ADD, false>{});
+    case EW_SUB: return bcast ? f(EwBinaryRow<EW_SUB, true>{}) : f(EwBinaryRow<EW_SUB, false>{});
+    case EW_MUL: return bcast ? f(EwBinaryRow<EW_MUL, true>{}) : f(EwBinaryRow<EW_MUL, false>{});
+    default: return f(EwBinaryRow<EW_NEG, false>{});
+    }
 }
 
+// ---------------------------------------------------------------- the inversion's kernel
 // Batched inversion: wave w of the launch owns the tile [w 64 E, (w + 1) 64 E); lane l its elements l, l + 64, ... so that every
 // load and store of the wave covers 64 consecutive elements.  No lane leaves early (the ragged last tile is predicated inside
 // ew_inv_lane): the zero count is summed over the wave and added to *zeros by one lane, one atomic a wave that met a zero.
@@ -163,25 +169,14 @@ __global__ void __launch_bounds__(256) k_ew_inv(const FpParams<NL> P, const uint
     }
 }
 
-template <int NL, int NW>
-static void launch_binary(const FpParams<NL> &P, int op, bool bcast, const uint32_t *a, const uint32_t *b, uint32_t *out, int64_t count, unsigned blocks, hipStream_t s) {
-    switch (op) {
-    case EW_ADD: if (bcast) k_ew_binary<NL, NW, EW_ADD, true><<<blocks, 256, 0, s>>>(P, a, b, out, count); else k_ew_binary<NL, NW, EW_ADD, false><<<blocks, 256, 0, s>>>(P, a, b, out, count); break;
-    case EW_SUB: if (bcast) k_ew_binary<NL, NW, EW_SUB, true><<<blocks, 256, 0, s>>>(P, a, b, out, count); else k_ew_binary<NL, NW, EW_SUB, false><<<blocks, 256, 0, s>>>(P, a, b, out, count); break;
-    case EW_MUL: if (bcast) k_ew_binary<NL, NW, EW_MUL, true><<<blocks, 256, 0, s>>>(P, a, b, out, count); else k_ew_binary<NL, NW, EW_MUL, false><<<blocks, 256, 0, s>>>(P, a, b, out, count); break;
-    default: k_ew_binary<NL, NW, EW_NEG, false><<<blocks, 256, 0, s>>>(P, a, nullptr, out, count); break;
-    }
-}
-
-// host: the same element functions over `count` elements
+// host: the same rows (the inversion: the same lane function, tile by tile) over `count` elements
 template <int NL, int NW>
 static int selftest_ew(const uint64_t *p_limbs, int what, const uint64_t *const *ops, uint64_t *out, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
     const int op = what & 0xff;
     const bool bcast = (what & HB_EW_SELFTEST_BROADCAST) != 0;
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    uint32_t *o = reinterpret_cast<uint32_t *>(out);
+    uint32_t *o = u32(out);
     if (op == HB_EW_SELFTEST_INV) {
         constexpr int E = EwTile<NL>::E;
         uint64_t zeros = 0;
@@ -191,19 +186,13 @@ static int selftest_ew(const uint64_t *p_limbs, int what, const uint64_t *const 
         if (ops[1]) *const_cast<uint64_t *>(ops[1]) = zeros;
         return HB_OK;
     }
-    const uint32_t none[NW] = {};
-    for (int64_t i = 0; i < count; i++) {
-        uint32_t r[NW];
-        switch (op) {
-        case EW_ADD: ew_binary_elem<NL, NW, EW_ADD>(r, W(ops[0], i), W(ops[1], bcast ? 0 : i), P); break;
-        case EW_SUB: ew_binary_elem<NL, NW, EW_SUB>(r, W(ops[0], i), W(ops[1], bcast ? 0 : i), P); break;
-        case EW_MUL: ew_binary_elem<NL, NW, EW_MUL>(r, W(ops[0], i), W(ops[1], bcast ? 0 : i), P); break;
-        case EW_NEG: ew_binary_elem<NL, NW, EW_NEG>(r, W(ops[0], i), none, P); break;
-        default: ew_beaver_elem<NL, NW>(r, W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), W(ops[4], i), P); break;
-        }
-        memcpy(o + i * NW, r, NW * 4);
+    if (op == HB_EW_SELFTEST_BEAVER) {
+        const EwBeaverArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), o};
+        host_rows<EwBeaverRow, NL, NW>(A, 1, count, P);
+        return HB_OK;
     }
-    return HB_OK;
+    const EwBinaryArgs A = {u32(ops[0]), u32(ops[1]), o};
+    return with_binary_row(op, bcast, [&](auto row) { host_rows<decltype(row), NL, NW>(A, 1, count, P); return (int)HB_OK; });
 }
 
 }  // namespace hb
@@ -217,14 +206,9 @@ int hb_ew_op(hb_ctx *ctx, int op, const uint64_t *a_dev, const uint64_t *b_dev, 
     // a broadcast operand is read by every wave of the launch: it cannot also be the output of more than its own element
     if (op != HB_EW_NEG && b_broadcast && count > 1 && out_dev == b_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_ew_op: out aliases the broadcast operand");
     if (count == 0) return HB_OK;
-    const int64_t blocks = (count + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_ew_op: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    HB_DISPATCH(ctx,
-        (launch_binary<9, 8>(ctx->pw, op, b_broadcast != 0, (const uint32_t *)a_dev, (const uint32_t *)b_dev, (uint32_t *)out_dev, count, (unsigned)blocks, s)),
-        (launch_binary<3, 2>(ctx->pn, op, b_broadcast != 0, (const uint32_t *)a_dev, (const uint32_t *)b_dev, (uint32_t *)out_dev, count, (unsigned)blocks, s)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    HB_ROW_BLOCKS(ctx, "hb_ew_op");
+    const EwBinaryArgs A = {u32(a_dev), u32(b_dev), u32(out_dev)};
+    return with_binary_row(op, b_broadcast != 0, [&](auto row) { return launch_rows<decltype(row)>(ctx, A, (unsigned)blocks, s, count); });
 }
 
 int hb_ew_beaver(hb_ctx *ctx, const uint64_t *d_dev, const uint64_t *e_dev, const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev,
@@ -232,14 +216,9 @@ int hb_ew_beaver(hb_ctx *ctx, const uint64_t *d_dev, const uint64_t *e_dev, cons
     if (!ctx || count < 0) return HB_ERR_BAD_ARG;
     if (count > 0 && (!d_dev || !e_dev || !p_dev || !q_dev || !pq_dev || !out_dev)) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
-    const int64_t blocks = (count + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_ew_beaver: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    HB_DISPATCH(ctx,
-        (k_ew_beaver<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, (const uint32_t *)d_dev, (const uint32_t *)e_dev, (const uint32_t *)p_dev, (const uint32_t *)q_dev, (const uint32_t *)pq_dev, (uint32_t *)out_dev, count)),
-        (k_ew_beaver<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, (const uint32_t *)d_dev, (const uint32_t *)e_dev, (const uint32_t *)p_dev, (const uint32_t *)q_dev, (const uint32_t *)pq_dev, (uint32_t *)out_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    HB_ROW_BLOCKS(ctx, "hb_ew_beaver");
+    const EwBeaverArgs A = {u32(d_dev), u32(e_dev), u32(p_dev), u32(q_dev), u32(pq_dev), u32(out_dev)};
+    return launch_rows<EwBeaverRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_ew_inv(hb_ctx *ctx, const uint64_t *in_dev, uint64_t *out_dev, int64_t count, int32_t *zeros_dev, void *stream) { HB_API_GUARD(ctx);

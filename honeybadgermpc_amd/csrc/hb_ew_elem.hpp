@@ -1,5 +1,6 @@
-// hb_ew_elem.hpp -- the per-element body of the fused Beaver step, shared by hb_ew.hip (k_ew_beaver) and hb_bf.hip
-// (k_bf_switch).  Host and device: the kernels only load, call and store, and the host self tests run the same functions.
+// hb_ew_elem.hpp -- the per-element bodies that several files share: the fused Beaver step (hb_ew.hip's EwBeaverRow, hb_bf.hip's
+// BfSwitchRow and every other step that multiplies shares) and the masked product a b + c of the offline phase (hb_off.hip's OffMulAddRow, hb_offpow.hip's
+// PowMaskRow).  Host and device: the rows only load, call and store, and the host self tests run the same functions.
 #pragma once
 #include "fp29.hpp"
 
@@ -34,6 +35,19 @@ HB_HD void ew_beaver_elem(uint32_t (&o)[NW], const uint32_t (&dw)[NW], const uin
     unpack<NL, NW>(x, pqw);
     fp_add<NL>(s, d, x, P);
     pack<NL, NW>(o, s);
+}
+
+// o = a b + c on packed words (the product as ew_binary_elem's MUL: ab / R, then times R^2)
+template <int NL, int NW>
+HB_HD void ew_mul_add_elem(uint32_t (&o)[NW], const uint32_t (&a)[NW], const uint32_t (&b)[NW], const uint32_t (&c)[NW], const FpParams<NL> &P) {
+    uint32_t ad[NL], bd[NL], cd[NL], t[NL], r[NL];
+    unpack<NL, NW>(ad, a);
+    unpack<NL, NW>(bd, b);
+    unpack<NL, NW>(cd, c);
+    mont_mul<NL>(t, bd, ad, P);
+    mont_mul<NL>(r, P.r2, t, P);
+    fp_add<NL>(t, r, cd, P);
+    pack<NL, NW>(o, t);
 }
 
 }  // namespace hb

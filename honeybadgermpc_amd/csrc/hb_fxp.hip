@@ -28,7 +28,7 @@
 //
 // Launch shape (all kernels): 256-thread workgroups, one element a thread in x; the tree's rows take the triple / node in
 // blockIdx.y.  No LDS, no grid stride, one launch a call.  Planes, triples and opened values are read once: the 32-byte width takes
-// the non-temporal loads, as k_ew_beaver.
+// the non-temporal loads, as EwBeaverRow.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
 //   FxpMaskRow<9, 8>           83 VGPRs with x (5 waves a SIMD), 68 without (7)     FxpMaskRow<3, 2>           34 / 27 VGPRs: 8 waves
 //   FxpTruncPrRow<9, 8>        43 VGPRs: 8 waves                                   FxpTruncPrRow<3, 2>        15 VGPRs: 8 waves

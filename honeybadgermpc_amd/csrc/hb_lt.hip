@@ -27,7 +27,7 @@
 //
 // Launch shape (all steps): 256-thread workgroups, one element a thread in x; LtLeavesRow takes the plane in blockIdx.y (c is one
 // element a thread and stays in L2 for the L planes).  No LDS, no grid stride, one launch a call.  Bit planes, triples and opened
-// values are read once: the 32-byte width takes the non-temporal loads, as k_ew_beaver.
+// values are read once: the 32-byte width takes the non-temporal loads, as EwBeaverRow.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
 //   LtMaskRow<9, 8>        29 VGPRs with b, 30 without: 8 waves a SIMD        LtMaskRow<3, 2>        12 VGPRs: 8 waves
 //   LtLeavesRow<9, 8>      41 VGPRs: 8 waves                                  LtLeavesRow<3, 2>      17 VGPRs: 8 waves

@@ -9,19 +9,21 @@
 //                for all or one an element.  2 rounds field multiplications an element with nothing but registers in between:
 //                x and the running round constant key + c are kept in Montgomery form (+ mont(1) a round), every round is one square
 //                and one product (mimc_chain), one conversion in and one out.  E = 1 or 2 independent elements a thread.
-// k_mimc_round   after the open of y = x - r:  x^3 = y^3 + 3 y^2 r + 3 y r2 + r3 by Horner, y (y (y + 3 r) + 3 r2) + r3 -- three
+// MimcRoundRow   after the open of y = x - r:  x^3 = y^3 + 3 y^2 r + 3 y r2 + r3 by Horner, y (y (y + 3 r) + 3 r2) + r3 -- three
 //                products -- and, in the same pass, the next round's array to open x^3 + (key + c + 1) - r_next (LAST: x^3 + key).
 //                5 reads and one write an element (6 + 1 with a key per element); the round's share is never materialised.
-// k_mimc_first   x + key - r_0, the first array to open (x an array or the counters).
+// MimcFirstRow   x + key - r_0, the first array to open (x an array or the counters).
 // A public constant is added to a Shamir share by every party alike, so the kernels do not ask which of x and key is shared.
 //
-// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions: the __global__ wrappers only
-// load, call them and store, and hb_selftest_mimc runs the very same functions on the host.
+// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions.  The two steps of the MPC round
+// are rows (hb_rows.hpp): k_rows runs them on the device and hb_selftest_mimc runs the very same rows, addressing included, on the
+// host.  k_mimc_plain keeps a kernel of its own (two elements a thread, another thread-to-element map); it only loads, calls the body
+// and stores, and the self test runs the same body.
 //
 // Launch shape (all kernels): 256-thread workgroups, E elements a thread (E = 1 but for the paired cleartext variant), grid =
 // ceil(count / (256 E)), no LDS, no grid stride, one launch a call.  A key for all is read from one address by every lane and made
-// wave-uniform with readfirstlane (as k_ew_binary's broadcast operand): its digits and the round constant live in SGPRs.  The
-// operands of a round are read once: the 32-byte width takes the non-temporal loads, as k_ew_beaver.
+// wave-uniform with readfirstlane (DeviceMem::same, as EwBinaryRow's broadcast operand): its digits and the round constant live in
+// SGPRs.  The operands of a round are read once: the 32-byte width takes the non-temporal loads, as EwBeaverRow.
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage) and the timings: DESIGN.md section 3k.
 #include "hb_common.hpp"
 #include "hb_rows.hpp"
@@ -179,20 +181,49 @@ HB_HD void mimc_round_elem(uint32_t (&o)[NW], const uint32_t (&yw)[NW], const ui
     pack<NL, NW>(o, z);
 }
 
-// ---------------------------------------------------------------- kernels
-// read-once operands (what was just opened, the round's cube)
-// the key of element i; BCAST: element 0 for every lane, made wave-uniform with readfirstlane (UNIFORM) -- but for the paired
-// cleartext kernel: in the 32-byte width the forced scalars of its two chains spilled 25 SGPRs; left to the compiler it spills none
-template <int NW, bool BCAST, bool UNIFORM = true> __device__ __forceinline__ void mimc_load_key(uint32_t (&w)[NW], const uint32_t *key, int64_t i) {
-    if constexpr (BCAST) {
-        load_words<NW>(w, key);
-        if constexpr (UNIFORM) {
-#pragma unroll
-            for (int q = 0; q < NW; q++) w[q] = __builtin_amdgcn_readfirstlane(w[q]);
-        }
-    } else {
-        load_words<NW>(w, key + i * NW);
+// ---------------------------------------------------------------- the rows of the MPC rounds (host and device, over a memory policy: hb_rows.hpp)
+// A key for all is mem.same's element: wave-uniform on the device, its digits and the round constant in SGPRs.  What was just opened
+// and the round's cube are read once (mem.once).  out may be any operand but a broadcast key: a row reads before it stores.
+template <int NL> struct MimcFirstArgs { const uint32_t *x, *key, *r0; uint32_t *out; FpConst<NL> start; };
+
+template <bool BCAST> struct MimcFirstRow {
+    template <int NL, int NW, class Mem> HB_HD static void run(const MimcFirstArgs<NL> &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t xw[NW], kw[NW], rw[NW], ow[NW];
+        if (A.x) mem.load(xw, A.x, i);
+        if constexpr (BCAST) mem.same(kw, A.key); else mem.load(kw, A.key, i);
+        mem.once(rw, A.r0, i);
+        mimc_first_elem<NL, NW>(ow, A.x == nullptr, xw, A.start.d, i, kw, rw, P);
+        mem.store(A.out, i, ow);
     }
+};
+
+// cst = ctr + 1 mod p; LAST: r_next is not read
+template <int NL> struct MimcRoundArgs { const uint32_t *y, *r, *r2, *r3, *key, *r_next; uint32_t *out; FpConst<NL> cst; };
+
+template <bool LAST, bool BCAST> struct MimcRoundRow {
+    template <int NL, int NW, class Mem> HB_HD static void run(const MimcRoundArgs<NL> &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t yw[NW], rw[NW], r2w[NW], r3w[NW], kw[NW], rnw[NW], ow[NW];
+        mem.once(yw, A.y, i); mem.once(rw, A.r, i); mem.once(r2w, A.r2, i);
+        mem.once(r3w, A.r3, i);
+        if constexpr (BCAST) mem.same(kw, A.key); else mem.load(kw, A.key, i);
+        if constexpr (!LAST) mem.once(rnw, A.r_next, i);
+        mimc_round_elem<NL, NW, LAST>(ow, yw, rw, r2w, r3w, kw, A.cst.d, rnw, P);
+        mem.store(A.out, i, ow);
+    }
+};
+
+// f(the row of (last, broadcast)): the one choice of the launch and of the self test
+template <class F> static int with_round_row(bool last, bool bcast, F &&f) {
+    if (last) return bcast ? f(MimcRoundRow<true, true>{}) : f(MimcRoundRow<true, false>{});
+    return bcast ? f(MimcRoundRow<false, true>{}) : f(MimcRoundRow<false, false>{});
+}
+
+// ---------------------------------------------------------------- the cleartext cipher's kernel
+// the key of element i; BCAST: element 0 for every lane, wave-uniform (DeviceMem::same) where UNIFORM -- which the paired kernel is
+// not: in the 32-byte width the forced scalars of its two chains spilled 25 SGPRs; left to the compiler it spills none
+template <int NW, bool BCAST, bool UNIFORM> __device__ __forceinline__ void mimc_load_key(uint32_t (&w)[NW], const uint32_t *key, int64_t i) {
+    if constexpr (BCAST && UNIFORM) DeviceMem<NW>().same(w, key);
+    else load_words<NW>(w, key + (BCAST ? 0 : i) * NW);
 }
 
 // Thread t of block b owns elements b 256 E + t + 256 e, e < E.  A slot past `count` repeats the thread's first element and is not
@@ -218,33 +249,6 @@ __global__ void __launch_bounds__(256) k_mimc_plain(const FpParams<NL> P, const 
         if (first + 256 * e < count) store_words<NW>(out + idx[e] * NW, ow[e]);
 }
 
-template <int NL, int NW, bool BCAST>
-__global__ void __launch_bounds__(256) k_mimc_first(const FpParams<NL> P, const uint32_t *x, const FpConst<NL> start, const uint32_t *key, const uint32_t *r0,
-                                                    uint32_t *out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t xw[NW], kw[NW], rw[NW], ow[NW];
-    if (x) load_words<NW>(xw, x + i * NW);
-    mimc_load_key<NW, BCAST>(kw, key, i);
-    load_once<NW>(rw, r0 + i * NW);
-    mimc_first_elem<NL, NW>(ow, x == nullptr, xw, start.d, i, kw, rw, P);
-    store_words<NW>(out + i * NW, ow);
-}
-
-template <int NL, int NW, bool LAST, bool BCAST>
-__global__ void __launch_bounds__(256) k_mimc_round(const FpParams<NL> P, const uint32_t *y, const uint32_t *r, const uint32_t *r2, const uint32_t *r3,
-                                                    const uint32_t *key, const FpConst<NL> cst, const uint32_t *r_next, uint32_t *out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t yw[NW], rw[NW], r2w[NW], r3w[NW], kw[NW], rnw[NW], ow[NW];
-    load_once<NW>(yw, y + i * NW); load_once<NW>(rw, r + i * NW); load_once<NW>(r2w, r2 + i * NW);
-    load_once<NW>(r3w, r3 + i * NW);
-    mimc_load_key<NW, BCAST>(kw, key, i);
-    if constexpr (!LAST) load_once<NW>(rnw, r_next + i * NW);
-    mimc_round_elem<NL, NW, LAST>(ow, yw, rw, r2w, r3w, kw, cst.d, rnw, P);
-    store_words<NW>(out + i * NW, ow);
-}
-
 // ---------------------------------------------------------------- host side
 // v mod p as digits (v < 2^63)
 template <int NL> static FpConst<NL> mimc_small(const FpParams<NL> &P, uint64_t v) {
@@ -256,8 +260,8 @@ template <int NL> static FpConst<NL> mimc_small(const FpParams<NL> &P, uint64_t 
     return c;
 }
 // the counter's start from its packed words (NULL: 0); false if it is not below p
-template <int NL, int NW> static bool mimc_start(FpConst<NL> &c, const FpParams<NL> &P, const uint64_t *start_host) {
-    if (start_host) return host_digits<NL, NW>(c.d, P, start_host);
+template <int NL> static bool mimc_start(FpConst<NL> &c, const FpParams<NL> &P, const uint64_t *start_host) {
+    if (start_host) return host_digits<NL, words_of(NL)>(c.d, P, start_host);
     small_digits<NL>(c.d, 0);
     return true;
 }
@@ -273,37 +277,18 @@ static void launch_plain(const FpParams<NL> &P, const uint32_t *x, const FpConst
         else k_mimc_plain<NL, NW, 1, false><<<blocks, 256, 0, s>>>(P, x, start, key, addend, subtract, rounds, out, count);
     }
 }
-template <int NL, int NW>
-static void launch_first(const FpParams<NL> &P, const uint32_t *x, const FpConst<NL> &start, const uint32_t *key, bool bcast, const uint32_t *r0, uint32_t *out,
-                         int64_t count, unsigned blocks, hipStream_t s) {
-    if (bcast) k_mimc_first<NL, NW, true><<<blocks, 256, 0, s>>>(P, x, start, key, r0, out, count);
-    else k_mimc_first<NL, NW, false><<<blocks, 256, 0, s>>>(P, x, start, key, r0, out, count);
-}
-template <int NL, int NW>
-static void launch_round(const FpParams<NL> &P, const uint32_t *y, const uint32_t *r, const uint32_t *r2, const uint32_t *r3, const uint32_t *key, bool bcast,
-                         int64_t ctr, const uint32_t *r_next, uint32_t *out, int64_t count, unsigned blocks, hipStream_t s) {
-    const FpConst<NL> cst = mimc_small<NL>(P, (uint64_t)ctr + 1);
-    if (r_next) {
-        if (bcast) k_mimc_round<NL, NW, false, true><<<blocks, 256, 0, s>>>(P, y, r, r2, r3, key, cst, r_next, out, count);
-        else k_mimc_round<NL, NW, false, false><<<blocks, 256, 0, s>>>(P, y, r, r2, r3, key, cst, r_next, out, count);
-    } else {
-        if (bcast) k_mimc_round<NL, NW, true, true><<<blocks, 256, 0, s>>>(P, y, r, r2, r3, key, cst, nullptr, out, count);
-        else k_mimc_round<NL, NW, true, false><<<blocks, 256, 0, s>>>(P, y, r, r2, r3, key, cst, nullptr, out, count);
-    }
-}
-
-// host: the same element functions over `count` elements
+// host: the rounds as the rows the device runs, the cleartext cipher as the same element function over `count` elements
 template <int NL, int NW>
 static int selftest_mimc(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const uint64_t *start_host, bool bcast, int flags, int64_t arg,
                          uint64_t *out, int64_t count) {
     FpParams<NL> P;
     fp_params_from_limbs(P, p_limbs);
     FpConst<NL> start;
-    if (!mimc_start<NL, NW>(start, P, start_host)) return HB_ERR_BAD_ARG;
-    auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
-    uint32_t *o = reinterpret_cast<uint32_t *>(out);
-    const uint32_t none[NW] = {};
+    if (!mimc_start(start, P, start_host)) return HB_ERR_BAD_ARG;
+    uint32_t *o = u32(out);
     if (what == HB_MIMC_SELFTEST_PLAIN) {
+        auto W = [](const uint64_t *base, int64_t i) -> const uint32_t (&)[NW] { return *reinterpret_cast<const uint32_t(*)[NW]>(reinterpret_cast<const uint32_t *>(base) + i * NW); };
+        const uint32_t none[NW] = {};
         const bool counter = ops[0] == nullptr, has_addend = ops[2] != nullptr, subtract = (flags & HB_MIMC_SUB) != 0;
         if (flags & HB_MIMC_PAIR) {
             for (int64_t i = 0; i < count; i += 2) {
@@ -331,18 +316,13 @@ static int selftest_mimc(const uint64_t *p_limbs, int what, const uint64_t *cons
         }
         return HB_OK;
     }
-    const FpConst<NL> cst = mimc_small<NL>(P, (uint64_t)arg + 1);
-    for (int64_t i = 0; i < count; i++) {
-        uint32_t r[NW];
-        if (what == HB_MIMC_SELFTEST_FIRST)
-            mimc_first_elem<NL, NW>(r, ops[0] == nullptr, ops[0] ? W(ops[0], i) : none, start.d, i, W(ops[1], bcast ? 0 : i), W(ops[2], i), P);
-        else if (ops[5])
-            mimc_round_elem<NL, NW, false>(r, W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), W(ops[4], bcast ? 0 : i), cst.d, W(ops[5], i), P);
-        else
-            mimc_round_elem<NL, NW, true>(r, W(ops[0], i), W(ops[1], i), W(ops[2], i), W(ops[3], i), W(ops[4], bcast ? 0 : i), cst.d, none, P);
-        memcpy(o + i * NW, r, NW * 4);
+    if (what == HB_MIMC_SELFTEST_FIRST) {
+        const MimcFirstArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), o, start};
+        if (bcast) host_rows<MimcFirstRow<true>, NL, NW>(A, 1, count, P); else host_rows<MimcFirstRow<false>, NL, NW>(A, 1, count, P);
+        return HB_OK;
     }
-    return HB_OK;
+    const MimcRoundArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), o, mimc_small<NL>(P, (uint64_t)arg + 1)};
+    return with_round_row(ops[5] == nullptr, bcast, [&](auto row) { host_rows<decltype(row), NL, NW>(A, 1, count, P); return (int)HB_OK; });
 }
 
 }  // namespace hb
@@ -358,7 +338,7 @@ int hb_mimc_plain(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *start_host
     if (key_broadcast && count > 1 && out_dev == key_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_plain: out aliases the broadcast key");
     FpConst<9> sw;
     FpConst<3> sn;
-    if (!(ctx->n_limbs == 4 ? mimc_start<9, 8>(sw, ctx->pw, start_host) : mimc_start<3, 2>(sn, ctx->pn, start_host)))
+    if (!(ctx->n_limbs == 4 ? mimc_start(sw, ctx->pw, start_host) : mimc_start(sn, ctx->pn, start_host)))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_plain: start is not below the modulus");
     if (count == 0) return HB_OK;
     const bool pair = (flags & HB_MIMC_PAIR) != 0;
@@ -379,17 +359,17 @@ int hb_mimc_first(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *start_host
     if (key_broadcast && count > 1 && out_dev == key_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_first: out aliases the broadcast key");
     FpConst<9> sw;
     FpConst<3> sn;
-    if (!(ctx->n_limbs == 4 ? mimc_start<9, 8>(sw, ctx->pw, start_host) : mimc_start<3, 2>(sn, ctx->pn, start_host)))
+    if (!(ctx->n_limbs == 4 ? mimc_start(sw, ctx->pw, start_host) : mimc_start(sn, ctx->pn, start_host)))
         return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_first: start is not below the modulus");
     if (count == 0) return HB_OK;
-    const int64_t blocks = (count + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_mimc_first: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t *x = (const uint32_t *)x_dev, *k = (const uint32_t *)key_dev, *r0 = (const uint32_t *)r0_dev;
-    HB_DISPATCH(ctx, (launch_first<9, 8>(ctx->pw, x, sw, k, key_broadcast != 0, r0, (uint32_t *)out_dev, count, (unsigned)blocks, s)),
-                (launch_first<3, 2>(ctx->pn, x, sn, k, key_broadcast != 0, r0, (uint32_t *)out_dev, count, (unsigned)blocks, s)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    HB_ROW_BLOCKS(ctx, "hb_mimc_first");
+    // (the start was refused above, ahead of the batch's size as ever; here it becomes the row's argument)
+    auto fill = [&](auto &A, const auto &P) {
+        A.x = u32(x_dev); A.key = u32(key_dev); A.r0 = u32(r0_dev); A.out = u32(out_dev);
+        return mimc_start(A.start, P, start_host);
+    };
+    if (key_broadcast) return launch_rows<MimcFirstRow<true>, MimcFirstArgs>(ctx, fill, (unsigned)blocks, s, count);
+    return launch_rows<MimcFirstRow<false>, MimcFirstArgs>(ctx, fill, (unsigned)blocks, s, count);
 }
 
 int hb_mimc_round(hb_ctx *ctx, const uint64_t *y_dev, const uint64_t *r_dev, const uint64_t *r2_dev, const uint64_t *r3_dev, const uint64_t *key_dev,
@@ -398,15 +378,13 @@ int hb_mimc_round(hb_ctx *ctx, const uint64_t *y_dev, const uint64_t *r_dev, con
     if (ctr < 0 || ctr == INT64_MAX) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_round: the round counter must be in [0, 2^63 - 1)");
     if (key_broadcast && count > 1 && out_dev == key_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_mimc_round: out aliases the broadcast key");
     if (count == 0) return HB_OK;
-    const int64_t blocks = (count + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_mimc_round: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t *y = (const uint32_t *)y_dev, *r = (const uint32_t *)r_dev, *r2 = (const uint32_t *)r2_dev, *r3 = (const uint32_t *)r3_dev;
-    const uint32_t *k = (const uint32_t *)key_dev, *rn = (const uint32_t *)r_next_dev;
-    HB_DISPATCH(ctx, (launch_round<9, 8>(ctx->pw, y, r, r2, r3, k, key_broadcast != 0, ctr, rn, (uint32_t *)out_dev, count, (unsigned)blocks, s)),
-                (launch_round<3, 2>(ctx->pn, y, r, r2, r3, k, key_broadcast != 0, ctr, rn, (uint32_t *)out_dev, count, (unsigned)blocks, s)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    HB_ROW_BLOCKS(ctx, "hb_mimc_round");
+    auto fill = [&](auto &A, const auto &P) {
+        A.y = u32(y_dev); A.r = u32(r_dev); A.r2 = u32(r2_dev); A.r3 = u32(r3_dev); A.key = u32(key_dev); A.r_next = u32(r_next_dev); A.out = u32(out_dev);
+        A.cst = mimc_small(P, (uint64_t)ctr + 1);
+        return true;
+    };
+    return with_round_row(r_next_dev == nullptr, key_broadcast != 0, [&](auto row) { return launch_rows<decltype(row), MimcRoundArgs>(ctx, fill, (unsigned)blocks, s, count); });
 }
 
 int hb_selftest_mimc(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const uint64_t *start, int key_broadcast, int flags,

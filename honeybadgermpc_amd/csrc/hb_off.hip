@@ -2,7 +2,7 @@
 // generate_triples, generate_bits) -- restated on fp29.hpp, not translated.  The protocol is honeybadgermpc_amd/offline.py; the three
 // places where composing the library's existing entry points is wasteful are kernels here.
 //
-// k_off_mul_add        out = a b + c: the masked local product of both generators (a b + r_2t for triples, :179; u u + r_2t for bits,
+// OffMulAddRow         out = a b + c: the masked local product of both generators (a b + r_2t for triples, :179; u u + r_2t for bits,
 //                      :218).  Three reads and one write an element instead of hb_ew_op(MUL) + hb_ew_op(ADD)'s five and two.
 // k_off_invsqrt_scale  the finish of generate_bits (:223, u / sqrt(u^2)): x the opened u^2, w = x^(-1/2) computed directly and
 //                      out = u w (HB_OFF_PM1), (u w + 1) / 2 (HB_OFF_01) or w itself (no u).  With p - 1 = q 2^s and c = z^q for the
@@ -22,21 +22,24 @@
 //                      writes: per column j < k, is the t-sharing of exact degree t, the 2t-sharing of exact degree 2t, and are the
 //                      two constant terms equal.  Words are compared, nothing is multiplied.
 //
-// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions: the __global__ wrappers below
-// only load, call them and store, and hb_selftest_off runs the very same functions on the host.
+// Operands and results are packed canonical residues.  The per-element bodies are HB_HD functions.  The masked product is a row
+// (hb_rows.hpp): k_rows runs it on the device and hb_selftest_off runs the very same row, addressing included, on the host.  The
+// other two keep kernels of their own (wave sums: no lane may leave early); those only load, call the bodies and store, and the
+// self test runs the same bodies.
 //
 // Launch shapes (all kernels: 256-thread workgroups, no LDS, no grid stride, one launch a call):
-//   k_off_mul_add        one element a thread; grid = ceil(count / 256)
+//   k_rows<OffMulAddRow> one element a thread; grid = ceil(count / 256)
 //   k_off_invsqrt_scale  one element a thread; grid = ceil(count / 256); no lane leaves early: a lane past `count` works on x = 1 and
 //                        stores nothing; the two status counts are summed over the wave and added by one lane
 //   k_off_degree_check   one column pair (j, k + j) a thread, walking the n coefficient rows (every load of a wave covers 64
 //                        consecutive elements); grid = ceil(k / 256); the three counts are summed over the wave and added by one lane
 // Compiler's report (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch = 0 bytes for every kernel):
-//   k_off_mul_add<9, 8>        62 VGPRs: 8 waves a SIMD       k_off_mul_add<3, 2>        21 VGPRs: 8 waves
+//   k_rows<OffMulAddRow, 9, 8> 62 VGPRs: 8 waves a SIMD       k_rows<OffMulAddRow, 3, 2> 21 VGPRs: 8 waves
 //   k_off_invsqrt_scale<9, 8>  98 VGPRs: 4 waves              k_off_invsqrt_scale<3, 2>  31 VGPRs: 8 waves
 //   k_off_degree_check<8>      44 VGPRs: 8 waves              k_off_degree_check<2>      20 VGPRs: 8 waves
 // (the constants and the table of the inverse root are read through wave-uniform addresses: scalar loads, scalar branches)
 #include "hb_common.hpp"
+#include "hb_ew_elem.hpp"
 #include "hb_rows.hpp"
 
 using namespace hb;
@@ -54,18 +57,7 @@ struct OffConsts {
 };
 
 // ---------------------------------------------------------------- per-element bodies (host and device)
-// o = a b + c on packed words (the product as ew_binary_elem's MUL: ab / R, then times R^2)
-template <int NL, int NW>
-HB_HD void off_mul_add_elem(uint32_t (&o)[NW], const uint32_t (&a)[NW], const uint32_t (&b)[NW], const uint32_t (&c)[NW], const FpParams<NL> &P) {
-    uint32_t ad[NL], bd[NL], cd[NL], t[NL], r[NL];
-    unpack<NL, NW>(ad, a);
-    unpack<NL, NW>(bd, b);
-    unpack<NL, NW>(cd, c);
-    mont_mul<NL>(t, bd, ad, P);
-    mont_mul<NL>(r, P.r2, t, P);
-    fp_add<NL>(t, r, cd, P);
-    pack<NL, NW>(o, t);
-}
+// The masked product o = a b + c is ew_mul_add_elem of hb_ew_elem.hpp (hb_offpow.hip multiplies its powers with the same body).
 
 HB_HD uint32_t off_exp_bit(const OffConsts &K, int b) {
     const uint64_t w = b < 64 ? K.e[0] : (b < 128 ? K.e[1] : (b < 192 ? K.e[2] : K.e[3]));
@@ -170,20 +162,22 @@ template <int NW> HB_HD int off_degree_check_column(const uint32_t *coeffs, int 
     return ((lead_a == 0 || above_a != 0) ? 1 : 0) | ((lead_b == 0 || above_b != 0) ? 2 : 0) | (diff ? 4 : 0);
 }
 
-// ---------------------------------------------------------------- kernels
-// No __restrict__: out may be a, b or c, and b may be a (a thread reads its element before it writes it).
-template <int NL, int NW>
-__global__ void __launch_bounds__(256) k_off_mul_add(const FpParams<NL> P, const uint32_t *a, const uint32_t *b, const uint32_t *c, uint32_t *out, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    uint32_t aw[NW], bw[NW], cw[NW], ow[NW];
-    load_words<NW>(aw, a + i * NW);
-    load_words<NW>(bw, b + i * NW);
-    load_words<NW>(cw, c + i * NW);
-    off_mul_add_elem<NL, NW>(ow, aw, bw, cw, P);
-    store_words<NW>(out + i * NW, ow);
-}
+// ---------------------------------------------------------------- the row of the masked product (host and device: hb_rows.hpp)
+// out may be a, b or c, and b may be a: the row reads its three operands before it stores.
+struct OffMulAddArgs { const uint32_t *a, *b, *c; uint32_t *out; };
 
+struct OffMulAddRow {
+    template <int NL, int NW, class Mem> HB_HD static void run(const OffMulAddArgs &A, int, int64_t i, int64_t, const Mem &mem, const FpParams<NL> &P) {
+        uint32_t aw[NW], bw[NW], cw[NW], ow[NW];
+        mem.load(aw, A.a, i);
+        mem.load(bw, A.b, i);
+        mem.load(cw, A.c, i);
+        ew_mul_add_elem<NL, NW>(ow, aw, bw, cw, P);
+        mem.store(A.out, i, ow);
+    }
+};
+
+// ---------------------------------------------------------------- kernels of a shape of their own (wave sums: no lane leaves early)
 __device__ __forceinline__ int off_wave_sum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -305,7 +299,7 @@ static int off_blob(hb_ctx *ctx, const uint8_t **out, hipStream_t s) {
     return HB_OK;
 }
 
-// host: the same element functions over `count` elements
+// host: the masked product as the row the device runs, the other two as the same element functions over `count` elements
 template <int NL, int NW>
 static int selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, uint64_t *out, int64_t count) {
     FpParams<NL> P;
@@ -315,10 +309,8 @@ static int selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const ui
     uint32_t *o = reinterpret_cast<uint32_t *>(out);
     uint32_t r[NW];
     if (op == HB_OFF_SELFTEST_MUL_ADD) {
-        for (int64_t i = 0; i < count; i++) {
-            off_mul_add_elem<NL, NW>(r, W(ops[0], i), W(ops[1], i), W(ops[2], i), P);     // read whole before the write: out may be an operand
-            memcpy(o + i * NW, r, NW * 4);
-        }
+        const OffMulAddArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), o};
+        host_rows<OffMulAddRow, NL, NW>(A, 1, count, P);
         return HB_OK;
     }
     if (op == HB_OFF_SELFTEST_INVSQRT) {
@@ -351,18 +343,12 @@ static int selftest_off(const uint64_t *p_limbs, int n_limbs, int what, const ui
 
 extern "C" {
 
-
 int hb_off_mul_add(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *c_dev, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
     if (!ctx || count < 0 || (count > 0 && (!a_dev || !b_dev || !c_dev || !out_dev))) return HB_ERR_BAD_ARG;
     if (count == 0) return HB_OK;
-    const int64_t blocks = (count + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_off_mul_add: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    HB_DISPATCH(ctx,
-        (k_off_mul_add<9, 8><<<(unsigned)blocks, 256, 0, s>>>(ctx->pw, u32(a_dev), u32(b_dev), u32(c_dev), (uint32_t *)out_dev, count)),
-        (k_off_mul_add<3, 2><<<(unsigned)blocks, 256, 0, s>>>(ctx->pn, u32(a_dev), u32(b_dev), u32(c_dev), (uint32_t *)out_dev, count)));
-    HB_LAUNCH_CHECK(ctx);
-    return HB_OK;
+    HB_ROW_BLOCKS(ctx, "hb_off_mul_add");
+    const OffMulAddArgs A = {u32(a_dev), u32(b_dev), u32(c_dev), u32(out_dev)};
+    return launch_rows<OffMulAddRow>(ctx, A, (unsigned)blocks, s, count);
 }
 
 int hb_off_invsqrt_scale(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *u_dev, int mode, uint64_t *out_dev, int64_t count, int32_t *status_dev, void *stream) {

@@ -19,6 +19,7 @@
 //   k_rows<PowMaskRow, 9, 8>    63 VGPRs: 8 waves a SIMD       k_rows<PowMaskRow, 3, 2>    20 VGPRs: 8 waves
 //   k_rows<PowFinishRow, 9, 8>  28 VGPRs: 8 waves              k_rows<PowFinishRow, 3, 2>  13 VGPRs: 8 waves
 #include "hb_common.hpp"
+#include "hb_ew_elem.hpp"
 #include "hb_rows.hpp"
 
 using namespace hb;
@@ -41,19 +42,7 @@ HB_HD void pow_split(int64_t e, int64_t total, int w, int64_t &c, int &j) {
 }
 HB_HD int64_t pow_cell(const PowArgs &A, int64_t c, int q) { return c * A.item_stride + (int64_t)q * A.power_stride; }
 
-// o = a b + c on packed words (the product as ew_binary_elem's MUL: ab / R, then times R^2)
-template <int NL, int NW>
-HB_HD void pow_mul_add_elem(uint32_t (&o)[NW], const uint32_t (&a)[NW], const uint32_t (&b)[NW], const uint32_t (&c)[NW], const FpParams<NL> &P) {
-    uint32_t ad[NL], bd[NL], cd[NL], t[NL], r[NL];
-    unpack<NL, NW>(ad, a);
-    unpack<NL, NW>(bd, b);
-    unpack<NL, NW>(cd, c);
-    mont_mul<NL>(t, bd, ad, P);
-    mont_mul<NL>(r, P.r2, t, P);
-    fp_add<NL>(t, r, cd, P);
-    pack<NL, NW>(o, t);
-}
-
+// The masked product a b + c is ew_mul_add_elem of hb_ew_elem.hpp (hb_off.hip's OffMulAddRow computes the same).
 struct PowMaskRow {
     template <int NL, int NW, class Mem> HB_HD static void run(const PowArgs &A, int, int64_t e, int64_t total, const Mem &mem, const FpParams<NL> &P) {
         int64_t c;
@@ -68,7 +57,7 @@ struct PowMaskRow {
             mem.load(b, A.powers, pow_cell(A, c, j));
         }
         mem.once(r, A.r, e);
-        pow_mul_add_elem<NL, NW>(o, a, b, r, P);
+        ew_mul_add_elem<NL, NW>(o, a, b, r, P);
         mem.store(A.out, e, o);
     }
 };

@@ -1,17 +1,19 @@
 // hb_rows.hpp -- what the share-array step files share, one of each.
 //   The helpers -- the read-once load, the small element helpers (word_bit, diff_elem, small_digits, FpConst), the host's digits of a
 //   constant (host_digits, host_mont) and the argument checks of the entry points (u32, overlap, RowSpan / outputs_apart, modulus_bits,
-//   HB_ROW_BLOCKS) -- serve all of them: hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_mimc.hip, hb_bf.hip,
-//   hb_off.hip, hb_offsb.hip, hb_mat.hip and hb_sort.hip.
-//   The shape of a step -- the memory policies, k_rows, host_rows, launch_rows -- serves hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip,
-//   hb_eq.hip, hb_jj.hip, hb_offpow.hip, hb_offsb.hip and hb_sort.hip: every step of theirs is a row.  hb_mimc.hip (two elements a thread, a specialised key load), hb_bf.hip
-//   (two indices an element), hb_off.hip and hb_mat.hip (tiles) have kernels of other shapes and use the helpers alone.
+//   HB_ROW_BLOCKS) -- serve all of them: hb_ew.hip, hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_mimc.hip,
+//   hb_bf.hip, hb_off.hip, hb_offpow.hip, hb_offsb.hip, hb_mat.hip and hb_sort.hip.
+//   The shape of a step -- the memory policies, k_rows, host_rows, launch_rows -- serves hb_ew.hip, hb_fxp.hip, hb_bd.hip, hb_div.hip,
+//   hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_mimc.hip, hb_bf.hip, hb_off.hip, hb_offpow.hip, hb_offsb.hip and hb_sort.hip.  Every step of
+//   theirs is a row but for four kernels that keep a shape of their own: k_ew_inv, k_off_invsqrt_scale and k_off_degree_check (wave
+//   sums: no lane may leave early) and k_mimc_plain (two elements a thread).  hb_mat.hip (tiles, LDS) uses the helpers alone.
 //
 // A step is a ROW: a type with
 //     template <int NL, int NW, class Mem> HB_HD static void run(const Args &A, int y, int64_t i, int64_t count, const Mem &mem, const FpParams<NL> &P)
 // that works element i of row y (a node, a triple, a plane, a product: whatever the step counts in blockIdx.y) -- which operands it
 // loads, which element body it calls, where it stores.  Args is the step's argument struct, handed to the kernel by value; Mem is a
-// memory policy: load / once (w, base, element index) and store (base, element index, w), element index = row * count + i.  k_rows
+// memory policy: load / once (w, base, element index) and store (base, element index, w), element index = row * count + i; same (w,
+// base), the element all of a launch share, and pair (x, y, base, even element index), two neighbours moved as one access.  k_rows
 // runs a row on the device (256-thread workgroups, one element a thread in x, the row in blockIdx.y, no LDS, no grid stride), host_rows
 // runs the same row on the host, so a host self test exercises the addressing the device runs, not a restatement of it.
 #pragma once
@@ -60,11 +62,33 @@ template <int NW> struct DeviceMem {
     __device__ __forceinline__ void load(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { load_words<NW>(w, base + e * NW); }
     __device__ __forceinline__ void once(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { load_once<NW>(w, base + e * NW); }
     __device__ __forceinline__ void store(uint32_t *base, int64_t e, const uint32_t (&w)[NW]) const { store_words<NW>(base + e * NW, w); }
+    // element 0 of base, the operand every element of the launch shares: every lane reads the one address (one transaction a wave)
+    // and readfirstlane makes the words wave-uniform, so its digits live in SGPRs and its unpack is scalar work
+    __device__ __forceinline__ void same(uint32_t (&w)[NW], const uint32_t *base) const {
+        load_words<NW>(w, base);
+#pragma unroll
+        for (int q = 0; q < NW; q++) w[q] = __builtin_amdgcn_readfirstlane(w[q]);
+    }
+    // elements e and e + 1, e even: two 8-byte elements are one 16-byte access (the caller sees to it that base is 16-byte aligned)
+    __device__ __forceinline__ void pair(uint32_t (&x)[NW], uint32_t (&y)[NW], const uint32_t *base, int64_t e) const {
+        if constexpr (NW == 2) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(base + e * NW);
+            x[0] = v.x; x[1] = v.y; y[0] = v.z; y[1] = v.w;
+        } else {
+            load_words<NW>(x, base + e * NW);
+            load_words<NW>(y, base + (e + 1) * NW);
+        }
+    }
 };
 template <int NW> struct HostMem {
     void load(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { memcpy(w, base + e * NW, NW * 4); }
     void once(uint32_t (&w)[NW], const uint32_t *base, int64_t e) const { memcpy(w, base + e * NW, NW * 4); }
     void store(uint32_t *base, int64_t e, const uint32_t (&w)[NW]) const { memcpy(base + e * NW, w, NW * 4); }
+    void same(uint32_t (&w)[NW], const uint32_t *base) const { memcpy(w, base, NW * 4); }
+    void pair(uint32_t (&x)[NW], uint32_t (&y)[NW], const uint32_t *base, int64_t e) const {
+        memcpy(x, base + e * NW, NW * 4);
+        memcpy(y, base + (e + 1) * NW, NW * 4);
+    }
 };
 
 // ---------------------------------------------------------------- a row on the device and on the host

@@ -1,13 +1,18 @@
-// A stand-alone HOST program over hb_selftest_lt, hb_selftest_eq and hb_selftest_jj for AddressSanitizer and UBSan: the rows of
-// csrc/hb_lt.hip, hb_eq.hip and hb_jj.hip (hb_rows.hpp: host_rows runs what k_rows runs) compiled WITH the sanitizers into this program;
-// the rest of the library comes from libhbmpc_hip.so as it is.  No GPU is touched.
+// A stand-alone HOST program over hb_selftest_lt, hb_selftest_eq, hb_selftest_jj, hb_selftest_ew, hb_selftest_off, hb_selftest_mimc and
+// hb_selftest_bf for AddressSanitizer and UBSan: the rows of csrc/hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_ew.hip, hb_off.hip, hb_mimc.hip and
+// hb_bf.hip (hb_rows.hpp: host_rows runs what k_rows runs) compiled WITH the sanitizers into this program; the rest of the library
+// comes from libhbmpc_hip.so as it is.  No GPU is touched.
 //
-//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//         scratch/asan_rows.cpp honeybadgermpc_amd/csrc/hb_lt.hip honeybadgermpc_amd/csrc/hb_eq.hip honeybadgermpc_amd/csrc/hb_jj.hip \
-//         -Lhoneybadgermpc_amd/lib -lhbmpc_hip -Wl,-rpath,$PWD/honeybadgermpc_amd/lib -o scratch/asan_rows && scratch/asan_rows
+//   C=honeybadgermpc_amd/csrc; hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
+//         -Xarch_host -fno-omit-frame-pointer scratch/asan_rows.cpp $C/hb_lt.hip $C/hb_eq.hip $C/hb_jj.hip $C/hb_ew.hip $C/hb_off.hip \
+//         $C/hb_mimc.hip $C/hb_bf.hip -Lhoneybadgermpc_amd/lib -lhbmpc_hip -Wl,-rpath,$PWD/honeybadgermpc_amd/lib -o scratch/asan_rows \
+//         && scratch/asan_rows
 //
-// Every step at count = 3, rows = 3 (hb_eq), a triples' row stride of count + 3 (hb_jj), both widths.  Every operand and output is a heap
-// buffer of exactly the documented size, so a row that reads or writes one row past an array is a report.
+// Every step of lt, eq and jj at count = 3, rows = 3 (hb_eq), a triples' row stride of count + 3 (hb_jj); the element-wise, mul-add and
+// MiMC rows at 1, 255, 256, 257 and 513 elements with a key or an operand for all (HostMem::same: ONE element on the heap) and one an
+// element; a butterfly layer at k = 2, 4 and 1024 and every stride the GPU suite runs (HostMem::pair at stride 1 in the 8-byte width).
+// Both widths.  Every operand and output is a heap buffer of exactly the documented size, so a row that reads or writes one element
+// past an array is a report.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -170,6 +175,64 @@ static void jubjub(const uint64_t *p, int64_t m) {
     }
 }
 
+static const int64_t COUNTS[5] = {1, 255, 256, 257, 513};
+
+static void elementwise(const uint64_t *p, int64_t n) {
+    Elems a(n), b(n), one(1), d(n), e(n), tp(n), tq(n), tpq(n);
+    for (int op = HB_EW_ADD; op <= HB_EW_NEG; op++)
+        for (int bcast = 0; bcast < (op == HB_EW_NEG ? 1 : 2); bcast++)
+            for (int alias = 0; alias < 3; alias++) {                       // out a fresh array, a itself, b itself (where b is an array)
+                if (alias == 2 && (bcast || op == HB_EW_NEG)) continue;
+                Elems x(n), y(n), out(n);
+                const uint64_t *ops[2] = {x, op == HB_EW_NEG ? nullptr : bcast ? one.p : y.p};
+                CHECK(hb_selftest_ew(p, NL, op | (bcast ? HB_EW_SELFTEST_BROADCAST : 0), ops, alias == 0 ? out.p : alias == 1 ? x.p : y.p, n) == HB_OK);
+            }
+    Elems out(n);
+    const uint64_t *ops[5] = {d, e, tp, tq, tpq};
+    CHECK(hb_selftest_ew(p, NL, HB_EW_SELFTEST_BEAVER, ops, out.p, n) == HB_OK);
+}
+
+static void mul_add(const uint64_t *p, int64_t n) {
+    for (int shape = 0; shape < 3; shape++) {                               // plain; b is a (the square); out is c
+        Elems a(n), b(n), c(n), out(n);
+        const uint64_t *ops[3] = {a, shape == 1 ? a.p : b.p, c};
+        CHECK(hb_selftest_off(p, NL, HB_OFF_SELFTEST_MUL_ADD, ops, shape == 2 ? c.p : out.p, n) == HB_OK);
+    }
+}
+
+static void mimc_rounds(const uint64_t *p, int64_t n) {
+    std::vector<uint64_t> start(p, p + NL);
+    start[0] -= 3;                                                         // the counters wrap
+    Elems x(n), r0(n), y(n), r(n), r2(n), r3(n), rn(n), keys(n), key(1);
+    for (int bcast = 0; bcast < 2; bcast++) {
+        const uint64_t *k = bcast ? key.p : keys.p;
+        for (int counter = 0; counter < 2; counter++) {
+            Elems out(n);
+            const uint64_t *ops[3] = {counter ? nullptr : x.p, k, r0};
+            CHECK(hb_selftest_mimc(p, NL, HB_MIMC_SELFTEST_FIRST, ops, counter ? start.data() : nullptr, bcast, 0, 0, out.p, n) == HB_OK);
+        }
+        for (int last = 0; last < 2; last++)
+            for (int64_t ctr : {(int64_t)0, (int64_t)1 << 62}) {
+                Elems out(n);
+                const uint64_t *ops[6] = {y, r, r2, r3, k, last ? nullptr : rn.p};
+                CHECK(hb_selftest_mimc(p, NL, HB_MIMC_SELFTEST_ROUND, ops, nullptr, bcast, 0, ctr, out.p, n) == HB_OK);
+            }
+    }
+}
+
+static void butterfly(const uint64_t *p, int64_t k, int a) {
+    const int64_t half = k / 2;
+    Elems in(k), bits(half), tp(half), tq(half), tpq(half), d(half), e(half);
+    for (int has_bits = 0; has_bits < 2; has_bits++) {
+        Elems masked(has_bits ? k : half);
+        const uint64_t *ops[4] = {in, has_bits ? bits.p : nullptr, has_bits ? tp.p : nullptr, tq};
+        CHECK(hb_selftest_bf(p, NL, HB_BF_SELFTEST_MASK, ops, k, a, masked.p) == HB_OK);
+    }
+    Elems out(k);
+    const uint64_t *ops[6] = {in, d, e, tp, tq, tpq};
+    CHECK(hb_selftest_bf(p, NL, HB_BF_SELFTEST_SWITCH, ops, k, a, out.p) == HB_OK);
+}
+
 int main() {
     for (int wide = 1; wide >= 0; wide--) {
         NL = wide ? 4 : 1;
@@ -177,6 +240,10 @@ int main() {
         less_than(p, wide ? 255 : 64, 3);
         equality(p, 3, 3);
         jubjub(p, 3);
+        for (int64_t n : COUNTS) { elementwise(p, n); mul_add(p, n); mimc_rounds(p, n); }
+        butterfly(p, 2, 0);
+        for (int a : {0, 1}) butterfly(p, 4, a);
+        for (int a : {0, 5, 9}) butterfly(p, 1024, a);
     }
     printf(fails ? "asan_rows: %d check(s) FAILED\n" : "asan_rows ok\n", fails);
     return fails ? 1 : 0;

@@ -15,7 +15,11 @@ Network: n = 4, t = 1, every party in this process over an in-process transport,
 loop included: it is NOT kernel time.
 
 --kernels runs three layers of each version at k = 2^20 over BLS12-381 and nothing else (for a kernel trace).
-No GPU: fails (there is nothing to fall back to)."""
+No GPU: fails (there is nothing to fall back to).
+
+With --steps instead: the mask and the switch of a layer alone at both widths (BLS12-381 Fr and 2^64 - 59), k = 2^21 (2^20 switches), HIP events around one launch
+with the host kept ahead of the device (one_launch of scratch/time_share_comparison.py).  Run it against two builds of the library
+(HBMPC_HIP_LIB) in one visit to compare them."""
 import asyncio
 import socket
 import sys
@@ -227,12 +231,39 @@ def time_network(reps):
         torch.cuda.empty_cache()
 
 
+def time_steps(reps, label):
+    """--steps: the mask (with and without the signs) and the switch of one layer alone, both widths, k = 2^21 (2^20 switches), strides
+    1 (in the 8-byte width: the instantiation that takes a switch's two inputs in one access), 2^5 and k / 2"""
+    from time_share_comparison import fmt as band, one_launch, rnd as draw
+
+    print(f"# scratch/time_butterfly.py --steps, {reps} runs a figure, HIP events around one launch: median (min .. max); {label}")
+    pad = torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    k = 1 << 21
+    for p, width in ((BLS, "<9, 8>"), (P64, "<3, 2>")):
+        ctx = Context.get(p)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(19)
+        x, (bits, tp, tq, tpq, d, e) = draw(ctx, gen, k), [draw(ctx, gen, k // 2) for _ in range(6)]
+        out = ctx.empty(k)
+        steps = []
+        for a in (0, 5, 20):
+            steps.append((f"BfMaskRow<true> stride 2^{a}", lambda a=a: bn.mask_layer(ctx, x, bits, tp, tq, a, out=out)))
+            steps.append((f"BfMaskRow<false> stride 2^{a}", lambda a=a: bn.mask_layer(ctx, x, None, None, tq, a, out=out[:k // 2])))
+            steps.append((f"BfSwitchRow stride 2^{a}", lambda a=a: bn.switch_layer(ctx, x, d, e, tp, tq, tpq, a, out=out)))
+        for step, fn in steps:
+            print(f"step {step + ' ' + width:34s} {band(one_launch(reps, fn, pad))}", flush=True)
+        del steps
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     if not torch.cuda.is_available():
         raise SystemExit("scratch/time_butterfly.py needs the GPU")
     reps = int(args[0]) if args and args[0].isdigit() else 20
     label = args[args.index("--label") + 1] if "--label" in args else "working tree"
+    if "--steps" in args:
+        return time_steps(max(20, reps), label)
     if "--kernels" in args:
         ctx = Context.get(BLS)
         gen = torch.Generator(device="cuda")

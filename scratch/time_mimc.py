@@ -19,7 +19,11 @@ both widths, one and two elements a thread, alternated; also as field multiplica
 chain (2 * rounds an element; the three conversions are not counted).
 
 --kernels runs three rounds of each version at 2^20 over BLS12-381 and two cleartext launches, and nothing else (for a kernel trace).
-No GPU: fails (there is nothing to fall back to)."""
+No GPU: fails (there is nothing to fall back to).
+
+With --steps instead: the first mask and the cubing round alone at both widths (BLS12-381 Fr and 2^64 - 59), 2^20 elements, HIP events around one launch
+with the host kept ahead of the device (one_launch of scratch/time_share_comparison.py).  Run it against two builds of the library
+(HBMPC_HIP_LIB) in one visit to compare them."""
 import asyncio
 import socket
 import sys
@@ -276,12 +280,39 @@ def time_plain(reps):
             torch.cuda.empty_cache()
 
 
+def time_steps(reps, label):
+    """--steps: the first mask and the cubing round alone (last and not, a key for all and a key an element), both widths, 2^20 elements"""
+    from time_share_comparison import fmt as band, one_launch, rnd as draw
+
+    print(f"# scratch/time_mimc.py --steps, {reps} runs a figure, HIP events around one launch: median (min .. max); {label}")
+    pad = torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    count = 1 << 20
+    for p, width in ((BLS, "<9, 8>"), (P64, "<3, 2>")):
+        ctx = Context.get(p)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(19)
+        x, r0, y, r, r2, r3, rn, keys = (draw(ctx, gen, count) for _ in range(8))
+        key, out = ctx.upload_ints([0x1234567]), ctx.empty(count)
+        steps = []
+        for k, kname in ((key, "key for all"), (keys, "key an element")):
+            steps.append((f"MimcFirstRow {kname}", lambda k=k: mimc.first_mask(ctx, x, k, r0, out=out)))
+            steps.append((f"MimcFirstRow counters, {kname}", lambda k=k: mimc.first_mask(ctx, None, k, r0, start=5, out=out)))
+            steps.append((f"MimcRoundRow {kname}", lambda k=k: mimc.cube_round(ctx, y, r, r2, r3, k, 80, r_next=rn, out=out)))
+            steps.append((f"MimcRoundRow last, {kname}", lambda k=k: mimc.cube_round(ctx, y, r, r2, r3, k, 160, out=out)))
+        for step, fn in steps:
+            print(f"step {step + ' ' + width:46s} {band(one_launch(reps, fn, pad))}", flush=True)
+        del steps
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     if not torch.cuda.is_available():
         raise SystemExit("scratch/time_mimc.py needs the GPU")
     reps = int(args[0]) if args and args[0].isdigit() else 20
     label = args[args.index("--label") + 1] if "--label" in args else "working tree"
+    if "--steps" in args:
+        return time_steps(max(20, reps), label)
     if "--kernels" in args:
         ctx = Context.get(BLS)
         gen = torch.Generator(device="cuda")

@@ -14,7 +14,11 @@
     every party's coroutine on the one device: wall clock from the first coroutine's start to the last one's end with the device
     synchronised, 3 runs after a warm-up at k = 256.  Context, not judged against anything.
 
-No GPU: fails (there is nothing to fall back to)."""
+No GPU: fails (there is nothing to fall back to).
+
+With --steps instead: mul_add alone at both widths (BLS12-381 Fr and 2^64 - 59), 2^20 elements, HIP events around one launch
+with the host kept ahead of the device (one_launch of scratch/time_share_comparison.py).  Run it against two builds of the library
+(HBMPC_HIP_LIB) in one visit to compare them."""
 import asyncio
 import os
 import socket
@@ -181,12 +185,34 @@ def protocol(ctx, k, runs):
     return out
 
 
+def time_steps(reps, label):
+    """--steps: mul_add alone (a b + c, and the square a a + c written over c), both widths, 2^20 elements"""
+    from time_share_comparison import fmt as band, one_launch, rnd as draw
+
+    print(f"# scratch/time_offline.py --steps, {reps} runs a figure, HIP events around one launch: median (min .. max); {label}")
+    pad = torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    count = 1 << 20
+    for p, width in ((BLS, "<9, 8>"), ((1 << 64) - 59, "<3, 2>")):
+        ctx = Context.get(p)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(19)
+        a, b, c = (draw(ctx, gen, count) for _ in range(3))
+        out = ctx.empty(count)
+        steps = [("OffMulAddRow", lambda: offline.mul_add(ctx, a, b, c, out=out)), ("OffMulAddRow square, out = c", lambda: offline.mul_add(ctx, a, a, c, out=c))]
+        for step, fn in steps:
+            print(f"step {step + ' ' + width:34s} {band(one_launch(reps, fn, pad))}", flush=True)
+        del steps
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     if not torch.cuda.is_available():
         raise SystemExit("scratch/time_offline.py needs the GPU")
     reps = max(30, int(args[0])) if args and args[0].isdigit() else 30
     label = args[args.index("--label") + 1] if "--label" in args else "working tree"
+    if "--steps" in args:
+        return time_steps(max(20, int(args[0])) if args and args[0].isdigit() else 20, label)
     path = args[args.index("--out") + 1] if "--out" in args else os.path.join("profiles", "offline.txt")
     say(f"# scratch/time_offline.py, {reps} runs a figure: median (min .. max); {torch.cuda.get_device_name(0)} on {socket.gethostname()}; {label}")
     gen = torch.Generator(device="cuda")

@@ -3,7 +3,11 @@ BLS12-381's scalar field (32-byte elements) and over 2^64 - 59 (8-byte elements)
 step; and the route a user had before these kernels (download_ints, the list comprehension on Python ints, upload_ints) at 2^20:
    python scratch/time_share_arith.py [reps] [--label TEXT] > profiles/ew_share_arith.txt
 Every call of a timed loop works on the next of a rotation of operand sets that together exceed 1 GiB (the chip's 256 MB of cache
-holds none of them by the time its turn comes again); every event object is recorded once before the timed region."""
+holds none of them by the time its turn comes again); every event object is recorded once before the timed region.
+
+With --steps instead: every binary op and the Beaver step alone at both widths (BLS12-381 Fr and 2^64 - 59), 2^20 elements, HIP events around one launch
+with the host kept ahead of the device (one_launch of scratch/time_share_comparison.py).  Run it against two builds of the library
+(HBMPC_HIP_LIB) in one visit to compare them."""
 import socket
 import sys
 import time
@@ -37,10 +41,37 @@ def timed(calls, reps):
     return float(np.median([a.elapsed_time(b) for a, b in evs])) * 1e3
 
 
+def time_steps(reps, label):
+    """--steps: every binary op (b an array, b one element for all) and the Beaver step alone, both widths, 2^20 elements"""
+    from time_share_comparison import fmt as band, one_launch, rnd as draw
+
+    print(f"# scratch/time_share_arith.py --steps, {reps} runs a figure, HIP events around one launch: median (min .. max); {label}")
+    pad = torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    count = 1 << 20
+    for p, width in ((BLS, "<9, 8>"), (P64, "<3, 2>")):
+        ctx = Context.get(p)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(19)
+        a, b, d, e, tp, tq, tpq = (draw(ctx, gen, count) for _ in range(7))
+        out = ctx.empty(count)
+        steps = []
+        for name, fn in (("ADD", sa.add), ("SUB", sa.sub), ("MUL", sa.mul)):
+            steps.append((f"EwBinaryRow {name}", lambda fn=fn: fn(ctx, a, b, out=out)))
+            steps.append((f"EwBinaryRow {name} broadcast", lambda fn=fn: fn(ctx, a, 0x1234567, out=out)))
+        steps.append(("EwBinaryRow NEG", lambda: sa.neg(ctx, a, out=out)))
+        steps.append(("EwBeaverRow", lambda: sa.beaver_combine(ctx, d, e, tp, tq, tpq, out=out)))
+        for step, fn in steps:
+            print(f"step {step + ' ' + width:34s} {band(one_launch(reps, fn, pad))}", flush=True)
+        del steps
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     reps = int(args[0]) if args and args[0].isdigit() else 40
     label = args[args.index("--label") + 1] if "--label" in args else "working tree"
+    if "--steps" in args:
+        return time_steps(max(20, reps), label)
     print(f"# scratch/time_share_arith.py, {reps} calls a figure (medians); {torch.cuda.get_device_name(0)} on {socket.gethostname()}; {label}")
     print("# us = microseconds a call between HIP events; rotation = operand sets cycled through (together > 1 GiB)")
     gen = torch.Generator(device="cuda")

@@ -199,4 +199,5 @@ def main():
               f"composed / fused = {np.median(tc) / np.median(tf):5.2f}   {'bit-equal' if same else 'MISMATCH'}   {rows * count * nmul / np.median(tf) / 1e3:7.1f} G mul/s", flush=True)
 
 
-main()
+if __name__ == "__main__":
+    main()

@@ -1,8 +1,7 @@
 """CPU-only: the wiring model of honeybadgermpc_amd.butterfly_network against tests/golden/butterfly_network.json (written by
 scratch/gen_butterfly_golden.py from the reference's own iterated_butterfly_network, run in the clear), and the per-element
-bodies of the butterfly kernels (csrc/hb_bf.hip) run on the host through hb_selftest_bf -- the same HB_HD functions k_bf_mask and
-k_bf_switch call -- against Python ints.  Exact equality."""
-import ctypes
+bodies of the butterfly kernels (csrc/hb_bf.hip) run on the host through hb_selftest_bf -- the rows BfMaskRow and BfSwitchRow that the
+device runs -- against Python ints.  Exact equality."""
 import itertools
 import json
 import os
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import BLS, REPO
+from selftest_cases import run_bf as run
 
 from honeybadgermpc_amd import butterfly_network as bn
 
@@ -26,19 +26,6 @@ def golden():
         g = json.load(f)
     assert int(g["modulus"]) == BLS and [c["k"] for c in g["cases"]] == [2, 4, 8, 32]
     return [{"k": c["k"], "inputs": [int(v) for v in c["inputs"]], "signs": c["signs"], "output": [int(v) for v in c["output"]]} for c in g["cases"]]
-
-
-def run(p, nl, what, operands, k, a, n_out):
-    """hb_selftest_bf over lists of ints (None: a NULL operand) -> (rc, list of ints)"""
-    from honeybadgermpc_amd._capi import ints_to_limbs, limbs_to_ints, load_library, np_ptr
-
-    lib = load_library()
-    nb = 8 * nl
-    arrays = [None if o is None else ints_to_limbs(list(o) or [0], p, nb) for o in operands]
-    ptrs = (ctypes.c_void_p * 6)(*[None if x is None else x.ctypes.data for x in arrays])
-    out = np.zeros((max(n_out, 1), nl), dtype=np.uint64)
-    rc = lib.hb_selftest_bf(np_ptr(ints_to_limbs([p], p + 1, nb)), nl, what, ptrs, k, a, np_ptr(out))
-    return rc, limbs_to_ints(out[:n_out], nb)
 
 
 def mask_ref(p, xs, bits, ps, qs, k, a):

@@ -361,3 +361,42 @@ def test_golden_signs_give_the_reference_output():
         for mode in ("per_layer", "upfront"):
             for i in range(4):
                 assert results[mode][i][1] == want, (c["k"], mode, i)
+
+
+@pytest.mark.parametrize("k, strides", [(2, (0,)), (4, (0, 1)), (1024, (0, 5, 9))], ids=["k2", "k4", "k1024"])
+@pytest.mark.parametrize("p", (BLS, P64), ids=("bls", "2^64-59"))
+def test_mask_and_switch_equal_the_host_self_test(p, k, strides):
+    """One row body: the device's mask (with and without the signs) and switch of a layer equal, bit for bit, what hb_selftest_bf
+    computes on the host from the same inputs: the self test runs the rows the kernels run, addressing included.  Both instantiations;
+    every stride of 2 and 4 inputs, the first, a middle and the last of 1024 (512 switches: two workgroups).  At stride 1 in the 8-byte
+    width `inputs` is given once 16-byte aligned and once as a view that starts 8 bytes off, so the instantiation that takes a
+    switch's two inputs in one access and the general one both run."""
+    import selftest_cases as stc
+    from honeybadgermpc_amd import butterfly_network as bn
+
+    MASK, SWITCH = 0, 1
+    ctx = _ctx(p)
+    torch, nl, half = ctx.torch, ctx.n_limbs, k // 2
+    rnd = random.Random(k + nl)
+
+    def draw(count, shift):
+        xs = [rnd.randrange(p) for _ in range(count)]
+        for i, v in enumerate((0, 1, p - 1)):
+            xs[(shift + i) % count] = v
+        return xs
+
+    xs = draw(k, 0)
+    bits, ps, qs, pqs, d, e = (draw(half, i) for i in range(6))
+    aligned = ctx.upload_ints(xs)
+    off_by_one = ctx.upload_ints([0] + xs)[1:]
+    assert aligned.data_ptr() % 16 == 0 and off_by_one.data_ptr() % 16 == 8 * nl % 16
+    up = ctx.upload_ints
+    for a in strides:
+        for x in (aligned, off_by_one) if (nl == 1 and a == 0) else (aligned,):
+            rc, want = stc.run_bf(p, nl, MASK, [xs, bits, ps, qs], k, a, k)
+            assert rc == 0 and torch.equal(bn.mask_layer(ctx, x, up(bits), up(ps), up(qs), a), up(want)), (a, x.data_ptr() % 16)
+            rc, want = stc.run_bf(p, nl, MASK, [xs, None, None, qs], k, a, half)
+            assert rc == 0 and torch.equal(bn.mask_layer(ctx, x, None, None, up(qs), a), up(want)), (a, x.data_ptr() % 16)
+            rc, want = stc.run_bf(p, nl, SWITCH, [xs, d, e, ps, qs, pqs], k, a, k)
+            assert rc == 0 and torch.equal(bn.switch_layer(ctx, x, up(d), up(e), up(ps), up(qs), up(pqs), a), up(want)), (a, x.data_ptr() % 16)
+    torch.cuda.synchronize()

@@ -480,3 +480,43 @@ def test_protocol_fewer_rounds_narrow_field_and_bad_cubes():
 
     results, _ = _run_parties(p, n, t, set(), rnd, refused)
     assert results[0] == 0                                               # nothing was opened
+
+
+def _with_corners(rnd, p, count, shift):
+    """random residues with 0, 1 and p - 1 among them, at positions that differ from operand to operand"""
+    xs = [rnd.randrange(p) for _ in range(count)]
+    for k, v in enumerate((0, 1, p - 1)):
+        xs[(shift + k) % count] = v
+    return xs
+
+
+@pytest.mark.parametrize("count", (1, 255, 256, 257, 513))
+@pytest.mark.parametrize("p", (BLS, P64), ids=("bls", "2^64-59"))
+def test_first_and_round_equal_the_host_self_test(p, count):
+    """One row body: the device's first mask (x an array, and the counters from start = p - 3, which wrap) and its cubing round (last
+    and not, ctr = 0 and 2^62), each under a key for all and a key an element, equal, bit for bit, what hb_selftest_mimc computes on the
+    host from the same inputs: the self test runs the rows the kernels run, addressing included.  Both instantiations; one lane, a
+    full workgroup, one lane into a second, a ragged third."""
+    import selftest_cases as stc
+    from honeybadgermpc_amd.progs import mimc
+
+    ROUND, FIRST = 1, 2
+    ctx = _ctx(p)
+    torch, nl = ctx.torch, ctx.n_limbs
+    rnd = random.Random(7 * count + nl)
+    x, r0, y, r, r2, r3, rn, keys = (_with_corners(rnd, p, count, k) for k in range(8))
+
+    def same(dev, host):
+        rc, want = host
+        return rc == 0 and tuple(dev.shape) == (count, nl) and torch.equal(dev, ctx.upload_ints(want))
+
+    up = ctx.upload_ints
+    for key, bcast in [(k, 1) for k in (0, 1, p - 1, rnd.randrange(p))] + [(keys, 0)]:
+        kdev, khost = (key, [key]) if bcast else (up(key), key)
+        assert same(mimc.first_mask(ctx, up(x), kdev, up(r0)), stc.run_mimc(p, nl, FIRST, [x, khost, r0], count, bcast=bcast)), (bcast, key)
+        assert same(mimc.first_mask(ctx, None, kdev, up(r0), start=p - 3), stc.run_mimc(p, nl, FIRST, [None, khost, r0], count, start=p - 3, bcast=bcast)), (bcast, key)
+        for ctr in (0, 1 << 62):
+            for nxt in (rn, None):
+                got = mimc.cube_round(ctx, up(y), up(r), up(r2), up(r3), kdev, ctr, None if nxt is None else up(nxt))
+                assert same(got, stc.run_mimc(p, nl, ROUND, [y, r, r2, r3, khost, nxt], count, arg=ctr, bcast=bcast)), (bcast, key, ctr, nxt is None)
+    torch.cuda.synchronize()

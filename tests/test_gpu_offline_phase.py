@@ -450,3 +450,35 @@ def test_generate_bits_finish_refuses_what_has_no_root():
         for mode in (offline.PM1, offline.ZERO_ONE):
             with pytest.raises(AssertionError):
                 offline.invsqrt_scale(ctx, ctx.upload_ints(x), u, mode)
+
+
+@pytest.mark.parametrize("count", (1, 255, 256, 257, 513))
+@pytest.mark.parametrize("p", (BLS, P64), ids=("bls", "2^64-59"))
+def test_mul_add_equals_the_host_self_test(p, count):
+    """One row body: the device's a b + c -- plain, with b the array a itself (the square) and written over c -- equals, bit for bit,
+    what hb_selftest_off computes on the host from the same inputs: the self test runs the row the kernel runs, addressing included.
+    Both instantiations; one lane, a full workgroup, one lane into a second, a ragged third."""
+    import selftest_cases as stc
+    from honeybadgermpc_amd import offline
+
+    ctx = _ctx(p)
+    nl = ctx.n_limbs
+    rnd = random.Random(count)
+    cols = []
+    for shift in range(3):
+        xs = [rnd.randrange(p) for _ in range(count)]
+        for k, v in enumerate((0, 1, p - 1)):
+            xs[(shift + k) % count] = v
+        cols.append(xs)
+
+    def same(dev, host):
+        rc, want = host
+        return rc == 0 and tuple(dev.shape) == (count, nl) and ctx.torch.equal(dev, ctx.upload_ints(want))
+
+    a, b, c = (ctx.upload_ints(v) for v in cols)
+    assert same(offline.mul_add(ctx, a, b, c), stc.run_off_mul_add(p, nl, *cols))
+    assert same(offline.mul_add(ctx, a, a, c), stc.run_off_mul_add(p, nl, *cols, b_is_a=True))
+    assert offline.mul_add(ctx, a, b, c, out=c) is c and same(c, stc.run_off_mul_add(p, nl, *cols, out_is=2))
+    c = ctx.upload_ints(cols[2])
+    assert offline.mul_add(ctx, a, a, c, out=c) is c and same(c, stc.run_off_mul_add(p, nl, *cols, b_is_a=True, out_is=2))
+    ctx.torch.cuda.synchronize()

@@ -412,3 +412,50 @@ def test_narrow_field_beaver_end_to_end():
         assert opened == [a * b % p for a, b in zip(x, y)], i
         assert seen == (2, 1)
     ctx.torch.cuda.synchronize()
+
+
+def _with_corners(rnd, p, count, shift):
+    """random residues with 0, 1 and p - 1 among them, at positions that differ from operand to operand"""
+    xs = [rnd.randrange(p) for _ in range(count)]
+    for k, v in enumerate((0, 1, p - 1)):
+        xs[(shift + k) % count] = v
+    return xs
+
+
+@pytest.mark.parametrize("count", (1, 255, 256, 257, 513))
+@pytest.mark.parametrize("p, nl", [(BLS, 4), ((1 << 64) - 59, 1)], ids=["bls", "2^64-59"])
+def test_every_row_equals_the_host_self_test(p, nl, count):
+    """One row body: the device's output of every binary op -- with and without a broadcast b, in place on a and on b -- and of the
+    Beaver step equals, bit for bit, what hb_selftest_ew computes on the host from the same inputs: the self test runs the rows the
+    kernel runs, addressing included.  Both instantiations; one lane, a full workgroup, one lane into a second, a ragged third."""
+    import selftest_cases as stc
+    from honeybadgermpc_amd import share_arithmetic as sa
+
+    ADD, SUB, MUL, NEG, BEAVER, BROADCAST = 0, 1, 2, 3, 4, 0x100
+    ctx = _ctx(p, nl)
+    torch = ctx.torch
+    rnd = random.Random(1000 * nl + count)
+    a, b = _with_corners(rnd, p, count, 0), _with_corners(rnd, p, count, 1)
+
+    def same(dev, host):
+        return tuple(dev.shape) == (count, nl) and torch.equal(dev, ctx.upload_ints(host))
+
+    for op, fn in ((ADD, sa.add), (SUB, sa.sub), (MUL, sa.mul)):
+        want = stc.run_ew(p, nl, op, [a, b], count)
+        ta, tb = ctx.upload_ints(a), ctx.upload_ints(b)
+        assert same(fn(ctx, ta, tb), want), op
+        assert fn(ctx, ta, tb, out=ta) is ta and same(ta, want), (op, "in place on a")
+        ta = ctx.upload_ints(a)
+        assert fn(ctx, ta, tb, out=tb) is tb and same(tb, want), (op, "in place on b")
+        for s in (0, 1, p - 1, rnd.randrange(p)):
+            want = stc.run_ew(p, nl, op | BROADCAST, [a, [s]], count)
+            ta = ctx.upload_ints(a)
+            assert same(fn(ctx, ta, s), want), (op, s)
+            assert fn(ctx, ta, s, out=ta) is ta and same(ta, want), (op, s, "in place on a")
+    want = stc.run_ew(p, nl, NEG, [a], count)
+    ta = ctx.upload_ints(a)
+    assert same(sa.neg(ctx, ta), want)
+    assert sa.neg(ctx, ta, out=ta) is ta and same(ta, want)
+    cols = [_with_corners(rnd, p, count, k) for k in range(5)]
+    assert same(sa.beaver_combine(ctx, *(ctx.upload_ints(c) for c in cols)), stc.run_ew(p, nl, BEAVER, cols, count))
+    torch.cuda.synchronize()

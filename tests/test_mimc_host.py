@@ -1,18 +1,17 @@
 """CPU-only: the host model of honeybadgermpc_amd.progs.mimc against tests/golden/mimc.json (written by scratch/gen_mimc_golden.py
 from the reference's own mimc_plain and ROUND), and the per-element bodies of the MiMC kernels (csrc/hb_mimc.hip) run on the host
-through hb_selftest_mimc -- the same HB_HD functions k_mimc_plain, k_mimc_round and k_mimc_first call -- against Python ints.
+through hb_selftest_mimc -- the body k_mimc_plain calls and the rows MimcRoundRow and MimcFirstRow that the device runs -- against Python ints.
 Exact equality."""
-import ctypes
 import itertools
 import json
 import os
 import random
 import re
 
-import numpy as np
 import pytest
 
 from conftest import BLS, REPO
+from selftest_cases import run_mimc as run
 
 from honeybadgermpc_amd.progs import mimc
 
@@ -27,20 +26,6 @@ def golden():
         g = json.load(f)
     assert int(g["modulus"]) == BLS and len(g["cases"]) >= 40
     return g["ROUND"], [(int(c["x"]), int(c["k"]), int(c["out"])) for c in g["cases"]]
-
-
-def run(p, nl, what, operands, count, arg=0, start=None, bcast=0, flags=0):
-    """hb_selftest_mimc over lists of ints (None: a NULL operand) -> (rc, list of ints)"""
-    from honeybadgermpc_amd._capi import ints_to_limbs, limbs_to_ints, load_library, np_ptr
-
-    lib = load_library()
-    nb = 8 * nl
-    arrays = [None if o is None else ints_to_limbs(list(o) or [0], p, nb) for o in operands]
-    ptrs = (ctypes.c_void_p * 6)(*[None if x is None else x.ctypes.data for x in arrays])
-    st = None if start is None else ints_to_limbs([start], start + 1, nb)
-    out = np.zeros((max(count, 1), nl), dtype=np.uint64)
-    rc = lib.hb_selftest_mimc(np_ptr(ints_to_limbs([p], p + 1, nb)), nl, what, ptrs, None if st is None else np_ptr(st), bcast, flags, arg, np_ptr(out), count)
-    return rc, limbs_to_ints(out[:count], nb)
 
 
 def round_ref(p, y, r, r2, r3, key, ctr, r_next):

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 from conftest import BLS, REPO
+from selftest_cases import run_off as _call
+from selftest_cases import run_off_mul_add as mul_add
 
 from honeybadgermpc_amd import offline
 
@@ -41,24 +43,6 @@ def _ints(arr, nl, count):
     from honeybadgermpc_amd._capi import limbs_to_ints
 
     return limbs_to_ints(arr[:count], 8 * nl) if count else []
-
-
-def _call(p, nl, what, ptrs, out, count):
-    from honeybadgermpc_amd._capi import ints_to_limbs, np_ptr
-
-    ops = (ctypes.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
-    return _lib().hb_selftest_off(np_ptr(ints_to_limbs([p], p + 1, 8 * nl)), nl, what, ops, out, count)
-
-
-def mul_add(p, nl, a, b, c, b_is_a=False, out_is=None):
-    """-> (rc, out); b_is_a: the b pointer is a's; out_is: 0, 1 or 2 -- the output pointer is that operand's"""
-    count = len(a)
-    arrs = [_limbs(v, p, nl) for v in (a, b, c)]
-    if b_is_a:
-        arrs[1] = arrs[0]
-    out = arrs[out_is] if out_is is not None else np.zeros((max(count, 1), nl), dtype=np.uint64)
-    rc = _call(p, nl, MUL_ADD, [x.ctypes.data for x in arrs], out.ctypes.data, count)
-    return rc, _ints(out, nl, count)
 
 
 def invsqrt(p, nl, x, u, mode):

@@ -1,5 +1,5 @@
 """CPU-only: the per-element bodies of the element-wise kernels (csrc/hb_ew.hip) run on the host through hb_selftest_ew --
-the same HB_HD functions k_ew_binary, k_ew_beaver and k_ew_inv call -- against Python int arithmetic.  Exact equality."""
+the rows EwBinaryRow and EwBeaverRow that the device runs and the lane function k_ew_inv calls -- against Python int arithmetic.  Exact equality."""
 import ctypes
 import itertools
 import random
@@ -8,26 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import BLS
+from selftest_cases import run_ew as run
 
 PRIMES = [(BLS, 4), (13, 4), (53, 4), ((1 << 256) - 189, 4), ((1 << 255) - 19, 4), (13, 1), ((1 << 64) - 59, 1), (0xFFFFFFFF00000001, 1)]
 IDS = ["bls", "13w", "53w", "2^256-189", "2^255-19", "13n", "2^64-59", "goldilocks"]
 ADD, SUB, MUL, NEG, BEAVER, INV, BROADCAST = 0, 1, 2, 3, 4, 5, 0x100
-
-
-def run(p, nl, what, operands, count, extra=None):
-    """hb_selftest_ew over lists of ints -> list of ints"""
-    from honeybadgermpc_amd._capi import ints_to_limbs, limbs_to_ints, load_library, np_ptr
-
-    lib = load_library()
-    nb = 8 * nl
-    arrays = [ints_to_limbs(list(o), p, nb) for o in operands]
-    ptrs = (ctypes.c_void_p * 5)(*[a.ctypes.data for a in arrays])
-    if extra is not None:
-        ptrs[1] = extra.ctypes.data
-    out = np.zeros((max(count, 1), nl), dtype=np.uint64)
-    rc = lib.hb_selftest_ew(np_ptr(ints_to_limbs([p], p + 1, nb)), nl, what, ptrs, np_ptr(out), count)
-    assert rc == 0, rc
-    return limbs_to_ints(out[:count], nb)
 
 
 def tuples(p, arity, rnd, n_random=200):
