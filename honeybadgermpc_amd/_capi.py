@@ -51,6 +51,7 @@ HB_FXP_SELFTEST_MASK, HB_FXP_SELFTEST_TRUNC_PR, HB_FXP_SELFTEST_LEAVES = 0, 1, 2
 HB_FXP_SELFTEST_CARRY_MASK, HB_FXP_SELFTEST_CARRY_COMBINE, HB_FXP_SELFTEST_FINISH = 3, 4, 5
 HB_SORT_SELFTEST_CMP_MASK, HB_SORT_SELFTEST_SWAP_MASK, HB_SORT_SELFTEST_SWAP_FINISH = 0, 1, 2
 HB_BD_SELFTEST_LEAVES, HB_BD_SELFTEST_PREFIX_MASK, HB_BD_SELFTEST_PREFIX_COMBINE, HB_BD_SELFTEST_SUM_MASK, HB_BD_SELFTEST_SUM_COMBINE = 0, 1, 2, 3, 4
+HB_DEMUX_SELFTEST_LEAVES, HB_DEMUX_SELFTEST_MASK, HB_DEMUX_SELFTEST_FINISH = 0, 1, 2
 HB_DIV_SIGN, HB_DIV_NORM, HB_DIV_FIRST, HB_DIV_TRUNC = 0, 1, 2, 3
 HB_DIV_T_RESULT, HB_DIV_T_RECIP, HB_DIV_T_GOLD = 0, 1, 2
 HB_DIV_SELFTEST_OR_MASK, HB_DIV_SELFTEST_OR_COMBINE, HB_DIV_SELFTEST_NORM_MASK, HB_DIV_SELFTEST_PRODUCT_STEP, HB_DIV_SELFTEST_TRUNC_STEP = 0, 1, 2, 3, 4
@@ -162,6 +163,9 @@ SYMBOLS = {
     "hb_bd_prefix_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_bd_sum_mask": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_bd_sum_combine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_demux_leaves": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "hb_demux_mask": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp]),
+    "hb_demux_finish": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp]),
     "hb_div_pair_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_div_or_mask": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_div_or_combine": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
@@ -251,6 +255,7 @@ SYMBOLS = {
     "hb_selftest_pairing": (_i, [_i, _vp, _i, _i64, _vp, _i64]),
     "hb_selftest_fxp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_bd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
+    "hb_selftest_demux": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_div": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_eq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_lt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),

@@ -584,6 +584,15 @@ class FixedPointArray:
 
         return await bit_decompose(self.co, self.shares, bits, triples, self.k, m, self.kappa)
 
+    async def lookup(self, table, m, bits, bd_triples, demux_triples):
+        """-> a (W, count, limbs) tensor of shares of row int(a * 2**f) of the public table (N, W), N <= 2^m, for a non-negative array
+        below 2^m (an index at or above N gives 0): bit_decomposition.bit_decompose, then demux.demux, then demux.lookup"""
+        from . import demux
+        from .bit_decomposition import bit_decompose
+
+        planes = await bit_decompose(self.co, self.shares, bits, bd_triples, self.k, m, self.kappa)
+        return demux.lookup(self.ctx, await demux.demux(self.co, planes, demux_triples), table)
+
     async def open(self):
         """-> list[float], decoded with the signed rule of FixedPoint.open (fixedpoint.py:253-257)"""
         opened = await self.co.open_share_array(self.shares)

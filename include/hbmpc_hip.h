@@ -505,6 +505,30 @@ int hb_bd_sum_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev,
 int hb_bd_sum_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m,
                       const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- one-hot demultiplexer of shared index bits (hb_demux.hip) ---------------------------------------------------------------
+ * From this party's shares of the m bits of an index s = sum_i 2^i b_i (rows of bits_dev, least significant first, 1 <= m <= 12),
+ * shares of e_j = [s == j], j < 2^m, for arrays of `count` indices; arrays of several rows are row-major with `count` elements a row.
+ * Level 0 starts from m groups of width 1; a level merges the groups (0, 1), (2, 3), .. counted from the least significant by a Beaver
+ * outer product -- a low group of wl bits with one-hot vector A and a high group of wh bits with vector B give
+ * out[hi 2^wl + lo] = A[lo] B[hi] -- and carries an odd last group unchanged: ceil(log2 m) levels.  A width-1 group is never stored, its
+ * vector (1 - b, b) is read from the bit plane.  Merged groups live in groups_dev, [sum over the levels of their products][count]: a
+ * level writes its merges in order from the row where the levels before it ended, and the last level's 2^m rows are the result.
+ * hb_demux_leaves  m == 1: out_dev [2][count] = (1 - b, b).
+ * hb_demux_mask    out_dev [sum (2^wl + 2^wh)][count], the level's ONE array to open: for each merge in order 2^wl rows A[lo] - P[lo],
+ *                  then 2^wh rows B[hi] - Q[hi]; ta_dev holds this party's shares of P then Q in exactly that row order.  groups_dev may
+ *                  be NULL at level 0 (every factor is a bit plane).
+ * hb_demux_finish  opened_dev = that array opened, tab_dev [sum 2^(wl + wh)][count] the triples' products, merge by merge, row
+ *                  hi 2^wl + lo = P[lo] Q[hi]: the level's rows of groups_dev = d_lo e_hi + d_lo Q_hi + e_hi P_lo + PQ.  Rows of other
+ *                  levels are left untouched.
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: m outside 1 .. 12, a
+ * level the wiring does not have, null pointers (with count > 0), a negative count, an output that overlaps an input;
+ * HB_ERR_UNSUPPORTED: a batch too large for one launch.  count == 0 returns HB_OK and launches nothing. */
+int hb_demux_leaves(hb_ctx *ctx, const uint64_t *bits_dev, uint64_t *out_dev, int64_t count, void *stream);
+int hb_demux_mask(hb_ctx *ctx, const uint64_t *bits_dev, const uint64_t *groups_dev, int m, int level, const uint64_t *ta_dev, uint64_t *out_dev,
+                  int64_t count, void *stream);
+int hb_demux_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tab_dev, int m, int level, uint64_t *groups_dev,
+                    int64_t count, void *stream);
+
 /* ---- division of shared fixed-point numbers by a shared divisor (hb_div.hip) ----------------------------------------------
  * Catrina and Saxena's FPDiv / AppRcr / Norm for signed k-bit values with f fractional bits, for arrays of `count` values; everything
  * between two opens is one launch.  Operands and results are canonical residues; arrays of several rows are row-major with `count`
@@ -1143,6 +1167,16 @@ int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 #define HB_BD_SELFTEST_SUM_COMBINE 4
 int hb_selftest_bd(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                    uint64_t *const *outs, int64_t count);
+/* host-side run of the demultiplexer's rows (no GPU needed) over host memory, a whole step at a time, with the index arithmetic and the
+ * argument checks of the entry points.  params = {m, level}:
+ *   what = HB_DEMUX_SELFTEST_LEAVES  operands[0] = bits [1][count]; outs[0] [2][count]; params are not read
+ *          HB_DEMUX_SELFTEST_MASK    operands[0..2] = bits [m][count], groups, ta; outs[0] as hb_demux_mask writes out_dev
+ *          HB_DEMUX_SELFTEST_FINISH  operands[0..2] = opened, ta, tab; outs[0] = groups, the level's rows updated in place */
+#define HB_DEMUX_SELFTEST_LEAVES 0
+#define HB_DEMUX_SELFTEST_MASK 1
+#define HB_DEMUX_SELFTEST_FINISH 2
+int hb_selftest_demux(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                      uint64_t *const *outs, int64_t count);
 /* host-side run of the division kernels' bodies (no GPU needed) over host memory, a whole level or step at a time; parameters are
  * checked as the device calls check them:
  *   what = HB_DIV_SELFTEST_OR_MASK       params = {n_planes, level, from_top}; operands[0..2] = y, ta, tb; outs[0] as hb_div_or_mask writes
