@@ -277,6 +277,7 @@ DEBUG_SYMBOLS = {
     "hb_debug_rf_profile": (None, [_i]),
     "hb_debug_mat_split": (None, [_i]),
     "hb_debug_matvec_route": (_i, [_vp, _vp, _i64, _vp]),
+    "hb_debug_fft_route": (_i, [_vp, _i, _i, _i, _vp]),
     "hb_debug_fs_pack_rows": (_i, [_i, _i, _i, _vp, _vp]),
     "hb_debug_fs_pack_points": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "hb_debug_fs_slot": (_i, [_i, _i, _vp, _i, _i, _vp]),

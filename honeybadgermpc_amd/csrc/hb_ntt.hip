@@ -423,6 +423,9 @@ template <int NL> static LazyConsts<NL> lazy_consts(hb_ctx *ctx) {
     return lc;
 }
 
+// polynomials a workgroup of the LDS launch takes when the batch holds that many (launch_ntt_lds and fft_route both ask here)
+static int ntt_lds_pb(int n) { const int pb = n <= 2048 ? 2048 / n : 1; return pb > 256 ? 256 : pb; }
+
 // LDS NTT launcher with views; returns HB_ERR_UNSUPPORTED when the order does not fit LDS
 int launch_ntt_lds(hb_ctx *ctx, const uint32_t *tw, int n, const uint32_t *in, hb_view iv, int64_t in_count, int d, int k,
                    uint32_t *out, hb_view ov, int64_t out_count, const int32_t *check_mask_dev, int32_t *mismatch_dev,
@@ -432,7 +435,7 @@ int launch_ntt_lds(hb_ctx *ctx, const uint32_t *tw, int n, const uint32_t *in, h
     const size_t elem_lds = (size_t)ctx->nl() * 4;
     // radix-8 units: n / 8 per polynomial and pass; 2048 / n polynomials give the 256 threads one unit each (72 KB of data:
     // two workgroups per CU)
-    int PB = n <= 2048 ? 2048 / n : 1; if (PB > 256) PB = 256;
+    int PB = ntt_lds_pb(n);
     if ((int64_t)PB > C) PB = (int)C;
     const size_t lds = ((size_t)PB * n + (size_t)(n > 1 ? n / 2 : 1)) * elem_lds + (size_t)PB * 4;
     if (lds > 160 * 1024) return fail(ctx, HB_ERR_UNSUPPORTED, "ntt: order does not fit LDS");
@@ -498,6 +501,34 @@ void host_pow2(const FpParams<NL> &P, const uint64_t *w_limbs, int e, uint64_t *
     for (int i = 0; i < NW / 2; i++) out_limbs[i] = (uint64_t)ww[2 * i] | ((uint64_t)ww[2 * i + 1] << 32);
 }
 
+// The path of an evaluation of order n = 2^logn with d coefficients and k outputs a polynomial (hb_fft_batch_evaluate takes its
+// decision here, hb_debug_fft_route reports it): r[0] = FFT_MATVEC .. FFT_STAGE_LOOP, r[1], r[2] = n1, n2 of the four-step,
+// r[3] = polynomials a workgroup of the LDS launch.
+enum { FFT_MATVEC = 0, FFT_LDS = 1, FFT_FOUR_STEP = 2, FFT_STAGE_LOOP = 3 };
+void fft_route(hb_ctx *ctx, int n, int logn, int d, int k, int32_t r[4]) {
+    r[0] = FFT_MATVEC; r[1] = r[2] = r[3] = 0;
+    const int dd = d < n ? d : n;
+    const int NLr = ctx->nl();
+    // cost model in v_mad_u64_u32 per polynomial (DESIGN.md): lazy mat-vec vs radix-2 butterflies
+    const double mads_prod = (double)NLr * NLr, mads_red = mads_prod + 4.0 * NLr;
+    const double cost_mv = (double)k * dd * mads_prod + (double)k * mads_red;
+    const double cost_ntt = 0.5 * n * logn * (mads_prod + mads_red);
+    const bool table_ok = (double)k * dd <= 4.0e6;   // matrix kept small
+    if (dd == 0 || (table_ok && cost_mv <= cost_ntt) || n == 1) return;
+    const size_t elem_lds = (size_t)NLr * 4;
+    if (((size_t)n + n / 2) * elem_lds <= 160 * 1024) {     // data + twiddles in LDS
+        r[0] = FFT_LDS; r[3] = ntt_lds_pb(n);
+        return;
+    }
+    // large order: four steps over the LDS kernel (n = n1 n2, both factors at most 2048)
+    if (logn <= 22 && !env_hook(ENV_NTT_STAGE_LOOP)) {
+        const int l1 = (logn + 1) / 2, l2 = logn - l1;
+        r[0] = FFT_FOUR_STEP; r[1] = 1 << l1; r[2] = 1 << l2;
+        return;
+    }
+    r[0] = FFT_STAGE_LOOP;                                  // HB_NTT_STAGE_LOOP=1, orders beyond 2^22
+}
+
 }  // namespace
 
 extern "C" {
@@ -512,13 +543,12 @@ int hb_fft_batch_evaluate(hb_ctx *ctx, const uint64_t *omega_host, int order, co
     const int n = order;
     int logn = 0; while ((1 << logn) < n) logn++;
     const int dd = d < n ? d : n;
-    const int NLr = ctx->nl();
-    // cost model in v_mad_u64_u32 per polynomial (DESIGN.md): lazy mat-vec vs radix-2 butterflies
-    const double mads_prod = (double)NLr * NLr, mads_red = mads_prod + 4.0 * NLr;
-    const double cost_mv = (double)k * dd * mads_prod + (double)k * mads_red;
-    const double cost_ntt = 0.5 * n * logn * (mads_prod + mads_red);
-    const bool table_ok = (double)k * dd <= 4.0e6;   // matrix kept small
-    if (dd == 0 || (table_ok && cost_mv <= cost_ntt) || n == 1) {
+    int32_t route[4];
+    fft_route(ctx, n, logn, d, k, route);
+    // no coefficient: every output is zero (k_matvec over an empty inner dimension would prefetch term 0 of a table and an input row that
+    // do not exist)
+    if (dd == 0) { HB_HIP(ctx, hipMemsetAsync(out_dev, 0, (size_t)C * k * ctx->elem_words() * 4, s)); return HB_OK; }
+    if (route[0] == FFT_MATVEC) {
         // Vandermonde matrix at x_i = omega^i, i < k, over the first dd coefficients
         std::string key = "W:" + std::to_string(n) + ":" + std::to_string(k) + ":" + std::to_string(dd) + ":";
         key.append(reinterpret_cast<const char *>(omega_host), (size_t)ctx->n_limbs * 8);
@@ -537,14 +567,13 @@ int hb_fft_batch_evaluate(hb_ctx *ctx, const uint64_t *omega_host, int order, co
     }
     uint32_t *tw = nullptr;
     int rc = get_twiddles(ctx, omega_host, n, &tw, s); if (rc) return rc;
-    const size_t elem_lds = (size_t)NLr * 4;
-    if (((size_t)n + n / 2) * elem_lds <= 160 * 1024) {     // data + twiddles in LDS
+    if (route[0] == FFT_LDS) {
         hb_view iv{d, 1}, ov{k, 1};
         return launch_ntt_lds(ctx, tw, n, (const uint32_t *)coeffs_dev, iv, INT64_MAX, d, k, (uint32_t *)out_dev, ov, INT64_MAX, nullptr, nullptr, C, s);
     }
     // large order: four steps over the LDS kernel (n = n1 n2, both factors at most 2048), one polynomial at a time
-    if (logn <= 22 && !env_hook(ENV_NTT_STAGE_LOOP)) {
-        const int l1 = (logn + 1) / 2, l2 = logn - l1, n1 = 1 << l1, n2 = 1 << l2;
+    if (route[0] == FFT_FOUR_STEP) {
+        const int n1 = route[1], n2 = route[2], l1 = (logn + 1) / 2, l2 = logn - l1;       // n1 = 2^l1, n2 = 2^l2
         uint64_t w1[4] = {0, 0, 0, 0}, w2[4] = {0, 0, 0, 0};           // omega^n2 (order n1), omega^n1 (order n2)
         if (ctx->n_limbs == 4) { host_pow2<9, 8>(ctx->pw, omega_host, l2, w1); host_pow2<9, 8>(ctx->pw, omega_host, l1, w2); }
         else { host_pow2<3, 2>(ctx->pn, omega_host, l2, w1); host_pow2<3, 2>(ctx->pn, omega_host, l1, w2); }
@@ -583,6 +612,7 @@ int hb_fft_batch_evaluate(hb_ctx *ctx, const uint64_t *omega_host, int order, co
         return HB_OK;                                   // asynchronous like the LDS path: the scratch is only touched in stream order
     }
     // (HB_NTT_STAGE_LOOP=1, orders beyond 2^22: stage by stage over a digit buffer in HBM)
+    const size_t elem_lds = (size_t)ctx->nl() * 4;
     if ((double)C * n * elem_lds > 64.0e9) return fail(ctx, HB_ERR_UNSUPPORTED, "fft: scratch too large");
     uint32_t *buf = nullptr;
     HB_HIP(ctx, hipMalloc(&buf, (size_t)C * n * elem_lds));
@@ -598,6 +628,14 @@ int hb_fft_batch_evaluate(hb_ctx *ctx, const uint64_t *omega_host, int order, co
     HB_LAUNCH_CHECK(ctx);
     HB_HIP(ctx, hipStreamSynchronize(s));
     HB_HIP(ctx, hipFree(buf));
+    return HB_OK;
+}
+
+// hbmpc_hip_debug.h: the route hb_fft_batch_evaluate takes, from the function it decides with; launches nothing
+int hb_debug_fft_route(hb_ctx *ctx, int order, int d, int k, int32_t *out) { HB_API_GUARD(ctx);
+    if (!ctx || !out || order <= 0 || (order & (order - 1)) || k < 0 || k > order || d < 0) return HB_ERR_BAD_ARG;
+    int logn = 0; while ((1 << logn) < order) logn++;
+    fft_route(ctx, order, logn, d, k, out);
     return HB_OK;
 }
 

@@ -44,6 +44,13 @@ void hb_debug_mat_split(int mode);
  * PEEL = out[4], K = out[1] / 4).  Builds the handle's int8 image if no launch has yet -- exactly as the first launch would, the
  * environment hooks of that moment included -- and launches no mat-vec.  out: int32[8], host. */
 int hb_debug_matvec_route(hb_ctx *ctx, const hb_matrix *m, int64_t C, int32_t *out);
+/* Which path an hb_fft_batch_evaluate of this order with d coefficients and k outputs a polynomial takes, asked of the call's own rule
+ * (fft_route, hb_ntt.hip: the call itself decides there), the environment hooks of the moment included; no launch.  out[0] = 0 the
+ * Vandermonde mat-vec at the powers of omega (d = 0: the outputs are zero-filled instead), 1 the whole transform in LDS (k_ntt_lds), 2 the four-step transform over it, 3 the stage
+ * loop over HBM (HB_NTT_STAGE_LOOP=1, orders beyond 2^22); out[1], out[2] = n1, n2 of the four-step (else 0); out[3] = polynomials a
+ * workgroup of the LDS launch takes when the batch holds at least as many (else 0).  The same argument checks as the call: HB_ERR_BAD_ARG
+ * where it would refuse.  out: int32[4], host. */
+int hb_debug_fft_route(hb_ctx *ctx, int order, int d, int k, int32_t *out);
 /* The packed last row tile of the fused decode + validate kernel (csrc/hb_mfma_fused.hip, FsPack), host arithmetic only.
  * hb_debug_fs_pack_rows: the decision for an image of n_coef coefficient rows (small[i] != 0: row i has no digit above the eighth) and nc
  * compared rows over d terms; returns 1 if the last tile packs, out[0] = merged rows, out[1] = single-group rows, out[2..9] = the

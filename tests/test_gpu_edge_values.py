@@ -271,8 +271,10 @@ def test_mimc_kernels_at_pool_values(p):
 @pytest.mark.parametrize("order", [8, 64, 512, 4096])
 @pytest.mark.parametrize("p", [BLS, GOLDILOCKS], ids=["bls", "goldilocks"])
 def test_ntt_at_edge_values(p, order):
-    """one, two and three radix-8 stages and the four-step transform: coefficients that are pool values, and coefficients chosen by the
-    inverse transform so that the OUTPUTS are pool values"""
+    """one, two, three and four radix-8 passes of the LDS kernel, and -- bls-4096 alone -- the four-step transform (4096 elements of 36 bytes
+    with their twiddles do not fit the LDS; Goldilocks' 12-byte elements do, so goldilocks-4096 is still the LDS kernel: the four-step on
+    1-limb contexts is test_gpu_ntt.py's): coefficients that are pool values, and coefficients chosen by the inverse transform so that the
+    OUTPUTS are pool values"""
     from honeybadgermpc_amd import ntl
 
     g = next(a for a in range(2, 1000) if pow(a, (p - 1) // 2, p) != 1)

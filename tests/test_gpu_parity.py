@@ -629,24 +629,41 @@ def test_fft_vs_oracle(hip, golden, n, d, k, c):
 
 def test_fft_four_step_equals_the_stage_loop_and_narrow_contexts(hip, monkeypatch):
     """the four-step transform against the stage-by-stage loop it replaces (HB_NTT_STAGE_LOOP=1), and on a 1-limb context
-    (p = 2^64 - 2^32 + 1, 2-adicity 32)"""
+    (p = 2^64 - 2^32 + 1, 2-adicity 32): order 8192 still fits the LDS kernel there (12-byte elements), order 2^14 is the first that takes
+    the four steps.  Which path a call takes is asked of the library (hb_debug_fft_route: 1 LDS, 2 four-step, 3 stage loop)."""
+    from honeybadgermpc_amd._capi import Context, np_ptr
     from honeybadgermpc_amd.field import GF
     from honeybadgermpc_amd.polynomial import get_omega
+
+    def route(p, order, d, k):
+        ctx = Context.get(p)
+        out = np.zeros(4, dtype=np.int32)
+        ctx.check(ctx.lib.hb_debug_fft_route(ctx.h, order, d, k, np_ptr(out)), "hb_debug_fft_route")
+        return [int(v) for v in out]
 
     n = 1 << 14
     omega = get_omega(GF(P), n, seed=0).value
     rnd = random.Random(14)
     rows = rand_rows(rnd, P, 2, 9000)
+    assert route(P, n, 9000, n) == [2, 128, 128, 0]
     got = hip.fft_batch_evaluate(rows, omega, P, n, n)
     set_hook(monkeypatch, "HB_NTT_STAGE_LOOP", "1")
+    assert route(P, n, 9000, n)[0] == 3
     assert hip.fft_batch_evaluate(rows, omega, P, n, n) == got
-    monkeypatch.delenv("HB_NTT_STAGE_LOOP")
+    clear_hook(monkeypatch, "HB_NTT_STAGE_LOOP")
+    assert route(P, n, 9000, n)[0] == 2
     gold = (1 << 64) - (1 << 32) + 1
     g = 7
     om = pow(g, (gold - 1) // 8192, gold)
     assert pow(om, 4096, gold) == gold - 1
     rows = rand_rows(rnd, gold, 3, 5000)
+    assert route(gold, 8192, 5000, 8192) == [1, 0, 0, 1]
     assert hip.fft_batch_evaluate(rows, om, gold, 8192, 8192) == oracle.fft_batch_evaluate(rows, om, gold, 8192, 8192)
+    om = pow(g, (gold - 1) // n, gold)
+    assert pow(om, n // 2, gold) == gold - 1
+    rows = rand_rows(rnd, gold, 3, 9000)
+    assert route(gold, n, 9000, n) == [2, 128, 128, 0]
+    assert hip.fft_batch_evaluate(rows, om, gold, n, n) == oracle.fft_batch_evaluate(rows, om, gold, n, n)
 
 
 def test_fft_small_primes(hip):
