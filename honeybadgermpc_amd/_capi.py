@@ -283,7 +283,11 @@ DEBUG_SYMBOLS = {
     "hb_debug_fs_slot": (_i, [_i, _i, _vp, _i, _i, _vp]),
     "hb_debug_fs_last_pack": (_i, []),
     "hb_debug_fs_last_mscale": (_i, []),
+    "hb_debug_pair_op": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_debug_g1_wire_op": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _vp]),
 }
+# the Fq operations hb_debug_pair_op and the self test's tower case take beside HB_PAIR_OP_* (hbmpc_hip_debug.h)
+HB_PAIR_OP_FQ_MUL, HB_PAIR_OP_FQ_MUL_LAZY, HB_PAIR_OP_FQ_INV = 17, 18, 19
 
 _lib = None
 

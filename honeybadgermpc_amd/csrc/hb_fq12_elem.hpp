@@ -1,6 +1,8 @@
 // hb_fq12_elem.hpp -- the tower Fq2 -> Fq6 -> Fq12 of BLS12-381 over the 14-digit Fq of hb_g1_elem.hpp, the Miller loop over prepared
 // G2 lines and the final exponentiation.  Host and device: k_pair_product of hb_pair.hip only loads, calls and stores, and
-// hb_selftest_pairing runs the same functions over host memory.
+// hb_selftest_pairing runs the same functions over host memory.  pair_tower_elem is ONE operation of the tower or of Fq on given
+// operands: the self test's tower case on the host and k_pair_op (hb_debug_pair_op) on the device both call it, so the device build of
+// these bodies -- fq_mul_call, the PAIR_FN calls, Fq12 values in private memory -- is tested at chosen operands, not only inside a pairing.
 //
 //   Fq2 = Fq[u] / (u^2 + 1),   Fq6 = Fq2[v] / (v^3 - (1 + u)),   Fq12 = Fq6[w] / (w^2 - v)           (the reference crate's tower)
 //
@@ -26,6 +28,7 @@
 // DESIGN 3x for the registers and bytes of scratch this costs and why it was kept.
 #pragma once
 #include "hb_g1_elem.hpp"
+#include "../../include/hbmpc_hip_debug.h"
 
 namespace hb {
 
@@ -435,6 +438,65 @@ HB_HD void fq12_store(uint32_t *p, const Fq12E &a, const FpParams<QL> &P) {
 HB_HD void pair_load_coef(Fq2E &r, const uint32_t *__restrict__ p) {
 #pragma unroll
     for (int q = 0; q < QL; q++) { r.c0[q] = p[q]; r.c1[q] = p[QL + q]; }
+}
+
+// ---------------------------------------------------------------- one operation of the tower, for the self test and k_pair_op
+// Does the operation read b?  And does it take this arg: the Frobenius power 1..3, the two shift counts of FQ_MUL_LAZY, else 0.
+HB_HD bool pair_op_two(int op) {
+    return op == HB_PAIR_OP_FQ2_MUL || op == HB_PAIR_OP_FQ6_MUL || op == HB_PAIR_OP_FQ12_MUL || op == HB_PAIR_OP_FQ6_MUL_BY_01 || op == HB_PAIR_OP_FQ6_MUL_BY_1 ||
+           op == HB_PAIR_OP_FQ12_MUL_BY_014 || op == HB_PAIR_OP_FQ_MUL || op == HB_PAIR_OP_FQ_MUL_LAZY;
+}
+HB_HD bool pair_op_arg_ok(int op, int64_t arg) {
+    if (op == HB_PAIR_OP_FQ12_FROBENIUS) return arg >= 1 && arg <= 3;
+    if (op == HB_PAIR_OP_FQ_MUL_LAZY) return arg >= 0 && (arg & ~0x33ll) == 0;
+    return arg == 0;
+}
+// r = k a, k = 2^sh, by doublings without the conditional subtraction: what the Karatsuba operand sums are made of (LAZY SUMS)
+HB_HD void fq_shift_lazy(uint32_t (&r)[QL], const uint32_t (&a)[QL], int sh) {
+    fp_set<QL>(r, a);
+#pragma unroll 1
+    for (int k = 0; k < sh; k++) fq_add_lazy(r, r, r);
+}
+// r = op(a, b): HB_PAIR_OP_* of hbmpc_hip.h and the Fq operations of hbmpc_hip_debug.h.  An operation on a smaller field takes the
+// leading coordinates and copies the rest of a through; MUL_BY_01 / MUL_BY_1 / MUL_BY_014 take their sparse factor from the head of b.
+// Returns false (r = a) for an unknown op or an arg the op does not take.  r is neither a nor b.
+HB_HD bool pair_tower_elem(Fq12E &r, const Fq12E &a, const Fq12E &b, int op, int64_t arg, const FpParams<QL> &P) {
+    fq12_set(r, a);
+    if (!pair_op_arg_ok(op, arg)) return false;
+    switch (op) {
+    case HB_PAIR_OP_FQ2_MUL: fq2_mul(r.c0.c0, a.c0.c0, b.c0.c0, P); break;
+    case HB_PAIR_OP_FQ2_SQR: fq2_sqr(r.c0.c0, a.c0.c0, P); break;
+    case HB_PAIR_OP_FQ2_MUL_NR: fq2_mul_nr(r.c0.c0, a.c0.c0, P); break;
+    case HB_PAIR_OP_FQ2_INV: fq2_inv(r.c0.c0, a.c0.c0, P); break;
+    case HB_PAIR_OP_FQ6_MUL: fq6_mul(r.c0, a.c0, b.c0, P); break;
+    case HB_PAIR_OP_FQ6_MUL_BY_01: fq6_mul_by_01(r.c0, a.c0, b.c0.c0, b.c0.c1, P); break;
+    case HB_PAIR_OP_FQ6_MUL_BY_1: fq6_mul_by_1(r.c0, a.c0, b.c0.c0, P); break;
+    case HB_PAIR_OP_FQ6_MUL_NR: fq6_mul_nr(r.c0, a.c0, P); break;
+    case HB_PAIR_OP_FQ6_INV: fq6_inv(r.c0, a.c0, P); break;
+    case HB_PAIR_OP_FQ12_MUL: fq12_mul(r, a, b, P); break;
+    case HB_PAIR_OP_FQ12_SQR: fq12_sqr(r, a, P); break;
+    case HB_PAIR_OP_FQ12_MUL_BY_014: fq12_mul_by_014(r, a, b.c0.c0, b.c0.c1, b.c0.c2, P); break;
+    case HB_PAIR_OP_FQ12_CONJ: fq12_conj(r, a, P); break;
+    case HB_PAIR_OP_FQ12_FROBENIUS:
+        if (arg == 1) fq12_frobenius<1>(r, a, P);
+        else if (arg == 2) fq12_frobenius<2>(r, a, P);
+        else fq12_frobenius<3>(r, a, P);
+        break;
+    case HB_PAIR_OP_FQ12_INV: fq12_inv(r, a, P); break;
+    case HB_PAIR_OP_FQ12_FINAL_EXP: fq12_final_exp(r, a, P); break;
+    case HB_PAIR_OP_FQ12_CYCLO_SQR: fq12_cyclo_sqr(r, a, P); break;
+    case HB_PAIR_OP_FQ_MUL: fq_mul(r.c0.c0.c0, a.c0.c0.c0, b.c0.c0.c0, P); break;
+    case HB_PAIR_OP_FQ_MUL_LAZY: {
+        uint32_t s[QL], t[QL];
+        fq_shift_lazy(s, a.c0.c0.c0, (int)(arg >> 4));
+        fq_shift_lazy(t, b.c0.c0.c0, (int)(arg & 3));
+        fq_mul(r.c0.c0.c0, s, t, P);
+        break;
+    }
+    case HB_PAIR_OP_FQ_INV: fq_inv(r.c0.c0.c0, a.c0.c0.c0, P); break;
+    default: return false;
+    }
+    return true;
 }
 
 // ---------------------------------------------------------------- the loop

@@ -28,8 +28,11 @@
 //                     held across it); status_i, the point or zeros, rejected items counted (atomicAdd).
 //                     Every lane runs the whole chain whatever its flags say: the loops are wave-uniform.
 //   k_g1_compress     words -> bytes and two comparisons: no field product
+//   k_g1_wire_op      hb_debug_g1_wire_op (hbmpc_hip_debug.h): the bare root (wire_sqrt_elem) or phi (g1_phi_elem) on the caller's operands,
+//                     the per-item functions of the self test's SQRT and PHI cases: for the tests
 // Compiler's report and timings: profiles/g1_wire.txt.
 #include "hb_g1_wire_elem.hpp"
+#include "../../include/hbmpc_hip_debug.h"
 
 using namespace hb;
 
@@ -55,6 +58,22 @@ __global__ void __launch_bounds__(256) k_g1_compress(const WireConsts K, const u
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     g1_compress_elem(enc + i * G1_ENC_WORDS, p + i * G1_PT, K);
+}
+
+// the bare root or phi on given operands (hb_debug_g1_wire_op): the per-item functions of the self test's SQRT and PHI cases
+__global__ void __launch_bounds__(256) k_g1_wire_op(const WireConsts K, int what, const uint32_t *__restrict__ in, uint32_t *__restrict__ out, int32_t *__restrict__ flags,
+                                                    int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const FpParams<QL> P = fq_params();
+    if (what == HB_G1_WIRE_SELFTEST_SQRT) {
+        const int32_t f = wire_sqrt_elem(out + i * QW, in + i * QW, K, P);
+        if (f < 0) {
+            const uint32_t z[QW] = {};
+            store_words<QW>(out + i * QW, z);
+        }
+        flags[i] = f;
+    } else g1_phi_elem(out + i * G1_PT, in + i * G1_PT, K, P);
 }
 
 // ---------------------------------------------------------------- host side
@@ -182,6 +201,21 @@ int hb_g1_compress(hb_ctx *ctx, const uint64_t *p_dev, void *bytes_dev, int64_t 
     return HB_OK;
 }
 
+// hbmpc_hip_debug.h: the bare square root or phi on the device at the caller's operands
+int hb_debug_g1_wire_op(hb_ctx *ctx, int what, const uint64_t *in_dev, uint64_t *out_dev, int32_t *flags_dev, int64_t count, void *stream) {
+    const bool root = what == HB_G1_WIRE_SELFTEST_SQRT;
+    G1_WIRE_ENTER("hb_debug_g1_wire_op", count, !in_dev || !out_dev || (root && !flags_dev));
+    if (!root && what != HB_G1_WIRE_SELFTEST_PHI) return fail(ctx, HB_ERR_BAD_ARG, "hb_debug_g1_wire_op: what is HB_G1_WIRE_SELFTEST_SQRT or HB_G1_WIRE_SELFTEST_PHI");
+    if (count == 0) return HB_OK;
+    if (!wire_aligned(in_dev) || !wire_aligned(out_dev)) return fail(ctx, HB_ERR_BAD_ARG, "hb_debug_g1_wire_op: the operands and the output must be aligned to 16 bytes");
+    const int64_t bytes = count * (root ? QW : G1_PT) * 4;
+    if (wire_overlap(out_dev, bytes, in_dev, bytes) || (root && (wire_overlap(flags_dev, count * 4, in_dev, bytes) || wire_overlap(flags_dev, count * 4, out_dev, bytes))))
+        return fail(ctx, HB_ERR_BAD_ARG, "hb_debug_g1_wire_op: an output overlaps the input or the other output");
+    k_g1_wire_op<<<blocks, 256, 0, s>>>(*K, what, (const uint32_t *)in_dev, (uint32_t *)out_dev, flags_dev, count);
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
 int hb_selftest_g1_wire(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count) {
     if (!operands || !operands[0] || count < 0 || !out || arg || !wire_aligned(operands[0]) || !wire_aligned(out)) return HB_ERR_BAD_ARG;
     const WireConsts *K = g1_wire_consts();
@@ -214,14 +248,9 @@ int hb_selftest_g1_wire(int what, const uint64_t *const *operands, int flags, in
         if (flags) return HB_ERR_BAD_ARG;
         int32_t *square = reinterpret_cast<int32_t *>(o + count * QW);
         for (int64_t i = 0; i < count; i++) {
-            uint32_t a[QL], y[QL];
-            load_digits<QL, QW>(a, in + i * QW);
-            if (!fq_below_q(a, P)) return HB_ERR_BAD_ARG;
-            fq_to_mont(a, a, P);
-            square[i] = fq_sqrt(y, a, K->S, P) ? 1 : 0;
-            fq_from_mont(a, y, P);
-            if (!square[i]) fq_zero(a);
-            store_digits<QL, QW>(o + i * QW, a);
+            const int32_t f = wire_sqrt_elem(o + i * QW, in + i * QW, *K, P);
+            if (f < 0) return HB_ERR_BAD_ARG;
+            square[i] = f;
         }
         return HB_OK;
     }

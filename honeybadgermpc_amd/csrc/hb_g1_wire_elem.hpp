@@ -59,6 +59,19 @@ HB_HD bool fq_sqrt(uint32_t (&y)[QL], const uint32_t (&a)[QL], const WireSched &
     fq_mul(t, y, y, P);
     return fp_eq<QL>(t, a);
 }
+// The bare root of six words of canonical residue (the self test's SQRT case and k_g1_wire_op): out = a^((Q + 1) / 4) if that squares
+// to a, else zero; returns 1 a square, 0 not, -1 for a not below Q (nothing written)
+HB_HD int32_t wire_sqrt_elem(uint32_t *out, const uint32_t *in, const WireConsts &K, const FpParams<QL> &P) {
+    uint32_t a[QL], y[QL];
+    load_digits<QL, QW>(a, in);
+    if (!fq_below_q(a, P)) return -1;
+    fq_to_mont(a, a, P);
+    const int32_t square = fq_sqrt(y, a, K.S, P) ? 1 : 0;
+    fq_from_mont(a, y, P);
+    if (!square) fq_zero(a);
+    store_digits<QL, QW>(out, a);
+    return square;
+}
 // x^3 + 4, Montgomery residues
 HB_HD void g1_curve_rhs(uint32_t (&r)[QL], const uint32_t (&x)[QL], const FpParams<QL> &P) {
     uint32_t four[QL];

@@ -19,6 +19,9 @@
 //
 // One lane an item, 64 lanes a workgroup.  An Fq12 is 168 words; the loop holds one, the final exponentiation five, and the Fq12
 // products are real calls (hb_fq12_elem.hpp), so these values live in private memory.  DESIGN 3x has the compiler's figures.
+//
+// k_pair_op (hb_debug_pair_op, hbmpc_hip_debug.h) is the tests' door to the same bodies: ONE tower or Fq operation a launch on the
+// caller's operands (pair_tower_elem, which the self test's tower case runs on the host), same geometry, a status an item.
 #include "hb_fq12_elem.hpp"
 
 using namespace hb;
@@ -42,6 +45,27 @@ __global__ void __launch_bounds__(PAIR_WG) k_pair_product(const uint32_t *__rest
         verdict[i] = v;
         if (!v) atomicAdd(rejected, 1);
     }
+}
+
+// One operation of the tower on given operands (hb_debug_pair_op): load, pair_tower_elem, store.  `two` and the validity of op and arg
+// are the host's; a lane whose residues are not all below Q computes on the reduced words, as k_pair_product does, and stores zeros.
+__global__ void __launch_bounds__(PAIR_WG) k_pair_op(int op, int64_t arg, int two, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out,
+                                                      int32_t *__restrict__ status, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * PAIR_WG + threadIdx.x;
+    if (i >= count) return;
+    const FpParams<QL> P = fq_params();
+    Fq12E x, y, r;
+    bool ok = fq12_load(x, a + i * GT_WORDS, P);
+    if (two) ok = fq12_load(y, b + i * GT_WORDS, P) && ok;
+    else fq12_set(y, x);
+    ok = pair_tower_elem(r, x, y, op, arg, P) && ok;
+    if (ok) fq12_store(out + i * GT_WORDS, r, P);
+    else {
+        const uint32_t z[QW] = {};
+#pragma unroll
+        for (int k = 0; k < 12; k++) store_words<QW>(out + i * GT_WORDS + k * QW, z);
+    }
+    status[i] = ok ? 1 : 0;
 }
 
 static bool pair_overlap(const void *a, int64_t na, const void *b, int64_t nb) {
@@ -100,6 +124,28 @@ int hb_pair_product(hb_ctx *ctx, const void *const *tables_dev, int K, const uin
     return HB_OK;
 }
 
+// hbmpc_hip_debug.h: one tower or Fq operation on the device at the caller's operands; the checks are hb_pair_product's
+int hb_debug_pair_op(hb_ctx *ctx, int op, int64_t arg, const uint64_t *a_dev, const uint64_t *b_dev, uint64_t *out_dev, int32_t *status_dev, int64_t count, void *stream) {
+    HB_API_GUARD(ctx);
+    { const int rc = g1_ctx_ok(ctx, "hb_debug_pair_op"); if (rc != HB_OK) return rc; }
+    if (!pair_consts_ok()) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_debug_pair_op: the Frobenius constants do not derive from Q");
+    if (op < 0 || op > HB_PAIR_OP_FQ_INV || !pair_op_arg_ok(op, arg)) return fail(ctx, HB_ERR_BAD_ARG, "hb_debug_pair_op: an unknown operation or an arg it does not take");
+    const bool two = pair_op_two(op);
+    if (count < 0 || (count > 0 && (!a_dev || (two && !b_dev) || !out_dev || !status_dev))) return fail(ctx, HB_ERR_BAD_ARG, "hb_debug_pair_op: a null pointer or a negative count");
+    if (count > (INT64_MAX >> 20) || (count + PAIR_WG - 1) / PAIR_WG > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_debug_pair_op: batch too large for one launch");
+    if (count == 0) return HB_OK;
+    if ((((uintptr_t)a_dev | (uintptr_t)(two ? b_dev : nullptr) | (uintptr_t)out_dev) & 15u) || ((uintptr_t)status_dev & 3u))
+        return fail(ctx, HB_ERR_BAD_ARG, "hb_debug_pair_op: the operands and the output must be aligned to 16 bytes");
+    const int64_t bytes = count * GT_WORDS * 4;
+    bool clash = pair_overlap(out_dev, bytes, a_dev, bytes) || pair_overlap(status_dev, count * 4, a_dev, bytes) || pair_overlap(status_dev, count * 4, out_dev, bytes);
+    if (two) clash = clash || pair_overlap(out_dev, bytes, b_dev, bytes) || pair_overlap(status_dev, count * 4, b_dev, bytes);
+    if (clash) return fail(ctx, HB_ERR_BAD_ARG, "hb_debug_pair_op: an output overlaps an input or the other output");
+    k_pair_op<<<(unsigned)((count + PAIR_WG - 1) / PAIR_WG), PAIR_WG, 0, (hipStream_t)stream>>>(op, arg, two ? 1 : 0, (const uint32_t *)a_dev, (const uint32_t *)(two ? b_dev : a_dev),
+                                                                                                 (uint32_t *)out_dev, status_dev, count);
+    HB_LAUNCH_CHECK(ctx);
+    return HB_OK;
+}
+
 int hb_selftest_pairing(int what, const uint64_t *const *operands, int flags, int64_t arg, uint64_t *out, int64_t count) {
     if (!operands || count < 0 || !out || !pair_consts_ok()) return HB_ERR_BAD_ARG;
     const FpParams<QL> P = fq_params();
@@ -109,40 +155,15 @@ int hb_selftest_pairing(int what, const uint64_t *const *operands, int flags, in
     switch (what) {
     case HB_PAIR_SELFTEST_TOWER: {
         // operands[0..1] = a, b: Fq12 elements, twelve residues each; an operation on a smaller field takes the leading coordinates and
-        // copies the rest of a through
-        const bool two = flags == HB_PAIR_OP_FQ2_MUL || flags == HB_PAIR_OP_FQ6_MUL || flags == HB_PAIR_OP_FQ12_MUL || flags == HB_PAIR_OP_FQ6_MUL_BY_01 ||
-                         flags == HB_PAIR_OP_FQ6_MUL_BY_1 || flags == HB_PAIR_OP_FQ12_MUL_BY_014;
-        if (!need(two ? 2 : 1) || (flags == HB_PAIR_OP_FQ12_FROBENIUS ? (arg < 1 || arg > 3) : arg != 0)) return HB_ERR_BAD_ARG;
+        // copies the rest of a through; flags also takes the Fq operations of hbmpc_hip_debug.h (pair_tower_elem, which k_pair_op runs too)
+        const bool two = pair_op_two(flags);
+        if (!need(two ? 2 : 1) || !pair_op_arg_ok(flags, arg)) return HB_ERR_BAD_ARG;
         for (int64_t i = 0; i < count; i++) {
             Fq12E a, b, r;
             if (!fq12_load(a, U(0) + i * GT_WORDS, P)) return HB_ERR_BAD_ARG;
             if (two) { if (!fq12_load(b, U(1) + i * GT_WORDS, P)) return HB_ERR_BAD_ARG; }
             else fq12_set(b, a);
-            fq12_set(r, a);
-            switch (flags) {
-            case HB_PAIR_OP_FQ2_MUL: fq2_mul(r.c0.c0, a.c0.c0, b.c0.c0, P); break;
-            case HB_PAIR_OP_FQ2_SQR: fq2_sqr(r.c0.c0, a.c0.c0, P); break;
-            case HB_PAIR_OP_FQ2_MUL_NR: fq2_mul_nr(r.c0.c0, a.c0.c0, P); break;
-            case HB_PAIR_OP_FQ2_INV: fq2_inv(r.c0.c0, a.c0.c0, P); break;
-            case HB_PAIR_OP_FQ6_MUL: fq6_mul(r.c0, a.c0, b.c0, P); break;
-            case HB_PAIR_OP_FQ6_MUL_BY_01: fq6_mul_by_01(r.c0, a.c0, b.c0.c0, b.c0.c1, P); break;
-            case HB_PAIR_OP_FQ6_MUL_BY_1: fq6_mul_by_1(r.c0, a.c0, b.c0.c0, P); break;
-            case HB_PAIR_OP_FQ6_MUL_NR: fq6_mul_nr(r.c0, a.c0, P); break;
-            case HB_PAIR_OP_FQ6_INV: fq6_inv(r.c0, a.c0, P); break;
-            case HB_PAIR_OP_FQ12_MUL: fq12_mul(r, a, b, P); break;
-            case HB_PAIR_OP_FQ12_SQR: fq12_sqr(r, a, P); break;
-            case HB_PAIR_OP_FQ12_MUL_BY_014: fq12_mul_by_014(r, a, b.c0.c0, b.c0.c1, b.c0.c2, P); break;
-            case HB_PAIR_OP_FQ12_CONJ: fq12_conj(r, a, P); break;
-            case HB_PAIR_OP_FQ12_FROBENIUS:
-                if (arg == 1) fq12_frobenius<1>(r, a, P);
-                else if (arg == 2) fq12_frobenius<2>(r, a, P);
-                else fq12_frobenius<3>(r, a, P);
-                break;
-            case HB_PAIR_OP_FQ12_INV: fq12_inv(r, a, P); break;
-            case HB_PAIR_OP_FQ12_FINAL_EXP: fq12_final_exp(r, a, P); break;
-            case HB_PAIR_OP_FQ12_CYCLO_SQR: fq12_cyclo_sqr(r, a, P); break;
-            default: return HB_ERR_BAD_ARG;
-            }
+            if (!pair_tower_elem(r, a, b, flags, arg, P)) return HB_ERR_BAD_ARG;
             fq12_store(o + i * GT_WORDS, r, P);
         }
         return HB_OK;

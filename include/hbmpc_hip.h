@@ -1113,6 +1113,7 @@ int hb_selftest_g1_wire(int what, const uint64_t *const *operands, int flags, in
  *                                    MUL_BY_01 / MUL_BY_1 / MUL_BY_014 take their sparse factor's Fq2 coefficients from the head of b.
  *                                    FROBENIUS: arg = 1, 2 or 3.  FINAL_EXP: out = a^(3 (Q^12 - 1) / R).
  *                                    CYCLO_SQR: Granger and Scott's squaring, a square only for a in the cyclotomic subgroup.
+ *                                    flags also takes the three Fq operations of hbmpc_hip_debug.h (coordinate 0 alone).
  *          HB_PAIR_SELFTEST_PREPARE  operands[0] = the 204 Fq2 coefficients hb_pair_prepare takes; count = 1; out = the table
  *          HB_PAIR_SELFTEST_PRODUCT  operands[0] = points (count, K, 12), operands[1..K] = tables; flags = K; arg = mode; out = GT
  *                                    elements, or `count` int32 verdicts then the int32 count of rejected items */

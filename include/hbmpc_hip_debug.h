@@ -66,6 +66,34 @@ int hb_debug_fs_pack_points(const int32_t *xz, int d, int n_coef, int nc, int32_
 int hb_debug_fs_slot(int nm, int ns, const int32_t *single, int i, int n_out, int32_t *kind);
 int hb_debug_fs_last_pack(void);
 int hb_debug_fs_last_mscale(void);
+/* The tower bodies of csrc/hb_fq12_elem.hpp on the DEVICE, one operation a launch: what hb_selftest_pairing(HB_PAIR_SELFTEST_TOWER) runs
+ * on the host (the same function, pair_tower_elem), so that the device build of the Fq, Fq2, Fq6 and Fq12 code can be fed chosen operands
+ * instead of what a Miller loop happens to produce.  k_pair_op: 64-lane workgroups, one item a lane, as k_pair_product.
+ *   op     an HB_PAIR_OP_* of hbmpc_hip.h (arg as there: the Frobenius power, else 0) or one of the three Fq operations below, which
+ *          work on coordinate 0 of a (and of b) and copy the other eleven coordinates of a through:
+ *            HB_PAIR_OP_FQ_MUL       a0 b0 mod Q: to Montgomery form, one fq_mul, back; arg = 0
+ *            HB_PAIR_OP_FQ_MUL_LAZY  arg = 16 log2(ka) + log2(kb), ka, kb in {1, 2, 4, 8}: ka a0 and kb b0 formed by fq_add_lazy doublings of
+ *                                    the Montgomery residues (no conditional subtraction: the Karatsuba factor sums of the tower, up to
+ *                                    8 Q), ONE fq_mul, back: ka kb a0 b0 mod Q
+ *            HB_PAIR_OP_FQ_INV       1 / a0 mod Q, 0 -> 0; arg = 0
+ *          The self test takes these three op codes too.
+ *   a_dev, b_dev, out_dev  72 words an item, twelve residues; b_dev is read by the two-operand operations only (may be null otherwise)
+ *   status_dev[i] = 1 if every residue of item i that was read is below Q, else 0 and the item's output is zero-filled
+ * HB_ERR_BAD_ARG: an unknown op, an arg the op does not take, a null pointer, a negative count, a pointer not aligned to 16 bytes, an
+ * output overlapping an input or the other output.  A zero count returns HB_OK and launches nothing.  A context over R in four limbs, as
+ * hb_pair_product; asynchronous on `stream`, nothing allocated. */
+#define HB_PAIR_OP_FQ_MUL 17
+#define HB_PAIR_OP_FQ_MUL_LAZY 18
+#define HB_PAIR_OP_FQ_INV 19
+int hb_debug_pair_op(hb_ctx *ctx, int op, int64_t arg, const uint64_t *a_dev, const uint64_t *b_dev, uint64_t *out_dev, int32_t *status_dev, int64_t count, void *stream);
+/* The bare square root and endomorphism of csrc/hb_g1_wire_elem.hpp on the DEVICE: the per-item functions of the self test's
+ * HB_G1_WIRE_SELFTEST_SQRT and HB_G1_WIRE_SELFTEST_PHI cases (`what` is one of the two), 256-lane workgroups, one item a lane.
+ *   SQRT  in_dev: 6 words an item, a residue a; out_dev: 6 words, a^((Q + 1) / 4) if that squares to a, else zero; flags_dev[i] = 1 a
+ *         square, 0 not, -1 a not below Q (output zero)
+ *   PHI   in_dev, out_dev: 12 words an item, a point (x, y) -> (beta x, y); flags_dev is not used and may be null
+ * HB_ERR_BAD_ARG: another `what`, a null pointer, a negative count, a pointer not aligned to 16 bytes, overlapping buffers.  A zero count
+ * returns HB_OK and launches nothing.  A context over R in four limbs. */
+int hb_debug_g1_wire_op(hb_ctx *ctx, int what, const uint64_t *in_dev, uint64_t *out_dev, int32_t *flags_dev, int64_t count, void *stream);
 
 
 #ifdef __cplusplus

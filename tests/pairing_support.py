@@ -50,6 +50,13 @@ def tower(op, a, b=None, arg=0):
     return gt_unwords(out[:72 * len(a)])
 
 
+def tower_words(op, a, b=None, arg=0):
+    """the same on (count, 72) uint64 words -> (count, 72) uint64"""
+    rc, out = selftest(TOWER, [a] + ([b] if b is not None else []), op, arg, len(a), 72 * len(a))
+    assert rc == 0, (op, rc)
+    return out[:72 * len(a)].reshape(len(a), 72)
+
+
 def coeff_words(q):
     """the 204 Fq2 coefficients of a host G2 as hb_pair_prepare takes them"""
     return s.words([v for triple in prepare_g2(q) for c in triple for v in (c.c0, c.c1)], 6)

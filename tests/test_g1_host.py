@@ -5,6 +5,7 @@ import random
 import numpy as np
 import pytest
 
+import fq_cases as fc
 import g1_support as s
 from g1_support import ADD, CHECK, COMMIT, DOUBLE, EVAL, FQ_MUL, GENERAL, K_BCAST, P_BCAST, SCALAR_MUL, SUBTRACT, TABLE, VERIFY
 
@@ -13,8 +14,7 @@ from honeybadgermpc_amd.bls12_381 import G1, Q, R
 
 def test_fq_products():
     rnd = random.Random(11)
-    ones13 = (1 << 377) - 1                                  # thirteen 29-bit digits of all ones, the top digit 0
-    ones_top = (0xC << 377) | ones13                         # ... and the largest top digit below Q's
+    ones13, ones_top = fc.ONES13, fc.ONES_TOP                # thirteen 29-bit digits of all ones, the top digit 0 or the largest below Q's
     assert ones13 < ones_top < Q
     a = [rnd.randrange(Q) for _ in range(200)] + [Q - 1, 0, ones13, ones_top, ones13, Q - 1, 1]
     b = [rnd.randrange(Q) for _ in range(200)] + [Q - 1, Q - 1, ones13, ones_top, ones_top, ones_top, Q - 1]
@@ -22,6 +22,17 @@ def test_fq_products():
     assert rc == 0 and s.unwords(out[:6 * len(a)], 6) == [x * y % Q for x, y in zip(a, b)]
     rc, _ = s.selftest(FQ_MUL, [s.words([Q], 6), s.words([1], 6)], 0, 0, 1, 6)
     assert rc != 0                                           # operands are residues below Q
+
+
+def test_fq_products_over_every_ordered_pair_of_the_edge_pool():
+    """fq_mul at fq_cases.fq_edge_pool(): digit and word boundaries, Q - 1, all-ones digits and the Montgomery pre-images of all of them;
+    the pairing self test runs the same pairs through the tower's entry (test_pairing_host.py), the device through hb_debug_pair_op"""
+    pool = fc.fq_edge_pool()
+    w = s.words(pool, 6)
+    n = len(pool)
+    ia, ib = np.repeat(np.arange(n), n), np.tile(np.arange(n), n)
+    rc, out = s.selftest(FQ_MUL, [w[ia], w[ib]], 0, 0, n * n, 6 * n * n)
+    assert rc == 0 and s.unwords(out[:6 * n * n], 6) == [x * y % Q for x in pool for y in pool]
 
 
 @pytest.mark.parametrize("flags", [0, SUBTRACT, GENERAL, GENERAL | SUBTRACT], ids=["mixed", "mixed-sub", "general", "general-sub"])

@@ -11,17 +11,17 @@ import os
 import random
 import re
 
+import numpy as np
 import pytest
 
+import fq_cases as fc
 import pairing_support as ps
 from conftest import GOLDEN, REPO
+from fq_cases import OPS
 
 from honeybadgermpc_amd import _capi
 from honeybadgermpc_amd.bls12_381 import G1, Q, R
 from honeybadgermpc_amd.bls12_381_pairing import BLS_X, FROBENIUS_FQ12_C1, Fq2, Fq6, Fq12, G2, N_LINES, final_exponentiation, pair, pairing_product, prepare_g2
-
-OPS = dict(FQ2_MUL=0, FQ2_SQR=1, FQ2_MUL_NR=2, FQ2_INV=3, FQ6_MUL=4, FQ6_MUL_BY_01=5, FQ6_MUL_BY_1=6, FQ6_MUL_NR=7, FQ6_INV=8, FQ12_MUL=9, FQ12_SQR=10,
-           FQ12_MUL_BY_014=11, FQ12_CONJ=12, FQ12_FROBENIUS=13, FQ12_INV=14, FQ12_FINAL_EXP=15, FQ12_CYCLO_SQR=16)
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,54 +92,18 @@ def test_model_tower_laws():
 
 
 # ---------------------------------------------------------------- the self test (the kernels' bodies on the host) against the model
-def _rand12(rnd):
-    return Fq12.from_coords([rnd.randrange(Q) for _ in range(12)])
-
-
-def _edge_operands():
-    """Fq12 operands: random ones, then 0, 1 and Q - 1 in every coordinate in turn (the others random), then all-equal edge values"""
-    rnd = random.Random(5)
-    out = [_rand12(rnd) for _ in range(4)]
-    for k in range(12):
-        for v in (0, 1, Q - 1):
-            co = [rnd.randrange(Q) for _ in range(12)]
-            co[k] = v
-            out.append(Fq12.from_coords(co))
-    out += [Fq12.from_coords([v] * 12) for v in (0, 1, Q - 1)] + [Fq12.one()]
-    return out
-
-
-def _model_op(name, a, b, arg):
-    f2 = lambda x: Fq12(Fq6(x, a.c0.c1, a.c0.c2), a.c1)
-    f6 = lambda x: Fq12(x, a.c1)
-    return {
-        "FQ2_MUL": lambda: f2(a.c0.c0 * b.c0.c0),
-        "FQ2_SQR": lambda: f2(a.c0.c0.square()),
-        "FQ2_MUL_NR": lambda: f2(a.c0.c0.mul_by_nonresidue()),
-        "FQ2_INV": lambda: f2(a.c0.c0.inverse()),
-        "FQ6_MUL": lambda: f6(a.c0 * b.c0),
-        "FQ6_MUL_BY_01": lambda: f6(a.c0.mul_by_01(b.c0.c0, b.c0.c1)),
-        "FQ6_MUL_BY_1": lambda: f6(a.c0.mul_by_1(b.c0.c0)),
-        "FQ6_MUL_NR": lambda: f6(a.c0.mul_by_nonresidue()),
-        "FQ6_INV": lambda: f6(a.c0.inverse()),
-        "FQ12_MUL": lambda: a * b,
-        "FQ12_SQR": lambda: a.square(),
-        "FQ12_MUL_BY_014": lambda: a.mul_by_014(b.c0.c0, b.c0.c1, b.c0.c2),
-        "FQ12_CONJ": lambda: a.conjugate(),
-        "FQ12_FROBENIUS": lambda: a.frobenius_map(arg),
-        "FQ12_INV": lambda: a.inverse(),
-    }[name]()
+_rand12 = fc.rand12
 
 
 @pytest.mark.parametrize("name", [n for n in OPS if n not in ("FQ12_FINAL_EXP", "FQ12_CYCLO_SQR")])
 def test_selftest_tower_operation_matches_the_model(name):
-    a = _edge_operands()
-    b = a[1:] + a[:1]
-    two = name in ("FQ2_MUL", "FQ6_MUL", "FQ6_MUL_BY_01", "FQ6_MUL_BY_1", "FQ12_MUL", "FQ12_MUL_BY_014")
+    """over fq_cases.tower_operands(): the random and 0 / 1 / Q - 1 operands, every value of the Fq edge pool at every coordinate, and
+    the sparse elements; b is the list rotated by one"""
     for arg in ((1, 2, 3) if name == "FQ12_FROBENIUS" else (0,)):
-        got = ps.tower(OPS[name], a, b if two else None, arg)
-        want = [_model_op(name, x, y, arg) for x, y in zip(a, b)]
-        assert got == want, (name, arg)
+        a, b, want = fc.tower_case(name, arg)
+        got = ps.tower_words(OPS[name], a, b, arg)
+        assert np.array_equal(got, want), (name, arg, [int(i) for i in np.nonzero((got != want).any(axis=1))[0]])
+    assert len(fc.tower_operands()) > 64 + len(fc.fq_edge_pool())
 
 
 def test_selftest_inverse_with_c1_zero_and_frobenius_twelve_times():
@@ -159,16 +123,55 @@ def test_selftest_cyclotomic_squaring_equals_the_plain_one_after_the_easy_part()
     """Granger and Scott's squaring (the powers by |x| of the final exponentiation use it) is a squaring only in the cyclotomic subgroup:
     compared with fq12_sqr and with the model on elements that have been through the easy part f^((Q^6 - 1)(Q^2 + 1)), edge coordinates in
     the inputs included, and on 1; on an element outside the subgroup the two differ."""
-    def easy(f):
-        r = f.conjugate() * f.inverse()
-        return r.frobenius_map(2) * r
-
-    raw = [x for x in _edge_operands()[:12] if not (x.c0.is_zero() and x.c1.is_zero())]
-    cyc = [easy(x) for x in raw] + [Fq12.one()]
+    raw, cyc = fc.cyclotomic_operands()
     got = ps.tower(OPS["FQ12_CYCLO_SQR"], cyc)
     assert got == ps.tower(OPS["FQ12_SQR"], cyc) == [x.square() for x in cyc]
     assert all((x.conjugate() * x).is_one() for x in cyc)              # x^(Q^6 + 1) = 1
     assert ps.tower(OPS["FQ12_CYCLO_SQR"], raw[:1]) != ps.tower(OPS["FQ12_SQR"], raw[:1])
+
+
+# ---------------------------------------------------------------- the Fq operations of the debug header, through the same self test
+def test_selftest_fq_mul_over_every_ordered_pair_of_the_edge_pool():
+    a, b, want = fc.fq_mul_case()
+    assert len(a) == len(fc.fq_edge_pool()) ** 2 > 10000
+    got = ps.tower_words(fc.FQ_OPS["FQ_MUL"], a, b)
+    assert np.array_equal(got, want), [int(i) for i in np.nonzero((got != want).any(axis=1))[0]][:8]
+    assert np.array_equal(got[:, 6:], a[:, 6:]) and a[:, 6:].any()           # the other eleven coordinates are copied through
+
+
+@pytest.mark.parametrize("sa", range(4))
+@pytest.mark.parametrize("sb", range(4))
+def test_selftest_fq_mul_of_lazy_operand_sums_up_to_eight_q(sa, sb):
+    """ka a and kb b formed without a conditional subtraction, as the Karatsuba factor sums are; with the pre-image of Q - 1 the
+    Montgomery digits are Q - 1 themselves and sa = sb = 3 multiplies 8 (Q - 1) by 8 (Q - 1): the bound LAZY SUMS states"""
+    arg, a, b, want = fc.fq_mul_lazy_case(sa, sb)
+    assert len(a) == 36 and fc.pre_image(Q - 1) * fc.MONT % Q == Q - 1
+    got = ps.tower_words(fc.FQ_OPS["FQ_MUL_LAZY"], a, b, arg)
+    assert np.array_equal(got, want), (sa, sb, [int(i) for i in np.nonzero((got != want).any(axis=1))[0]])
+
+
+def test_selftest_fq_inverse_over_the_edge_pool():
+    a, want = fc.fq_inv_case()
+    got = ps.tower_words(fc.FQ_OPS["FQ_INV"], a)
+    assert np.array_equal(got, want)
+    x, y = ps.s.unwords(a[:, :6], 6), ps.s.unwords(got[:, :6], 6)
+    assert all((u * v % Q == 1) if u else (v == 0) for u, v in zip(x, y)) and 0 in x
+
+
+def test_edge_pool_holds_what_it_claims():
+    pool = fc.fq_edge_pool()
+    assert list(pool) == sorted(set(pool)) and pool[0] == 0 and pool[-1] == Q - 1
+    for v in (1, 2, Q - 2, (Q - 1) // 2, (Q + 1) // 2, fc.ONES13, fc.ONES_TOP, (1 << 29) - 1, (1 << 377) + 1, (1 << 352) - 1, (1 << 384) % Q):
+        assert v in pool and fc.pre_image(v) in pool
+    n = len(pool)
+    walk = fc.tower_operands()[len(fc.edge_operands()):len(fc.edge_operands()) + n]
+    for k in (0, 5, 11):                                                     # every value sits at every coordinate once
+        assert sorted(x.coords()[k] for x in walk) == list(pool)
+    assert _capi.HB_PAIR_OP_FQ_MUL == 17 and _capi.HB_PAIR_OP_FQ_MUL_LAZY == 18 and _capi.HB_PAIR_OP_FQ_INV == 19
+    with open(os.path.join(REPO, "include", "hbmpc_hip_debug.h")) as f:
+        text = f.read()
+    for name, value in fc.FQ_OPS.items():
+        assert re.search(r"#define HB_PAIR_OP_" + name + r" " + str(value) + r"\b", text)
 
 
 def test_selftest_refuses_bad_arguments():
@@ -176,6 +179,11 @@ def test_selftest_refuses_bad_arguments():
     assert ps.selftest(ps.TOWER, [a], 99, 0, 1, 72)[0] == _capi.HB_ERR_BAD_ARG
     assert ps.selftest(ps.TOWER, [a], OPS["FQ12_FROBENIUS"], 4, 1, 72)[0] == _capi.HB_ERR_BAD_ARG
     assert ps.selftest(ps.TOWER, [a], OPS["FQ12_MUL"], 0, 1, 72)[0] == _capi.HB_ERR_BAD_ARG        # the second operand is missing
+    assert ps.selftest(ps.TOWER, [a], fc.FQ_OPS["FQ_MUL"], 0, 1, 72)[0] == _capi.HB_ERR_BAD_ARG
+    assert ps.selftest(ps.TOWER, [a], fc.FQ_OPS["FQ_INV"], 1, 1, 72)[0] == _capi.HB_ERR_BAD_ARG
+    for arg in (-1, 4, 0x40, 0x133):                                       # the shift counts are two bits each
+        assert ps.selftest(ps.TOWER, [a, a], fc.FQ_OPS["FQ_MUL_LAZY"], arg, 1, 72)[0] == _capi.HB_ERR_BAD_ARG
+    assert ps.selftest(ps.TOWER, [a], 20, 0, 1, 72)[0] == _capi.HB_ERR_BAD_ARG
     big = a.copy()
     big[0, :6] = ps.s.words([Q], 6)[0]
     assert ps.selftest(ps.TOWER, [big], OPS["FQ12_SQR"], 0, 1, 72)[0] == _capi.HB_ERR_BAD_ARG     # a residue not below Q
