@@ -215,129 +215,121 @@ struct BdSumCombineRow {
     }
 };
 
-// ---------------------------------------------------------------- host: the same rows over `count` elements
-template <int NL, int NW>
-static int selftest_bd(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    FpParams<NL> P;
-    fp_params_from_limbs(P, p_limbs);
-    const int m = (int)params[0], l = (int)params[1], n = m - 1;
-    if (what == HB_BD_SELFTEST_LEAVES) {
-        const LeavesArgs A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1]), m};
-        host_rows<BdLeavesRow, NL, NW>(A, n ? 1 : 0, count, P);                  // m == 1: no plane, and c is not looked at
-    } else if (what == HB_BD_SELFTEST_PREFIX_MASK) {
-        const BdPrefixArgs A = {nullptr, u32(ops[2]), u32(ops[3]), nullptr, const_cast<uint32_t *>(u32(ops[0])), const_cast<uint32_t *>(u32(ops[1])), u32(outs[0]), l, bd_g_only(n, l)};
-        host_rows<BdPrefixMaskRow, NL, NW>(A, bd_level_triples(n, l), count, P);
-    } else if (what == HB_BD_SELFTEST_PREFIX_COMBINE) {
-        const BdPrefixArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0]), u32(outs[1]), nullptr, l, bd_g_only(n, l)};
-        host_rows<BdPrefixCombineRow, NL, NW>(A, bd_active(n, l), count, P);
-    } else if (what == HB_BD_SELFTEST_SUM_MASK) {
-        const BdSumArgs A = {nullptr, u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), nullptr, u32(outs[0]), nullptr};
-        host_rows<BdSumMaskRow, NL, NW>(A, n, count, P);
-    } else {
-        const BdSumArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), nullptr, u32(outs[0])};
-        host_rows<BdSumCombineRow, NL, NW>(A, m, count, P);
-    }
-    return HB_OK;
-}
-
+// ---------------------------------------------------------------- host side
+// One step function a step (hb_rows.hpp): its checks, Args fill and row count run under a DeviceRun in the entry point, a HostRun in hb_selftest_bd.
 // m within the modulus and at most 256 planes
 static bool bd_m_ok(int bits, int m) { return fxp_m_ok(bits, m) && m - 1 <= 256; }
 static bool bd_level_ok(int m, int level) { return level >= 0 && level < bd_levels(m - 1); }
+
+template <class Run> static int bd_leaves_step(const Run &run, const uint64_t *c, const uint64_t *bits, int m, uint64_t *g, uint64_t *p, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    if (!bd_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_leaves: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (count > 0 && m > 1 && (!c || !bits || !g || !p)) return HB_ERR_BAD_ARG;
+    if (count == 0 || m == 1) return HB_OK;
+    const RowSpan outs[2] = {{g, m - 1}, {p, m - 1}}, ins[2] = {{c, 1}, {bits, m - 1}};
+    if (!outputs_apart(outs, 2, ins, 2, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_leaves: g and p are arrays of their own");
+    return run_leaves<BdLeavesRow>(run, {u32(c), u32(bits), u32(g), u32(p), m}, count);
+}
+
+template <class Run> static int bd_prefix_mask_step(const Run &run, const uint64_t *g, const uint64_t *p, int m, int level, const uint64_t *ta, const uint64_t *tb,
+                                                    uint64_t *masked, int64_t count) {
+    if (count < 0 || (count > 0 && (!g || !p || !ta || !tb || !masked))) return HB_ERR_BAD_ARG;
+    if (!bd_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_prefix_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (!bd_level_ok(m, level)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_prefix_mask: no such level");
+    if (count == 0) return HB_OK;
+    const int n = m - 1, triples = bd_level_triples(n, level);
+    const RowSpan outs[1] = {{masked, 2 * triples}}, ins[4] = {{g, n}, {p, n}, {ta, triples}, {tb, triples}};
+    if (!outputs_apart(outs, 1, ins, 4, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_prefix_mask: masked is an array of its own");
+    const BdPrefixArgs A = {nullptr, u32(ta), u32(tb), nullptr, const_cast<uint32_t *>(u32(g)), const_cast<uint32_t *>(u32(p)), u32(masked), level,
+                            bd_g_only(n, level)};
+    return run.template rows<BdPrefixMaskRow>(A, triples, count);
+}
+
+template <class Run> static int bd_prefix_combine_step(const Run &run, const uint64_t *opened, uint64_t *g, uint64_t *p, int m, int level, const uint64_t *ta,
+                                                       const uint64_t *tb, const uint64_t *tab, int64_t count) {
+    if (count < 0 || (count > 0 && (!opened || !g || !p || !ta || !tb || !tab))) return HB_ERR_BAD_ARG;
+    if (!bd_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_prefix_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (!bd_level_ok(m, level)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_prefix_combine: no such level");
+    if (count == 0) return HB_OK;
+    const int n = m - 1, triples = bd_level_triples(n, level);
+    const RowSpan outs[2] = {{g, n}, {p, n}}, ins[4] = {{opened, 2 * triples}, {ta, triples}, {tb, triples}, {tab, triples}};
+    if (!outputs_apart(outs, 2, ins, 4, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_prefix_combine: g and p are arrays of their own");
+    const BdPrefixArgs A = {u32(opened), u32(ta), u32(tb), u32(tab), u32(g), u32(p), nullptr, level, bd_g_only(n, level)};
+    return run.template rows<BdPrefixCombineRow>(A, bd_active(n, level), count);
+}
+
+template <class Run> static int bd_sum_mask_step(const Run &run, const uint64_t *c, const uint64_t *bits, const uint64_t *g, int m, const uint64_t *ta,
+                                                 const uint64_t *tb, uint64_t *masked, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    if (!bd_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_sum_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (count > 0 && m > 1 && (!c || !bits || !g || !ta || !tb || !masked)) return HB_ERR_BAD_ARG;
+    if (count == 0 || m == 1) return HB_OK;
+    const RowSpan outs[1] = {{masked, 2 * (m - 1)}}, ins[5] = {{c, 1}, {bits, m}, {g, m - 1}, {ta, m - 1}, {tb, m - 1}};
+    if (!outputs_apart(outs, 1, ins, 5, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_sum_mask: masked is an array of its own");
+    const BdSumArgs A = {nullptr, u32(c), u32(bits), u32(g), u32(ta), u32(tb), nullptr, u32(masked), nullptr};
+    return run.template rows<BdSumMaskRow>(A, m - 1, count);
+}
+
+template <class Run> static int bd_sum_combine_step(const Run &run, const uint64_t *opened, const uint64_t *c, const uint64_t *bits, const uint64_t *g, int m,
+                                                    const uint64_t *ta, const uint64_t *tb, const uint64_t *tab, uint64_t *out, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    if (!bd_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_sum_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
+    if (count > 0 && (!c || !bits || !out || (m > 1 && (!opened || !g || !ta || !tb || !tab)))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const bool prod = m > 1;                                                    // with m == 1 there is no product: its operands are not looked at
+    const RowSpan outs[1] = {{out, m}};
+    const RowSpan ins[7] = {{c, 1}, {bits, m}, {prod ? opened : nullptr, 2 * (m - 1)}, {prod ? g : nullptr, m - 1}, {prod ? ta : nullptr, m - 1},
+                            {prod ? tb : nullptr, m - 1}, {prod ? tab : nullptr, m - 1}};
+    if (!outputs_apart(outs, 1, ins, 7, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_bd_sum_combine: out is an array of its own");
+    const BdSumArgs A = {u32(opened), u32(c), u32(bits), u32(g), u32(ta), u32(tb), u32(tab), nullptr, u32(out)};
+    return run.template rows<BdSumCombineRow>(A, m, count);
+}
 
 }  // namespace hb
 
 extern "C" {
 
 int hb_bd_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int m, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_leaves: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
-    if (count > 0 && m > 1 && (!c_dev || !bits_dev || !g_dev || !p_dev)) return HB_ERR_BAD_ARG;
-    if (count == 0 || m == 1) return HB_OK;
-    const RowSpan outs[2] = {{g_dev, m - 1}, {p_dev, m - 1}}, ins[2] = {{c_dev, 1}, {bits_dev, m - 1}};
-    if (!outputs_apart(outs, 2, ins, 2, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_leaves: g and p are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_bd_leaves");
-    return launch_leaves<BdLeavesRow>(ctx, {u32(c_dev), u32(bits_dev), u32(g_dev), u32(p_dev), m}, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : bd_leaves_step(DeviceRun{ctx, (hipStream_t)stream, "hb_bd_leaves"}, c_dev, bits_dev, m, g_dev, p_dev, count);
 }
 
 int hb_bd_prefix_mask(hb_ctx *ctx, const uint64_t *g_dev, const uint64_t *p_dev, int m, int level, const uint64_t *ta_dev, const uint64_t *tb_dev,
                       uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!g_dev || !p_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
-    if (!bd_level_ok(m, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: no such level");
-    if (count == 0) return HB_OK;
-    const int n = m - 1, triples = bd_level_triples(n, level);
-    const RowSpan outs[1] = {{masked_dev, 2 * triples}}, ins[4] = {{g_dev, n}, {p_dev, n}, {ta_dev, triples}, {tb_dev, triples}};
-    if (!outputs_apart(outs, 1, ins, 4, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_mask: masked is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_bd_prefix_mask");
-    const BdPrefixArgs A = {nullptr, u32(ta_dev), u32(tb_dev), nullptr, const_cast<uint32_t *>(u32(g_dev)), const_cast<uint32_t *>(u32(p_dev)), u32(masked_dev), level,
-                            bd_g_only(n, level)};
-    return launch_rows<BdPrefixMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)triples), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : bd_prefix_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_bd_prefix_mask"}, g_dev, p_dev, m, level, ta_dev, tb_dev, masked_dev,
+                                                       count);
 }
 
 int hb_bd_prefix_combine(hb_ctx *ctx, const uint64_t *opened_dev, uint64_t *g_dev, uint64_t *p_dev, int m, int level, const uint64_t *ta_dev,
                          const uint64_t *tb_dev, const uint64_t *tab_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!opened_dev || !g_dev || !p_dev || !ta_dev || !tb_dev || !tab_dev))) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
-    if (!bd_level_ok(m, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: no such level");
-    if (count == 0) return HB_OK;
-    const int n = m - 1, triples = bd_level_triples(n, level);
-    const RowSpan outs[2] = {{g_dev, n}, {p_dev, n}}, ins[4] = {{opened_dev, 2 * triples}, {ta_dev, triples}, {tb_dev, triples}, {tab_dev, triples}};
-    if (!outputs_apart(outs, 2, ins, 4, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_prefix_combine: g and p are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_bd_prefix_combine");
-    const BdPrefixArgs A = {u32(opened_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(g_dev), u32(p_dev), nullptr, level, bd_g_only(n, level)};
-    return launch_rows<BdPrefixCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)bd_active(n, level)), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : bd_prefix_combine_step(DeviceRun{ctx, (hipStream_t)stream, "hb_bd_prefix_combine"}, opened_dev, g_dev, p_dev, m, level, ta_dev,
+                                                          tb_dev, tab_dev, count);
 }
 
 int hb_bd_sum_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m, const uint64_t *ta_dev, const uint64_t *tb_dev,
                    uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_mask: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
-    if (count > 0 && m > 1 && (!c_dev || !bits_dev || !g_dev || !ta_dev || !tb_dev || !masked_dev)) return HB_ERR_BAD_ARG;
-    if (count == 0 || m == 1) return HB_OK;
-    const RowSpan outs[1] = {{masked_dev, 2 * (m - 1)}}, ins[5] = {{c_dev, 1}, {bits_dev, m}, {g_dev, m - 1}, {ta_dev, m - 1}, {tb_dev, m - 1}};
-    if (!outputs_apart(outs, 1, ins, 5, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_mask: masked is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_bd_sum_mask");
-    const BdSumArgs A = {nullptr, u32(c_dev), u32(bits_dev), u32(g_dev), u32(ta_dev), u32(tb_dev), nullptr, u32(masked_dev), nullptr};
-    return launch_rows<BdSumMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)(m - 1)), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : bd_sum_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_bd_sum_mask"}, c_dev, bits_dev, g_dev, m, ta_dev, tb_dev, masked_dev, count);
 }
 
 int hb_bd_sum_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *c_dev, const uint64_t *bits_dev, const uint64_t *g_dev, int m, const uint64_t *ta_dev,
                       const uint64_t *tb_dev, const uint64_t *tab_dev, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!bd_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_combine: needs 0 < m <= bits(p) - 2 and m - 1 <= 256");
-    if (count > 0 && (!c_dev || !bits_dev || !out_dev || (m > 1 && (!opened_dev || !g_dev || !ta_dev || !tb_dev || !tab_dev)))) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    const bool prod = m > 1;                                                    // with m == 1 there is no product: its operands are not looked at
-    const RowSpan outs[1] = {{out_dev, m}};
-    const RowSpan ins[7] = {{c_dev, 1}, {bits_dev, m}, {prod ? opened_dev : nullptr, 2 * (m - 1)}, {prod ? g_dev : nullptr, m - 1}, {prod ? ta_dev : nullptr, m - 1},
-                            {prod ? tb_dev : nullptr, m - 1}, {prod ? tab_dev : nullptr, m - 1}};
-    if (!outputs_apart(outs, 1, ins, 7, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_bd_sum_combine: out is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_bd_sum_combine");
-    const BdSumArgs A = {u32(opened_dev), u32(c_dev), u32(bits_dev), u32(g_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), nullptr, u32(out_dev)};
-    return launch_rows<BdSumCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)m), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : bd_sum_combine_step(DeviceRun{ctx, (hipStream_t)stream, "hb_bd_sum_combine"}, opened_dev, c_dev, bits_dev, g_dev, m, ta_dev, tb_dev,
+                                                       tab_dev, out_dev, count);
 }
 
-int hb_selftest_bd(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
+// params: m, level
+int hb_selftest_bd(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
+    if (!p_limbs || !ops || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 2; i++) if (params[i] < -(1 << 30) || params[i] > (1 << 30)) return HB_ERR_BAD_ARG;
+    const HostRun run = {p_limbs, n_limbs};
     const int m = (int)params[0], level = (int)params[1];
-    if (!bd_m_ok(modulus_bits(p_limbs, n_limbs), m)) return HB_ERR_BAD_ARG;
-    int n_ops = 0, n_outs = 1;
     switch (what) {
-    case HB_BD_SELFTEST_LEAVES: n_ops = 2; n_outs = 2; break;
-    case HB_BD_SELFTEST_PREFIX_MASK: if (!bd_level_ok(m, level)) return HB_ERR_BAD_ARG; n_ops = 4; break;
-    case HB_BD_SELFTEST_PREFIX_COMBINE: if (!bd_level_ok(m, level)) return HB_ERR_BAD_ARG; n_ops = 4; n_outs = 2; break;
-    case HB_BD_SELFTEST_SUM_MASK: n_ops = 5; break;
-    case HB_BD_SELFTEST_SUM_COMBINE: n_ops = 7; break;
+    case HB_BD_SELFTEST_LEAVES: return bd_leaves_step(run, ops[0], ops[1], m, outs[0], outs[1], count);
+    case HB_BD_SELFTEST_PREFIX_MASK: return bd_prefix_mask_step(run, ops[0], ops[1], m, level, ops[2], ops[3], outs[0], count);
+    case HB_BD_SELFTEST_PREFIX_COMBINE: return bd_prefix_combine_step(run, ops[0], outs[0], outs[1], m, level, ops[1], ops[2], ops[3], count);
+    case HB_BD_SELFTEST_SUM_MASK: return bd_sum_mask_step(run, ops[0], ops[1], ops[2], m, ops[3], ops[4], outs[0], count);
+    case HB_BD_SELFTEST_SUM_COMBINE: return bd_sum_combine_step(run, ops[0], ops[1], ops[2], ops[3], m, ops[4], ops[5], ops[6], outs[0], count);
     default: return HB_ERR_BAD_ARG;
     }
-    // with m == 1 there is no plane and no product: only c, bits and the result of the sum step are looked at
-    for (int i = 0; i < n_ops; i++)
-        if (count > 0 && !operands[i] && (m > 1 || (what == HB_BD_SELFTEST_SUM_COMBINE && (i == 1 || i == 2)))) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_outs; i++)
-        if (count > 0 && !outs[i] && (m > 1 || what == HB_BD_SELFTEST_SUM_COMBINE)) return HB_ERR_BAD_ARG;
-    if (n_limbs == 4) return selftest_bd<9, 8>(p_limbs, what, operands, params, outs, count);
-    return selftest_bd<3, 2>(p_limbs, what, operands, params, outs, count);
 }
 
 }  // extern "C"

@@ -185,7 +185,9 @@ struct DmFinishRow {
     }
 };
 
-// ---------------------------------------------------------------- host side: what the entry points and the self test refuse
+// ---------------------------------------------------------------- host side: what the steps refuse, and the step functions (hb_rows.hpp)
+// A step function is the checks, the Args fill and the row count, run with a DeviceRun by the entry point and with a HostRun by
+// hb_selftest_demux.
 static bool dm_m_ok(int m) { return m >= 1 && m <= DM_MAX_BITS; }
 static bool dm_level_ok(int m, int level) { return level >= 0 && level < dm_levels(m); }
 
@@ -229,88 +231,70 @@ static bool dm_finish_ok(const void *opened, const void *ta, const void *tab, co
     return outputs_apart(outs, 1, ins, 3, row);
 }
 
+template <class Run> static int demux_leaves_step(const Run &run, const uint64_t *bits, uint64_t *out, int64_t count) {
+    if (!dm_leaves_ok(bits, out, count, run.elem_bytes())) return run.fail(HB_ERR_BAD_ARG, "hb_demux_leaves: null operand, count < 0, or out not an array of its own");
+    if (count == 0) return HB_OK;
+    DmArgs A{};
+    A.bits = u32(bits); A.out = u32(out);
+    return run.template rows<DmLeavesRow>(A, 2, count);
+}
+
+template <class Run> static int demux_mask_step(const Run &run, const uint64_t *bits, const uint64_t *groups, int m, int level, const uint64_t *ta, uint64_t *out,
+                                                int64_t count) {
+    if (!dm_m_ok(m)) return run.fail(HB_ERR_BAD_ARG, "hb_demux_mask: needs 1 <= m <= 12");
+    if (!dm_level_ok(m, level)) return run.fail(HB_ERR_BAD_ARG, "hb_demux_mask: no such level");
+    DmArgs A{};
+    dm_plan(m, level, A.L);
+    if (!dm_mask_ok(bits, groups, ta, out, m, A.L, count, run.elem_bytes()))
+        return run.fail(HB_ERR_BAD_ARG, "hb_demux_mask: null operand, count < 0, or out not an array of its own");
+    if (count == 0) return HB_OK;
+    A.bits = u32(bits); A.groups_in = u32(groups); A.ta = u32(ta); A.out = u32(out);
+    return run.template rows<DmMaskRow>(A, A.L.opened, count);
+}
+
+template <class Run> static int demux_finish_step(const Run &run, const uint64_t *opened, const uint64_t *ta, const uint64_t *tab, int m, int level, uint64_t *groups,
+                                                  int64_t count) {
+    if (!dm_m_ok(m)) return run.fail(HB_ERR_BAD_ARG, "hb_demux_finish: needs 1 <= m <= 12");
+    if (!dm_level_ok(m, level)) return run.fail(HB_ERR_BAD_ARG, "hb_demux_finish: no such level");
+    DmArgs A{};
+    dm_plan(m, level, A.L);
+    if (!dm_finish_ok(opened, ta, tab, groups, m, A.L, count, run.elem_bytes()))
+        return run.fail(HB_ERR_BAD_ARG, "hb_demux_finish: null operand, count < 0, or groups not an array of its own");
+    if (count == 0) return HB_OK;
+    A.opened = u32(opened); A.ta = u32(ta); A.tab = u32(tab); A.out = u32(groups);
+    return run.template rows<DmFinishRow>(A, A.L.products, count);
+}
+
 }  // namespace hb
 
 extern "C" {
 
 int hb_demux_leaves(hb_ctx *ctx, const uint64_t *bits_dev, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx) return HB_ERR_BAD_ARG;
-    if (!dm_leaves_ok(bits_dev, out_dev, count, 8 * ctx->n_limbs)) return fail(ctx, HB_ERR_BAD_ARG, "hb_demux_leaves: null operand, count < 0, or out not an array of its own");
-    if (count == 0) return HB_OK;
-    HB_ROW_BLOCKS(ctx, "hb_demux_leaves");
-    DmArgs A{};
-    A.bits = u32(bits_dev); A.out = u32(out_dev);
-    return launch_rows<DmLeavesRow>(ctx, A, dim3((unsigned)blocks, 2u), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : demux_leaves_step(DeviceRun{ctx, (hipStream_t)stream, "hb_demux_leaves"}, bits_dev, out_dev, count);
 }
 
 int hb_demux_mask(hb_ctx *ctx, const uint64_t *bits_dev, const uint64_t *groups_dev, int m, int level, const uint64_t *ta_dev, uint64_t *out_dev, int64_t count,
                   void *stream) { HB_API_GUARD(ctx);
-    if (!ctx) return HB_ERR_BAD_ARG;
-    if (!dm_m_ok(m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_demux_mask: needs 1 <= m <= 12");
-    if (!dm_level_ok(m, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_demux_mask: no such level");
-    DmArgs A{};
-    dm_plan(m, level, A.L);
-    if (!dm_mask_ok(bits_dev, groups_dev, ta_dev, out_dev, m, A.L, count, 8 * ctx->n_limbs))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_demux_mask: null operand, count < 0, or out not an array of its own");
-    if (count == 0) return HB_OK;
-    HB_ROW_BLOCKS(ctx, "hb_demux_mask");
-    A.bits = u32(bits_dev); A.groups_in = u32(groups_dev); A.ta = u32(ta_dev); A.out = u32(out_dev);
-    return launch_rows<DmMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)A.L.opened), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : demux_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_demux_mask"}, bits_dev, groups_dev, m, level, ta_dev, out_dev, count);
 }
 
 int hb_demux_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tab_dev, int m, int level, uint64_t *groups_dev, int64_t count,
                     void *stream) { HB_API_GUARD(ctx);
-    if (!ctx) return HB_ERR_BAD_ARG;
-    if (!dm_m_ok(m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_demux_finish: needs 1 <= m <= 12");
-    if (!dm_level_ok(m, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_demux_finish: no such level");
-    DmArgs A{};
-    dm_plan(m, level, A.L);
-    if (!dm_finish_ok(opened_dev, ta_dev, tab_dev, groups_dev, m, A.L, count, 8 * ctx->n_limbs))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_demux_finish: null operand, count < 0, or groups not an array of its own");
-    if (count == 0) return HB_OK;
-    HB_ROW_BLOCKS(ctx, "hb_demux_finish");
-    A.opened = u32(opened_dev); A.ta = u32(ta_dev); A.tab = u32(tab_dev); A.out = u32(groups_dev);
-    return launch_rows<DmFinishRow>(ctx, A, dim3((unsigned)blocks, (unsigned)A.L.products), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : demux_finish_step(DeviceRun{ctx, (hipStream_t)stream, "hb_demux_finish"}, opened_dev, ta_dev, tab_dev, m, level, groups_dev, count);
 }
 
+// params: m, level
 int hb_selftest_demux(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
     if (!p_limbs || !operands || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
-    if (what != HB_DEMUX_SELFTEST_LEAVES && what != HB_DEMUX_SELFTEST_MASK && what != HB_DEMUX_SELFTEST_FINISH) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 2; i++) if (params[i] < -(1 << 30) || params[i] > (1 << 30)) return HB_ERR_BAD_ARG;
+    const HostRun run = {p_limbs, n_limbs};
     const int m = (int)params[0], level = (int)params[1];
-    DmArgs A{};
-    int rows = 2;
-    if (what == HB_DEMUX_SELFTEST_LEAVES) {
-        if (!dm_leaves_ok(operands[0], outs[0], count, 8 * n_limbs)) return HB_ERR_BAD_ARG;
-        A.bits = u32(operands[0]); A.out = u32(outs[0]);
-    } else {
-        if (!dm_m_ok(m) || !dm_level_ok(m, level)) return HB_ERR_BAD_ARG;
-        dm_plan(m, level, A.L);
-        if (what == HB_DEMUX_SELFTEST_MASK) {
-            if (!dm_mask_ok(operands[0], operands[1], operands[2], outs[0], m, A.L, count, 8 * n_limbs)) return HB_ERR_BAD_ARG;
-            A.bits = u32(operands[0]); A.groups_in = u32(operands[1]); A.ta = u32(operands[2]); A.out = u32(outs[0]);
-            rows = A.L.opened;
-        } else {
-            if (!dm_finish_ok(operands[0], operands[1], operands[2], outs[0], m, A.L, count, 8 * n_limbs)) return HB_ERR_BAD_ARG;
-            A.opened = u32(operands[0]); A.ta = u32(operands[1]); A.tab = u32(operands[2]); A.out = u32(outs[0]);
-            rows = A.L.products;
-        }
+    switch (what) {
+    case HB_DEMUX_SELFTEST_LEAVES: return demux_leaves_step(run, operands[0], outs[0], count);
+    case HB_DEMUX_SELFTEST_MASK: return demux_mask_step(run, operands[0], operands[1], m, level, operands[2], outs[0], count);
+    case HB_DEMUX_SELFTEST_FINISH: return demux_finish_step(run, operands[0], operands[1], operands[2], m, level, outs[0], count);
+    default: return HB_ERR_BAD_ARG;
     }
-    if (count == 0) return HB_OK;
-    if (n_limbs == 4) {
-        FpParams<9> P;
-        fp_params_from_limbs(P, p_limbs);
-        if (what == HB_DEMUX_SELFTEST_LEAVES) host_rows<DmLeavesRow, 9, 8>(A, rows, count, P);
-        else if (what == HB_DEMUX_SELFTEST_MASK) host_rows<DmMaskRow, 9, 8>(A, rows, count, P);
-        else host_rows<DmFinishRow, 9, 8>(A, rows, count, P);
-    } else {
-        FpParams<3> P;
-        fp_params_from_limbs(P, p_limbs);
-        if (what == HB_DEMUX_SELFTEST_LEAVES) host_rows<DmLeavesRow, 3, 2>(A, rows, count, P);
-        else if (what == HB_DEMUX_SELFTEST_MASK) host_rows<DmMaskRow, 3, 2>(A, rows, count, P);
-        else host_rows<DmFinishRow, 3, 2>(A, rows, count, P);
-    }
-    return HB_OK;
 }
 
 }  // extern "C"

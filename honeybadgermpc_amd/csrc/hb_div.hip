@@ -291,6 +291,7 @@ HB_HD static void run(const DivTruncArgs<NL> &A, int q, int64_t i, int64_t count
 };
 
 // ---------------------------------------------------------------- host side
+// One step function a step (hb_rows.hpp): its checks, Args fill and row count run under a DeviceRun in the entry point, a HostRun in hb_selftest_div.
 static bool div_or_ok(int n, int level) { return n >= 1 && n <= 256 && level >= 0 && level < bd_levels(n); }
 static bool div_product_ok(int bits, int mode, int products, int width, int m, int kappa) {
     switch (mode) {
@@ -329,37 +330,6 @@ static bool div_trunc_consts(DivTruncArgs<NL> &A, const FpParams<NL> &P, const u
     return A.mode == HB_DIV_T_GOLD ? host_digits<NL, words_of(NL)>(A.alpha.d, P, alpha_host) : true;
 }
 
-// host: the same rows over `count` elements
-template <int NL, int NW>
-static int selftest_div(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    FpParams<NL> P;
-    fp_params_from_limbs(P, p_limbs);
-    if (what == HB_DIV_SELFTEST_OR_MASK || what == HB_DIV_SELFTEST_OR_COMBINE) {
-        const bool mask = what == HB_DIV_SELFTEST_OR_MASK;
-        const DivOrArgs A = {mask ? nullptr : u32(ops[0]), u32(ops[1]), u32(ops[2]), mask ? nullptr : u32(ops[3]), mask ? const_cast<uint32_t *>(u32(ops[0])) : u32(outs[0]),
-                             mask ? u32(outs[0]) : nullptr, (int)params[0], (int)params[1], (int)params[2]};
-        if (mask) host_rows<DivOrMaskRow, NL, NW>(A, bd_active(A.n, A.level), count, P);
-        else host_rows<DivOrCombineRow, NL, NW>(A, bd_active(A.n, A.level), count, P);
-    } else if (what == HB_DIV_SELFTEST_PAIR_MASK) {
-        const DivPairArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0])};
-        host_rows<DivPairMaskRow, NL, NW>(A, 1, count, P);
-    } else if (what == HB_DIV_SELFTEST_NORM_MASK) {
-        const DivNormArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(outs[0]), u32(outs[1]), (int)params[0]};
-        host_rows<DivNormMaskRow, NL, NW>(A, 1, count, P);
-    } else if (what == HB_DIV_SELFTEST_PRODUCT_STEP) {
-        DivProductArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(outs[0]), u32(outs[1]),
-                                (int)params[0], (int)params[1], (int)(params[2] + params[4]), (int)params[3]};
-        if (!div_product_consts<NL>(A, P, ops[5], (int)params[2])) return HB_ERR_BAD_ARG;
-        host_rows<DivProductRow, NL, NW>(A, div_product_rows(A.mode, A.products), count, P);
-    } else {
-        DivTruncArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(outs[0]),
-                              (int)params[0], (int)params[1], (int)params[2], (int)params[3]};
-        if (!div_trunc_consts<NL>(A, P, ops[2], ops[3])) return HB_ERR_BAD_ARG;
-        host_rows<DivTruncRow, NL, NW>(A, A.products ? A.products : 1, count, P);
-    }
-    return HB_OK;
-}
-
 // which operands a step reads, as a bit mask over the operand tables of the header
 static unsigned div_product_needs(int mode, bool nxt) {
     unsigned need = 0xFu;                                                       // opened, ta, tb, tab
@@ -378,149 +348,165 @@ static unsigned div_trunc_needs(int mode, int rows, int products) {
     return need;
 }
 
+template <class Run> static int div_or_mask_step(const Run &run, const uint64_t *y, int n_planes, int level, int from_top, const uint64_t *ta, const uint64_t *tb,
+                                                 uint64_t *masked, int64_t count) {
+    if (count < 0 || (count > 0 && (!y || !ta || !tb || !masked))) return HB_ERR_BAD_ARG;
+    if (!div_or_ok(n_planes, level)) return run.fail(HB_ERR_BAD_ARG, "hb_div_or_mask: needs 1 <= n_planes <= 256 and a level the network has");
+    if (count == 0) return HB_OK;
+    const int nodes = bd_active(n_planes, level);
+    const int64_t rb = run.elem_bytes() * count;
+    const RowSpan outs[1] = {{masked, 2 * nodes}}, ins[3] = {{y, n_planes}, {ta, nodes}, {tb, nodes}};
+    if (!outputs_apart(outs, 1, ins, 3, rb)) return run.fail(HB_ERR_BAD_ARG, "hb_div_or_mask: masked is an array of its own");
+    const DivOrArgs A = {nullptr, u32(ta), u32(tb), nullptr, const_cast<uint32_t *>(u32(y)), u32(masked), n_planes, level, from_top ? 1 : 0};
+    return run.template rows<DivOrMaskRow>(A, nodes, count);
+}
+
+template <class Run> static int div_or_combine_step(const Run &run, const uint64_t *opened, uint64_t *y, int n_planes, int level, int from_top, const uint64_t *ta,
+                                                    const uint64_t *tb, const uint64_t *tab, int64_t count) {
+    if (count < 0 || (count > 0 && (!opened || !y || !ta || !tb || !tab))) return HB_ERR_BAD_ARG;
+    if (!div_or_ok(n_planes, level)) return run.fail(HB_ERR_BAD_ARG, "hb_div_or_combine: needs 1 <= n_planes <= 256 and a level the network has");
+    if (count == 0) return HB_OK;
+    const int nodes = bd_active(n_planes, level);
+    const int64_t rb = run.elem_bytes() * count;
+    const RowSpan outs[1] = {{y, n_planes}}, ins[4] = {{opened, 2 * nodes}, {ta, nodes}, {tb, nodes}, {tab, nodes}};
+    if (!outputs_apart(outs, 1, ins, 4, rb)) return run.fail(HB_ERR_BAD_ARG, "hb_div_or_combine: y is an array of its own");
+    const DivOrArgs A = {u32(opened), u32(ta), u32(tb), u32(tab), u32(y), nullptr, n_planes, level,
+                         from_top ? 1 : 0};
+    return run.template rows<DivOrCombineRow>(A, nodes, count);
+}
+
+template <class Run> static int div_pair_mask_step(const Run &run, const uint64_t *x, const uint64_t *y, const uint64_t *ta, const uint64_t *tb, uint64_t *masked,
+                                                   int64_t count) {
+    if (count < 0 || (count > 0 && (!x || !y || !ta || !tb || !masked))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t rb = run.elem_bytes() * count;
+    const RowSpan outs[1] = {{masked, 2}}, ins[4] = {{x, 1}, {y, 1}, {ta, 1}, {tb, 1}};
+    if (!outputs_apart(outs, 1, ins, 4, rb)) return run.fail(HB_ERR_BAD_ARG, "hb_div_pair_mask: masked is an array of its own");
+    const DivPairArgs A = {u32(x), u32(y), u32(ta), u32(tb), u32(masked)};
+    return run.template rows<DivPairMaskRow>(A, 1, count);
+}
+
+template <class Run> static int div_norm_mask_step(const Run &run, const uint64_t *x, const uint64_t *y, int n_planes, const uint64_t *u, const uint64_t *ta,
+                                                   const uint64_t *tb, uint64_t *masked, uint64_t *v, int64_t count) {
+    if (count < 0 || (count > 0 && (!x || !y || !ta || !tb || !masked || !v))) return HB_ERR_BAD_ARG;
+    if (n_planes < 1 || n_planes > 256) return run.fail(HB_ERR_BAD_ARG, "hb_div_norm_mask: needs 1 <= n_planes <= 256");
+    if (count == 0) return HB_OK;
+    const int products = u ? 2 : 1;
+    const int64_t rb = run.elem_bytes() * count;
+    const RowSpan outs[2] = {{masked, 2 * products}, {v, 1}}, ins[5] = {{x, 1}, {y, n_planes}, {u, 1}, {ta, products}, {tb, products}};
+    if (!outputs_apart(outs, 2, ins, 5, rb)) return run.fail(HB_ERR_BAD_ARG, "hb_div_norm_mask: masked and v are arrays of their own");
+    const DivNormArgs A = {u32(x), u32(y), u32(u), u32(ta), u32(tb), u32(masked),
+                           u32(v), n_planes};
+    return run.template rows<DivNormMaskRow>(A, 1, count);
+}
+
+template <class Run> static int div_product_step(const Run &run, int mode, int products, const uint64_t *opened, const uint64_t *ta, const uint64_t *tb,
+                                                 const uint64_t *tab, const uint64_t *aux, const uint64_t *cst_host, const uint64_t *nxt_a, const uint64_t *nxt_b,
+                                                 const uint64_t *bits, int width, int m, int kappa, uint64_t *out0, uint64_t *out1, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    if (!div_product_ok(run.bits(), mode, products, width, m, kappa))
+        return run.fail(HB_ERR_BAD_ARG, "hb_div_product_step: unknown mode, a product count the mode does not take, or a truncation the modulus has no room for");
+    if (mode == HB_DIV_NORM && (!nxt_a) != (!nxt_b)) return run.fail(HB_ERR_BAD_ARG, "hb_div_product_step: nxt_a and nxt_b go together");
+    const bool nxt = mode == HB_DIV_NORM && nxt_a;
+    const unsigned need = div_product_needs(mode, nxt);
+    const int o0 = div_product_out0_rows(mode, products), o1 = div_product_out1_rows(mode, products), sets = div_product_sets(mode, products);
+    if ((need & (1u << 5)) && !cst_host) return HB_ERR_BAD_ARG;
+    if (count > 0 && (!opened || !ta || !tb || !tab || !out0 || (o1 && !out1) || ((need & (1u << 4)) && !aux) || ((need & (1u << 8)) && !bits)))
+        return HB_ERR_BAD_ARG;
+    const int64_t rb = run.elem_bytes() * count;
+    const RowSpan outs[2] = {{out0, o0}, {o1 ? out1 : nullptr, o1}};
+    const RowSpan ins[8] = {{opened, 2 * products}, {ta, products}, {tb, products}, {tab, products}, {(need & (1u << 4)) ? aux : nullptr, 1},
+                            {nxt ? nxt_a : nullptr, 1}, {nxt ? nxt_b : nullptr, 1}, {sets ? bits : nullptr, (int64_t)sets * (width + kappa)}};
+    if (count > 0 && !outputs_apart(outs, 2, ins, 8, rb)) return run.fail(HB_ERR_BAD_ARG, "hb_div_product_step: the outputs are arrays of their own");
+    const int rc = run.template rows<DivProductRow, DivProductArgs>([&](auto &A, const auto &P) {
+        A = {u32(opened), u32(ta), u32(tb), u32(tab), u32(aux), nxt ? u32(nxt_a) : nullptr, nxt ? u32(nxt_b) : nullptr, u32(bits),
+             u32(out0), u32(out1), mode, products, width + kappa, m};
+        return div_product_consts(A, P, cst_host, width);
+    }, div_product_rows(mode, products), count);
+    return rc == HB_ERR_BAD_ARG ? run.fail(rc, "hb_div_product_step: the constant is not below the modulus") : rc;
+}
+
+template <class Run> static int div_trunc_step(const Run &run, int mode, int rows, int products, const uint64_t *opened, const uint64_t *s, int m,
+                                               const uint64_t *inv2m_host, const uint64_t *alpha_host, const uint64_t *x, const uint64_t *ext0, const uint64_t *ext1,
+                                               const uint64_t *ta, const uint64_t *tb, uint64_t *out, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    if (!div_trunc_ok(run.bits(), mode, rows, products, m))
+        return run.fail(HB_ERR_BAD_ARG, "hb_div_trunc_step: unknown mode, row or product counts the mode does not take, or m outside 0 < m <= bits(p) - 2");
+    const unsigned need = div_trunc_needs(mode, rows, products);
+    if (!inv2m_host || ((need & (1u << 3)) && !alpha_host)) return HB_ERR_BAD_ARG;
+    if (count > 0 && (!opened || !s || !out || ((need & (1u << 4)) && !x) || ((need & (1u << 5)) && (!ext0 || !ext1)) ||
+                      ((need & (1u << 7)) && (!ta || !tb))))
+        return HB_ERR_BAD_ARG;
+    const int64_t rb = run.elem_bytes() * count;
+    const RowSpan outs[1] = {{out, products ? 2 * products : 1}};
+    const RowSpan ins[7] = {{opened, rows}, {s, rows}, {(need & (1u << 4)) ? x : nullptr, 1}, {(need & (1u << 5)) ? ext0 : nullptr, 1},
+                            {(need & (1u << 5)) ? ext1 : nullptr, 1}, {products ? ta : nullptr, products}, {products ? tb : nullptr, products}};
+    if (count > 0 && !outputs_apart(outs, 1, ins, 7, rb)) return run.fail(HB_ERR_BAD_ARG, "hb_div_trunc_step: out is an array of its own");
+    const int rc = run.template rows<DivTruncRow, DivTruncArgs>([&](auto &A, const auto &P) {
+        A = {u32(opened), u32(s), u32(x), u32(ext0), u32(ext1), u32(ta), u32(tb), u32(out), mode, rows, products, m};
+        return div_trunc_consts(A, P, inv2m_host, alpha_host);
+    }, products ? products : 1, count);
+    return rc == HB_ERR_BAD_ARG ? run.fail(rc, "hb_div_trunc_step: a constant is not below the modulus") : rc;
+}
+
 }  // namespace hb
 
 extern "C" {
 
 int hb_div_or_mask(hb_ctx *ctx, const uint64_t *y_dev, int n_planes, int level, int from_top, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev,
                    int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!y_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (!div_or_ok(n_planes, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_mask: needs 1 <= n_planes <= 256 and a level the network has");
-    if (count == 0) return HB_OK;
-    const int nodes = bd_active(n_planes, level);
-    const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[1] = {{masked_dev, 2 * nodes}}, ins[3] = {{y_dev, n_planes}, {ta_dev, nodes}, {tb_dev, nodes}};
-    if (!outputs_apart(outs, 1, ins, 3, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_mask: masked is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_div_or_mask");
-    const DivOrArgs A = {nullptr, u32(ta_dev), u32(tb_dev), nullptr, const_cast<uint32_t *>(u32(y_dev)), u32(masked_dev), n_planes, level, from_top ? 1 : 0};
-    return launch_rows<DivOrMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)nodes), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : div_or_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_div_or_mask"}, y_dev, n_planes, level, from_top, ta_dev, tb_dev, masked_dev,
+                                                    count);
 }
 
 int hb_div_or_combine(hb_ctx *ctx, const uint64_t *opened_dev, uint64_t *y_dev, int n_planes, int level, int from_top, const uint64_t *ta_dev, const uint64_t *tb_dev,
                       const uint64_t *tab_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!opened_dev || !y_dev || !ta_dev || !tb_dev || !tab_dev))) return HB_ERR_BAD_ARG;
-    if (!div_or_ok(n_planes, level)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_combine: needs 1 <= n_planes <= 256 and a level the network has");
-    if (count == 0) return HB_OK;
-    const int nodes = bd_active(n_planes, level);
-    const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[1] = {{y_dev, n_planes}}, ins[4] = {{opened_dev, 2 * nodes}, {ta_dev, nodes}, {tb_dev, nodes}, {tab_dev, nodes}};
-    if (!outputs_apart(outs, 1, ins, 4, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_or_combine: y is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_div_or_combine");
-    const DivOrArgs A = {u32(opened_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(y_dev), nullptr, n_planes, level,
-                         from_top ? 1 : 0};
-    return launch_rows<DivOrCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)nodes), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : div_or_combine_step(DeviceRun{ctx, (hipStream_t)stream, "hb_div_or_combine"}, opened_dev, y_dev, n_planes, level, from_top, ta_dev,
+                                                       tb_dev, tab_dev, count);
 }
 
 int hb_div_pair_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, int64_t count,
                      void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!x_dev || !y_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[1] = {{masked_dev, 2}}, ins[4] = {{x_dev, 1}, {y_dev, 1}, {ta_dev, 1}, {tb_dev, 1}};
-    if (!outputs_apart(outs, 1, ins, 4, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_pair_mask: masked is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_div_pair_mask");
-    const DivPairArgs A = {u32(x_dev), u32(y_dev), u32(ta_dev), u32(tb_dev), u32(masked_dev)};
-    return launch_rows<DivPairMaskRow>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : div_pair_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_div_pair_mask"}, x_dev, y_dev, ta_dev, tb_dev, masked_dev, count);
 }
 
 int hb_div_norm_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, int n_planes, const uint64_t *u_dev, const uint64_t *ta_dev, const uint64_t *tb_dev,
                      uint64_t *masked_dev, uint64_t *v_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!x_dev || !y_dev || !ta_dev || !tb_dev || !masked_dev || !v_dev))) return HB_ERR_BAD_ARG;
-    if (n_planes < 1 || n_planes > 256) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_norm_mask: needs 1 <= n_planes <= 256");
-    if (count == 0) return HB_OK;
-    const int products = u_dev ? 2 : 1;
-    const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[2] = {{masked_dev, 2 * products}, {v_dev, 1}}, ins[5] = {{x_dev, 1}, {y_dev, n_planes}, {u_dev, 1}, {ta_dev, products}, {tb_dev, products}};
-    if (!outputs_apart(outs, 2, ins, 5, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_norm_mask: masked and v are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_div_norm_mask");
-    const DivNormArgs A = {u32(x_dev), u32(y_dev), u32(u_dev), u32(ta_dev), u32(tb_dev), u32(masked_dev),
-                           u32(v_dev), n_planes};
-    return launch_rows<DivNormMaskRow>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : div_norm_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_div_norm_mask"}, x_dev, y_dev, n_planes, u_dev, ta_dev, tb_dev, masked_dev,
+                                                      v_dev, count);
 }
 
 int hb_div_product_step(hb_ctx *ctx, int mode, int products, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev,
                         const uint64_t *aux_dev, const uint64_t *cst_host, const uint64_t *nxt_a_dev, const uint64_t *nxt_b_dev, const uint64_t *bits_dev, int width, int m,
                         int kappa, uint64_t *out0_dev, uint64_t *out1_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!div_product_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), mode, products, width, m, kappa))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: unknown mode, a product count the mode does not take, or a truncation the modulus has no room for");
-    if (mode == HB_DIV_NORM && (!nxt_a_dev) != (!nxt_b_dev)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: nxt_a and nxt_b go together");
-    const bool nxt = mode == HB_DIV_NORM && nxt_a_dev;
-    const unsigned need = div_product_needs(mode, nxt);
-    const int o0 = div_product_out0_rows(mode, products), o1 = div_product_out1_rows(mode, products), sets = div_product_sets(mode, products);
-    if ((need & (1u << 5)) && !cst_host) return HB_ERR_BAD_ARG;
-    if (count > 0 && (!opened_dev || !ta_dev || !tb_dev || !tab_dev || !out0_dev || (o1 && !out1_dev) || ((need & (1u << 4)) && !aux_dev) || ((need & (1u << 8)) && !bits_dev)))
-        return HB_ERR_BAD_ARG;
-    const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[2] = {{out0_dev, o0}, {o1 ? out1_dev : nullptr, o1}};
-    const RowSpan ins[8] = {{opened_dev, 2 * products}, {ta_dev, products}, {tb_dev, products}, {tab_dev, products}, {(need & (1u << 4)) ? aux_dev : nullptr, 1},
-                            {nxt ? nxt_a_dev : nullptr, 1}, {nxt ? nxt_b_dev : nullptr, 1}, {sets ? bits_dev : nullptr, (int64_t)sets * (width + kappa)}};
-    if (count > 0 && !outputs_apart(outs, 2, ins, 8, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_product_step: the outputs are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_div_product_step");
-    const int rc = launch_rows<DivProductRow, DivProductArgs>(ctx, [&](auto &A, const auto &P) {
-        A = {u32(opened_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(aux_dev), nxt ? u32(nxt_a_dev) : nullptr, nxt ? u32(nxt_b_dev) : nullptr, u32(bits_dev),
-             u32(out0_dev), u32(out1_dev), mode, products, width + kappa, m};
-        return div_product_consts(A, P, cst_host, width);
-    }, dim3((unsigned)blocks, (unsigned)div_product_rows(mode, products)), s, count);
-    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_div_product_step: the constant is not below the modulus") : rc;
+    return !ctx ? HB_ERR_BAD_ARG : div_product_step(DeviceRun{ctx, (hipStream_t)stream, "hb_div_product_step"}, mode, products, opened_dev, ta_dev, tb_dev, tab_dev,
+                                                    aux_dev, cst_host, nxt_a_dev, nxt_b_dev, bits_dev, width, m, kappa, out0_dev, out1_dev, count);
 }
 
 int hb_div_trunc_step(hb_ctx *ctx, int mode, int rows, int products, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
                       const uint64_t *alpha_host, const uint64_t *x_dev, const uint64_t *ext0_dev, const uint64_t *ext1_dev, const uint64_t *ta_dev, const uint64_t *tb_dev,
                       uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (!div_trunc_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), mode, rows, products, m))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_div_trunc_step: unknown mode, row or product counts the mode does not take, or m outside 0 < m <= bits(p) - 2");
-    const unsigned need = div_trunc_needs(mode, rows, products);
-    if (!inv2m_host || ((need & (1u << 3)) && !alpha_host)) return HB_ERR_BAD_ARG;
-    if (count > 0 && (!opened_dev || !s_dev || !out_dev || ((need & (1u << 4)) && !x_dev) || ((need & (1u << 5)) && (!ext0_dev || !ext1_dev)) ||
-                      ((need & (1u << 7)) && (!ta_dev || !tb_dev))))
-        return HB_ERR_BAD_ARG;
-    const int64_t rb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[1] = {{out_dev, products ? 2 * products : 1}};
-    const RowSpan ins[7] = {{opened_dev, rows}, {s_dev, rows}, {(need & (1u << 4)) ? x_dev : nullptr, 1}, {(need & (1u << 5)) ? ext0_dev : nullptr, 1},
-                            {(need & (1u << 5)) ? ext1_dev : nullptr, 1}, {products ? ta_dev : nullptr, products}, {products ? tb_dev : nullptr, products}};
-    if (count > 0 && !outputs_apart(outs, 1, ins, 7, rb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_div_trunc_step: out is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_div_trunc_step");
-    const int rc = launch_rows<DivTruncRow, DivTruncArgs>(ctx, [&](auto &A, const auto &P) {
-        A = {u32(opened_dev), u32(s_dev), u32(x_dev), u32(ext0_dev), u32(ext1_dev), u32(ta_dev), u32(tb_dev), u32(out_dev), mode, rows, products, m};
-        return div_trunc_consts(A, P, inv2m_host, alpha_host);
-    }, dim3((unsigned)blocks, (unsigned)(products ? products : 1)), s, count);
-    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_div_trunc_step: a constant is not below the modulus") : rc;
+    return !ctx ? HB_ERR_BAD_ARG : div_trunc_step(DeviceRun{ctx, (hipStream_t)stream, "hb_div_trunc_step"}, mode, rows, products, opened_dev, s_dev, m, inv2m_host,
+                                                  alpha_host, x_dev, ext0_dev, ext1_dev, ta_dev, tb_dev, out_dev, count);
 }
 
-int hb_selftest_div(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
+// params: as the header lists them for each step
+int hb_selftest_div(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
+    if (!p_limbs || !ops || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 5; i++) if (params[i] < -(1 << 30) || params[i] > (1 << 30)) return HB_ERR_BAD_ARG;
-    const int bits = modulus_bits(p_limbs, n_limbs);
-    unsigned need = 0;
-    int n_outs = 1;
+    const HostRun run = {p_limbs, n_limbs};
+    const int a = (int)params[0], b = (int)params[1], c = (int)params[2], d = (int)params[3], e = (int)params[4];
     switch (what) {
-    case HB_DIV_SELFTEST_OR_MASK: if (!div_or_ok((int)params[0], (int)params[1])) return HB_ERR_BAD_ARG; need = 0x7u; break;
-    case HB_DIV_SELFTEST_OR_COMBINE: if (!div_or_ok((int)params[0], (int)params[1])) return HB_ERR_BAD_ARG; need = 0xFu; break;
-    case HB_DIV_SELFTEST_PAIR_MASK: need = 0xFu; break;
-    case HB_DIV_SELFTEST_NORM_MASK: if (params[0] < 1 || params[0] > 256) return HB_ERR_BAD_ARG; need = 0x1Bu; n_outs = 2; break;
-    case HB_DIV_SELFTEST_PRODUCT_STEP:
-        if (!div_product_ok(bits, (int)params[0], (int)params[1], (int)params[2], (int)params[3], (int)params[4])) return HB_ERR_BAD_ARG;
-        if (params[0] == HB_DIV_NORM && (!operands[6]) != (!operands[7])) return HB_ERR_BAD_ARG;
-        need = div_product_needs((int)params[0], params[0] == HB_DIV_NORM && operands[6]);
-        if ((need & (1u << 5)) && !operands[5]) return HB_ERR_BAD_ARG;
-        need &= ~(1u << 5);
-        n_outs = div_product_out1_rows((int)params[0], (int)params[1]) ? 2 : 1;
-        break;
-    case HB_DIV_SELFTEST_TRUNC_STEP:
-        if (!div_trunc_ok(bits, (int)params[0], (int)params[1], (int)params[2], (int)params[3])) return HB_ERR_BAD_ARG;
-        need = div_trunc_needs((int)params[0], (int)params[1], (int)params[2]);
-        if (!operands[2] || ((need & (1u << 3)) && !operands[3])) return HB_ERR_BAD_ARG;
-        need &= ~(3u << 2);
-        break;
+    case HB_DIV_SELFTEST_OR_MASK: return div_or_mask_step(run, ops[0], a, b, c, ops[1], ops[2], outs[0], count);
+    case HB_DIV_SELFTEST_OR_COMBINE: return div_or_combine_step(run, ops[0], outs[0], a, b, c, ops[1], ops[2], ops[3], count);
+    case HB_DIV_SELFTEST_PAIR_MASK: return div_pair_mask_step(run, ops[0], ops[1], ops[2], ops[3], outs[0], count);
+    case HB_DIV_SELFTEST_NORM_MASK: return div_norm_mask_step(run, ops[0], ops[1], a, ops[2], ops[3], ops[4], outs[0], outs[1], count);
+    case HB_DIV_SELFTEST_PRODUCT_STEP:                                          // mode, products, width, m, kappa
+        return div_product_step(run, a, b, ops[0], ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], ops[7], ops[8], c, d, e, outs[0], outs[1], count);
+    case HB_DIV_SELFTEST_TRUNC_STEP:                                            // mode, rows, products, m
+        return div_trunc_step(run, a, b, c, ops[0], ops[1], d, ops[2], ops[3], ops[4], ops[5], ops[6], ops[7], ops[8], outs[0], count);
     default: return HB_ERR_BAD_ARG;
     }
-    for (int i = 0; i < 9; i++) if (count > 0 && (need & (1u << i)) && !operands[i]) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_outs; i++) if (count > 0 && !outs[i]) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    if (n_limbs == 4) return selftest_div<9, 8>(p_limbs, what, operands, params, outs, count);
-    return selftest_div<3, 2>(p_limbs, what, operands, params, outs, count);
 }
 
 }  // extern "C"

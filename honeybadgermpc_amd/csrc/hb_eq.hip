@@ -251,6 +251,7 @@ struct EqFinishRow {
 };
 
 // ---------------------------------------------------------------- host side
+// One step function a step (hb_rows.hpp): its checks, Args fill and row count run under a DeviceRun in the entry point, a HostRun in hb_selftest_eq.
 static bool eq_make_sched(EqSched &S, const uint64_t *p_limbs, int n_limbs) {
     uint64_t e[4] = {0, 0, 0, 0};
     for (int i = 0; i < n_limbs; i++) e[i] = p_limbs[i];
@@ -330,36 +331,83 @@ template <int NL> static bool eq_finish_consts(EqFinishConsts<NL> &K, const FpPa
 
 static bool eq_rows_ok(int rows) { return rows >= 1 && rows <= 4096; }
 
-// host: the same rows over `count` elements
-template <int NL, int NW>
-static int selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, void *const *outs, int64_t count) {
-    FpParams<NL> P;
-    fp_params_from_limbs(P, p_limbs);
-    const int64_t rows = params[0];
-    const int mode = (int)params[1];
-    EqSched S;
-    if (!eq_make_sched(S, p_limbs, n_limbs)) return HB_ERR_BAD_ARG;
-    if (what == HB_EQ_SELFTEST_LEGENDRE) {
-        const EqLegendreArgs A = {S, u32(ops[0]), (int8_t *)outs[0]};
-        host_rows<EqLegendreRow, NL, NW>(A, 1, count, P);
-    } else if (what == HB_EQ_SELFTEST_MASK1) {
-        const EqMask1Args A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(outs[0]), rows};
-        if (A.y) host_rows<EqMask1Row<true>, NL, NW>(A, (int)rows, count, P);
-        else host_rows<EqMask1Row<false>, NL, NW>(A, (int)rows, count, P);
-    } else if (what == HB_EQ_SELFTEST_MID) {
-        EqMidArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(ops[9]),
-                           u32(outs[0]), u32(outs[1]), rows};
-        if (!eq_mid_consts(A.K, P, ops[10])) return HB_ERR_BAD_ARG;
-        host_rows<EqMidRow, NL, NW>(A, (int)rows, count, P);
-    } else if (what == HB_EQ_SELFTEST_CSHARE) {
-        const EqCshareArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(outs[0]), rows};
-        host_rows<EqCshareRow, NL, NW>(A, (int)rows, count, P);
-    } else {
-        EqFinishArgs<NL> A = {S, u32(ops[0]), u32(ops[1]), u32(outs[0]), (int32_t *)outs[1]};
-        if (!eq_finish_consts(A.K, P, p_limbs, n_limbs, mode, ops[2])) return HB_ERR_BAD_ARG;
-        host_rows<EqFinishRow, NL, NW>(A, (int)rows, count, P);
+template <class Run> static int legendre_step(const Run &run, const uint64_t *a, int8_t *out, int64_t count) {
+    if (count < 0 || (count > 0 && (!a || !out))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    EqLegendreArgs A = {{}, u32(a), out};
+    if (!eq_make_sched(A.S, run.modulus(), run.limbs())) return run.fail(HB_ERR_UNSUPPORTED, "hb_legendre: no schedule for this modulus");
+    if (overlap(out, count, a, count * run.elem_bytes())) return run.fail(HB_ERR_BAD_ARG, "hb_legendre: out overlaps a");
+    return run.template rows<EqLegendreRow>(A, 1, count);
+}
+
+template <class Run> static int eq_mask1_step(const Run &run, const uint64_t *x, const uint64_t *y, const uint64_t *r, const uint64_t *rp, const uint64_t *pa,
+                                              const uint64_t *qa, const uint64_t *pb, const uint64_t *qb, uint64_t *masked, int rows, int64_t count) {
+    if (count < 0 || (count > 0 && (!x || !r || !rp || !pa || !qa || !pb || !qb || !masked))) return HB_ERR_BAD_ARG;
+    if (!eq_rows_ok(rows)) return run.fail(HB_ERR_BAD_ARG, "hb_eq_mask1: needs 1 <= rows <= 4096");
+    if (count == 0) return HB_OK;
+    const RowSpan outs[1] = {{masked, 4 * rows}},
+                 ins[8] = {{x, 1}, {y, 1}, {r, rows}, {rp, rows}, {pa, rows}, {qa, rows}, {pb, rows}, {qb, rows}};
+    if (!outputs_apart(outs, 1, ins, 8, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
+    const EqMask1Args A = {u32(x), u32(y), u32(r), u32(rp), u32(pa), u32(qa), u32(pb), u32(qb), u32(masked), rows};
+    if (y) return run.template rows<EqMask1Row<true>>(A, rows, count);
+    return run.template rows<EqMask1Row<false>>(A, rows, count);
+}
+
+template <class Run> static int eq_mid_step(const Run &run, const uint64_t *opened, const uint64_t *pa, const uint64_t *qa, const uint64_t *pqa, const uint64_t *pb,
+                                            const uint64_t *qb, const uint64_t *pqb, const uint64_t *bits, const uint64_t *pc, const uint64_t *qc,
+                                            const uint64_t *nr_host, uint64_t *masked2, uint64_t *dr, int rows, int64_t count) {
+    if (count < 0 || !nr_host) return HB_ERR_BAD_ARG;
+    const uint64_t *planes[9] = {pa, qa, pqa, pb, qb, pqb, bits, pc, qc};
+    if (count > 0) {
+        for (const uint64_t *in : planes) if (!in) return HB_ERR_BAD_ARG;
+        if (!opened || !masked2 || !dr) return HB_ERR_BAD_ARG;
     }
-    return HB_OK;
+    if (!eq_rows_ok(rows)) return run.fail(HB_ERR_BAD_ARG, "hb_eq_mid: needs 1 <= rows <= 4096");
+    const RowSpan outs[2] = {{masked2, 2 * rows}, {dr, rows}};
+    RowSpan ins[10] = {{opened, 4 * rows}};
+    for (int k = 0; k < 9; k++) ins[1 + k] = {planes[k], rows};
+    if (!outputs_apart(outs, 2, ins, 10, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_eq_mid: the outputs are arrays of their own");
+    const int rc = run.template rows<EqMidRow, EqMidArgs>([&](auto &A, const auto &P) {
+        A.opened = u32(opened); A.pa = u32(pa); A.qa = u32(qa); A.pqa = u32(pqa); A.pb = u32(pb); A.qb = u32(qb); A.pqb = u32(pqb);
+        A.bits = u32(bits); A.pc = u32(pc); A.qc = u32(qc); A.masked2 = u32(masked2); A.dr = u32(dr); A.rows = rows;
+        return eq_mid_consts(A.K, P, nr_host);
+    }, rows, count);
+    return rc == HB_ERR_BAD_ARG ? run.fail(rc, "hb_eq_mid: nr must be a residue class other than 0 and 1") : rc;
+}
+
+template <class Run> static int eq_cshare_step(const Run &run, const uint64_t *opened2, const uint64_t *dr, const uint64_t *pc, const uint64_t *qc, const uint64_t *pqc,
+                                               uint64_t *c, int rows, int64_t count) {
+    if (count < 0 || (count > 0 && (!opened2 || !dr || !pc || !qc || !pqc || !c))) return HB_ERR_BAD_ARG;
+    if (!eq_rows_ok(rows)) return run.fail(HB_ERR_BAD_ARG, "hb_eq_cshare: needs 1 <= rows <= 4096");
+    if (count == 0) return HB_OK;
+    // c == dr is the permitted alias: dr is then left out of the inputs c must keep apart from
+    const RowSpan outs[1] = {{c, rows}},
+                 ins[5] = {{opened2, 2 * rows}, {c == dr ? nullptr : dr, rows}, {pc, rows}, {qc, rows}, {pqc, rows}};
+    if (!outputs_apart(outs, 1, ins, 5, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_eq_cshare: c may be dr itself and no other input");
+    const EqCshareArgs A = {u32(opened2), u32(dr), u32(pc), u32(qc), u32(pqc), u32(c), rows};
+    return run.template rows<EqCshareRow>(A, rows, count);
+}
+
+template <class Run> static int eq_finish_step(const Run &run, const uint64_t *c, const uint64_t *bits, int mode, const uint64_t *nr_host, uint64_t *factor,
+                                               int32_t *zero_rows, int rows, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    if (mode != HB_EQ_BIT && mode != HB_EQ_REFERENCE) return run.fail(HB_ERR_BAD_ARG, "hb_eq_finish: unknown mode");
+    if ((mode == HB_EQ_REFERENCE && !nr_host) || (count > 0 && (!c || !bits || !factor || !zero_rows))) return HB_ERR_BAD_ARG;
+    if (!eq_rows_ok(rows)) return run.fail(HB_ERR_BAD_ARG, "hb_eq_finish: needs 1 <= rows <= 4096");
+    EqSched S;
+    if (!eq_make_sched(S, run.modulus(), run.limbs())) return run.fail(HB_ERR_UNSUPPORTED, "hb_eq_finish: no schedule for this modulus");
+    // factor == c and factor == bits are the permitted aliases: such an input is left out of those factor must keep apart from;
+    // zero_rows is 4 bytes a row, not rows of elements
+    const int64_t row_bytes = run.elem_bytes() * count, zb = 4 * (int64_t)rows;
+    const RowSpan outs[1] = {{factor, rows}}, ins[2] = {{factor == c ? nullptr : c, rows}, {factor == bits ? nullptr : bits, rows}};
+    if (count > 0 && (!outputs_apart(outs, 1, ins, 2, row_bytes) || overlap(zero_rows, zb, c, rows * row_bytes) ||
+                      overlap(zero_rows, zb, bits, rows * row_bytes) || overlap(zero_rows, zb, factor, rows * row_bytes)))
+        return run.fail(HB_ERR_BAD_ARG, "hb_eq_finish: factor may be c or bits themselves; zero_rows is an array of its own");
+    const int rc = run.template rows<EqFinishRow, EqFinishArgs>([&](auto &A, const auto &P) {
+        A.S = S; A.c = u32(c); A.bits = u32(bits); A.factor = u32(factor); A.zero_rows = zero_rows;
+        return eq_finish_consts(A.K, P, run.modulus(), run.limbs(), mode, nr_host);
+    }, rows, count);
+    return rc == HB_ERR_BAD_ARG ? run.fail(rc, "hb_eq_finish: nr must be a residue class other than 0 and 1") : rc;
 }
 
 }  // namespace hb
@@ -367,110 +415,48 @@ static int selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uin
 extern "C" {
 
 int hb_legendre(hb_ctx *ctx, const uint64_t *a_dev, int8_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!a_dev || !out_dev))) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    EqLegendreArgs A = {{}, u32(a_dev), out_dev};
-    if (!eq_make_sched(A.S, ctx->p_limbs, ctx->n_limbs)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_legendre: no schedule for this modulus");
-    if (overlap(out_dev, count, a_dev, count * 8 * (int64_t)ctx->n_limbs)) return fail(ctx, HB_ERR_BAD_ARG, "hb_legendre: out overlaps a");
-    HB_ROW_BLOCKS(ctx, "hb_legendre");
-    return launch_rows<EqLegendreRow>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : legendre_step(DeviceRun{ctx, (hipStream_t)stream, "hb_legendre"}, a_dev, out_dev, count);
 }
 
 int hb_eq_mask1(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *r_dev, const uint64_t *rp_dev, const uint64_t *pa_dev, const uint64_t *qa_dev,
                 const uint64_t *pb_dev, const uint64_t *qb_dev, uint64_t *masked_dev, int rows, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!x_dev || !r_dev || !rp_dev || !pa_dev || !qa_dev || !pb_dev || !qb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: needs 1 <= rows <= 4096");
-    if (count == 0) return HB_OK;
-    const RowSpan outs[1] = {{masked_dev, 4 * rows}},
-                 ins[8] = {{x_dev, 1}, {y_dev, 1}, {r_dev, rows}, {rp_dev, rows}, {pa_dev, rows}, {qa_dev, rows}, {pb_dev, rows}, {qb_dev, rows}};
-    if (!outputs_apart(outs, 1, ins, 8, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mask1: masked is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_eq_mask1");
-    const dim3 grid((unsigned)blocks, (unsigned)rows);
-    const EqMask1Args A = {u32(x_dev), u32(y_dev), u32(r_dev), u32(rp_dev), u32(pa_dev), u32(qa_dev), u32(pb_dev), u32(qb_dev), u32(masked_dev), rows};
-    if (y_dev) return launch_rows<EqMask1Row<true>>(ctx, A, grid, s, count);
-    return launch_rows<EqMask1Row<false>>(ctx, A, grid, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : eq_mask1_step(DeviceRun{ctx, (hipStream_t)stream, "hb_eq_mask1"}, x_dev, y_dev, r_dev, rp_dev, pa_dev, qa_dev, pb_dev, qb_dev,
+                                                 masked_dev, rows, count);
 }
 
 int hb_eq_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *pa_dev, const uint64_t *qa_dev, const uint64_t *pqa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev,
               const uint64_t *pqb_dev, const uint64_t *bits_dev, const uint64_t *pc_dev, const uint64_t *qc_dev, const uint64_t *nr_host, uint64_t *masked2_dev,
               uint64_t *dr_dev, int rows, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || !nr_host) return HB_ERR_BAD_ARG;
-    const uint64_t *planes[9] = {pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, bits_dev, pc_dev, qc_dev};
-    if (count > 0) {
-        for (const uint64_t *in : planes) if (!in) return HB_ERR_BAD_ARG;
-        if (!opened_dev || !masked2_dev || !dr_dev) return HB_ERR_BAD_ARG;
-    }
-    if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: needs 1 <= rows <= 4096");
-    const RowSpan outs[2] = {{masked2_dev, 2 * rows}, {dr_dev, rows}};
-    RowSpan ins[10] = {{opened_dev, 4 * rows}};
-    for (int k = 0; k < 9; k++) ins[1 + k] = {planes[k], rows};
-    if (!outputs_apart(outs, 2, ins, 10, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_mid: the outputs are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_eq_mid");
-    const int rc = launch_rows<EqMidRow, EqMidArgs>(ctx, [&](auto &A, const auto &P) {
-        A.opened = u32(opened_dev); A.pa = u32(pa_dev); A.qa = u32(qa_dev); A.pqa = u32(pqa_dev); A.pb = u32(pb_dev); A.qb = u32(qb_dev); A.pqb = u32(pqb_dev);
-        A.bits = u32(bits_dev); A.pc = u32(pc_dev); A.qc = u32(qc_dev); A.masked2 = u32(masked2_dev); A.dr = u32(dr_dev); A.rows = rows;
-        return eq_mid_consts(A.K, P, nr_host);
-    }, dim3((unsigned)blocks, (unsigned)rows), s, count);
-    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_eq_mid: nr must be a residue class other than 0 and 1") : rc;
+    return !ctx ? HB_ERR_BAD_ARG : eq_mid_step(DeviceRun{ctx, (hipStream_t)stream, "hb_eq_mid"}, opened_dev, pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, bits_dev,
+                                               pc_dev, qc_dev, nr_host, masked2_dev, dr_dev, rows, count);
 }
 
 int hb_eq_cshare(hb_ctx *ctx, const uint64_t *opened2_dev, const uint64_t *dr_dev, const uint64_t *pc_dev, const uint64_t *qc_dev, const uint64_t *pqc_dev, uint64_t *c_dev,
                  int rows, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!opened2_dev || !dr_dev || !pc_dev || !qc_dev || !pqc_dev || !c_dev))) return HB_ERR_BAD_ARG;
-    if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_cshare: needs 1 <= rows <= 4096");
-    if (count == 0) return HB_OK;
-    // c == dr is the permitted alias: dr is then left out of the inputs c must keep apart from
-    const RowSpan outs[1] = {{c_dev, rows}},
-                 ins[5] = {{opened2_dev, 2 * rows}, {c_dev == dr_dev ? nullptr : dr_dev, rows}, {pc_dev, rows}, {qc_dev, rows}, {pqc_dev, rows}};
-    if (!outputs_apart(outs, 1, ins, 5, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_cshare: c may be dr itself and no other input");
-    HB_ROW_BLOCKS(ctx, "hb_eq_cshare");
-    const EqCshareArgs A = {u32(opened2_dev), u32(dr_dev), u32(pc_dev), u32(qc_dev), u32(pqc_dev), u32(c_dev), rows};
-    return launch_rows<EqCshareRow>(ctx, A, dim3((unsigned)blocks, (unsigned)rows), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : eq_cshare_step(DeviceRun{ctx, (hipStream_t)stream, "hb_eq_cshare"}, opened2_dev, dr_dev, pc_dev, qc_dev, pqc_dev, c_dev, rows, count);
 }
 
 int hb_eq_finish(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int mode, const uint64_t *nr_host, uint64_t *factor_dev, int32_t *zero_rows_dev, int rows,
                  int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (mode != HB_EQ_BIT && mode != HB_EQ_REFERENCE) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_finish: unknown mode");
-    if ((mode == HB_EQ_REFERENCE && !nr_host) || (count > 0 && (!c_dev || !bits_dev || !factor_dev || !zero_rows_dev))) return HB_ERR_BAD_ARG;
-    if (!eq_rows_ok(rows)) return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_finish: needs 1 <= rows <= 4096");
-    EqSched S;
-    if (!eq_make_sched(S, ctx->p_limbs, ctx->n_limbs)) return fail(ctx, HB_ERR_UNSUPPORTED, "hb_eq_finish: no schedule for this modulus");
-    // factor == c and factor == bits are the permitted aliases: such an input is left out of those factor must keep apart from;
-    // zero_rows is 4 bytes a row, not rows of elements
-    const int64_t row_bytes = 8 * (int64_t)ctx->n_limbs * count, zb = 4 * (int64_t)rows;
-    const RowSpan outs[1] = {{factor_dev, rows}}, ins[2] = {{factor_dev == c_dev ? nullptr : c_dev, rows}, {factor_dev == bits_dev ? nullptr : bits_dev, rows}};
-    if (count > 0 && (!outputs_apart(outs, 1, ins, 2, row_bytes) || overlap(zero_rows_dev, zb, c_dev, rows * row_bytes) ||
-                      overlap(zero_rows_dev, zb, bits_dev, rows * row_bytes) || overlap(zero_rows_dev, zb, factor_dev, rows * row_bytes)))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_eq_finish: factor may be c or bits themselves; zero_rows is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_eq_finish");
-    const int rc = launch_rows<EqFinishRow, EqFinishArgs>(ctx, [&](auto &A, const auto &P) {
-        A.S = S; A.c = u32(c_dev); A.bits = u32(bits_dev); A.factor = u32(factor_dev); A.zero_rows = zero_rows_dev;
-        return eq_finish_consts(A.K, P, ctx->p_limbs, ctx->n_limbs, mode, nr_host);
-    }, dim3((unsigned)blocks, (unsigned)rows), s, count);
-    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_eq_finish: nr must be a residue class other than 0 and 1") : rc;
+    return !ctx ? HB_ERR_BAD_ARG : eq_finish_step(DeviceRun{ctx, (hipStream_t)stream, "hb_eq_finish"}, c_dev, bits_dev, mode, nr_host, factor_dev, zero_rows_dev, rows,
+                                                  count);
 }
 
-int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, void *const *outs, int64_t count) {
-    if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
-    const int64_t rows = params[0], mode = params[1];
-    int n_ops = 0, n_outs = 1;
+// params: rows, mode (read by the steps that take them)
+int hb_selftest_eq(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, void *const *outs, int64_t count) {
+    if (!p_limbs || !ops || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
+    if (params[0] != (int)params[0] || params[1] != (int)params[1]) return HB_ERR_BAD_ARG;    // rows, mode: the steps take them as int
+    const HostRun run = {p_limbs, n_limbs};
+    const int rows = (int)params[0], mode = (int)params[1];
     switch (what) {
-    case HB_EQ_SELFTEST_LEGENDRE: n_ops = 1; break;
-    case HB_EQ_SELFTEST_MASK1: n_ops = 8; break;
-    case HB_EQ_SELFTEST_MID: n_ops = 11; n_outs = 2; break;
-    case HB_EQ_SELFTEST_CSHARE: n_ops = 5; break;
-    case HB_EQ_SELFTEST_FINISH: n_ops = 2; n_outs = 2; if (mode != HB_EQ_BIT && mode != HB_EQ_REFERENCE) return HB_ERR_BAD_ARG; break;
+    case HB_EQ_SELFTEST_LEGENDRE: return legendre_step(run, ops[0], (int8_t *)outs[0], count);
+    case HB_EQ_SELFTEST_MASK1: return eq_mask1_step(run, ops[0], ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], ops[7], (uint64_t *)outs[0], rows, count);
+    case HB_EQ_SELFTEST_MID:
+        return eq_mid_step(run, ops[0], ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], ops[7], ops[8], ops[9], ops[10], (uint64_t *)outs[0], (uint64_t *)outs[1], rows, count);
+    case HB_EQ_SELFTEST_CSHARE: return eq_cshare_step(run, ops[0], ops[1], ops[2], ops[3], ops[4], (uint64_t *)outs[0], rows, count);
+    case HB_EQ_SELFTEST_FINISH: return eq_finish_step(run, ops[0], ops[1], mode, ops[2], (uint64_t *)outs[0], (int32_t *)outs[1], rows, count);
     default: return HB_ERR_BAD_ARG;
     }
-    if (what != HB_EQ_SELFTEST_LEGENDRE && !eq_rows_ok((int)(rows < 0 || rows > 4096 ? 0 : rows))) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_ops; i++)
-        if (count > 0 && !operands[i] && !(what == HB_EQ_SELFTEST_MASK1 && i == 1)) return HB_ERR_BAD_ARG;
-    if (what == HB_EQ_SELFTEST_MID && !operands[10]) return HB_ERR_BAD_ARG;
-    if (what == HB_EQ_SELFTEST_FINISH && ((mode == HB_EQ_REFERENCE && !operands[2]) || !outs[1])) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_outs; i++) if (count > 0 && !outs[i]) return HB_ERR_BAD_ARG;
-    if (n_limbs == 4) return selftest_eq<9, 8>(p_limbs, n_limbs, what, operands, params, outs, count);
-    return selftest_eq<3, 2>(p_limbs, n_limbs, what, operands, params, outs, count);
 }
 
 }  // extern "C"

@@ -167,6 +167,7 @@ struct FxpFinishRow {
 };
 
 // ---------------------------------------------------------------- host side
+// One step function a step (hb_rows.hpp): its checks, Args fill and row count run under a DeviceRun in the entry point, a HostRun in hb_selftest_fxp.
 // the constants of a step from its parameters; false if inv2m is not below the modulus
 template <int NL> static bool fxp_mask_consts(FxpMaskArgs<NL> &A, const FpParams<NL> &P, int k, int m, int kappa) {
     A.nbits = k + kappa; A.m = m;
@@ -186,36 +187,77 @@ template <int NL> static bool fxp_finish_consts(FxpFinishArgs<NL> &A, const FpPa
 static bool fxp_level_ok(int nodes, int root) { return nodes >= 2 && nodes <= 257 && (!root || nodes == 2); }
 static int fxp_level_triples(int nodes, int root) { return root ? 1 : 2 * (nodes / 2); }
 
-// host: the same rows over `count` elements
-template <int NL, int NW>
-static int selftest_fxp(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    FpParams<NL> P;
-    fp_params_from_limbs(P, p_limbs);
-    const int k = (int)params[0], m = (int)params[1], kappa = (int)params[2], aux = (int)params[3], root = (int)params[4];
-    if (what == HB_FXP_SELFTEST_MASK) {
-        FxpMaskArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1])};
-        fxp_mask_consts<NL>(A, P, k, m, kappa);
-        if (A.x) host_rows<FxpMaskRow<true>, NL, NW>(A, 1, count, P);
-        else host_rows<FxpMaskRow<false>, NL, NW>(A, 1, count, P);
-    } else if (what == HB_FXP_SELFTEST_TRUNC_PR) {
-        FxpTruncPrArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(outs[0])};
-        if (!fxp_trunc_pr_consts<NL>(A, P, m, ops[3])) return HB_ERR_BAD_ARG;
-        host_rows<FxpTruncPrRow, NL, NW>(A, 1, count, P);
-    } else if (what == HB_FXP_SELFTEST_LEAVES) {
-        const LeavesArgs A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1]), m};
-        host_rows<FxpLeavesRow, NL, NW>(A, 1, count, P);
-    } else if (what == HB_FXP_SELFTEST_CARRY_MASK) {
-        const FxpCarryMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0])};
-        host_rows<FxpCarryMaskRow, NL, NW>(A, fxp_level_triples(aux, root), count, P);
-    } else if (what == HB_FXP_SELFTEST_CARRY_COMBINE) {
-        const FxpCarryCombineArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(outs[0]), u32(outs[1]), aux / 2, root};
-        host_rows<FxpCarryCombineRow, NL, NW>(A, (aux + 1) / 2, count, P);
-    } else {
-        FxpFinishArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(outs[0])};
-        if (!fxp_finish_consts<NL>(A, P, m, aux, ops[4])) return HB_ERR_BAD_ARG;
-        host_rows<FxpFinishRow, NL, NW>(A, 1, count, P);
-    }
-    return HB_OK;
+template <class Run> static int fxp_mask_step(const Run &run, const uint64_t *x, const uint64_t *bits, int k, int m, int kappa, uint64_t *masked, uint64_t *r1,
+                                              int64_t count) {
+    if (count < 0 || (count > 0 && (!bits || !masked || !r1))) return HB_ERR_BAD_ARG;
+    if (!fxp_params_ok(run.bits(), k, m, kappa))
+        return run.fail(HB_ERR_BAD_ARG, "hb_fxp_mask: needs 0 < m < k, kappa >= 0 and k + kappa + 1 <= bits(p) - 1");
+    if (count > 0 && masked == r1) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_mask: masked and r1 are one array");
+    if (count == 0) return HB_OK;
+    const auto fill = [&](auto &A, const auto &P) {
+        A.x = u32(x); A.bits = u32(bits); A.masked = u32(masked); A.r1 = u32(r1);
+        return fxp_mask_consts(A, P, k, m, kappa);
+    };
+    if (x) return run.template rows<FxpMaskRow<true>, FxpMaskArgs>(fill, 1, count);
+    return run.template rows<FxpMaskRow<false>, FxpMaskArgs>(fill, 1, count);
+}
+
+template <class Run> static int fxp_trunc_pr_step(const Run &run, const uint64_t *x, const uint64_t *c, const uint64_t *r1, int m, const uint64_t *inv2m_host,
+                                                  uint64_t *out, int64_t count) {
+    if (count < 0 || !inv2m_host || (count > 0 && (!x || !c || !r1 || !out))) return HB_ERR_BAD_ARG;
+    if (!fxp_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_trunc_pr: needs 0 < m <= bits(p) - 2");
+    const int rc = run.template rows<FxpTruncPrRow, FxpTruncPrArgs>([&](auto &A, const auto &P) {
+        A.x = u32(x); A.c = u32(c); A.r1 = u32(r1); A.out = u32(out);
+        return fxp_trunc_pr_consts(A, P, m, inv2m_host);
+    }, 1, count);
+    return rc == HB_ERR_BAD_ARG ? run.fail(rc, "hb_fxp_trunc_pr: inv2m is not below the modulus") : rc;
+}
+
+template <class Run> static int fxp_ltl_leaves_step(const Run &run, const uint64_t *c, const uint64_t *bits, int m, uint64_t *g, uint64_t *p, int64_t count) {
+    if (count < 0 || (count > 0 && (!c || !bits || !g || !p))) return HB_ERR_BAD_ARG;
+    if (!fxp_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: needs 0 < m <= bits(p) - 2");
+    if (count == 0) return HB_OK;
+    const RowSpan outs[2] = {{g, m + 1}, {p, m + 1}}, ins[2] = {{c, 1}, {bits, m}};
+    if (!outputs_apart(outs, 2, ins, 2, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: g and p are arrays of their own");
+    return run_leaves<FxpLeavesRow>(run, {u32(c), u32(bits), u32(g), u32(p), m}, count);
+}
+
+template <class Run> static int fxp_carry_mask_step(const Run &run, const uint64_t *g, const uint64_t *p, int nodes, int root, const uint64_t *ta, const uint64_t *tb,
+                                                    uint64_t *masked, int64_t count) {
+    if (count < 0 || (count > 0 && (!g || !p || !ta || !tb || !masked))) return HB_ERR_BAD_ARG;
+    if (!fxp_level_ok(nodes, root)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_carry_mask: needs 2 <= nodes <= 257, and nodes == 2 at the root");
+    if (count == 0) return HB_OK;
+    const int triples = fxp_level_triples(nodes, root);
+    const RowSpan outs[1] = {{masked, 2 * triples}}, ins[4] = {{g, nodes}, {p, nodes}, {ta, triples}, {tb, triples}};
+    if (!outputs_apart(outs, 1, ins, 4, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_carry_mask: masked is an array of its own");
+    const FxpCarryMaskArgs A = {u32(g), u32(p), u32(ta), u32(tb), u32(masked)};
+    return run.template rows<FxpCarryMaskRow>(A, triples, count);
+}
+
+template <class Run> static int fxp_carry_combine_step(const Run &run, const uint64_t *opened, const uint64_t *g, const uint64_t *p, int nodes, int root,
+                                                       const uint64_t *ta, const uint64_t *tb, const uint64_t *tab, uint64_t *g_out, uint64_t *p_out, int64_t count) {
+    if (count < 0 || (count > 0 && (!opened || !g || !p || !ta || !tb || !tab || !g_out || (!root && !p_out)))) return HB_ERR_BAD_ARG;
+    if (!fxp_level_ok(nodes, root)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_carry_combine: needs 2 <= nodes <= 257, and nodes == 2 at the root");
+    if (count == 0) return HB_OK;
+    const int pairs = nodes / 2, out_nodes = (nodes + 1) / 2, triples = fxp_level_triples(nodes, root);
+    const RowSpan outs[2] = {{g_out, out_nodes}, {root ? nullptr : p_out, out_nodes}};
+    const RowSpan ins[6] = {{g, nodes}, {p, nodes}, {opened, 2 * triples}, {ta, triples}, {tb, triples}, {tab, triples}};
+    if (!outputs_apart(outs, 2, ins, 6, run.elem_bytes() * count)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_carry_combine: the outputs are arrays of their own");
+    const FxpCarryCombineArgs A = {u32(opened), u32(g), u32(p), u32(ta), u32(tb), u32(tab), u32(g_out), u32(p_out), pairs, root};
+    return run.template rows<FxpCarryCombineRow>(A, out_nodes, count);
+}
+
+template <class Run> static int fxp_div2m_finish_step(const Run &run, const uint64_t *x, const uint64_t *c, const uint64_t *r1, const uint64_t *carry, int m,
+                                                      const uint64_t *inv2m_host, int mode, uint64_t *out, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    if (mode != HB_FXP_MOD && mode != HB_FXP_TRUNC && mode != HB_FXP_NEG_TRUNC) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: unknown mode");
+    if ((mode != HB_FXP_MOD && !inv2m_host) || (count > 0 && (!c || !r1 || !carry || !out || (mode != HB_FXP_MOD && !x)))) return HB_ERR_BAD_ARG;
+    if (!fxp_m_ok(run.bits(), m)) return run.fail(HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: needs 0 < m <= bits(p) - 2");
+    const int rc = run.template rows<FxpFinishRow, FxpFinishArgs>([&](auto &A, const auto &P) {
+        A.x = u32(x); A.c = u32(c); A.r1 = u32(r1); A.carry = u32(carry); A.out = u32(out);
+        return fxp_finish_consts(A, P, m, mode, inv2m_host);
+    }, 1, count);
+    return rc == HB_ERR_BAD_ARG ? run.fail(rc, "hb_fxp_div2m_finish: inv2m is not below the modulus") : rc;
 }
 
 }  // namespace hb
@@ -224,104 +266,51 @@ extern "C" {
 
 int hb_fxp_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *bits_dev, int k, int m, int kappa, uint64_t *masked_dev, uint64_t *r1_dev, int64_t count,
                 void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!bits_dev || !masked_dev || !r1_dev))) return HB_ERR_BAD_ARG;
-    if (!fxp_params_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), k, m, kappa))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_mask: needs 0 < m < k, kappa >= 0 and k + kappa + 1 <= bits(p) - 1");
-    if (count > 0 && masked_dev == r1_dev) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_mask: masked and r1 are one array");
-    if (count == 0) return HB_OK;
-    HB_ROW_BLOCKS(ctx, "hb_fxp_mask");
-    const auto fill = [&](auto &A, const auto &P) {
-        A.x = u32(x_dev); A.bits = u32(bits_dev); A.masked = u32(masked_dev); A.r1 = u32(r1_dev);
-        return fxp_mask_consts(A, P, k, m, kappa);
-    };
-    if (x_dev) return launch_rows<FxpMaskRow<true>, FxpMaskArgs>(ctx, fill, (unsigned)blocks, s, count);
-    return launch_rows<FxpMaskRow<false>, FxpMaskArgs>(ctx, fill, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : fxp_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_fxp_mask"}, x_dev, bits_dev, k, m, kappa, masked_dev, r1_dev, count);
 }
 
 int hb_fxp_trunc_pr(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, int m, const uint64_t *inv2m_host, uint64_t *out_dev,
                     int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || !inv2m_host || (count > 0 && (!x_dev || !c_dev || !r1_dev || !out_dev))) return HB_ERR_BAD_ARG;
-    if (!fxp_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_trunc_pr: needs 0 < m <= bits(p) - 2");
-    HB_ROW_BLOCKS(ctx, "hb_fxp_trunc_pr");
-    const int rc = launch_rows<FxpTruncPrRow, FxpTruncPrArgs>(ctx, [&](auto &A, const auto &P) {
-        A.x = u32(x_dev); A.c = u32(c_dev); A.r1 = u32(r1_dev); A.out = u32(out_dev);
-        return fxp_trunc_pr_consts(A, P, m, inv2m_host);
-    }, (unsigned)blocks, s, count);
-    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_fxp_trunc_pr: inv2m is not below the modulus") : rc;
+    return !ctx ? HB_ERR_BAD_ARG : fxp_trunc_pr_step(DeviceRun{ctx, (hipStream_t)stream, "hb_fxp_trunc_pr"}, x_dev, c_dev, r1_dev, m, inv2m_host, out_dev, count);
 }
 
 int hb_fxp_ltl_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *bits_dev, int m, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!c_dev || !bits_dev || !g_dev || !p_dev))) return HB_ERR_BAD_ARG;
-    if (!fxp_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: needs 0 < m <= bits(p) - 2");
-    if (count == 0) return HB_OK;
-    const RowSpan outs[2] = {{g_dev, m + 1}, {p_dev, m + 1}}, ins[2] = {{c_dev, 1}, {bits_dev, m}};
-    if (!outputs_apart(outs, 2, ins, 2, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_ltl_leaves: g and p are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_fxp_ltl_leaves");
-    return launch_leaves<FxpLeavesRow>(ctx, {u32(c_dev), u32(bits_dev), u32(g_dev), u32(p_dev), m}, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : fxp_ltl_leaves_step(DeviceRun{ctx, (hipStream_t)stream, "hb_fxp_ltl_leaves"}, c_dev, bits_dev, m, g_dev, p_dev, count);
 }
 
 int hb_fxp_carry_mask(hb_ctx *ctx, const uint64_t *g_dev, const uint64_t *p_dev, int nodes, int root, const uint64_t *ta_dev, const uint64_t *tb_dev,
                       uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!g_dev || !p_dev || !ta_dev || !tb_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (!fxp_level_ok(nodes, root)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_mask: needs 2 <= nodes <= 257, and nodes == 2 at the root");
-    if (count == 0) return HB_OK;
-    const int triples = fxp_level_triples(nodes, root);
-    const RowSpan outs[1] = {{masked_dev, 2 * triples}}, ins[4] = {{g_dev, nodes}, {p_dev, nodes}, {ta_dev, triples}, {tb_dev, triples}};
-    if (!outputs_apart(outs, 1, ins, 4, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_mask: masked is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_fxp_carry_mask");
-    const FxpCarryMaskArgs A = {u32(g_dev), u32(p_dev), u32(ta_dev), u32(tb_dev), u32(masked_dev)};
-    return launch_rows<FxpCarryMaskRow>(ctx, A, dim3((unsigned)blocks, (unsigned)triples), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : fxp_carry_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_fxp_carry_mask"}, g_dev, p_dev, nodes, root, ta_dev, tb_dev, masked_dev,
+                                                       count);
 }
 
 int hb_fxp_carry_combine(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *g_dev, const uint64_t *p_dev, int nodes, int root, const uint64_t *ta_dev,
                          const uint64_t *tb_dev, const uint64_t *tab_dev, uint64_t *g_out_dev, uint64_t *p_out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!opened_dev || !g_dev || !p_dev || !ta_dev || !tb_dev || !tab_dev || !g_out_dev || (!root && !p_out_dev)))) return HB_ERR_BAD_ARG;
-    if (!fxp_level_ok(nodes, root)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_combine: needs 2 <= nodes <= 257, and nodes == 2 at the root");
-    if (count == 0) return HB_OK;
-    const int pairs = nodes / 2, out_nodes = (nodes + 1) / 2, triples = fxp_level_triples(nodes, root);
-    const RowSpan outs[2] = {{g_out_dev, out_nodes}, {root ? nullptr : p_out_dev, out_nodes}};
-    const RowSpan ins[6] = {{g_dev, nodes}, {p_dev, nodes}, {opened_dev, 2 * triples}, {ta_dev, triples}, {tb_dev, triples}, {tab_dev, triples}};
-    if (!outputs_apart(outs, 2, ins, 6, 8 * (int64_t)ctx->n_limbs * count)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_carry_combine: the outputs are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_fxp_carry_combine");
-    const FxpCarryCombineArgs A = {u32(opened_dev), u32(g_dev), u32(p_dev), u32(ta_dev), u32(tb_dev), u32(tab_dev), u32(g_out_dev), u32(p_out_dev), pairs, root};
-    return launch_rows<FxpCarryCombineRow>(ctx, A, dim3((unsigned)blocks, (unsigned)out_nodes), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : fxp_carry_combine_step(DeviceRun{ctx, (hipStream_t)stream, "hb_fxp_carry_combine"}, opened_dev, g_dev, p_dev, nodes, root, ta_dev,
+                                                          tb_dev, tab_dev, g_out_dev, p_out_dev, count);
 }
 
 int hb_fxp_div2m_finish(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *c_dev, const uint64_t *r1_dev, const uint64_t *carry_dev, int m, const uint64_t *inv2m_host,
                         int mode, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    if (mode != HB_FXP_MOD && mode != HB_FXP_TRUNC && mode != HB_FXP_NEG_TRUNC) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: unknown mode");
-    if ((mode != HB_FXP_MOD && !inv2m_host) || (count > 0 && (!c_dev || !r1_dev || !carry_dev || !out_dev || (mode != HB_FXP_MOD && !x_dev)))) return HB_ERR_BAD_ARG;
-    if (!fxp_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), m)) return fail(ctx, HB_ERR_BAD_ARG, "hb_fxp_div2m_finish: needs 0 < m <= bits(p) - 2");
-    HB_ROW_BLOCKS(ctx, "hb_fxp_div2m_finish");
-    const int rc = launch_rows<FxpFinishRow, FxpFinishArgs>(ctx, [&](auto &A, const auto &P) {
-        A.x = u32(x_dev); A.c = u32(c_dev); A.r1 = u32(r1_dev); A.carry = u32(carry_dev); A.out = u32(out_dev);
-        return fxp_finish_consts(A, P, m, mode, inv2m_host);
-    }, (unsigned)blocks, s, count);
-    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_fxp_div2m_finish: inv2m is not below the modulus") : rc;
+    return !ctx ? HB_ERR_BAD_ARG : fxp_div2m_finish_step(DeviceRun{ctx, (hipStream_t)stream, "hb_fxp_div2m_finish"}, x_dev, c_dev, r1_dev, carry_dev, m, inv2m_host,
+                                                         mode, out_dev, count);
 }
 
-int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
+// params: k, m, kappa, aux (nodes of a level, the finish's mode), root
+int hb_selftest_fxp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
+    if (!p_limbs || !ops || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 5; i++) if (params[i] < -(1 << 30) || params[i] > (1 << 30)) return HB_ERR_BAD_ARG;
-    const int bits = modulus_bits(p_limbs, n_limbs);
+    const HostRun run = {p_limbs, n_limbs};
     const int k = (int)params[0], m = (int)params[1], kappa = (int)params[2], aux = (int)params[3], root = (int)params[4];
-    int n_ops = 0, n_outs = 1, first_op = 0;
     switch (what) {
-    case HB_FXP_SELFTEST_MASK: if (!fxp_params_ok(bits, k, m, kappa)) return HB_ERR_BAD_ARG; n_ops = 2; n_outs = 2; first_op = 1; break;
-    case HB_FXP_SELFTEST_TRUNC_PR: if (!fxp_m_ok(bits, m) || !operands[3]) return HB_ERR_BAD_ARG; n_ops = 4; break;
-    case HB_FXP_SELFTEST_LEAVES: if (!fxp_m_ok(bits, m)) return HB_ERR_BAD_ARG; n_ops = 2; n_outs = 2; break;
-    case HB_FXP_SELFTEST_CARRY_MASK: if (!fxp_level_ok(aux, root)) return HB_ERR_BAD_ARG; n_ops = 4; break;
-    case HB_FXP_SELFTEST_CARRY_COMBINE: if (!fxp_level_ok(aux, root)) return HB_ERR_BAD_ARG; n_ops = 6; n_outs = root ? 1 : 2; break;
-    case HB_FXP_SELFTEST_FINISH:
-        if (!fxp_m_ok(bits, m) || (aux != HB_FXP_MOD && aux != HB_FXP_TRUNC && aux != HB_FXP_NEG_TRUNC) || (aux != HB_FXP_MOD && !operands[4])) return HB_ERR_BAD_ARG;
-        n_ops = 4; first_op = aux == HB_FXP_MOD ? 1 : 0; break;
+    case HB_FXP_SELFTEST_MASK: return fxp_mask_step(run, ops[0], ops[1], k, m, kappa, outs[0], outs[1], count);
+    case HB_FXP_SELFTEST_TRUNC_PR: return fxp_trunc_pr_step(run, ops[0], ops[1], ops[2], m, ops[3], outs[0], count);
+    case HB_FXP_SELFTEST_LEAVES: return fxp_ltl_leaves_step(run, ops[0], ops[1], m, outs[0], outs[1], count);
+    case HB_FXP_SELFTEST_CARRY_MASK: return fxp_carry_mask_step(run, ops[0], ops[1], aux, root, ops[2], ops[3], outs[0], count);
+    case HB_FXP_SELFTEST_CARRY_COMBINE: return fxp_carry_combine_step(run, ops[0], ops[1], ops[2], aux, root, ops[3], ops[4], ops[5], outs[0], outs[1], count);
+    case HB_FXP_SELFTEST_FINISH: return fxp_div2m_finish_step(run, ops[0], ops[1], ops[2], ops[3], m, ops[4], aux, outs[0], count);
     default: return HB_ERR_BAD_ARG;
     }
-    for (int i = first_op; i < n_ops; i++) if (count > 0 && !operands[i]) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_outs; i++) if (count > 0 && !outs[i]) return HB_ERR_BAD_ARG;
-    if (n_limbs == 4) return selftest_fxp<9, 8>(p_limbs, what, operands, params, outs, count);
-    return selftest_fxp<3, 2>(p_limbs, what, operands, params, outs, count);
 }
 
 }  // extern "C"

@@ -158,6 +158,12 @@ template <class Row> int launch_leaves(hb_ctx *ctx, const LeavesArgs &A, unsigne
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
+// the last line of a leaves step function (hb_rows.hpp): k_leaves on the device, the row's run on the host
+template <class Row> int run_leaves(const DeviceRun &run, const LeavesArgs &A, int64_t count) {
+    if (!run.fits(count)) return run.too_large();
+    return launch_leaves<Row>(run.ctx, A, (unsigned)run.blocks(count), run.s, count);
+}
+template <class Row> int run_leaves(const HostRun &run, const LeavesArgs &A, int64_t count) { return run.template rows<Row>(A, 1, count); }
 
 // ---------------------------------------------------------------- host side: argument checks
 static inline bool fxp_m_ok(int bits, int m) { return m > 0 && m <= bits - 2; }

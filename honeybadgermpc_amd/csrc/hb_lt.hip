@@ -277,152 +277,145 @@ struct LtXorFinishRow {
 };
 
 // ---------------------------------------------------------------- host side
+// One step function a step (hb_rows.hpp): its checks, Args fill and row count run under a DeviceRun in the entry point, a HostRun in hb_selftest_lt.
 static bool lt_mode_ok(int mode) { return mode == HB_LT_DIRECT || mode == HB_LT_REFERENCE; }
 
-// host: the same rows over `count` elements
-template <int NL, int NW>
-static int selftest_lt(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    FpParams<NL> P;
-    fp_params_from_limbs(P, p_limbs);
-    const int L = (int)params[0], mode = (int)params[1];
-    if (what == HB_LT_SELFTEST_MASK) {
-        const LtMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(outs[0])};
-        if (A.b) host_rows<LtMaskRow<true>, NL, NW>(A, 1, count, P);
-        else host_rows<LtMaskRow<false>, NL, NW>(A, 1, count, P);
-    } else if (what == HB_LT_SELFTEST_LEAVES) {
-        const LtLeavesArgs A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1]), L, mode};
-        host_rows<LtLeavesRow, NL, NW>(A, L, count, P);
-    } else if (what == HB_LT_SELFTEST_XOR_MASK) {
-        const LtXorMaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(outs[0]), u32(outs[1])};
-        host_rows<LtXorMaskRow, NL, NW>(A, 1, count, P);
-    } else if (what == HB_LT_SELFTEST_DMASK) {
-        const LtDmaskArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(outs[0]), u32(outs[1]), L};
-        host_rows<LtDmaskRow, NL, NW>(A, 1, count, P);
-    } else if (what == HB_LT_SELFTEST_MID) {
-        const LtMidArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(ops[6]), u32(ops[7]), u32(ops[8]), u32(ops[9]), u32(ops[10]),
-                             u32(outs[0]), u32(outs[1]), u32(outs[2]), L};
-        host_rows<LtMidRow, NL, NW>(A, 1, count, P);
-    } else {
-        const LtXorFinishArgs A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(outs[0])};
-        host_rows<LtXorFinishRow, NL, NW>(A, 1, count, P);
+template <class Run> static int lt_mask_step(const Run &run, const uint64_t *a, const uint64_t *b, const uint64_t *r, uint64_t *masked, int64_t count) {
+    if (count < 0 || (count > 0 && (!a || !r || !masked))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t eb = run.elem_bytes() * count;
+    const RowSpan outs[1] = {{masked, 1}}, ins[3] = {{a, 1}, {b, 1}, {r, 1}};
+    if (!outputs_apart(outs, 1, ins, 3, eb)) return run.fail(HB_ERR_BAD_ARG, "hb_lt_mask: masked is an array of its own");
+    const LtMaskArgs A = {u32(a), u32(b), u32(r), u32(masked)};
+    if (b) return run.template rows<LtMaskRow<true>>(A, 1, count);
+    return run.template rows<LtMaskRow<false>>(A, 1, count);
+}
+
+template <class Run> static int lt_leaves_step(const Run &run, const uint64_t *c, const uint64_t *r_bits, int L, int mode, uint64_t *g, uint64_t *p, int64_t count) {
+    if (count < 0 || (count > 0 && (!c || !r_bits || !g || !p))) return HB_ERR_BAD_ARG;
+    if (!lt_mode_ok(mode)) return run.fail(HB_ERR_BAD_ARG, "hb_lt_leaves: unknown mode");
+    if (L != run.bits()) return run.fail(HB_ERR_BAD_ARG, "hb_lt_leaves: L is the bit length of the modulus");
+    if (count == 0) return HB_OK;
+    const int64_t eb = run.elem_bytes() * count;
+    const RowSpan outs[2] = {{g, L}, {p, L}}, ins[2] = {{c, 1}, {r_bits, L}};
+    if (!outputs_apart(outs, 2, ins, 2, eb)) return run.fail(HB_ERR_BAD_ARG, "hb_lt_leaves: g and p are arrays of their own");
+    const LtLeavesArgs A = {u32(c), u32(r_bits), u32(g), u32(p), L, mode};
+    return run.template rows<LtLeavesRow>(A, L, count);
+}
+
+template <class Run> static int lt_xor_mask_step(const Run &run, const uint64_t *c, const uint64_t *r0, const uint64_t *w, const uint64_t *pa, const uint64_t *qa,
+                                                 uint64_t *u, uint64_t *masked, int64_t count) {
+    if (count < 0 || (count > 0 && (!c || !r0 || !w || !pa || !qa || !u || !masked))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t eb = run.elem_bytes() * count;
+    const RowSpan outs[2] = {{u, 1}, {masked, 2}}, ins[5] = {{c, 1}, {r0, 1}, {w, 1}, {pa, 1}, {qa, 1}};
+    if (!outputs_apart(outs, 2, ins, 5, eb)) return run.fail(HB_ERR_BAD_ARG, "hb_lt_xor_mask: u and masked are arrays of their own");
+    const LtXorMaskArgs A = {u32(c), u32(r0), u32(w), u32(pa), u32(qa), u32(u), u32(masked)};
+    return run.template rows<LtXorMaskRow>(A, 1, count);
+}
+
+template <class Run> static int lt_dmask_step(const Run &run, const uint64_t *c, const uint64_t *r0, const uint64_t *x, const uint64_t *s, const uint64_t *s_bits, int L,
+                                              const uint64_t *pa, const uint64_t *qa, const uint64_t *pb, const uint64_t *qb, uint64_t *u, uint64_t *masked,
+                                              int64_t count) {
+    if (count < 0 || (count > 0 && (!c || !r0 || !x || !s || !s_bits || !pa || !qa || !pb || !qb || !u || !masked)))
+        return HB_ERR_BAD_ARG;
+    if (L != run.bits()) return run.fail(HB_ERR_BAD_ARG, "hb_lt_dmask: L is the bit length of the modulus");
+    if (count == 0) return HB_OK;
+    const int64_t eb = run.elem_bytes() * count;
+    const RowSpan outs[2] = {{u, 1}, {masked, 5}},
+                 ins[9] = {{c, 1}, {r0, 1}, {x, 1}, {s, 1}, {s_bits, L}, {pa, 1}, {qa, 1}, {pb, 1}, {qb, 1}};
+    if (!outputs_apart(outs, 2, ins, 9, eb)) return run.fail(HB_ERR_BAD_ARG, "hb_lt_dmask: u and masked are arrays of their own");
+    const LtDmaskArgs A = {u32(c), u32(r0), u32(x), u32(s), u32(s_bits), u32(pa), u32(qa), u32(pb), u32(qb), u32(u), u32(masked), L};
+    return run.template rows<LtDmaskRow>(A, 1, count);
+}
+
+template <class Run> static int lt_mid_step(const Run &run, const uint64_t *opened, const uint64_t *u, const uint64_t *s_bits, int L, const uint64_t *pa,
+                                            const uint64_t *qa, const uint64_t *pqa, const uint64_t *pb, const uint64_t *qb, const uint64_t *pqb, const uint64_t *pc,
+                                            const uint64_t *qc, uint64_t *v, uint64_t *d0, uint64_t *masked, int64_t count) {
+    if (count < 0) return HB_ERR_BAD_ARG;
+    const uint64_t *trip[8] = {pa, qa, pqa, pb, qb, pqb, pc, qc};
+    if (count > 0) {
+        for (const uint64_t *t : trip) if (!t) return HB_ERR_BAD_ARG;
+        if (!opened || !u || !s_bits || !v || !d0 || !masked) return HB_ERR_BAD_ARG;
     }
-    return HB_OK;
+    if (L != run.bits()) return run.fail(HB_ERR_BAD_ARG, "hb_lt_mid: L is the bit length of the modulus");
+    if (count == 0) return HB_OK;
+    const int64_t eb = run.elem_bytes() * count;
+    const RowSpan outs[3] = {{v, 1}, {d0, 1}, {masked, 2}};
+    RowSpan ins[11] = {{opened, 5}, {u, 1}, {s_bits, L}};
+    for (int k = 0; k < 8; k++) ins[3 + k] = {trip[k], 1};
+    if (!outputs_apart(outs, 3, ins, 11, eb)) return run.fail(HB_ERR_BAD_ARG, "hb_lt_mid: the outputs are arrays of their own");
+    const LtMidArgs A = {u32(opened), u32(u), u32(s_bits), u32(pa), u32(qa), u32(pqa), u32(pb), u32(qb), u32(pqb), u32(pc), u32(qc),
+                         u32(v), u32(d0), u32(masked), L};
+    return run.template rows<LtMidRow>(A, 1, count);
+}
+
+template <class Run> static int lt_xor_finish_step(const Run &run, const uint64_t *opened, const uint64_t *u, const uint64_t *v, const uint64_t *p, const uint64_t *q,
+                                                   const uint64_t *pq, uint64_t *out, int64_t count) {
+    if (count < 0 || (count > 0 && (!opened || !u || !v || !p || !q || !pq || !out))) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t eb = run.elem_bytes() * count;
+    const RowSpan outs[1] = {{out, 1}}, ins[6] = {{opened, 2}, {u, 1}, {v, 1}, {p, 1}, {q, 1}, {pq, 1}};
+    if (!outputs_apart(outs, 1, ins, 6, eb)) return run.fail(HB_ERR_BAD_ARG, "hb_lt_xor_finish: out is an array of its own");
+    const LtXorFinishArgs A = {u32(opened), u32(u), u32(v), u32(p), u32(q), u32(pq), u32(out)};
+    return run.template rows<LtXorFinishRow>(A, 1, count);
 }
 
 }  // namespace hb
 
 extern "C" {
 
-#define LT_L_OK(ctx) (L == modulus_bits((ctx)->p_limbs, (ctx)->n_limbs))
-
 int hb_lt_mask(hb_ctx *ctx, const uint64_t *a_dev, const uint64_t *b_dev, const uint64_t *r_dev, uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!a_dev || !r_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[1] = {{masked_dev, 1}}, ins[3] = {{a_dev, 1}, {b_dev, 1}, {r_dev, 1}};
-    if (!outputs_apart(outs, 1, ins, 3, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mask: masked is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_lt_mask");
-    const LtMaskArgs A = {u32(a_dev), u32(b_dev), u32(r_dev), u32(masked_dev)};
-    if (b_dev) return launch_rows<LtMaskRow<true>>(ctx, A, (unsigned)blocks, s, count);
-    return launch_rows<LtMaskRow<false>>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : lt_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_lt_mask"}, a_dev, b_dev, r_dev, masked_dev, count);
 }
 
 int hb_lt_leaves(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r_bits_dev, int L, int mode, uint64_t *g_dev, uint64_t *p_dev, int64_t count, void *stream) {
     HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!c_dev || !r_bits_dev || !g_dev || !p_dev))) return HB_ERR_BAD_ARG;
-    if (!lt_mode_ok(mode)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: unknown mode");
-    if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: L is the bit length of the modulus");
-    if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[2] = {{g_dev, L}, {p_dev, L}}, ins[2] = {{c_dev, 1}, {r_bits_dev, L}};
-    if (!outputs_apart(outs, 2, ins, 2, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_leaves: g and p are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_lt_leaves");
-    const LtLeavesArgs A = {u32(c_dev), u32(r_bits_dev), u32(g_dev), u32(p_dev), L, mode};
-    return launch_rows<LtLeavesRow>(ctx, A, dim3((unsigned)blocks, (unsigned)L), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : lt_leaves_step(DeviceRun{ctx, (hipStream_t)stream, "hb_lt_leaves"}, c_dev, r_bits_dev, L, mode, g_dev, p_dev, count);
 }
 
 int hb_lt_xor_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *w_dev, const uint64_t *pa_dev, const uint64_t *qa_dev, uint64_t *u_dev,
                    uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!c_dev || !r0_dev || !w_dev || !pa_dev || !qa_dev || !u_dev || !masked_dev))) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[2] = {{u_dev, 1}, {masked_dev, 2}}, ins[5] = {{c_dev, 1}, {r0_dev, 1}, {w_dev, 1}, {pa_dev, 1}, {qa_dev, 1}};
-    if (!outputs_apart(outs, 2, ins, 5, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_mask: u and masked are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_lt_xor_mask");
-    const LtXorMaskArgs A = {u32(c_dev), u32(r0_dev), u32(w_dev), u32(pa_dev), u32(qa_dev), u32(u_dev), u32(masked_dev)};
-    return launch_rows<LtXorMaskRow>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : lt_xor_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_lt_xor_mask"}, c_dev, r0_dev, w_dev, pa_dev, qa_dev, u_dev, masked_dev,
+                                                    count);
 }
 
 int hb_lt_dmask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *r0_dev, const uint64_t *x_dev, const uint64_t *s_dev, const uint64_t *s_bits_dev, int L,
                 const uint64_t *pa_dev, const uint64_t *qa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev, uint64_t *u_dev, uint64_t *masked_dev, int64_t count,
                 void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!c_dev || !r0_dev || !x_dev || !s_dev || !s_bits_dev || !pa_dev || !qa_dev || !pb_dev || !qb_dev || !u_dev || !masked_dev)))
-        return HB_ERR_BAD_ARG;
-    if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: L is the bit length of the modulus");
-    if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[2] = {{u_dev, 1}, {masked_dev, 5}},
-                 ins[9] = {{c_dev, 1}, {r0_dev, 1}, {x_dev, 1}, {s_dev, 1}, {s_bits_dev, L}, {pa_dev, 1}, {qa_dev, 1}, {pb_dev, 1}, {qb_dev, 1}};
-    if (!outputs_apart(outs, 2, ins, 9, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_dmask: u and masked are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_lt_dmask");
-    const LtDmaskArgs A = {u32(c_dev), u32(r0_dev), u32(x_dev), u32(s_dev), u32(s_bits_dev), u32(pa_dev), u32(qa_dev), u32(pb_dev), u32(qb_dev), u32(u_dev), u32(masked_dev), L};
-    return launch_rows<LtDmaskRow>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : lt_dmask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_lt_dmask"}, c_dev, r0_dev, x_dev, s_dev, s_bits_dev, L, pa_dev, qa_dev, pb_dev,
+                                                 qb_dev, u_dev, masked_dev, count);
 }
 
 int hb_lt_mid(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *s_bits_dev, int L, const uint64_t *pa_dev, const uint64_t *qa_dev,
               const uint64_t *pqa_dev, const uint64_t *pb_dev, const uint64_t *qb_dev, const uint64_t *pqb_dev, const uint64_t *pc_dev, const uint64_t *qc_dev,
               uint64_t *v_dev, uint64_t *d0_dev, uint64_t *masked_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0) return HB_ERR_BAD_ARG;
-    const uint64_t *trip[8] = {pa_dev, qa_dev, pqa_dev, pb_dev, qb_dev, pqb_dev, pc_dev, qc_dev};
-    if (count > 0) {
-        for (const uint64_t *t : trip) if (!t) return HB_ERR_BAD_ARG;
-        if (!opened_dev || !u_dev || !s_bits_dev || !v_dev || !d0_dev || !masked_dev) return HB_ERR_BAD_ARG;
-    }
-    if (!LT_L_OK(ctx)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: L is the bit length of the modulus");
-    if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[3] = {{v_dev, 1}, {d0_dev, 1}, {masked_dev, 2}};
-    RowSpan ins[11] = {{opened_dev, 5}, {u_dev, 1}, {s_bits_dev, L}};
-    for (int k = 0; k < 8; k++) ins[3 + k] = {trip[k], 1};
-    if (!outputs_apart(outs, 3, ins, 11, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_mid: the outputs are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_lt_mid");
-    const LtMidArgs A = {u32(opened_dev), u32(u_dev), u32(s_bits_dev), u32(pa_dev), u32(qa_dev), u32(pqa_dev), u32(pb_dev), u32(qb_dev), u32(pqb_dev), u32(pc_dev), u32(qc_dev),
-                         u32(v_dev), u32(d0_dev), u32(masked_dev), L};
-    return launch_rows<LtMidRow>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : lt_mid_step(DeviceRun{ctx, (hipStream_t)stream, "hb_lt_mid"}, opened_dev, u_dev, s_bits_dev, L, pa_dev, qa_dev, pqa_dev, pb_dev,
+                                               qb_dev, pqb_dev, pc_dev, qc_dev, v_dev, d0_dev, masked_dev, count);
 }
 
 int hb_lt_xor_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *u_dev, const uint64_t *v_dev, const uint64_t *p_dev, const uint64_t *q_dev,
                      const uint64_t *pq_dev, uint64_t *out_dev, int64_t count, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || count < 0 || (count > 0 && (!opened_dev || !u_dev || !v_dev || !p_dev || !q_dev || !pq_dev || !out_dev))) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    const int64_t eb = 8 * (int64_t)ctx->n_limbs * count;
-    const RowSpan outs[1] = {{out_dev, 1}}, ins[6] = {{opened_dev, 2}, {u_dev, 1}, {v_dev, 1}, {p_dev, 1}, {q_dev, 1}, {pq_dev, 1}};
-    if (!outputs_apart(outs, 1, ins, 6, eb)) return fail(ctx, HB_ERR_BAD_ARG, "hb_lt_xor_finish: out is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_lt_xor_finish");
-    const LtXorFinishArgs A = {u32(opened_dev), u32(u_dev), u32(v_dev), u32(p_dev), u32(q_dev), u32(pq_dev), u32(out_dev)};
-    return launch_rows<LtXorFinishRow>(ctx, A, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : lt_xor_finish_step(DeviceRun{ctx, (hipStream_t)stream, "hb_lt_xor_finish"}, opened_dev, u_dev, v_dev, p_dev, q_dev, pq_dev, out_dev,
+                                                      count);
 }
 
-int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs, int64_t count) {
-    if (!p_limbs || !operands || !params || !outs || count < 0 || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
-    const int64_t L = params[0], mode = params[1];
-    int n_ops = 0, n_outs = 1, optional = -1;
-    bool needs_L = false;
+// params: L, mode (read by the steps that take them)
+int hb_selftest_lt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs, int64_t count) {
+    if (!p_limbs || !ops || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
+    if (params[0] != (int)params[0] || params[1] != (int)params[1]) return HB_ERR_BAD_ARG;    // L, mode: the steps take them as int
+    const HostRun run = {p_limbs, n_limbs};
+    const int L = (int)params[0], mode = (int)params[1];
     switch (what) {
-    case HB_LT_SELFTEST_MASK: n_ops = 3; optional = 1; break;
-    case HB_LT_SELFTEST_LEAVES: n_ops = 2; n_outs = 2; needs_L = true; if (!lt_mode_ok((int)(mode < 0 || mode > 1 ? -1 : mode))) return HB_ERR_BAD_ARG; break;
-    case HB_LT_SELFTEST_XOR_MASK: n_ops = 5; n_outs = 2; break;
-    case HB_LT_SELFTEST_DMASK: n_ops = 9; n_outs = 2; needs_L = true; break;
-    case HB_LT_SELFTEST_MID: n_ops = 11; n_outs = 3; needs_L = true; break;
-    case HB_LT_SELFTEST_XOR_FINISH: n_ops = 6; break;
+    case HB_LT_SELFTEST_MASK: return lt_mask_step(run, ops[0], ops[1], ops[2], outs[0], count);
+    case HB_LT_SELFTEST_LEAVES: return lt_leaves_step(run, ops[0], ops[1], L, mode, outs[0], outs[1], count);
+    case HB_LT_SELFTEST_XOR_MASK: return lt_xor_mask_step(run, ops[0], ops[1], ops[2], ops[3], ops[4], outs[0], outs[1], count);
+    case HB_LT_SELFTEST_DMASK: return lt_dmask_step(run, ops[0], ops[1], ops[2], ops[3], ops[4], L, ops[5], ops[6], ops[7], ops[8], outs[0], outs[1], count);
+    case HB_LT_SELFTEST_MID:
+        return lt_mid_step(run, ops[0], ops[1], ops[2], L, ops[3], ops[4], ops[5], ops[6], ops[7], ops[8], ops[9], ops[10], outs[0], outs[1], outs[2], count);
+    case HB_LT_SELFTEST_XOR_FINISH: return lt_xor_finish_step(run, ops[0], ops[1], ops[2], ops[3], ops[4], ops[5], outs[0], count);
     default: return HB_ERR_BAD_ARG;
     }
-    if (needs_L && L != modulus_bits(p_limbs, n_limbs)) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_ops; i++) if (count > 0 && !operands[i] && i != optional) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_outs; i++) if (count > 0 && !outs[i]) return HB_ERR_BAD_ARG;
-    if (n_limbs == 4) return selftest_lt<9, 8>(p_limbs, what, operands, params, outs, count);
-    return selftest_lt<3, 2>(p_limbs, what, operands, params, outs, count);
 }
 
-#undef LT_L_OK
 }  // extern "C"

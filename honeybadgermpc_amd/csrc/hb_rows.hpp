@@ -16,6 +16,17 @@
 // base), the element all of a launch share, and pair (x, y, base, even element index), two neighbours moved as one access.  k_rows
 // runs a row on the device (256-thread workgroups, one element a thread in x, the row in blockIdx.y, no LDS, no grid stride), host_rows
 // runs the same row on the host, so a host self test exercises the addressing the device runs, not a restatement of it.
+//
+// What stands in front of the row is written once too, as a STEP FUNCTION
+//     template <class Run> static int xx_step(const Run &run, <the entry point's arguments without ctx and stream>)
+// that holds the null checks, the parameter checks with their messages, the count == 0 return, the RowSpan lists and outputs_apart,
+// the Args initialiser (or fill lambda) and the row count, and ends in run.rows<Row>(A, rows, count).  Run says where: DeviceRun
+// (the context's field and stream; fail() sets the context's error text; rows() refuses a batch one launch cannot hold and calls
+// launch_rows) for the extern "C" entry point, HostRun (the modulus' limbs; fail() is the code alone; rows() calls host_rows) for
+// the case of hb_selftest_xx.  Both callers are one line, so the host self test runs the checks, the Args fill and the row count
+// the device runs: an operand swapped in an initialiser, a wrong row count or a span list one row short shows without a GPU, and
+// the self test refuses an output laid over an input as the entry point does (tests/row_refusal_cases.py).  hb_lt, hb_eq, hb_fxp,
+// hb_bd, hb_div, hb_sort and hb_demux have step functions; the other seven files still have entry point bodies and HB_ROW_BLOCKS.
 #pragma once
 #include "hb_common.hpp"
 
@@ -152,7 +163,8 @@ inline bool outputs_apart(const RowSpan *outs, int n_outs, const RowSpan *ins, i
 }
 
 // ---------------------------------------------------------------- host side: the launch
-// blocks of 256 elements in x, refused where one launch cannot hold them; s = the caller's stream
+// blocks of 256 elements in x, refused where one launch cannot hold them; s = the caller's stream (the files without step functions:
+// DeviceRun::too_large is the same refusal, and the macro goes when the last of them has them)
 #define HB_ROW_BLOCKS(ctx, name)                                                                                       \
     const int64_t blocks = (count + 255) / 256;                                                                        \
     if (blocks > 0x7fffffffLL) return fail(ctx, HB_ERR_UNSUPPORTED, name ": batch too large for one launch");          \
@@ -180,5 +192,63 @@ template <class Row, template <int> class ArgsT, class Fill> int launch_rows(hb_
     if (count) HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }
+
+// ---------------------------------------------------------------- where a step function runs (the header comment has the shape)
+// the device: the context's field (ctx->pw / ctx->pn as they stand: nothing is rebuilt a call) on stream s
+struct DeviceRun {
+    hb_ctx *ctx;
+    hipStream_t s;
+    const char *name;                                                           // the entry point's, for the refusals made here
+
+    const uint64_t *modulus() const { return ctx->p_limbs; }
+    int limbs() const { return ctx->n_limbs; }
+    int bits() const { return modulus_bits(ctx->p_limbs, ctx->n_limbs); }
+    int64_t elem_bytes() const { return 8 * (int64_t)ctx->n_limbs; }
+    int fail(int code, const char *msg) const { return hb::fail(ctx, code, msg); }
+
+    // blocks of 256 elements in x; where one launch cannot hold them the call is refused (the text is built on that path alone, so
+    // the path of a launch stays a compare and inlines)
+    static int64_t blocks(int64_t count) { return (count + 255) / 256; }
+    static bool fits(int64_t count) { return blocks(count) <= 0x7fffffffLL; }
+    __attribute__((noinline)) int too_large() const { return fail(HB_ERR_UNSUPPORTED, (std::string(name) + ": batch too large for one launch").c_str()); }
+
+    template <class Row, class Args> int rows(const Args &A, int n_rows, int64_t count) const {
+        if (!fits(count)) return too_large();
+        return launch_rows<Row>(ctx, A, dim3((unsigned)blocks(count), (unsigned)n_rows), s, count);
+    }
+    template <class Row, template <int> class ArgsT, class Fill> int rows(Fill &&fill, int n_rows, int64_t count) const {
+        if (!fits(count)) return too_large();
+        return launch_rows<Row, ArgsT>(ctx, fill, dim3((unsigned)blocks(count), (unsigned)n_rows), s, count);
+    }
+};
+
+// the host: FpParams from the modulus' limbs, the row walked by host_rows
+struct HostRun {
+    const uint64_t *p_limbs;
+    int n_limbs;                                                                // 4 or 1: the self test's front has seen to it
+
+    const uint64_t *modulus() const { return p_limbs; }
+    int limbs() const { return n_limbs; }
+    int bits() const { return modulus_bits(p_limbs, n_limbs); }
+    int64_t elem_bytes() const { return 8 * (int64_t)n_limbs; }
+    int fail(int code, const char *) const { return code; }
+
+    // the row over the field of NL digits, its Args set up by fill(A, P) as in launch_rows' second form
+    template <class Row, class ArgsN, int NL, class Fill> int walk(Fill &&fill, int n_rows, int64_t count) const {
+        FpParams<NL> P;
+        fp_params_from_limbs(P, p_limbs);
+        ArgsN A;
+        if (!fill(A, P)) return HB_ERR_BAD_ARG;
+        host_rows<Row, NL, words_of(NL)>(A, n_rows, count, P);
+        return HB_OK;
+    }
+    template <class Row, class Args> int rows(const Args &A0, int n_rows, int64_t count) const {
+        const auto copy = [&](Args &A, const auto &) { A = A0; return true; };
+        return n_limbs == 4 ? walk<Row, Args, 9>(copy, n_rows, count) : walk<Row, Args, 3>(copy, n_rows, count);
+    }
+    template <class Row, template <int> class ArgsT, class Fill> int rows(Fill &&fill, int n_rows, int64_t count) const {
+        return n_limbs == 4 ? walk<Row, ArgsT<9>, 9>(fill, n_rows, count) : walk<Row, ArgsT<3>, 3>(fill, n_rows, count);
+    }
+};
 
 }  // namespace hb

@@ -98,6 +98,7 @@ struct SortSwapFinishRow {
 };
 
 // ---------------------------------------------------------------- host side
+// One step function a step (hb_rows.hpp): its checks, Args fill and row count run under a DeviceRun in the entry point, a HostRun in hb_selftest_sort.
 static bool sort_width_ok(int width) { return width >= 1 && width <= 256; }
 
 // k and kappa as hb_fxp_mask checks them with m = k - 1
@@ -113,24 +114,60 @@ template <int NL> static bool sort_swap_consts(SortSwapMaskArgs<NL> &A, const Fp
     return fxp_finish_fill<NL>(A.K, P, k - 1, HB_FXP_NEG_TRUNC, inv2m_host);
 }
 
-// host: the same rows over the layer's slots.  params = {n, batch, width, a, r, d, cnt, k, kappa}
-template <int NL, int NW>
-static int selftest_sort(const uint64_t *p_limbs, int what, const uint64_t *const *ops, const SortLayer &L, int width, int k, int kappa, uint64_t *const *outs, int64_t slots) {
-    FpParams<NL> P;
-    fp_params_from_limbs(P, p_limbs);
-    if (what == HB_SORT_SELFTEST_CMP_MASK) {
-        SortCmpMaskArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(outs[0]), u32(outs[1]), L};
-        sort_cmp_consts<NL>(A, P, k, kappa);
-        host_rows<SortCmpMaskRow, NL, NW>(A, 1, slots, P);
-    } else if (what == HB_SORT_SELFTEST_SWAP_MASK) {
-        SortSwapMaskArgs<NL> A = {u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), u32(ops[4]), u32(ops[5]), u32(outs[0]), L, width};
-        if (!sort_swap_consts<NL>(A, P, k, ops[6])) return HB_ERR_BAD_ARG;
-        host_rows<SortSwapMaskRow, NL, NW>(A, 1, slots, P);
-    } else {
-        const SortSwapFinishArgs A = {u32(outs[0]), u32(ops[0]), u32(ops[1]), u32(ops[2]), u32(ops[3]), L, width};
-        host_rows<SortSwapFinishRow, NL, NW>(A, 1, slots, P);
-    }
-    return HB_OK;
+template <class Run> static int sort_cmp_mask_step(const Run &run, const uint64_t *table, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt,
+                                                   const uint64_t *bits, int k, int kappa, uint64_t *masked, uint64_t *r1) {
+    SortLayer L;
+    if (!sort_layer_ok(L, n, batch, a, r, d, cnt)) return run.fail(HB_ERR_BAD_ARG, "hb_sort_cmp_mask: not a layer of comparators inside n rows");
+    if (!sort_params_ok(run.bits(), k, kappa))
+        return run.fail(HB_ERR_BAD_ARG, "hb_sort_cmp_mask: needs k >= 2, kappa >= 0 and k + kappa + 1 <= bits(p) - 1");
+    const int64_t count = batch * cnt, eb = run.elem_bytes();
+    if (count > 0 && (!table || !bits || !masked || !r1)) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    if (overlap(masked, eb * count, r1, eb * count) || overlap(masked, eb * count, table, eb * L.plane) || overlap(r1, eb * count, table, eb * L.plane) ||
+        overlap(masked, eb * count, bits, eb * count * (k + kappa)) || overlap(r1, eb * count, bits, eb * count * (k + kappa)))
+        return run.fail(HB_ERR_BAD_ARG, "hb_sort_cmp_mask: masked and r1 are arrays of their own");
+    return run.template rows<SortCmpMaskRow, SortCmpMaskArgs>([&](auto &A, const auto &P) {
+        A.table = u32(table); A.bits = u32(bits); A.masked = u32(masked); A.r1 = u32(r1); A.L = L;
+        return sort_cmp_consts(A, P, k, kappa);
+    }, 1, count);
+}
+
+template <class Run> static int sort_swap_mask_step(const Run &run, const uint64_t *table, int width, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt,
+                                                    const uint64_t *c, const uint64_t *r1, const uint64_t *carry, const uint64_t *p, const uint64_t *q, int k,
+                                                    const uint64_t *inv2m_host, uint64_t *out) {
+    if (!inv2m_host) return HB_ERR_BAD_ARG;
+    SortLayer L;
+    if (!sort_layer_ok(L, n, batch, a, r, d, cnt)) return run.fail(HB_ERR_BAD_ARG, "hb_sort_swap_mask: not a layer of comparators inside n rows");
+    if (!sort_width_ok(width)) return run.fail(HB_ERR_BAD_ARG, "hb_sort_swap_mask: needs 1 <= width <= 256");
+    if (k < 2 || !fxp_m_ok(run.bits(), k - 1)) return run.fail(HB_ERR_BAD_ARG, "hb_sort_swap_mask: needs 2 <= k <= bits(p) - 1");
+    const int64_t count = batch * cnt, eb = run.elem_bytes();
+    if (count > 0 && (!table || !c || !r1 || !carry || !p || !q || !out)) return HB_ERR_BAD_ARG;
+    const int64_t ob = eb * count * 2 * width;
+    if (count > 0 && (overlap(out, ob, table, eb * L.plane * width) || overlap(out, ob, c, eb * count) || overlap(out, ob, r1, eb * count) ||
+                      overlap(out, ob, carry, eb * count) || overlap(out, ob, p, eb * count * width) || overlap(out, ob, q, eb * count * width)))
+        return run.fail(HB_ERR_BAD_ARG, "hb_sort_swap_mask: out is an array of its own");
+    const int rc = run.template rows<SortSwapMaskRow, SortSwapMaskArgs>([&](auto &A, const auto &P) {
+        A.table = u32(table); A.c = u32(c); A.r1 = u32(r1); A.carry = u32(carry); A.p = u32(p); A.q = u32(q); A.out = u32(out);
+        A.L = L; A.width = width;
+        return sort_swap_consts(A, P, k, inv2m_host);
+    }, 1, count);
+    return rc == HB_ERR_BAD_ARG ? run.fail(rc, "hb_sort_swap_mask: inv2m is not below the modulus") : rc;
+}
+
+template <class Run> static int sort_swap_finish_step(const Run &run, uint64_t *table, int width, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt,
+                                                      const uint64_t *opened, const uint64_t *p, const uint64_t *q, const uint64_t *pq) {
+    SortLayer L;
+    if (!sort_layer_ok(L, n, batch, a, r, d, cnt)) return run.fail(HB_ERR_BAD_ARG, "hb_sort_swap_finish: not a layer of comparators inside n rows");
+    if (!sort_width_ok(width)) return run.fail(HB_ERR_BAD_ARG, "hb_sort_swap_finish: needs 1 <= width <= 256");
+    const int64_t count = batch * cnt, eb = run.elem_bytes();
+    if (count > 0 && (!table || !opened || !p || !q || !pq)) return HB_ERR_BAD_ARG;
+    if (count == 0) return HB_OK;
+    const int64_t tb = eb * L.plane * width;
+    if (overlap(table, tb, opened, eb * count * 2 * width) || overlap(table, tb, p, eb * count * width) || overlap(table, tb, q, eb * count * width) ||
+        overlap(table, tb, pq, eb * count * width))
+        return run.fail(HB_ERR_BAD_ARG, "hb_sort_swap_finish: the table is an array of its own");
+    const SortSwapFinishArgs A = {u32(table), u32(opened), u32(p), u32(q), u32(pq), L, width};
+    return run.template rows<SortSwapFinishRow>(A, 1, count);
 }
 
 }  // namespace hb
@@ -139,83 +176,36 @@ extern "C" {
 
 int hb_sort_cmp_mask(hb_ctx *ctx, const uint64_t *table_dev, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt, const uint64_t *bits_dev, int k,
                      int kappa, uint64_t *masked_dev, uint64_t *r1_dev, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx) return HB_ERR_BAD_ARG;
-    SortLayer L;
-    if (!sort_layer_ok(L, n, batch, a, r, d, cnt)) return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_cmp_mask: not a layer of comparators inside n rows");
-    if (!sort_params_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), k, kappa))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_cmp_mask: needs k >= 2, kappa >= 0 and k + kappa + 1 <= bits(p) - 1");
-    const int64_t count = batch * cnt, eb = 8 * (int64_t)ctx->n_limbs;
-    if (count > 0 && (!table_dev || !bits_dev || !masked_dev || !r1_dev)) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    if (overlap(masked_dev, eb * count, r1_dev, eb * count) || overlap(masked_dev, eb * count, table_dev, eb * L.plane) || overlap(r1_dev, eb * count, table_dev, eb * L.plane) ||
-        overlap(masked_dev, eb * count, bits_dev, eb * count * (k + kappa)) || overlap(r1_dev, eb * count, bits_dev, eb * count * (k + kappa)))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_cmp_mask: masked and r1 are arrays of their own");
-    HB_ROW_BLOCKS(ctx, "hb_sort_cmp_mask");
-    return launch_rows<SortCmpMaskRow, SortCmpMaskArgs>(ctx, [&](auto &A, const auto &P) {
-        A.table = u32(table_dev); A.bits = u32(bits_dev); A.masked = u32(masked_dev); A.r1 = u32(r1_dev); A.L = L;
-        return sort_cmp_consts(A, P, k, kappa);
-    }, (unsigned)blocks, s, count);
+    return !ctx ? HB_ERR_BAD_ARG : sort_cmp_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_sort_cmp_mask"}, table_dev, n, batch, a, r, d, cnt, bits_dev, k, kappa,
+                                                      masked_dev, r1_dev);
 }
 
 int hb_sort_swap_mask(hb_ctx *ctx, const uint64_t *table_dev, int width, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt, const uint64_t *c_dev,
                       const uint64_t *r1_dev, const uint64_t *carry_dev, const uint64_t *p_dev, const uint64_t *q_dev, int k, const uint64_t *inv2m_host,
                       uint64_t *out_dev, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx || !inv2m_host) return HB_ERR_BAD_ARG;
-    SortLayer L;
-    if (!sort_layer_ok(L, n, batch, a, r, d, cnt)) return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_swap_mask: not a layer of comparators inside n rows");
-    if (!sort_width_ok(width)) return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_swap_mask: needs 1 <= width <= 256");
-    if (k < 2 || !fxp_m_ok(modulus_bits(ctx->p_limbs, ctx->n_limbs), k - 1)) return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_swap_mask: needs 2 <= k <= bits(p) - 1");
-    const int64_t count = batch * cnt, eb = 8 * (int64_t)ctx->n_limbs;
-    if (count > 0 && (!table_dev || !c_dev || !r1_dev || !carry_dev || !p_dev || !q_dev || !out_dev)) return HB_ERR_BAD_ARG;
-    const int64_t ob = eb * count * 2 * width;
-    if (count > 0 && (overlap(out_dev, ob, table_dev, eb * L.plane * width) || overlap(out_dev, ob, c_dev, eb * count) || overlap(out_dev, ob, r1_dev, eb * count) ||
-                      overlap(out_dev, ob, carry_dev, eb * count) || overlap(out_dev, ob, p_dev, eb * count * width) || overlap(out_dev, ob, q_dev, eb * count * width)))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_swap_mask: out is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_sort_swap_mask");
-    const int rc = launch_rows<SortSwapMaskRow, SortSwapMaskArgs>(ctx, [&](auto &A, const auto &P) {
-        A.table = u32(table_dev); A.c = u32(c_dev); A.r1 = u32(r1_dev); A.carry = u32(carry_dev); A.p = u32(p_dev); A.q = u32(q_dev); A.out = u32(out_dev);
-        A.L = L; A.width = width;
-        return sort_swap_consts(A, P, k, inv2m_host);
-    }, (unsigned)blocks, s, count);
-    return rc == HB_ERR_BAD_ARG ? fail(ctx, rc, "hb_sort_swap_mask: inv2m is not below the modulus") : rc;
+    return !ctx ? HB_ERR_BAD_ARG : sort_swap_mask_step(DeviceRun{ctx, (hipStream_t)stream, "hb_sort_swap_mask"}, table_dev, width, n, batch, a, r, d, cnt, c_dev, r1_dev,
+                                                       carry_dev, p_dev, q_dev, k, inv2m_host, out_dev);
 }
 
 int hb_sort_swap_finish(hb_ctx *ctx, uint64_t *table_dev, int width, int64_t n, int64_t batch, int a, int64_t r, int64_t d, int64_t cnt, const uint64_t *opened_dev,
                         const uint64_t *p_dev, const uint64_t *q_dev, const uint64_t *pq_dev, void *stream) { HB_API_GUARD(ctx);
-    if (!ctx) return HB_ERR_BAD_ARG;
-    SortLayer L;
-    if (!sort_layer_ok(L, n, batch, a, r, d, cnt)) return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_swap_finish: not a layer of comparators inside n rows");
-    if (!sort_width_ok(width)) return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_swap_finish: needs 1 <= width <= 256");
-    const int64_t count = batch * cnt, eb = 8 * (int64_t)ctx->n_limbs;
-    if (count > 0 && (!table_dev || !opened_dev || !p_dev || !q_dev || !pq_dev)) return HB_ERR_BAD_ARG;
-    if (count == 0) return HB_OK;
-    const int64_t tb = eb * L.plane * width;
-    if (overlap(table_dev, tb, opened_dev, eb * count * 2 * width) || overlap(table_dev, tb, p_dev, eb * count * width) || overlap(table_dev, tb, q_dev, eb * count * width) ||
-        overlap(table_dev, tb, pq_dev, eb * count * width))
-        return fail(ctx, HB_ERR_BAD_ARG, "hb_sort_swap_finish: the table is an array of its own");
-    HB_ROW_BLOCKS(ctx, "hb_sort_swap_finish");
-    const SortSwapFinishArgs A = {u32(table_dev), u32(opened_dev), u32(p_dev), u32(q_dev), u32(pq_dev), L, width};
-    return launch_rows<SortSwapFinishRow>(ctx, A, dim3((unsigned)blocks), s, count);
+    return !ctx ? HB_ERR_BAD_ARG : sort_swap_finish_step(DeviceRun{ctx, (hipStream_t)stream, "hb_sort_swap_finish"}, table_dev, width, n, batch, a, r, d, cnt,
+                                                         opened_dev, p_dev, q_dev, pq_dev);
 }
 
-int hb_selftest_sort(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params, uint64_t *const *outs) {
-    if (!p_limbs || !operands || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
+// params = {n, batch, width, a, r, d, cnt, k, kappa}
+int hb_selftest_sort(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *ops, const int64_t *params, uint64_t *const *outs) {
+    if (!p_limbs || !ops || !params || !outs || (n_limbs != 1 && n_limbs != 4)) return HB_ERR_BAD_ARG;
     for (int i = 0; i < 9; i++) if (params[i] < -((int64_t)1 << 41) || params[i] > ((int64_t)1 << 41)) return HB_ERR_BAD_ARG;
-    SortLayer L;
-    if (!sort_layer_ok(L, params[0], params[1], (int)params[3], params[4], params[5], params[6])) return HB_ERR_BAD_ARG;
-    const int width = (int)params[2], k = (int)params[7], kappa = (int)params[8], bits = modulus_bits(p_limbs, n_limbs);
-    const int64_t slots = params[1] * params[6];
-    int n_ops = 0, n_outs = 1;
+    const HostRun run = {p_limbs, n_limbs};
+    const int64_t n = params[0], batch = params[1], r = params[4], d = params[5], cnt = params[6];
+    const int width = (int)params[2], a = (int)params[3], k = (int)params[7], kappa = (int)params[8];
     switch (what) {
-    case HB_SORT_SELFTEST_CMP_MASK: if (!sort_params_ok(bits, k, kappa)) return HB_ERR_BAD_ARG; n_ops = 2; n_outs = 2; break;
-    case HB_SORT_SELFTEST_SWAP_MASK: if (!sort_width_ok(width) || k < 2 || !fxp_m_ok(bits, k - 1) || !operands[6]) return HB_ERR_BAD_ARG; n_ops = 6; break;
-    case HB_SORT_SELFTEST_SWAP_FINISH: if (!sort_width_ok(width)) return HB_ERR_BAD_ARG; n_ops = 4; break;
+    case HB_SORT_SELFTEST_CMP_MASK: return sort_cmp_mask_step(run, ops[0], n, batch, a, r, d, cnt, ops[1], k, kappa, outs[0], outs[1]);
+    case HB_SORT_SELFTEST_SWAP_MASK: return sort_swap_mask_step(run, ops[0], width, n, batch, a, r, d, cnt, ops[1], ops[2], ops[3], ops[4], ops[5], k, ops[6], outs[0]);
+    case HB_SORT_SELFTEST_SWAP_FINISH: return sort_swap_finish_step(run, outs[0], width, n, batch, a, r, d, cnt, ops[0], ops[1], ops[2], ops[3]);
     default: return HB_ERR_BAD_ARG;
     }
-    for (int i = 0; i < n_ops; i++) if (slots > 0 && !operands[i]) return HB_ERR_BAD_ARG;
-    for (int i = 0; i < n_outs; i++) if (slots > 0 && !outs[i]) return HB_ERR_BAD_ARG;
-    if (n_limbs == 4) return selftest_sort<9, 8>(p_limbs, what, operands, L, width, k, kappa, outs, slots);
-    return selftest_sort<3, 2>(p_limbs, what, operands, L, width, k, kappa, outs, slots);
 }
 
 }  // extern "C"

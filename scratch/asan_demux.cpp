@@ -9,7 +9,8 @@
 // The leaves, and the mask and the finish of every level of m = 2 .. 12, at count = 1, 3 and 65 in both widths.  The wiring is restated
 // here (groups paired from the least significant, an odd last one carried) to size the buffers: bits, groups, ta, tab, the opened
 // array and the outputs are heap buffers of exactly m, sum of products, sum (2^wl + 2^wh), sum 2^(wl + wh) rows of count elements,
-// so a cell addressed one element past an array is a report.
+// so a cell addressed one element past an array is a report.  The self test runs the step functions of the entry points
+// (hb_rows.hpp): every level also gets a finish with groups over tab's last row, and every m a level it does not have: both refused.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -76,6 +77,8 @@ int main() {
                     const uint64_t *fin_ops[3] = {masked.p, ta.p, tab.p};
                     uint64_t *fin_outs[1] = {groups.p};
                     CHECK(hb_selftest_demux(p, NL, HB_DEMUX_SELFTEST_FINISH, fin_ops, params, fin_outs, count) == HB_OK);
+                    uint64_t *over[1] = {tab.p + (size_t)(products[level] - 1) * count * NL};     // groups over the last row of tab: refused
+                    CHECK(hb_selftest_demux(p, NL, HB_DEMUX_SELFTEST_FINISH, fin_ops, params, over, count) == HB_ERR_BAD_ARG);
                 }
                 const int64_t bad[2] = {m, (int64_t)opened.size()};
                 const uint64_t *ops[3] = {bits.p, groups.p, bits.p};

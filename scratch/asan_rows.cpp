@@ -1,18 +1,21 @@
-// A stand-alone HOST program over hb_selftest_lt, hb_selftest_eq, hb_selftest_jj, hb_selftest_ew, hb_selftest_off, hb_selftest_mimc and
-// hb_selftest_bf for AddressSanitizer and UBSan: the rows of csrc/hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_ew.hip, hb_off.hip, hb_mimc.hip and
-// hb_bf.hip (hb_rows.hpp: host_rows runs what k_rows runs) compiled WITH the sanitizers into this program; the rest of the library
-// comes from libhbmpc_hip.so as it is.  No GPU is touched.
+// A stand-alone HOST program over hb_selftest_lt, hb_selftest_eq, hb_selftest_fxp, hb_selftest_bd, hb_selftest_div, hb_selftest_jj,
+// hb_selftest_ew, hb_selftest_off, hb_selftest_mimc and hb_selftest_bf for AddressSanitizer and UBSan: the rows of csrc/hb_lt.hip,
+// hb_eq.hip, hb_fxp.hip, hb_bd.hip, hb_div.hip, hb_jj.hip, hb_ew.hip, hb_off.hip, hb_mimc.hip and hb_bf.hip (hb_rows.hpp: host_rows runs
+// what k_rows runs) compiled WITH the sanitizers into this program; the rest of the library comes from libhbmpc_hip.so as it is.  No
+// GPU is touched.
 //
 //   C=honeybadgermpc_amd/csrc; hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
-//         -Xarch_host -fno-omit-frame-pointer scratch/asan_rows.cpp $C/hb_lt.hip $C/hb_eq.hip $C/hb_jj.hip $C/hb_ew.hip $C/hb_off.hip \
-//         $C/hb_mimc.hip $C/hb_bf.hip -Lhoneybadgermpc_amd/lib -lhbmpc_hip -Wl,-rpath,$PWD/honeybadgermpc_amd/lib -o scratch/asan_rows \
-//         && scratch/asan_rows
+//         -Xarch_host -fno-omit-frame-pointer scratch/asan_rows.cpp $C/hb_lt.hip $C/hb_eq.hip $C/hb_fxp.hip $C/hb_bd.hip $C/hb_div.hip \
+//         $C/hb_jj.hip $C/hb_ew.hip $C/hb_off.hip $C/hb_mimc.hip $C/hb_bf.hip -Lhoneybadgermpc_amd/lib -lhbmpc_hip \
+//         -Wl,-rpath,$PWD/honeybadgermpc_amd/lib -o scratch/asan_rows && scratch/asan_rows
 //
-// Every step of lt, eq and jj at count = 3, rows = 3 (hb_eq), a triples' row stride of count + 3 (hb_jj); the element-wise, mul-add and
-// MiMC rows at 1, 255, 256, 257 and 513 elements with a key or an operand for all (HostMem::same: ONE element on the heap) and one an
-// element; a butterfly layer at k = 2, 4 and 1024 and every stride the GPU suite runs (HostMem::pair at stride 1 in the 8-byte width).
-// Both widths.  Every operand and output is a heap buffer of exactly the documented size, so a row that reads or writes one element
-// past an array is a report.
+// Every step of lt, eq and jj at count = 3, rows = 3 (hb_eq), a triples' row stride of count + 3 (hb_jj); one tree level each of hb_fxp,
+// hb_bd and hb_div at count = 3; the element-wise, mul-add and MiMC rows at 1, 255, 256, 257 and 513 elements with a key or an operand
+// for all (HostMem::same: ONE element on the heap) and one an element; a butterfly layer at k = 2, 4 and 1024 and every stride the GPU
+// suite runs (HostMem::pair at stride 1 in the 8-byte width).  Both widths.  The self tests of lt, eq, fxp, bd and div run the step
+// functions of hb_rows.hpp (the checks, the Args fill and the row count of the entry points), so each of these families also gets one
+// call with an output over an input's last row and one with a parameter past its bound: both refused.  Every operand and output is a
+// heap buffer of exactly the documented size, so a row that reads or writes one element past an array is a report.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -86,6 +89,16 @@ static void less_than(const uint64_t *p, int L, int64_t n) {
         uint64_t *outs[1] = {out.p};
         CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_XOR_FINISH, ops, prm[0], outs, n) == HB_OK);
     }
+    {                                                                       // refused by the step function: masked over the last row of s_bits; L one short
+        Elems ou(n);
+        const uint64_t *ops[9] = {c, r, x, s, bits, t0, t1, t2, t3};
+        uint64_t *outs[2] = {ou.p, bits.p + (size_t)(L - 1) * n * NL};
+        const int64_t shortL[2] = {L - 1, HB_LT_REFERENCE};
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_DMASK, ops, prm[1], outs, n) == HB_ERR_BAD_ARG);
+        Elems masked(5 * n);
+        outs[1] = masked.p;
+        CHECK(hb_selftest_lt(p, NL, HB_LT_SELFTEST_DMASK, ops, shortL, outs, n) == HB_ERR_BAD_ARG);
+    }
 }
 
 static void equality(const uint64_t *p, int64_t rows, int64_t n) {
@@ -127,6 +140,59 @@ static void equality(const uint64_t *p, int64_t rows, int64_t n) {
         CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_FINISH, ops, prm[mode], outs, n) == HB_OK);
         CHECK(zero_rows.p[0] == 0 && zero_rows.p[1] == 1 && zero_rows.p[2] == 0);
         for (int l = 0; l < NL; l++) CHECK(factor.p[(size_t)(n + 1) * NL + l] == 0);
+    }
+    {                                                                       // refused by the step function: masked2 over the last row of qc; no rows
+        Elems dr(rc);
+        const uint64_t *ops[11] = {o4, t0, t1, t2, t3, t4, t5, bits, t6, t7, nr.data()};
+        void *outs[2] = {t7.p + (size_t)(rows - 1) * n * NL, dr.p};
+        const int64_t none[2] = {0, HB_EQ_BIT};
+        CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_MID, ops, prm[0], outs, n) == HB_ERR_BAD_ARG);
+        Elems masked2(2 * rc);
+        outs[0] = masked2.p;
+        CHECK(hb_selftest_eq(p, NL, HB_EQ_SELFTEST_MID, ops, none, outs, n) == HB_ERR_BAD_ARG);
+    }
+}
+
+// hb_fxp.hip, hb_bd.hip, hb_div.hip: one level of each family's tree through its step functions (carry level of 3 nodes, prefix level 0
+// of m = 3, OR level 0 of 2 planes), then the same call with the output over the last row of an input and with a parameter past its bound
+static void tree_levels(const uint64_t *p, int64_t n) {
+    Elems g(3 * n), q(3 * n), opened(4 * n), ta(2 * n), tb(2 * n), tab(2 * n);
+    {
+        Elems masked(4 * n);
+        const uint64_t *ops[4] = {g, q, ta, tb};
+        uint64_t *outs[1] = {masked.p}, *over[1] = {tb.p + (size_t)n * NL};
+        const int64_t level[5] = {0, 0, 0, 3, 0}, wide[5] = {0, 0, 0, 258, 0};
+        CHECK(hb_selftest_fxp(p, NL, HB_FXP_SELFTEST_CARRY_MASK, ops, level, outs, n) == HB_OK);
+        CHECK(hb_selftest_fxp(p, NL, HB_FXP_SELFTEST_CARRY_MASK, ops, level, over, n) == HB_ERR_BAD_ARG);
+        CHECK(hb_selftest_fxp(p, NL, HB_FXP_SELFTEST_CARRY_MASK, ops, wide, outs, n) == HB_ERR_BAD_ARG);
+        Elems g_out(2 * n), p_out(2 * n);
+        const uint64_t *cops[6] = {opened, g, q, ta, tb, tab};
+        uint64_t *couts[2] = {g_out.p, p_out.p};
+        CHECK(hb_selftest_fxp(p, NL, HB_FXP_SELFTEST_CARRY_COMBINE, cops, level, couts, n) == HB_OK);
+    }
+    {
+        Elems masked(2 * n), g2(2 * n), q2(2 * n);
+        const uint64_t *ops[4] = {g2, q2, ta, tb};
+        uint64_t *outs[1] = {masked.p}, *over[1] = {q2.p + (size_t)n * NL};
+        const int64_t level[2] = {3, 0}, none[2] = {3, 1};
+        CHECK(hb_selftest_bd(p, NL, HB_BD_SELFTEST_PREFIX_MASK, ops, level, outs, n) == HB_OK);
+        CHECK(hb_selftest_bd(p, NL, HB_BD_SELFTEST_PREFIX_MASK, ops, level, over, n) == HB_ERR_BAD_ARG);
+        CHECK(hb_selftest_bd(p, NL, HB_BD_SELFTEST_PREFIX_MASK, ops, none, outs, n) == HB_ERR_BAD_ARG);
+        const uint64_t *cops[4] = {opened, ta, tb, tab};
+        uint64_t *couts[2] = {g2.p, q2.p};
+        CHECK(hb_selftest_bd(p, NL, HB_BD_SELFTEST_PREFIX_COMBINE, cops, level, couts, n) == HB_OK);
+    }
+    {
+        Elems masked(2 * n), y(2 * n);
+        const uint64_t *ops[3] = {y, ta, tb};
+        uint64_t *outs[1] = {masked.p}, *over[1] = {y.p + (size_t)n * NL};
+        const int64_t level[5] = {2, 0, 1, 0, 0}, none[5] = {257, 0, 1, 0, 0};
+        CHECK(hb_selftest_div(p, NL, HB_DIV_SELFTEST_OR_MASK, ops, level, outs, n) == HB_OK);
+        CHECK(hb_selftest_div(p, NL, HB_DIV_SELFTEST_OR_MASK, ops, level, over, n) == HB_ERR_BAD_ARG);
+        CHECK(hb_selftest_div(p, NL, HB_DIV_SELFTEST_OR_MASK, ops, none, outs, n) == HB_ERR_BAD_ARG);
+        const uint64_t *cops[4] = {opened, ta, tb, tab};
+        uint64_t *couts[1] = {y.p};
+        CHECK(hb_selftest_div(p, NL, HB_DIV_SELFTEST_OR_COMBINE, cops, level, couts, n) == HB_OK);
     }
 }
 
@@ -239,6 +305,7 @@ int main() {
         const uint64_t *p = wide ? BLS : P64;
         less_than(p, wide ? 255 : 64, 3);
         equality(p, 3, 3);
+        tree_levels(p, 3);
         jubjub(p, 3);
         for (int64_t n : COUNTS) { elementwise(p, n); mul_add(p, n); mimc_rounds(p, n); }
         butterfly(p, 2, 0);

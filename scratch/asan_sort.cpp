@@ -6,7 +6,9 @@
 //         scratch/asan_sort.cpp honeybadgermpc_amd/csrc/hb_sort.hip \
 //         -Lhoneybadgermpc_amd/lib -lhbmpc_hip -Wl,-rpath,$PWD/honeybadgermpc_amd/lib -o scratch/asan_sort && scratch/asan_sort
 //
-// Every layer of the merge exchange over n = 13, 16 and 5 rows, batch 3, width 3, both element widths.  Every operand and output is a
+// Every layer of the merge exchange over n = 13, 16 and 5 rows, batch 3, width 3, both element widths; the self test runs the step
+// functions of the entry points (hb_rows.hpp), so every layer also gets a swap mask with out over tq's last element and one with
+// width 0: both refused.  Every operand and output is a
 // heap buffer of exactly the documented size, so a row that reads or writes one element past an array is a report; the last
 // comparator of the last array ends at the table's last row in the layers that reach row n - 1.
 #include <cstdint>
@@ -57,6 +59,15 @@ static void layer(const uint64_t *p, int64_t n, int64_t batch, int64_t width, in
         const uint64_t *ops[4] = {opened, tp, tq, tpq};
         uint64_t *outs[1] = {table.p};
         CHECK(hb_selftest_sort(p, NL, HB_SORT_SELFTEST_SWAP_FINISH, ops, prm, outs) == HB_OK);
+    }
+    if (slots > 0) {                                                        // refused by the step function: out over the last element of tq; no width
+        Elems out(2 * width * slots);
+        const uint64_t *ops[7] = {table, c, r1, carry, tp, tq, inv};
+        uint64_t *outs[1] = {tq.p + (size_t)(width * slots - 1) * NL};
+        const int64_t flat[9] = {n, batch, 0, a, r, d, cnt, k, kappa};
+        CHECK(hb_selftest_sort(p, NL, HB_SORT_SELFTEST_SWAP_MASK, ops, prm, outs) == HB_ERR_BAD_ARG);
+        outs[0] = out.p;
+        CHECK(hb_selftest_sort(p, NL, HB_SORT_SELFTEST_SWAP_MASK, ops, flat, outs) == HB_ERR_BAD_ARG);
     }
 }
 
