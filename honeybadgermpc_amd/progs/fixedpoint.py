@@ -547,6 +547,18 @@ class FixedPointArray:
 
         return self._like(await reciprocal(self.co, self.shares, bits, triples, self.f, self.k, self.kappa, theta, signed))
 
+    async def sqrt(self, bits, triples, theta=None):
+        """the square root of a non-negative array (fixedpoint_sqrt.sqrt): 0 <= self < 2^(k-1-f)"""
+        from .fixedpoint_sqrt import sqrt
+
+        return self._like(await sqrt(self.co, self.shares, bits, triples, self.f, self.k, self.kappa, theta))
+
+    async def rsqrt(self, bits, triples, theta=None):
+        """1 / sqrt(self) (fixedpoint_sqrt.rsqrt): 0 < self < 2^(k-1-f) and 1 / sqrt(self) < 2^(k-2-f)"""
+        from .fixedpoint_sqrt import rsqrt
+
+        return self._like(await rsqrt(self.co, self.shares, bits, triples, self.f, self.k, self.kappa, theta))
+
     async def ltz(self, bits, triples):
         """-> a (count, limbs) tensor of shares of [a < 0]"""
         return await ltz(self.co, self.shares, bits, triples, self.k, self.kappa)

@@ -586,6 +586,41 @@ int hb_div_trunc_step(hb_ctx *ctx, int mode, int rows, int products, const uint6
                       const uint64_t *inv2m_host, const uint64_t *alpha_host, const uint64_t *x_dev, const uint64_t *ext0_dev,
                       const uint64_t *ext1_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- square root and inverse square root of shared fixed-point numbers (hb_fxsqrt.hip) -----------------------------------------
+ * The steps of progs/fixedpoint_sqrt.py that the division does not already have, for arrays of `count` unsigned k-bit values with f
+ * fractional bits (N = k - 1, beta = 2^N); the reference has no square root.  Operands and results are canonical residues; arrays of
+ * several rows are row-major, [rows][count].  "Products to truncation mask" is hb_div_product_step(HB_DIV_TRUNC) and the last step
+ * hb_div_trunc_step(HB_DIV_T_RESULT).
+ * hb_fxsqrt_norm_mask: y_dev [n_planes][count] the prefix OR from the top of the bits of x; weights_dev [sets][n_planes] (sets = 1 or 2)
+ *   the PUBLIC D_i = W_i - W_{i-1} mod p, one element each, the same for every element of the batch.  kept_dev [1 + sets][count] =
+ *   v = sum_i 2^(n_planes-1-i) (y_i - y_{i+1}), then T_s = sum_i D_{s,i} y_i = sum_i W_{s,i} (y_i - y_{i+1}); masked_dev rows 0, 1 = x - ta,
+ *   v - tb: the masked pair of [x v] as ONE array to open.
+ * hb_fxsqrt_first: opened_dev [2][count] that pair opened; c = [x v] by the Beaver combine with (ta, tb, tab), y0 = a - b c with the
+ *   constants a_host, b_host (one element each, host memory); h_dev = y0, masked_dev rows 0, 1 = c - nxt_a, y0 - nxt_b: the masked pair
+ *   of [c y0] as ONE array to open.
+ * hb_fxsqrt_trunc_step: opened_dev, s_dev [rows][count] the masked truncations opened and the kept product + r1; t_r = (s_r - (opened_r
+ *   mod 2^m)) inv2m with inv2m_host = 2^(-m) (one element, host memory), and
+ *     HB_FXSQRT_GH   rows = 2: (g, h) = (t_0, t_1); rows = 1: g = t_0, h = kept_in_dev [1][count].  which = 3.  kept_out_dev [2][count] =
+ *                    g, h; masked_dev rows 0, 1 = g - ta, h - tb
+ *     HB_FXSQRT_R    rows = 1, kept_in_dev [2][count] = g, h, cst_host = 3 beta: r = cst - t_0; which = 1: masked_dev = g - ta[0], r - tb[0];
+ *                    which = 2: h - ta[0], r - tb[0]; which = 3: both pairs, g's first (rows 0..3, two triples)
+ *     HB_FXSQRT_OUT  rows = 1 (which = 1 or 2) or 2 (which = 3), kept_in_dev [rows][count] the kept weights: masked_dev rows 2q, 2q + 1 =
+ *                    t_q - ta[q], kept_in[q] - tb[q]
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: an unknown mode, counts a
+ * mode does not take, more than 256 planes, m outside 0 < m <= bits(p) - 2, a constant not below the modulus, null pointers (with
+ * count > 0), a negative count, an output that overlaps an input or another output.  count == 0 returns HB_OK and launches nothing. */
+#define HB_FXSQRT_GH 0
+#define HB_FXSQRT_R 1
+#define HB_FXSQRT_OUT 2
+int hb_fxsqrt_norm_mask(hb_ctx *ctx, const uint64_t *x_dev, const uint64_t *y_dev, int n_planes, const uint64_t *weights_dev, int sets,
+                        const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *kept_dev, int64_t count, void *stream);
+int hb_fxsqrt_first(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev,
+                    const uint64_t *a_host, const uint64_t *b_host, const uint64_t *nxt_a_dev, const uint64_t *nxt_b_dev, uint64_t *masked_dev,
+                    uint64_t *h_dev, int64_t count, void *stream);
+int hb_fxsqrt_trunc_step(hb_ctx *ctx, int mode, int rows, int which, const uint64_t *opened_dev, const uint64_t *s_dev, int m,
+                         const uint64_t *inv2m_host, const uint64_t *cst_host, const uint64_t *kept_in_dev, const uint64_t *ta_dev,
+                         const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *kept_out_dev, int64_t count, void *stream);
+
 /* ---- equality of shared values (hb_eq.hip) ---------------------------------------------------------------------------------
  * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
  * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
@@ -1197,6 +1232,17 @@ int hb_selftest_demux(const uint64_t *p_limbs, int n_limbs, int what, const uint
 #define HB_DIV_SELFTEST_PAIR_MASK 5
 int hb_selftest_div(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                     uint64_t *const *outs, int64_t count);
+/* host-side run of the square root kernels' steps (no GPU needed) over host memory, a whole step at a time; parameters and overlaps
+ * are checked as the device calls check them:
+ *   what = HB_FXSQRT_SELFTEST_NORM_MASK   params = {n_planes, sets}; operands[0..4] = x, y, weights, ta, tb; outs[0..1] = masked, kept
+ *          HB_FXSQRT_SELFTEST_FIRST       operands[0..7] = opened, ta, tb, tab, a, b (one element each), nxt_a, nxt_b; outs[0..1] = masked, h
+ *          HB_FXSQRT_SELFTEST_TRUNC_STEP  params = {mode, rows, which, m}; operands[0..6] = opened, s, inv2m, cst (one element each; cst NULL
+ *                                         where the mode reads none), kept_in, ta, tb; outs[0..1] = masked, kept_out */
+#define HB_FXSQRT_SELFTEST_NORM_MASK 0
+#define HB_FXSQRT_SELFTEST_FIRST 1
+#define HB_FXSQRT_SELFTEST_TRUNC_STEP 2
+int hb_selftest_fxsqrt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                       uint64_t *const *outs, int64_t count);
 /* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
  *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
  *          HB_EQ_SELFTEST_MASK1     operands[0..7] = x, y (or NULL), r, rp, pa, qa, pb, qb; outs[0] as hb_eq_mask1 writes masked_dev
