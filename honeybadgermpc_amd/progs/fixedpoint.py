@@ -559,6 +559,18 @@ class FixedPointArray:
 
         return self._like(await rsqrt(self.co, self.shares, bits, triples, self.f, self.k, self.kappa, theta))
 
+    async def exp2(self, bits, triples, demux_triples, g=None):
+        """2^self (fixedpoint_exp.exp2): a result below 2^(k-2-f); below -f it is exactly 0"""
+        from .fixedpoint_exp import exp2
+
+        return self._like(await exp2(self.co, self.shares, bits, triples, demux_triples, self.f, self.k, self.kappa, g))
+
+    async def exp(self, bits, triples, demux_triples, g=None):
+        """e^self (fixedpoint_exp.exp): a result below 2^(k-2-f)"""
+        from .fixedpoint_exp import exp
+
+        return self._like(await exp(self.co, self.shares, bits, triples, demux_triples, self.f, self.k, self.kappa, g))
+
     async def ltz(self, bits, triples):
         """-> a (count, limbs) tensor of shares of [a < 0]"""
         return await ltz(self.co, self.shares, bits, triples, self.k, self.kappa)

@@ -621,6 +621,39 @@ int hb_fxsqrt_trunc_step(hb_ctx *ctx, int mode, int rows, int which, const uint6
                          const uint64_t *inv2m_host, const uint64_t *cst_host, const uint64_t *kept_in_dev, const uint64_t *ta_dev,
                          const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *kept_out_dev, int64_t count, void *stream);
 
+/* ---- base-2 and natural exponential of shared fixed-point numbers (hb_fxexp.hip) --------------------------------------------------
+ * The steps of progs/fixedpoint_exp.py that the demultiplexer and the division do not already have, for arrays of `count` values; the
+ * reference has no exponential.  Operands and results are canonical residues; arrays of several rows are row-major, [rows][count].
+ * The last truncation is hb_div_trunc_step(HB_DIV_T_RESULT).
+ * hb_fxexp_finish_lookup_mask: n_groups (1 .. 8) groups of index bits whose LAST demultiplexer level was just opened.  desc_host holds 6
+ *   ints a group: wl, wh, open_off, prod_off, table_off, slot.  The group's last merge joins a low factor of wl bits and a high one of wh
+ *   bits (1 <= wl, wh; wl + wh <= 12); rows open_off .. of opened_dev and of ta_dev are the 2^wl low rows and then the 2^wh high rows of
+ *   the level's opened array and of the triple's factors (hb_demux_mask's numbering), rows prod_off .. of tab_dev the 2^(wl + wh) triple
+ *   products, elements table_off .. of tables_dev the group's PUBLIC table T (one element an entry, the same for every element of the
+ *   batch).  F = sum_y T_y (d_lo e_hi + d_lo Q_hi + e_hi P_lo + PQ_y), y = hi 2^wl + lo: the table read at the one-hot vector, which is never
+ *   written.  wl = 1, wh = 0 is a group of ONE bit: open_off is its plane of bits_dev, and F = T_0 + (T_1 - T_0) b.  kept_dev [kept_rows][count]
+ *   row slot = F; for slot < 2 pairs also masked_dev [2 pairs][count] row slot = F - (slot even ? nxt_a : nxt_b)[slot / 2], nxt_a_dev,
+ *   nxt_b_dev [pairs][count] the factors of the next triples.  Rows of kept and masked that no group of the call names are left alone.
+ * hb_fxexp_products_trunc: 1 <= products <= 128.  opened_dev [2 products][count] the masked pairs opened, ta, tb, tab [products][count]:
+ *   v_r by the Beaver combine, then its truncation mask from planes r (width + kappa) .. of bits_dev: masked_dev [products][count] =
+ *   v_r + 2^(width-1) + r1 + 2^m r2 to open, s_dev [products][count] = v_r + r1.
+ * hb_fxexp_tree_step: 1 <= rows <= 128.  opened_dev, s_dev [rows][count] as above: t_j = (s_j - (opened_j mod 2^m)) inv2m with inv2m_host =
+ *   2^(-m) (one element, host memory).  The values are t_0 .. t_(rows-1) and, if carry_dev is not NULL, carry_dev [count] after them; pair
+ *   q of them goes to masked_dev rows 2q, 2q + 1 = v_2q - ta[q], v_(2q+1) - tb[q], and an odd last value to kept_dev [count].
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: counts or widths outside the
+ * ranges above, two groups in one slot, a slot at or above kept_rows, a truncation the modulus has no room for, a constant not below the
+ * modulus, null pointers (with count > 0), a negative count, an output that overlaps an input or another output.  count == 0 returns
+ * HB_OK and launches nothing. */
+int hb_fxexp_finish_lookup_mask(hb_ctx *ctx, const uint64_t *bits_dev, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tab_dev,
+                                const uint64_t *tables_dev, int n_groups, const int *desc_host, const uint64_t *nxt_a_dev, const uint64_t *nxt_b_dev,
+                                int pairs, uint64_t *masked_dev, uint64_t *kept_dev, int kept_rows, int64_t count, void *stream);
+int hb_fxexp_products_trunc(hb_ctx *ctx, int products, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev,
+                            const uint64_t *tab_dev, const uint64_t *bits_dev, int width, int m, int kappa, uint64_t *masked_dev, uint64_t *s_dev,
+                            int64_t count, void *stream);
+int hb_fxexp_tree_step(hb_ctx *ctx, int rows, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
+                       const uint64_t *carry_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *kept_dev,
+                       int64_t count, void *stream);
+
 /* ---- equality of shared values (hb_eq.hip) ---------------------------------------------------------------------------------
  * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
  * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
@@ -1243,6 +1276,19 @@ int hb_selftest_div(const uint64_t *p_limbs, int n_limbs, int what, const uint64
 #define HB_FXSQRT_SELFTEST_TRUNC_STEP 2
 int hb_selftest_fxsqrt(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                        uint64_t *const *outs, int64_t count);
+/* host-side run of the exponential kernels' steps (no GPU needed) over host memory, a whole step at a time; parameters and overlaps are
+ * checked as the device calls check them:
+ *   what = HB_FXEXP_SELFTEST_FINISH_LOOKUP_MASK  params = {n_groups, pairs, kept_rows, then desc: 6 ints a group}; operands[0..6] = bits,
+ *                                                opened, ta, tab, tables, nxt_a, nxt_b; outs[0..1] = masked, kept
+ *          HB_FXEXP_SELFTEST_PRODUCTS_TRUNC      params = {products, width, m, kappa}; operands[0..4] = opened, ta, tb, tab, bits; outs[0..1]
+ *                                                = masked, s
+ *          HB_FXEXP_SELFTEST_TREE_STEP           params = {rows, m}; operands[0..5] = opened, s, inv2m (one element), carry (or NULL), ta, tb;
+ *                                                outs[0..1] = masked, kept */
+#define HB_FXEXP_SELFTEST_FINISH_LOOKUP_MASK 0
+#define HB_FXEXP_SELFTEST_PRODUCTS_TRUNC 1
+#define HB_FXEXP_SELFTEST_TREE_STEP 2
+int hb_selftest_fxexp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                      uint64_t *const *outs, int64_t count);
 /* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
  *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
  *          HB_EQ_SELFTEST_MASK1     operands[0..7] = x, y (or NULL), r, rp, pa, qa, pb, qb; outs[0] as hb_eq_mask1 writes masked_dev
