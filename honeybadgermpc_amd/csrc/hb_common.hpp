@@ -114,6 +114,7 @@ enum EnvHook {
     ENV_MM8W_FLAT,
     ENV_MM8W_RQ,
     ENV_MM8W_TILE16,
+    ENV_MM8_NO_PREBIAS,
     ENV_MM8_NO_SKIP,
     ENV_NO_EVAL_FEW,
     ENV_NO_FUSED_MSCALE,

@@ -517,7 +517,7 @@ __global__ void __launch_bounds__(128) k_eval_few(const FpParams<NL> P, const ui
 
 // ---- environment hooks: one snapshot ---------------------------------------------------------------------------
 namespace hb {
-static const char *const ENV_NAMES[ENV_COUNT] = {"HB_CACHE_CAP", "HB_GAO_PAIR", "HB_MM8W_FLAT", "HB_MM8W_RQ", "HB_MM8W_TILE16", "HB_MM8_NO_SKIP", "HB_NO_EVAL_FEW", "HB_NO_FUSED_MSCALE", "HB_NO_FUSED_PACK", "HB_NO_FUSED_SMALL", "HB_NO_FUSED_VALIDATE", "HB_NO_MFMA", "HB_NO_MFMA_DECODE", "HB_NO_MFMA_WIDE", "HB_NO_NARROW_FAST", "HB_NO_QUICK", "HB_NO_QUICK_PLAN", "HB_NTT_STAGE_LOOP", "HB_PROBE_WGS", "HB_QUICK_NO_CAND", "HB_UPLOAD_MODE", "HB_WB_NO_GAO", "HB_WB_NO_UNIFORM"};
+static const char *const ENV_NAMES[ENV_COUNT] = {"HB_CACHE_CAP", "HB_GAO_PAIR", "HB_MM8W_FLAT", "HB_MM8W_RQ", "HB_MM8W_TILE16", "HB_MM8_NO_PREBIAS", "HB_MM8_NO_SKIP", "HB_NO_EVAL_FEW", "HB_NO_FUSED_MSCALE", "HB_NO_FUSED_PACK", "HB_NO_FUSED_SMALL", "HB_NO_FUSED_VALIDATE", "HB_NO_MFMA", "HB_NO_MFMA_DECODE", "HB_NO_MFMA_WIDE", "HB_NO_NARROW_FAST", "HB_NO_QUICK", "HB_NO_QUICK_PLAN", "HB_NTT_STAGE_LOOP", "HB_PROBE_WGS", "HB_QUICK_NO_CAND", "HB_UPLOAD_MODE", "HB_WB_NO_GAO", "HB_WB_NO_UNIFORM"};
 static std::string g_env_val[ENV_COUNT];
 static bool g_env_set[ENV_COUNT];
 static std::once_flag g_env_once;

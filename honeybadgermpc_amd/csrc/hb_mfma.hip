@@ -62,7 +62,12 @@ __device__ unsigned long long g_mm8_t[2048 * 8];
 #endif
 // SKIP: no entry of the matrix has a digit above the eighth in its first eight terms -- K-block 0 runs without its second digit group
 // (gen_mm8.py; checked when the image is built: Vandermonde matrices at the points 1 .. n, whose l-th powers stay below 2^56 for l < 8)
-template <int NKB, bool CHECK, bool RAGGED, bool SKIP>
+// PB: the element buffers are PRE-BIASED (gen_mm8.py, Mm8PhaseB).  The DMA is dealt by K-block -- one wave issues the four slots of a K-block,
+// so its own vmcnt(0) covers them -- and behind that wait, ahead of the unit's barrier, the wave rewrites its K-blocks in place: every
+// byte XOR 0x80, and granule j of a lane = {e0[2j], e1[2j], e0[2j+1], e1[2j+1]}, which is a file set of the phases as it lies.  The
+// bias and the interleave are then paid once per element and tile instead of once per half of every row-tile pass over the tile.
+// Never with CHECK, whose copy_dst reads raw elements out of the buffer.
+template <int NKB, bool CHECK, bool RAGGED, bool SKIP, bool PB = false>
 __global__ __launch_bounds__(256, 2) void k_mm8(const int4 *__restrict__ a8, const uint32_t *__restrict__ crowd,
                                                 const uint32_t *__restrict__ zero_src,
                                                 const uint32_t *__restrict__ in_pk, int64_t in_sc, int64_t in_sl,
@@ -110,6 +115,43 @@ __global__ __launch_bounds__(256, 2) void k_mm8(const int4 *__restrict__ a8, con
     // slot s = ((t * NKB + kb) * 2 + e) * 2 + h, dealt round-robin to the 4 waves; all of it wave-uniform
     auto issue_loads = [&](int64_t unit, int buf) {
         const int64_t c_last = (unit * tpw + tpw) * 16 - 1;
+        if constexpr (PB) {
+            static_assert(!PB || !CHECK, "CHECK reads raw elements out of xbuf");
+            // K-block q = t NKB + kb of the unit goes to wave q % 4, slots 4 q + 2 e + h.  Interior units: one scalar base a tile, the lane's two
+            // row offsets in one LDS read (an element's second half sixteen bytes on), and the four loads of the K-block in one block
+            const bool fast = fast_dma && c_last < n_chunks && c_last * in_sc + (int64_t)rowmax * in_sl < in_count;
+#pragma nounroll
+            for (int q = wave; q < tpw * NKB; q += 4) {
+                const int t = q / NKB, kb = q - t * NKB;
+                const uint32_t lds_dst = __builtin_amdgcn_readfirstlane(
+                    (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)(xbuf + (size_t)buf * bufsz + q * 4 * 64));
+                if (fast) {
+                    const uint64_t sbase = (uint64_t)(uintptr_t)in_pk + (uint64_t)((unit * tpw + t) * 16 * in_sc) * 32;
+                    const uint2 ro = *reinterpret_cast<const uint2 *>(rowoff + 8 * kb + 2 * g);
+                    const uint32_t voff0 = lane_off + ro.x, voff1 = lane_off + ro.y, voff0h = voff0 + 16, voff1h = voff1 + 16;
+                    uint32_t keep;
+                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
+                                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
+                                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
+                                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\ts_mov_b32 m0, %0"
+                                 : "=&s"(keep) : "v"(voff0), "v"(voff0h), "v"(voff1), "v"(voff1h), "s"(sbase), "s"(lds_dst) : "memory", "scc");
+                    continue;
+                }
+                int64_t chunk = (unit * tpw + t) * 16 + n;
+                if (chunk >= n_chunks) chunk = n_chunks - 1;
+#pragma nounroll
+                for (int eh = 0; eh < 4; eh++) {
+                    const int64_t idx = chunk * in_sc + (int64_t)rowl[8 * kb + 2 * g + (eh >> 1)] * in_sl;
+                    const uint4 *src = (idx < in_count) ? reinterpret_cast<const uint4 *>(in_pk) + idx * 2 + (eh & 1)
+                                                        : reinterpret_cast<const uint4 *>(zero_src) + (eh & 1);
+                    const uint32_t dst = lds_dst + eh * 1024;
+                    uint32_t keep;
+                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                                 : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+                }
+            }
+            return;
+        }
         if (fast_dma && c_last < n_chunks && c_last * in_sc + (int64_t)rowmax * in_sl < in_count) {
             for (int s = wave; s < n_slots; s += 4) {
                 const int h = s & 1, e = (s >> 1) & 1, q = s >> 2, t = q / NKB, kb = q - t * NKB;
@@ -139,6 +181,23 @@ __global__ __launch_bounds__(256, 2) void k_mm8(const int4 *__restrict__ a8, con
                          : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
         }
     };
+    // PB: the wave's K-blocks of a buffer, raw as the DMA left them (the caller has waited for it), rewritten in place: per lane and K-block four
+    // ds_read_b128, sixteen XORs, four ds_write_b128 -- the lane's own four granules, nobody else's.  The writes are waited for here: the
+    // unit's barrier stands for them towards the other waves
+    auto prebias = [&](int b) {
+        // (at most two trips: unrolled or interleaved, its trip counts cost scalar registers that the reductions want)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+        for (int q = wave; q < tpw * NKB; q += 4) {
+            uint4 *p = xbuf + (size_t)b * bufsz + (size_t)q * 4 * 64 + lane;
+            const uint4 a0 = p[0], a1 = p[64], c0 = p[128], c1 = p[192];     // (e0 lo, e0 hi, e1 lo, e1 hi)
+            const uint32_t m = 0x80808080u;
+            p[0] = make_uint4(a0.x ^ m, c0.x ^ m, a0.y ^ m, c0.y ^ m);
+            p[64] = make_uint4(a0.z ^ m, c0.z ^ m, a0.w ^ m, c0.w ^ m);
+            p[128] = make_uint4(a1.x ^ m, c1.x ^ m, a1.y ^ m, c1.y ^ m);
+            p[192] = make_uint4(a1.z ^ m, c1.z ^ m, a1.w ^ m, c1.w ^ m);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
     const v4i biasv = v4i{MM8_BIAS, MM8_BIAS, MM8_BIAS, MM8_BIAS};
     uint32_t k256 = 256u, k16m = 1u << 24;      // opaque, so that the word assembly stays two v_mad_u64_u32 per word
     int32_t s1 = 1, s256 = 256, s64k = 1 << 16, s16m = 1 << 24;   // and the gathering of the fold's columns one v_mad_i64_i32 each
@@ -167,6 +226,7 @@ __global__ __launch_bounds__(256, 2) void k_mm8(const int4 *__restrict__ a8, con
     }
     if (threadIdx.x < MM8_FOLD_Q) foldl[threadIdx.x] = reinterpret_cast<const v4i *>(crowd + (size_t)n_rt * 256)[threadIdx.x];
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if constexpr (PB) { if (unit < n_units) prebias(0); }
     // the fold's A operand: lane (m, g') of the diagonal block g' = m / 4 reads its 16 digits, every other lane the row's zero bytes
     const v4i *fold_lane = reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(foldl) + (g == (n >> 2) ? 16 * n : 256));
     MM8_T(0);   // prologue
@@ -215,7 +275,8 @@ __global__ __launch_bounds__(256, 2) void k_mm8(const int4 *__restrict__ a8, con
                 // higher priority -- a wave in a phase loses little by waiting a slot (the matrix pipe is 16 cycles an MFMA whatever rides beside
                 // it), a wave in its reduction holds the unit's barrier (round 6: the open 136.5 -> 133.3 us; the phases ABOVE the rest: 135.5)
                 __builtin_amdgcn_s_setprio(0);
-                Mm8Phase<NKB, 0, SKIP>::run(acc, xs_addr, as_addr, biasv);
+                if constexpr (PB) Mm8PhaseB<NKB, 0, SKIP>::run(acc, xs_addr, as_addr, biasv);
+                else Mm8Phase<NKB, 0, SKIP>::run(acc, xs_addr, as_addr, biasv);
                 __builtin_amdgcn_s_setprio(2);
                 __builtin_amdgcn_sched_barrier(0);
                 MM8_T(3);   // MFMA half 0
@@ -238,7 +299,8 @@ __global__ __launch_bounds__(256, 2) void k_mm8(const int4 *__restrict__ a8, con
                 __builtin_amdgcn_sched_barrier(0);
                 MM8_T(4);   // parking of half 0
                 __builtin_amdgcn_s_setprio(0);
-                Mm8Phase<NKB, 1, SKIP>::run(acc, xs_addr, as_addr, biasv);
+                if constexpr (PB) Mm8PhaseB<NKB, 1, SKIP>::run(acc, xs_addr, as_addr, biasv);
+                else Mm8Phase<NKB, 1, SKIP>::run(acc, xs_addr, as_addr, biasv);
                 __builtin_amdgcn_s_setprio(2);
                 __builtin_amdgcn_sched_barrier(0);
                 MM8_T(5);   // MFMA half 1
@@ -368,6 +430,10 @@ __global__ __launch_bounds__(256, 2) void k_mm8(const int4 *__restrict__ a8, con
             }
             MM8_T(7);   // word assembly + reduction + stores
         }
+        // PB: the wave's share of the next unit has landed (the wait ahead of its last reduction, or the one of a wave without a row tile):
+        // rewritten here, behind the stores and with no accumulator alive, on the way to the barrier
+        if constexpr (PB) { if (unit + gridDim.x < n_units) prebias(buf ^ 1); }
+        MM8_T(6);   // (PB: the rewrite's ticks join the wait for the DMA it follows)
     }
 #ifdef HB_MM8_TIMING
     if (lane == 0 && blockIdx.x < 512) for (int k = 0; k < 8; k++) g_mm8_t[(blockIdx.x * 4 + wave) * 8 + k] = tacc[k];
@@ -650,7 +716,7 @@ int mm8_from_fast(hb_ctx *ctx, const FastMatrix *f, Mm8Matrix **out, hipStream_t
         }
     }
     Mm8Matrix *m = new Mm8Matrix();
-    m->n_out = n_out; m->d = d; m->nkb = nkb; m->n_rt = n_rt; m->skip01 = skip01; m->a8 = nullptr; m->crow = nullptr; m->zero = nullptr;
+    m->n_out = n_out; m->d = d; m->nkb = nkb; m->n_rt = n_rt; m->skip01 = skip01; m->prebias = !env_hook(ENV_MM8_NO_PREBIAS); m->a8 = nullptr; m->crow = nullptr; m->zero = nullptr;
     m->bp = bpar;
     {   // 2^256 - p, 32-bit words
         Big pn(9, 0); pn[8] = 1;
@@ -692,14 +758,15 @@ int launch_mm8(hb_ctx *ctx, const Mm8Matrix *m, const uint32_t *in, hb_view iv, 
     const bool check = check_mask_dev != nullptr;
     // the last row tile holds at most 8 rows: its outputs 2 and 3 are padding and their reduction can be skipped
     const bool ragged = !check && (m->n_out % 16) >= 1 && (m->n_out % 16) <= 8;
-#define MM8_LAUNCH_(NKB, CHK, RG, SK)                                                                                 \
+#define MM8_LAUNCH_(NKB, CHK, RG, SK) do { if (!(CHK) && m->prebias) MM8_LAUNCH__(NKB, CHK, RG, SK, !(CHK)); else MM8_LAUNCH__(NKB, CHK, RG, SK, false); } while (0)
+#define MM8_LAUNCH__(NKB, CHK, RG, SK, PB)                                                                                 \
     do {                                                                                                          \
         static std::atomic<unsigned long long> attr_done{0};   /* one bit per device: the attribute is per device */                                                                            \
         if (!((attr_done.load() >> (ctx->device & 63)) & 1ull)) {                                                                                         \
-            HB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm8<NKB, CHK, RG, SK>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)); \
+            HB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm8<NKB, CHK, RG, SK, PB>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)); \
             attr_done.fetch_or(1ull << (ctx->device & 63));                                                                                     \
         }                                                                                                         \
-        hipLaunchKernelGGL((k_mm8<NKB, CHK, RG, SK>), dim3((unsigned)blocks), dim3(256), lds, s, m->a8, m->crow, m->zero, in, iv.stride_c, \
+        hipLaunchKernelGGL((k_mm8<NKB, CHK, RG, SK, PB>), dim3((unsigned)blocks), dim3(256), lds, s, m->a8, m->crow, m->zero, in, iv.stride_c, \
                            iv.stride_l, in_rows_dev, in_count, m->d, out, ov.stride_c, ov.stride_l, out_count,   \
                            check_mask_dev, check_rows_dev, mismatch_dev, copy_dst, cpv.stride_c, cpv.stride_l, copy_count, copy_rows,         \
                            m->n_out, m->n_rt, tpw, C, n_units, m->bp);             \
@@ -716,6 +783,7 @@ int launch_mm8(hb_ctx *ctx, const Mm8Matrix *m, const uint32_t *in, hb_view iv, 
 #undef MM8_LAUNCH
 #undef MM8_LAUNCH_SK
 #undef MM8_LAUNCH_
+#undef MM8_LAUNCH__
     HB_LAUNCH_CHECK(ctx);
     return HB_OK;
 }

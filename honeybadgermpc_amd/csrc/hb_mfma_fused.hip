@@ -371,11 +371,28 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
     }
     // the slots [buffer][tile][half][column] of a padding term, 256 in all: no scaling task ever writes them, and they are all that is
     // zeroed -- every other slot is written by the unit's scaling tasks before a pass reads it
+    // (MSC: the buffers hold biased bytes in the interleaved granules of put_biased below -- a padding term's dwords are the same 256 bytes
+    // a buffer and tile, positions e and 2 + e of its lane's four granules; its matrix digits are zero, so zeros serve there too)
     for (int i = threadIdx.x; i < (8 * NKB - d) * 256; i += NT) {
         const int l = d + (i >> 8), b = (i >> 7) & 1, t = (i >> 5) & 3, h = (i >> 4) & 1, c = i & 15;
         const int kb = l >> 3, gg = (l & 7) >> 1, e = l & 1;
-        xbuf[(size_t)b * bufsz + (size_t)((((t * NKB + kb) * 2 + e) * 2 + h) * 64) + (c + 16 * gg)] = make_uint4(0, 0, 0, 0);
+        if constexpr (MSC) {
+            uint32_t *gr = reinterpret_cast<uint32_t *>(xbuf + (size_t)b * bufsz + (size_t)(((t * NKB + kb) * 4 + 2 * h) * 64) + (c + 16 * gg)) + e;
+            gr[0] = 0; gr[2] = 0; gr[256] = 0; gr[258] = 0;
+        } else
+            xbuf[(size_t)b * bufsz + (size_t)((((t * NKB + kb) * 2 + e) * 2 + h) * 64) + (c + 16 * gg)] = make_uint4(0, 0, 0, 0);
     }
+    // MSC: a scaled element enters LDS as the passes' B operand wants it (gen_mm8.py, the pre-biased phases): every byte XOR 0x80, and
+    // granule j of lane (n, gg) of K-block kb holds {e0[2j], e1[2j], e0[2j+1], e1[2j+1]} -- element e's words 2 j and 2 j + 1 at dwords e
+    // and 2 + e.  The lane and its four granules (slots 4 (t NKB + kb) + j) are the ones the raw layout gives the pair of elements
+    auto put_biased = [&](uint4 *dst, int t, int kb, int gg, int e, const uint32_t (&w)[NW]) __attribute__((always_inline)) {
+        uint32_t *gr = reinterpret_cast<uint32_t *>(dst + (size_t)((t * NKB + kb) * 4) * 64 + (n + 16 * gg)) + e;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            gr[256 * j] = w[2 * j] ^ 0x80808080u;
+            gr[256 * j + 2] = w[2 * j + 1] ^ 0x80808080u;
+        }
+    };
     // (tile, row tile) pairs of a unit: wave w takes w, w + 8, ...; which terms of the next unit a wave scales beside its passes: split.terms
     const int n_pairs = FS_TPW * n_rt;
     const uint32_t my_terms = (uint32_t)__builtin_amdgcn_readfirstlane((int)split.terms[wave]);
@@ -526,9 +543,12 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                 for (int k = 0; k < NW; k++) w[k] = ok ? (take ? u[k] : w[k]) : 0u;
             }
             const int kb = l >> 3, gg = (l & 7) >> 1, e = l & 1;
-            uint4 *slot = dst + (size_t)(((t * NKB + kb) * 2 + e) * 2) * 64 + (n + 16 * gg);
-            slot[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            slot[64] = make_uint4(w[4], w[5], w[6], w[7]);
+            if constexpr (MSC) put_biased(dst, t, kb, gg, e, w);
+            else {
+                uint4 *slot = dst + (size_t)(((t * NKB + kb) * 2 + e) * 2) * 64 + (n + 16 * gg);
+                slot[0] = make_uint4(w[0], w[1], w[2], w[3]);
+                slot[64] = make_uint4(w[4], w[5], w[6], w[7]);
+            }
 #pragma unroll
             for (int k = 0; k < NW; k++) xw[k] = xn[k];
             ok = okn;
@@ -583,11 +603,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
 #pragma unroll
                         for (int k = 0; k < NW; k++) w[k] = okf[j] ? w[k] : 0u;
                     }
-                    // (a term the wave does not have is a padding term of K-block j: its slot takes the zeros it must hold)
-                    const int gg = (l & 7) >> 1, e = l & 1;
-                    uint4 *slot = xbuf + (size_t)(((t * NKB + j) * 2 + e) * 2) * 64 + (n + 16 * gg);
-                    slot[0] = make_uint4(w[0], w[1], w[2], w[3]);
-                    slot[64] = make_uint4(w[4], w[5], w[6], w[7]);
+                    // (a term the wave does not have is a padding term of K-block j: its digits are zero, whatever its dwords hold)
+                    put_biased(xbuf, t, j, (l & 7) >> 1, l & 1, w);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -682,7 +699,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                     asm volatile("" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                     __builtin_amdgcn_s_setprio(0);
-                    Mm8PhasePacked<NKB, 0>::run(acc, xs_addr, as_addr, biaspv);
+                    if constexpr (MSC) Mm8PhasePackedB<NKB, 0>::run(acc, xs_addr, as_addr, biaspv);
+                    else Mm8PhasePacked<NKB, 0>::run(acc, xs_addr, as_addr, biaspv);
                     __builtin_amdgcn_s_setprio(2);
                     __builtin_amdgcn_sched_barrier(0);
                     FS_T(3);
@@ -702,7 +720,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                     __builtin_amdgcn_sched_barrier(0);
                     FS_T(4);
                     __builtin_amdgcn_s_setprio(0);
-                    Mm8PhasePacked<NKB, 1>::run(acc, xs_addr, as_addr, biaspv);
+                    if constexpr (MSC) Mm8PhasePackedB<NKB, 1>::run(acc, xs_addr, as_addr, biaspv);
+                    else Mm8PhasePacked<NKB, 1>::run(acc, xs_addr, as_addr, biaspv);
                     __builtin_amdgcn_s_setprio(2);
                     __builtin_amdgcn_sched_barrier(0);
                     FS_T(5);
@@ -746,7 +765,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_setprio(0);        // (the phases yield to reductions and scaling: hb_mfma.hip, k_mm8)
-                Mm8Phase<NKB, 0, false>::run(acc, xs_addr, as_addr, biasv);
+                if constexpr (MSC) Mm8PhaseB<NKB, 0, false>::run(acc, xs_addr, as_addr, biasv);
+                else Mm8Phase<NKB, 0, false>::run(acc, xs_addr, as_addr, biasv);
                 __builtin_amdgcn_s_setprio(2);
                 __builtin_amdgcn_sched_barrier(0);
                 FS_T(3);
@@ -767,7 +787,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_mm8f(const int4 *__restric
                 __builtin_amdgcn_sched_barrier(0);
                 FS_T(4);
                 __builtin_amdgcn_s_setprio(0);
-                Mm8Phase<NKB, 1, false>::run(acc, xs_addr, as_addr, biasv);
+                if constexpr (MSC) Mm8PhaseB<NKB, 1, false>::run(acc, xs_addr, as_addr, biasv);
+                else Mm8Phase<NKB, 1, false>::run(acc, xs_addr, as_addr, biasv);
                 __builtin_amdgcn_s_setprio(2);
                 __builtin_amdgcn_sched_barrier(0);
                 FS_T(5);

@@ -28,6 +28,7 @@ struct BarrettParams {
 struct Mm8Matrix {
     int n_out, d, nkb, n_rt;
     bool skip01;       // digit group 1 of K-block 0 is zero in every row tile (k_mm8<.., SKIP>)
+    bool prebias;      // launches without CHECK bias and interleave the elements once, in LDS (k_mm8<.., PB>); HB_MM8_NO_PREBIAS=1 when the image is built: never
     int4 *a8;          // [n_rt][nkb][2 digit groups][64 lanes] 16 balanced digits each: lane (r, g) = row 16 rt + 4 (r % 4) + r / 4;
                        // byte j = 4 dd + bi is digit 7 + 8 G - 4 (dd >> 1) - bi of term 8 kb + 2 g + (dd & 1)
     uint32_t *crow;    // [n_rt * 16][16]: per row eight pairs [bias of the fold's four columns + constant word]; then the fold table
