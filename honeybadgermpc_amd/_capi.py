@@ -59,6 +59,7 @@ HB_DIV_SELFTEST_PAIR_MASK = 5
 HB_FXSQRT_GH, HB_FXSQRT_R, HB_FXSQRT_OUT = 0, 1, 2
 HB_FXSQRT_SELFTEST_NORM_MASK, HB_FXSQRT_SELFTEST_FIRST, HB_FXSQRT_SELFTEST_TRUNC_STEP = 0, 1, 2
 HB_FXEXP_SELFTEST_FINISH_LOOKUP_MASK, HB_FXEXP_SELFTEST_PRODUCTS_TRUNC, HB_FXEXP_SELFTEST_TREE_STEP = 0, 1, 2
+HB_FXLOG_SELFTEST_FIRST, HB_FXLOG_SELFTEST_LEVEL, HB_FXLOG_SELFTEST_POLY_MASK, HB_FXLOG_SELFTEST_FINISH = 0, 1, 2, 3
 HB_EQ_BIT, HB_EQ_REFERENCE = 0, 1
 HB_EQ_SELFTEST_LEGENDRE, HB_EQ_SELFTEST_MASK1, HB_EQ_SELFTEST_MID, HB_EQ_SELFTEST_CSHARE, HB_EQ_SELFTEST_FINISH = 0, 1, 2, 3, 4
 HB_LT_DIRECT, HB_LT_REFERENCE = 0, 1
@@ -181,6 +182,10 @@ SYMBOLS = {
     "hb_fxexp_finish_lookup_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _vp]),
     "hb_fxexp_products_trunc": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hb_fxexp_tree_step": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxlog_first": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxlog_level": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxlog_poly_mask": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "hb_fxlog_finish": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "hb_legendre": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "hb_eq_mask1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "hb_eq_mid": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
@@ -268,6 +273,7 @@ SYMBOLS = {
     "hb_selftest_div": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_fxsqrt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_fxexp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
+    "hb_selftest_fxlog": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_eq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_lt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_off": (_i, [_vp, _i, _i, _vp, _vp, _i64]),

@@ -571,6 +571,18 @@ class FixedPointArray:
 
         return self._like(await exp(self.co, self.shares, bits, triples, demux_triples, self.f, self.k, self.kappa, g))
 
+    async def log2(self, bits, triples):
+        """log2(self) (fixedpoint_log.log2): 0 < self < 2^(k-1-f)"""
+        from .fixedpoint_log import log2
+
+        return self._like(await log2(self.co, self.shares, bits, triples, self.f, self.k, self.kappa))
+
+    async def log(self, bits, triples):
+        """ln(self) (fixedpoint_log.log): 0 < self < 2^(k-1-f)"""
+        from .fixedpoint_log import log
+
+        return self._like(await log(self.co, self.shares, bits, triples, self.f, self.k, self.kappa))
+
     async def ltz(self, bits, triples):
         """-> a (count, limbs) tensor of shares of [a < 0]"""
         return await ltz(self.co, self.shares, bits, triples, self.k, self.kappa)

@@ -654,7 +654,39 @@ int hb_fxexp_tree_step(hb_ctx *ctx, int rows, const uint64_t *opened_dev, const 
                        const uint64_t *carry_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *kept_dev,
                        int64_t count, void *stream);
 
-/* ---- equality of shared values (hb_eq.hip) ---------------------------------------------------------------------------------
+/* ---- base-2, natural and public-base logarithm of shared fixed-point numbers (hb_fxlog.hip) --------------------------------------
+ * The steps of progs/fixedpoint_log.py that the division, the square root and the exponential do not already have, for arrays of
+ * `count` unsigned k-bit values with f fractional bits (N = k - 1, beta = 2^N); the reference has no logarithm.  Operands and results
+ * are canonical residues; arrays of several rows are row-major, [rows][count].  The scale step is hb_fxsqrt_norm_mask with the weights
+ * of the integer part and of Y = beta [x != 0]; "products to truncation masks" is hb_fxexp_products_trunc.  A polynomial of degree d, 2
+ * <= d <= 64, in t = 4 c - 3 Y is evaluated from the powers t^1 .. t^d, power j in row j - 1 of powers_dev [d][count]; level l = 1 ..
+ * ceil(log2 d) forms the powers half < j <= min(2 half, d), half = 2^(l-1), product q of it being [t^half t^(q+1)].
+ * hb_fxlog_first: opened_dev [2][count] the masked pair of [x v] opened; c = [x v] by the Beaver combine with (ta, tb, tab), t = 4 c -
+ *   3 ybig; row 0 of powers_dev = t, masked_dev rows 0, 1 = t - nxt_a, t - nxt_b: the masked pair of [t t] as ONE array to open.
+ * hb_fxlog_level: 1 <= level < ceil(log2 d).  opened_dev, s_dev [n][count], n the powers of `level`: the masked truncations opened
+ *   and the kept product + r1; power half + 1 + q = (s_q - (opened_q mod 2^m)) inv2m with inv2m_host = 2^(-m) (one element, host memory)
+ *   goes to row half + q of powers_dev, and masked_dev rows 2q, 2q + 1 = t^(2 half) - ta[q], t^(q+1) - tb[q] for the products of level
+ *   + 1 (ta, tb one row a product).  Rows below half of powers_dev are read.
+ * hb_fxlog_poly_mask: after the LAST level's open; opened_dev, s_dev, m_in, inv2m_host as above for that level, powers_dev rows below
+ *   its half read.  L = coef[0] ybig + sum_{j=1..d} coef[j] t^j with coef_dev [d + 1] PUBLIC, one element each, the same for every
+ *   element of the batch; bits_dev [width + kappa][count]: masked_dev = L + 2^(width-1) + r1 + 2^m_out r2 to open, s_out_dev = L + r1.
+ * hb_fxlog_finish: out = (s - (opened mod 2^m)) inv2m + ipart.
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: d or level outside the
+ * ranges above, m outside 0 < m <= bits(p) - 2, a truncation the modulus has no room for, a constant not below the modulus, null
+ * pointers (with count > 0), a negative count, an output that overlaps an input or another output.  count == 0 returns HB_OK and
+ * launches nothing. */
+int hb_fxlog_first(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev,
+                   const uint64_t *ybig_dev, const uint64_t *nxt_a_dev, const uint64_t *nxt_b_dev, uint64_t *masked_dev, uint64_t *powers_dev,
+                   int64_t count, void *stream);
+int hb_fxlog_level(hb_ctx *ctx, int level, int d, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
+                   const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *powers_dev, int64_t count, void *stream);
+int hb_fxlog_poly_mask(hb_ctx *ctx, int d, const uint64_t *opened_dev, const uint64_t *s_dev, int m_in, const uint64_t *inv2m_host,
+                       const uint64_t *powers_dev, const uint64_t *ybig_dev, const uint64_t *coef_dev, const uint64_t *bits_dev, int width,
+                       int m_out, int kappa, uint64_t *masked_dev, uint64_t *s_out_dev, int64_t count, void *stream);
+int hb_fxlog_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
+                    const uint64_t *ipart_dev, uint64_t *out_dev, int64_t count, void *stream);
+
+/* ---- equality of shared values (hb_eq.hip)---------------------------------------------------------------------------------
  * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
  * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
  * `count` elements, row j holding test bit j's value of every element; arrays of several rows are row-major.  Test bit j opens
@@ -1288,6 +1320,20 @@ int hb_selftest_fxsqrt(const uint64_t *p_limbs, int n_limbs, int what, const uin
 #define HB_FXEXP_SELFTEST_PRODUCTS_TRUNC 1
 #define HB_FXEXP_SELFTEST_TREE_STEP 2
 int hb_selftest_fxexp(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                      uint64_t *const *outs, int64_t count);
+/* host-side run of the logarithm kernels' steps (no GPU needed) over host memory, a whole step at a time; parameters and overlaps are
+ * checked as the device calls check them (params has five entries; those a step does not read are 0):
+ *   what = HB_FXLOG_SELFTEST_FIRST      operands[0..6] = opened, ta, tb, tab, ybig, nxt_a, nxt_b; outs[0..1] = masked, powers (row 0 written)
+ *          HB_FXLOG_SELFTEST_LEVEL      params = {level, d, m}; operands[0..4] = opened, s, inv2m (one element), ta, tb; outs[0..1] = masked,
+ *                                       powers [d][count], updated in place
+ *          HB_FXLOG_SELFTEST_POLY_MASK  params = {d, m_in, width, m_out, kappa}; operands[0..6] = opened, s, inv2m (one element), powers, ybig,
+ *                                       coef [d + 1], bits; outs[0..1] = masked, s_out
+ *          HB_FXLOG_SELFTEST_FINISH     params = {m}; operands[0..3] = opened, s, inv2m (one element), ipart; outs[0] = out */
+#define HB_FXLOG_SELFTEST_FIRST 0
+#define HB_FXLOG_SELFTEST_LEVEL 1
+#define HB_FXLOG_SELFTEST_POLY_MASK 2
+#define HB_FXLOG_SELFTEST_FINISH 3
+int hb_selftest_fxlog(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                       uint64_t *const *outs, int64_t count);
 /* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
  *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
