@@ -60,6 +60,7 @@ HB_FXSQRT_GH, HB_FXSQRT_R, HB_FXSQRT_OUT = 0, 1, 2
 HB_FXSQRT_SELFTEST_NORM_MASK, HB_FXSQRT_SELFTEST_FIRST, HB_FXSQRT_SELFTEST_TRUNC_STEP = 0, 1, 2
 HB_FXEXP_SELFTEST_FINISH_LOOKUP_MASK, HB_FXEXP_SELFTEST_PRODUCTS_TRUNC, HB_FXEXP_SELFTEST_TREE_STEP = 0, 1, 2
 HB_FXLOG_SELFTEST_FIRST, HB_FXLOG_SELFTEST_LEVEL, HB_FXLOG_SELFTEST_POLY_MASK, HB_FXLOG_SELFTEST_FINISH = 0, 1, 2, 3
+HB_FXTRIG_SELFTEST_FINISH_LOOKUP_MASK, HB_FXTRIG_SELFTEST_CPRODUCTS_TRUNC, HB_FXTRIG_SELFTEST_TREE_STEP = 0, 1, 2
 HB_EQ_BIT, HB_EQ_REFERENCE = 0, 1
 HB_EQ_SELFTEST_LEGENDRE, HB_EQ_SELFTEST_MASK1, HB_EQ_SELFTEST_MID, HB_EQ_SELFTEST_CSHARE, HB_EQ_SELFTEST_FINISH = 0, 1, 2, 3, 4
 HB_LT_DIRECT, HB_LT_REFERENCE = 0, 1
@@ -186,6 +187,9 @@ SYMBOLS = {
     "hb_fxlog_level": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_fxlog_poly_mask": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hb_fxlog_finish": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxtrig_finish_lookup_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i64, _vp]),
+    "hb_fxtrig_cproducts_trunc": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "hb_fxtrig_tree_step": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_legendre": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "hb_eq_mask1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "hb_eq_mid": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
@@ -274,6 +278,7 @@ SYMBOLS = {
     "hb_selftest_fxsqrt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_fxexp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_fxlog": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
+    "hb_selftest_fxtrig": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_eq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_lt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_off": (_i, [_vp, _i, _i, _vp, _vp, _i64]),

@@ -583,6 +583,26 @@ class FixedPointArray:
 
         return self._like(await log(self.co, self.shares, bits, triples, self.f, self.k, self.kappa))
 
+    async def sincos_turns(self, bits, triples, demux_triples, g=None, want=("sin", "cos")):
+        """sin and cos of self TURNS (fixedpoint_trig.sincos_turns): a tuple in the order of `want`, for any value"""
+        from .fixedpoint_trig import sincos_turns
+
+        return tuple(self._like(v) for v in await sincos_turns(self.co, self.shares, bits, triples, demux_triples, self.f, self.k, self.kappa, g, want))
+
+    async def sincos(self, bits, triples, demux_triples, g=None, want=("sin", "cos")):
+        """sin and cos of self radians (fixedpoint_trig.sincos): a tuple in the order of `want`, for any value"""
+        from .fixedpoint_trig import sincos
+
+        return tuple(self._like(v) for v in await sincos(self.co, self.shares, bits, triples, demux_triples, self.f, self.k, self.kappa, g, want))
+
+    async def sin(self, bits, triples, demux_triples, g=None):
+        """sin(self) (fixedpoint_trig.sin), self in radians: the preprocessing of want = ("sin",)"""
+        return (await self.sincos(bits, triples, demux_triples, g, ("sin",)))[0]
+
+    async def cos(self, bits, triples, demux_triples, g=None):
+        """cos(self) (fixedpoint_trig.cos), self in radians: the preprocessing of want = ("cos",)"""
+        return (await self.sincos(bits, triples, demux_triples, g, ("cos",)))[0]
+
     async def ltz(self, bits, triples):
         """-> a (count, limbs) tensor of shares of [a < 0]"""
         return await ltz(self.co, self.shares, bits, triples, self.k, self.kappa)

@@ -686,6 +686,45 @@ int hb_fxlog_poly_mask(hb_ctx *ctx, int d, const uint64_t *opened_dev, const uin
 int hb_fxlog_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
                     const uint64_t *ipart_dev, uint64_t *out_dev, int64_t count, void *stream);
 
+/* ---- sine and cosine of shared fixed-point numbers (hb_fxtrig.hip) ----------------------------------------------------------------
+ * The steps of progs/fixedpoint_trig.py that the demultiplexer and the exponential do not already have, for arrays of `count` values;
+ * the reference has no circular functions.  Operands and results are canonical residues; arrays of several rows are row-major,
+ * [rows][count].  A complex value is two rows, re (the cosine side) and then im.  A MODE says which components a level of the product
+ * tree keeps and how many triples a complex product takes: 0, both, THREE (Karatsuba: p0 = a.re b.re, p1 = a.im b.im, p2 = (a.re + a.im)
+ * (b.re + b.im); re = p0 - p1, im = p2 - p0 - p1); 1, re alone, the first TWO of them (re = p0 - p1); 2, im alone, all
+ * THREE (im = p2 - p0 - p1): a component kept alone is, share for share, the one kept beside the other.  With tp triples a product, triple r = tp q + t of product q takes rows 2 r and 2 r + 1 of a
+ * masked array [2 tp products][count]: operand a's value minus ta[r], operand b's minus tb[r] (hb_fxexp_products_trunc's convention);
+ * the values are re, im and (modes 0 and 2) re + im.
+ * hb_fxtrig_finish_lookup_mask: hb_fxexp_finish_lookup_mask's descriptors and operands; entries table_off .. of tables_dev are the group's
+ *   cos table, 2^(wl + wh) entries, and right after it its sin table, both read through the SAME one-hot vector in one pass over opened,
+ *   ta and tab.  Entries are signed: any canonical residue; one whose negative has fewer digits costs those.  A group of ONE bit (wl = 1,
+ *   wh = 0) has four entries C0, C1, S0, S1.  kept_dev [2 kept_slots][count] rows 2 slot, 2 slot + 1 = re, im; for slot < 2 pairs the value
+ *   is operand slot & 1 of product slot / 2 of a level in `mode` and its masked rows go to masked_dev [2 tp pairs][count] against
+ *   nxt_a_dev, nxt_b_dev [tp pairs][count].  split = 1, 2, 4, 8 or 16: the lanes an element's high indices are dealt to, summed across
+ *   the lanes at the end; every split gives the same bits.  Rows that no group of the call names are left alone.
+ * hb_fxtrig_cproducts_trunc: 1 <= products <= 64 complex products in `mode`.  opened_dev [2 tp products][count] the masked operands
+ *   opened, ta, tb, tab [tp products][count]; the kept components v (comps = 2 in mode 0, else 1; row comps q + c) and their truncation
+ *   masks from planes row (width + kappa) .. of bits_dev: masked_dev [comps products][count] = v + 2^(width-1) + r1 + 2^m r2 to open,
+ *   s_dev likewise = v + r1.
+ * hb_fxtrig_tree_step: opened_dev, s_dev [rows][count], 1 <= rows <= 128: t_j = (s_j - (opened_j mod 2^m)) inv2m with inv2m_host = 2^(-m)
+ *   (one element, host memory).  final = 1: kept_dev [rows][count] = t, the results; no carry.  final = 0: rows is even, the complex
+ *   values are (t_0, t_1), (t_2, t_3) .. and, if carry_dev is not NULL, carry_dev [2][count] after them; value u is operand u & 1 of
+ *   product u / 2 of the next level, whose mode is `mode`: its masked rows go to masked_dev against ta_dev, tb_dev [tp pairs][count], and
+ *   an odd last value to kept_dev [2][count].
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: counts, widths, a mode or
+ * a split outside the ranges above, two groups in one slot, a slot at or above kept_slots, a truncation the modulus has no room for, a
+ * constant not below the modulus, null pointers (with count > 0), a negative count, an output that overlaps an input or another
+ * output.  count == 0 returns HB_OK and launches nothing. */
+int hb_fxtrig_finish_lookup_mask(hb_ctx *ctx, const uint64_t *bits_dev, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tab_dev,
+                                 const uint64_t *tables_dev, int n_groups, const int *desc_host, const uint64_t *nxt_a_dev, const uint64_t *nxt_b_dev,
+                                 int pairs, int mode, int split, uint64_t *masked_dev, uint64_t *kept_dev, int kept_slots, int64_t count, void *stream);
+int hb_fxtrig_cproducts_trunc(hb_ctx *ctx, int products, int mode, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev,
+                              const uint64_t *tab_dev, const uint64_t *bits_dev, int width, int m, int kappa, uint64_t *masked_dev, uint64_t *s_dev,
+                              int64_t count, void *stream);
+int hb_fxtrig_tree_step(hb_ctx *ctx, int rows, int final, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
+                        const uint64_t *carry_dev, int mode, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *kept_dev,
+                        int64_t count, void *stream);
+
 /* ---- equality of shared values (hb_eq.hip)---------------------------------------------------------------------------------
  * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
  * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
@@ -1335,6 +1374,19 @@ int hb_selftest_fxexp(const uint64_t *p_limbs, int n_limbs, int what, const uint
 #define HB_FXLOG_SELFTEST_FINISH 3
 int hb_selftest_fxlog(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                       uint64_t *const *outs, int64_t count);
+/* host-side run of the sine and cosine kernels' steps (no GPU needed) over host memory, a whole step at a time; parameters and overlaps
+ * are checked as the device calls check them:
+ *   what = HB_FXTRIG_SELFTEST_FINISH_LOOKUP_MASK  params = {n_groups, pairs, kept_slots, mode, split, then desc: 6 ints a group};
+ *                                                 operands[0..6] = bits, opened, ta, tab, tables, nxt_a, nxt_b; outs[0..1] = masked, kept
+ *          HB_FXTRIG_SELFTEST_CPRODUCTS_TRUNC     params = {products, mode, width, m, kappa}; operands[0..4] = opened, ta, tb, tab, bits;
+ *                                                 outs[0..1] = masked, s
+ *          HB_FXTRIG_SELFTEST_TREE_STEP           params = {rows, final, m, mode}; operands[0..5] = opened, s, inv2m (one element), carry (or
+ *                                                 NULL), ta, tb; outs[0..1] = masked, kept */
+#define HB_FXTRIG_SELFTEST_FINISH_LOOKUP_MASK 0
+#define HB_FXTRIG_SELFTEST_CPRODUCTS_TRUNC 1
+#define HB_FXTRIG_SELFTEST_TREE_STEP 2
+int hb_selftest_fxtrig(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                       uint64_t *const *outs, int64_t count);
 /* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
  *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
  *          HB_EQ_SELFTEST_MASK1     operands[0..7] = x, y (or NULL), r, rp, pa, qa, pb, qb; outs[0] as hb_eq_mask1 writes masked_dev
