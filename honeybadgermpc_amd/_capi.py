@@ -61,6 +61,8 @@ HB_FXSQRT_SELFTEST_NORM_MASK, HB_FXSQRT_SELFTEST_FIRST, HB_FXSQRT_SELFTEST_TRUNC
 HB_FXEXP_SELFTEST_FINISH_LOOKUP_MASK, HB_FXEXP_SELFTEST_PRODUCTS_TRUNC, HB_FXEXP_SELFTEST_TREE_STEP = 0, 1, 2
 HB_FXLOG_SELFTEST_FIRST, HB_FXLOG_SELFTEST_LEVEL, HB_FXLOG_SELFTEST_POLY_MASK, HB_FXLOG_SELFTEST_FINISH = 0, 1, 2, 3
 HB_FXTRIG_SELFTEST_FINISH_LOOKUP_MASK, HB_FXTRIG_SELFTEST_CPRODUCTS_TRUNC, HB_FXTRIG_SELFTEST_TREE_STEP = 0, 1, 2
+HB_FXATAN_SELFTEST_SIGN_MASK, HB_FXATAN_SELFTEST_ABS, HB_FXATAN_SELFTEST_SELECT_MASK, HB_FXATAN_SELFTEST_SELECT, HB_FXATAN_SELFTEST_FIRST = 0, 1, 2, 3, 4
+HB_FXATAN_SELFTEST_LEVEL, HB_FXATAN_SELFTEST_POLY_MASK, HB_FXATAN_SELFTEST_ASSEMBLE, HB_FXATAN_SELFTEST_FINISH = 5, 6, 7, 8
 HB_EQ_BIT, HB_EQ_REFERENCE = 0, 1
 HB_EQ_SELFTEST_LEGENDRE, HB_EQ_SELFTEST_MASK1, HB_EQ_SELFTEST_MID, HB_EQ_SELFTEST_CSHARE, HB_EQ_SELFTEST_FINISH = 0, 1, 2, 3, 4
 HB_LT_DIRECT, HB_LT_REFERENCE = 0, 1
@@ -190,6 +192,15 @@ SYMBOLS = {
     "hb_fxtrig_finish_lookup_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i64, _vp]),
     "hb_fxtrig_cproducts_trunc": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hb_fxtrig_tree_step": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_sign_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_abs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_select_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_first": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_level": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_poly_mask": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_assemble": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hb_fxatan_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hb_legendre": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "hb_eq_mask1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "hb_eq_mid": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
@@ -279,6 +290,7 @@ SYMBOLS = {
     "hb_selftest_fxexp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_fxlog": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_fxtrig": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
+    "hb_selftest_fxatan": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_eq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_lt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64]),
     "hb_selftest_off": (_i, [_vp, _i, _i, _vp, _vp, _i64]),

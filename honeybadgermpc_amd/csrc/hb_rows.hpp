@@ -1,10 +1,10 @@
 // hb_rows.hpp -- what the share-array step files share, one of each.
 //   The helpers -- the read-once load, the small element helpers (word_bit, diff_elem, small_digits, FpConst), the host's digits of a
 //   constant (host_digits, host_mont) and the argument checks of the entry points (u32, overlap, RowSpan / outputs_apart, modulus_bits,
-//   HB_ROW_BLOCKS) -- serve all of them: hb_ew.hip, hb_fxp.hip, hb_bd.hip, hb_demux.hip, hb_div.hip, hb_fxsqrt.hip, hb_fxlog.hip, hb_fxtrig.hip, hb_lt.hip, hb_eq.hip,
+//   HB_ROW_BLOCKS) -- serve all of them: hb_ew.hip, hb_fxp.hip, hb_bd.hip, hb_demux.hip, hb_div.hip, hb_fxsqrt.hip, hb_fxlog.hip, hb_fxtrig.hip, hb_fxatan.hip, hb_lt.hip, hb_eq.hip,
 //   hb_jj.hip, hb_mimc.hip, hb_bf.hip, hb_off.hip, hb_offpow.hip, hb_offsb.hip, hb_mat.hip and hb_sort.hip.
 //   The shape of a step -- the memory policies, k_rows, host_rows, launch_rows -- serves hb_ew.hip, hb_fxp.hip, hb_bd.hip, hb_demux.hip,
-//   hb_div.hip, hb_fxsqrt.hip, hb_fxlog.hip, hb_fxtrig.hip, hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_mimc.hip, hb_bf.hip, hb_off.hip, hb_offpow.hip, hb_offsb.hip and hb_sort.hip.  Every step of
+//   hb_div.hip, hb_fxsqrt.hip, hb_fxlog.hip, hb_fxtrig.hip, hb_fxatan.hip, hb_lt.hip, hb_eq.hip, hb_jj.hip, hb_mimc.hip, hb_bf.hip, hb_off.hip, hb_offpow.hip, hb_offsb.hip and hb_sort.hip.  Every step of
 //   theirs is a row but for four kernels that keep a shape of their own: k_ew_inv, k_off_invsqrt_scale and k_off_degree_check (wave
 //   sums: no lane may leave early) and k_mimc_plain (two elements a thread).  hb_mat.hip (tiles, LDS) uses the helpers alone.
 //
@@ -26,7 +26,7 @@
 // the case of hb_selftest_xx.  Both callers are one line, so the host self test runs the checks, the Args fill and the row count
 // the device runs: an operand swapped in an initialiser, a wrong row count or a span list one row short shows without a GPU, and
 // the self test refuses an output laid over an input as the entry point does (tests/row_refusal_cases.py).  hb_lt, hb_eq, hb_fxp,
-// hb_bd, hb_div, hb_fxsqrt, hb_fxlog, hb_fxtrig, hb_sort and hb_demux have step functions; the other seven files still have entry point bodies and HB_ROW_BLOCKS.
+// hb_bd, hb_div, hb_fxsqrt, hb_fxlog, hb_fxtrig, hb_fxatan, hb_sort and hb_demux have step functions; the other seven files still have entry point bodies and HB_ROW_BLOCKS.
 #pragma once
 #include "hb_common.hpp"
 

@@ -50,8 +50,8 @@ Protocol level, coroutines over an OpenCoalescer (every party runs the same coro
                                                         matmul_width(k, inner) = 2 k + ceil(log2(inner)): 2 batches, m n truncation opens
 
 div2m and its kin take 3 + 2 carry_levels(m) launches for any count.  FixedPointArray wraps a share array with +, -, neg(), mul,
-div by a public number, divide by a shared one and reciprocal (progs/fixedpoint_division.py), ltz, lt, sort (progs/sorting.py) and
-open() -> list[float].
+div by a public number, divide by a shared one and reciprocal (progs/fixedpoint_division.py), atan2 and atan
+(progs/fixedpoint_atan.py), ltz, lt, sort (progs/sorting.py) and open() -> list[float].
 """
 from .._capi import HB_FXP_MOD, HB_FXP_NEG_TRUNC, HB_FXP_TRUNC
 from ..share_arithmetic import add, beaver_multiply_arrays, neg, sub
@@ -602,6 +602,18 @@ class FixedPointArray:
     async def cos(self, bits, triples, demux_triples, g=None):
         """cos(self) (fixedpoint_trig.cos), self in radians: the preprocessing of want = ("cos",)"""
         return (await self.sincos(bits, triples, demux_triples, g, ("cos",)))[0]
+
+    async def atan2(self, x, bits, triples, turns=False):
+        """atan2(self, x) in (-pi, pi] (fixedpoint_atan.atan2), self the ordinate; turns=True: in (-1/2, 1/2], sincos_turns' unit"""
+        from .fixedpoint_atan import atan2
+
+        return self._like(await atan2(self.co, self.shares, self._other(x), bits, triples, self.f, self.k, self.kappa, turns))
+
+    async def atan(self, bits, triples, turns=False):
+        """atan(self) (fixedpoint_atan.atan): atan2 against the public 1, the same preprocessing"""
+        from .fixedpoint_atan import atan
+
+        return self._like(await atan(self.co, self.shares, bits, triples, self.f, self.k, self.kappa, turns))
 
     async def ltz(self, bits, triples):
         """-> a (count, limbs) tensor of shares of [a < 0]"""

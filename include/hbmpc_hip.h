@@ -725,6 +725,60 @@ int hb_fxtrig_tree_step(hb_ctx *ctx, int rows, int final, const uint64_t *opened
                         const uint64_t *carry_dev, int mode, const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *kept_dev,
                         int64_t count, void *stream);
 
+/* ---- arctangent and atan2 of shared fixed-point numbers (hb_fxatan.hip) -----------------------------------------------------------
+ * The steps of progs/fixedpoint_atan.py between the opens of the comparison, the division and hb_fxexp_products_trunc, for arrays of
+ * `count` pairs (y, x) of signed k-bit values with f fractional bits (N = k - 1, beta = 2^N); the reference has no arctangent.  Operands
+ * and results are canonical residues; arrays of several rows are row-major, [rows][count].  A sign bit s stands for sigma = 1 - 2 s.
+ * An odd polynomial of degree d, 3 <= d <= 63 odd, J = (d - 1) / 2, in t = 2^shift q is evaluated from the odd powers t^(2j+1), row j of
+ * powers_dev [J + 1][count], and the squares u^(2^l), u = [t t]: level 0 forms u; level l = 1 .. levels = bit_length(J) forms t^(2j+1),
+ * 2^(l-1) <= j < min(2^l, J + 1), as [t^(2j+1-2^l) u^(2^(l-1))] (product q = j - 2^(l-1)) and, last and only if l < levels, u^(2^l) =
+ * [u^(2^(l-1)) u^(2^(l-1))]; every product is truncated by N bits.
+ * hb_fxatan_sign_mask: s_dev [2][count] = (sx, sy); masked_dev [6][count] = sx - ta[0], x - tb[0], sy - ta[1], y - tb[1], sigma_y - ta[2],
+ *   sx - tb[2]: the masked pairs of [sx x], [sy y] and g = [sigma_y sx] as ONE array to open.
+ * hb_fxatan_abs: opened_dev [6][count] that array opened, ta, tb, tab [3][count]; |x| = x - 2 [sx x], |y| = y - 2 [sy y], g, w = |x| - |y|;
+ *   bits_dev [k + kappa][count]: masked_dev [1][count] = w + 2^(k-1) + r1 + 2^(k-1) r2, the comparison's array to open; kept_dev
+ *   [5][count] = |x|, |y|, g, w, r1.
+ * hb_fxatan_select_mask: c = [w < 0]; masked_dev [4][count] = c - ta[0], w - tb[0], sigma_c - ta[1], sigma_x - tb[1].
+ * hb_fxatan_select: opened_dev [4][count], ta, tb, tab [2][count]; out_dev [3][count] = num = |y| + [c w], den = |x| - [c w], e1 =
+ *   [sigma_c sigma_x].
+ * hb_fxatan_first: t = 2^shift q, 0 <= shift <= 255; row 0 of powers_dev = t; masked_dev [4][count] = t - ta[0], t - tb[0], sigma_y -
+ *   ta[1], e1 - tb[1]: the masked pairs of [t t] and E = [sigma_y e1].
+ * hb_fxatan_level: 0 <= level < levels.  opened_dev, s_dev [n][count], n the products of `level`: the masked truncations opened and the
+ *   kept product + r1, truncated as (s - (opened mod 2^m)) inv2m with inv2m_host = 2^(-m) (one element, host memory); the odd powers go
+ *   to their rows of powers_dev, and masked_dev rows 2q, 2q + 1 are the masked pair of product q of level + 1 against ta[q], tb[q].
+ * hb_fxatan_poly_mask: after the LAST level's open; L = sum_{j=0..J} coef[j] t^(2j+1) with coef_dev [J + 1] PUBLIC, one element each;
+ *   bits_dev [width + kappa][count]: masked_dev = L + 2^(width-1) + r1 + 2^m_out r2 to open, s_out_dev = L + r1.
+ * hb_fxatan_assemble: a = (s - (opened mod 2^m)) inv2m; E = [sigma_y e1] from eopened_dev [2][count] (rows 2, 3 of the first step's array,
+ *   opened) and its triple (ea, eb, eab); masked_dev [2][count] = E - ta, a - tb; c_dev = A g + B (sigma_y - E), cst_host = (A, B), two
+ *   elements in host memory.
+ * hb_fxatan_finish: out = c + [E a] by the Beaver combine of opened_dev [2][count] with (ta, tb, tab).
+ * All are asynchronous on `stream`, one launch each, and allocate nothing.  HB_ERR_BAD_ARG before any launch: d, level or shift outside
+ * the ranges above, m outside 0 < m <= bits(p) - 2, a truncation the modulus has no room for, a constant not below the modulus, null
+ * pointers (with count > 0), a negative count, an output that overlaps an input or another output.  count == 0 returns HB_OK and
+ * launches nothing. */
+int hb_fxatan_sign_mask(hb_ctx *ctx, const uint64_t *s_dev, const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *ta_dev,
+                        const uint64_t *tb_dev, uint64_t *masked_dev, int64_t count, void *stream);
+int hb_fxatan_abs(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev,
+                  const uint64_t *x_dev, const uint64_t *y_dev, const uint64_t *bits_dev, int k, int kappa, uint64_t *masked_dev,
+                  uint64_t *kept_dev, int64_t count, void *stream);
+int hb_fxatan_select_mask(hb_ctx *ctx, const uint64_t *c_dev, const uint64_t *w_dev, const uint64_t *sx_dev, const uint64_t *ta_dev,
+                          const uint64_t *tb_dev, uint64_t *masked_dev, int64_t count, void *stream);
+int hb_fxatan_select(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev,
+                     const uint64_t *ax_dev, const uint64_t *ay_dev, uint64_t *out_dev, int64_t count, void *stream);
+int hb_fxatan_first(hb_ctx *ctx, const uint64_t *q_dev, int shift, const uint64_t *sy_dev, const uint64_t *e1_dev, const uint64_t *ta_dev,
+                    const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *powers_dev, int64_t count, void *stream);
+int hb_fxatan_level(hb_ctx *ctx, int level, int d, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
+                    const uint64_t *ta_dev, const uint64_t *tb_dev, uint64_t *masked_dev, uint64_t *powers_dev, int64_t count, void *stream);
+int hb_fxatan_poly_mask(hb_ctx *ctx, int d, const uint64_t *opened_dev, const uint64_t *s_dev, int m_in, const uint64_t *inv2m_host,
+                        const uint64_t *powers_dev, const uint64_t *coef_dev, const uint64_t *bits_dev, int width, int m_out, int kappa,
+                        uint64_t *masked_dev, uint64_t *s_out_dev, int64_t count, void *stream);
+int hb_fxatan_assemble(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *s_dev, int m, const uint64_t *inv2m_host,
+                       const uint64_t *eopened_dev, const uint64_t *ea_dev, const uint64_t *eb_dev, const uint64_t *eab_dev,
+                       const uint64_t *sy_dev, const uint64_t *g_dev, const uint64_t *cst_host, const uint64_t *ta_dev, const uint64_t *tb_dev,
+                       uint64_t *masked_dev, uint64_t *c_dev, int64_t count, void *stream);
+int hb_fxatan_finish(hb_ctx *ctx, const uint64_t *opened_dev, const uint64_t *ta_dev, const uint64_t *tb_dev, const uint64_t *tab_dev,
+                     const uint64_t *c_dev, uint64_t *out_dev, int64_t count, void *stream);
+
 /* ---- equality of shared values (hb_eq.hip)---------------------------------------------------------------------------------
  * The Equality mixin of progs/mixins/share_comparison.py:9-80, the probabilistic Legendre-symbol test, for arrays of `count` pairs
  * and `rows` test bits a pair.  Everywhere: operands and results are canonical residues; preprocessing arrives as planes, rows of
@@ -1386,6 +1440,31 @@ int hb_selftest_fxlog(const uint64_t *p_limbs, int n_limbs, int what, const uint
 #define HB_FXTRIG_SELFTEST_CPRODUCTS_TRUNC 1
 #define HB_FXTRIG_SELFTEST_TREE_STEP 2
 int hb_selftest_fxtrig(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
+                       uint64_t *const *outs, int64_t count);
+/* host-side run of the arctangent kernels' steps (no GPU needed) over host memory, a whole step at a time; parameters and overlaps are
+ * checked as the device calls check them (params has five entries; those a step does not read are 0):
+ *   what = HB_FXATAN_SELFTEST_SIGN_MASK    operands[0..4] = s, x, y, ta, tb; outs[0] = masked
+ *          HB_FXATAN_SELFTEST_ABS          params = {k, kappa}; operands[0..6] = opened, ta, tb, tab, x, y, bits; outs[0..1] = masked, kept
+ *          HB_FXATAN_SELFTEST_SELECT_MASK  operands[0..4] = c, w, sx, ta, tb; outs[0] = masked
+ *          HB_FXATAN_SELFTEST_SELECT       operands[0..5] = opened, ta, tb, tab, ax, ay; outs[0] = out
+ *          HB_FXATAN_SELFTEST_FIRST        params = {shift}; operands[0..4] = q, sy, e1, ta, tb; outs[0..1] = masked, powers (row 0 written)
+ *          HB_FXATAN_SELFTEST_LEVEL        params = {level, d, m}; operands[0..4] = opened, s, inv2m (one element), ta, tb; outs[0..1] =
+ *                                          masked, powers [J + 1][count], updated in place
+ *          HB_FXATAN_SELFTEST_POLY_MASK    params = {d, m_in, width, m_out, kappa}; operands[0..5] = opened, s, inv2m (one element), powers,
+ *                                          coef [J + 1], bits; outs[0..1] = masked, s_out
+ *          HB_FXATAN_SELFTEST_ASSEMBLE     params = {m}; operands[0..11] = opened, s, inv2m (one element), eopened, ea, eb, eab, sy, g, cst
+ *                                          (two elements), ta, tb; outs[0..1] = masked, c
+ *          HB_FXATAN_SELFTEST_FINISH       operands[0..4] = opened, ta, tb, tab, c; outs[0] = out */
+#define HB_FXATAN_SELFTEST_SIGN_MASK 0
+#define HB_FXATAN_SELFTEST_ABS 1
+#define HB_FXATAN_SELFTEST_SELECT_MASK 2
+#define HB_FXATAN_SELFTEST_SELECT 3
+#define HB_FXATAN_SELFTEST_FIRST 4
+#define HB_FXATAN_SELFTEST_LEVEL 5
+#define HB_FXATAN_SELFTEST_POLY_MASK 6
+#define HB_FXATAN_SELFTEST_ASSEMBLE 7
+#define HB_FXATAN_SELFTEST_FINISH 8
+int hb_selftest_fxatan(const uint64_t *p_limbs, int n_limbs, int what, const uint64_t *const *operands, const int64_t *params,
                        uint64_t *const *outs, int64_t count);
 /* host-side run of the equality kernels' bodies (no GPU needed) over host memory, element by element.  params = {rows, mode}:
  *   what = HB_EQ_SELFTEST_LEGENDRE  operands[0] = a; outs[0] = int8 [count]
